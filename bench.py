@@ -9,14 +9,20 @@ summaries to rank 0 with RCCL over xGMI (the only collective).  Weak scaling:
 every rank optimises its own 1024 seeds.
 
 value = (instances x 14 outer iterations, all ranks) / (max over ranks of the
-timed K steps).  Also reported (rank 0): C3/C4/C5, the PCIe-inclusive C2 rate,
+timed K steps).  A plain run does only that: set up, warm up, time the K steps, write
+the last step's results if asked (`--dump-outputs DIR`), print the result line.
+
+With `--full` it also reports (rank 0): the roofline and parity of the timed batch, for
+N>1 the result gather at its real size, C3/C4/C5, the PCIe-inclusive C2 rate,
 the drop-in B=1 latency per bundled track next to the reference's own CPU time,
 lap-time Δ statistics over instances against the CPU oracle, and the CPU
 baseline (the reference compiled from its sources, oracle/_ref, on one pinned
 core; the C restatement beside it).  The CPU work runs in a child process
 started before any GPU call (`--cpu-leg`), pinned away from the GPU host thread.
+`--no-cpu` and `--no-extras` trim a `--full` run.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--no-cpu] [--no-extras]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR]
+                       [--full [--no-cpu] [--no-extras]]
 Multi-GPU: python -m torch.distributed.run --nproc-per-node N bench.py --gpus N
 """
 from __future__ import annotations
@@ -826,6 +832,39 @@ def run_result_gather(res_buf, res, world, rank, dev, dist, backend, same_device
             "note": "outside the timed C2 steps; max over ranks of each rank's median gather time"}
 
 
+DUMP_MAX_BYTES = 48 * 2**20   # --dump-outputs: all files together (float64)
+DUMP_SEED = 20240607
+
+
+def dump_instances(B: int, bytes_per_instance: int) -> np.ndarray:
+    """The instances --dump-outputs writes: all B when they fit in DUMP_MAX_BYTES, else a
+    fixed sample of them (seeded, sorted; the same for every run with the same B and sizes)."""
+    n = max(1, min(B, DUMP_MAX_BYTES // bytes_per_instance))
+    if n >= B:
+        return np.arange(B, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(B, size=n, replace=False)).astype(np.int64)
+
+
+def dump_outputs(dirpath: str, res: dict) -> dict:
+    """What the last timed step left in the plan's bound outputs (rank 0's result block: x,
+    y, kappa, alpha_last, alpha_total, heading [B][N] and evals [B][MO]) as
+    <dirpath>/<name>.npy, float64, for the instances of dump_instances (their indices in
+    instance.npy).  Returns {file name: shape}."""
+    import torch
+
+    os.makedirs(dirpath, exist_ok=True)
+    B = int(res["x"].shape[0])
+    per_instance = 8 * (1 + sum(int(v[0].numel()) for v in res.values()))
+    idx = dump_instances(B, per_instance)
+    sel = torch.from_numpy(idx).to(res["x"].device)
+    arrays = {"instance": idx.astype(np.float64)}
+    for name, t in res.items():
+        arrays[name] = t.index_select(0, sel).cpu().numpy().astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirpath, name + ".npy"), a)
+    return {name + ".npy": list(a.shape) for name, a in arrays.items()}
+
+
 def _free_port() -> int:
     import socket
 
@@ -859,15 +898,18 @@ def launch_plan(gpus: int, env, argv) -> list | None:
             "--master-addr=127.0.0.1", f"--master-port={_free_port()}", os.path.abspath(__file__)] + list(argv)
 
 
-def backend_label(world: int, backend: str, same_device: bool) -> str:
-    """The `parallelism` string: what actually ran (backend and device placement)."""
+def backend_label(world: int, backend: str, same_device: bool, result_gather: bool = True) -> str:
+    """The `parallelism` string: what actually ran (backend and device placement;
+    result_gather: the whole-block gather of a --full run)."""
     if world == 1:
         return "dp1: one GPU, no collective"
     coll = "RCCL (torch.distributed nccl) over xGMI" if backend == "nccl" else f"torch.distributed {backend}"
     where = (f"{world} ranks on one GPU (same-device rehearsal)" if same_device
              else f"instances sharded over {world} GPUs, one rank per GPU")
-    return (f"dp{world}: {where}; per-step {coll} gather of per-instance summaries to rank 0, then one "
-            f"{coll} gather of every rank's whole result block (result_gather, outside the timed steps)")
+    label = f"dp{world}: {where}; per-step {coll} gather of per-instance summaries to rank 0"
+    if result_gather:
+        label += f", then one {coll} gather of every rank's whole result block (result_gather, outside the timed steps)"
+    return label
 
 
 def main():
@@ -876,8 +918,12 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=1024)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="only the timed C2 steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results (rank 0) as DIR/<name>.npy, float64")
+    ap.add_argument("--full", action="store_true",
+                    help="also: roofline, parity, result gather (N>1), C3/C4/C5 and drop-in legs, CPU baseline")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: no CPU leg")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: no C3/C4/C5, drop-in or CPU legs")
     ap.add_argument("--cpu-leg", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-budget", type=float, default=12.0)
     args = ap.parse_args()
@@ -899,7 +945,8 @@ def main():
     # the CPU leg (rank 0, any world size) starts before this process touches the GPU; the
     # other ranks keep off its pinned core
     HOST_CORES.update(os.sched_getaffinity(0))
-    cpu_proc = start_cpu_leg(args.cpu_budget) if (rank == 0 and not args.no_cpu and not args.no_extras) else None
+    extras_on = args.full and not args.no_extras
+    cpu_proc = start_cpu_leg(args.cpu_budget) if (rank == 0 and extras_on and not args.no_cpu) else None
     if rank != 0 and len(HOST_CORES) > 2:
         os.sched_setaffinity(0, set(HOST_CORES) - {min(HOST_CORES)})
     # rehearsal on a one-GPU box only: every rank on cuda:0, gloo instead of RCCL
@@ -975,13 +1022,15 @@ def main():
         elapsed = float(t.item())
     ms_per_step = elapsed / args.steps * 1e3
     total_outer = world * B * MO * args.steps
-    result_gather = run_result_gather(res_buf, res, world, rank, dev, dist, backend, same_device, B, N, MO) \
-        if world > 1 else None
     value = total_outer / elapsed
     tracks_per_s = world * B * args.steps / elapsed
+    # the last timed step's results, as its caller holds them (rank 0's bound output block)
+    dumped = dump_outputs(args.dump_outputs, res) if (args.dump_outputs and rank == 0) else None
+    result_gather = run_result_gather(res_buf, res, world, rank, dev, dist, backend, same_device, B, N, MO) \
+        if (args.full and world > 1) else None
 
     extras = {}
-    if not args.no_extras:
+    if extras_on:
         c4, c4_laps = run_c4(world, rank, local, dev, dist)
         c5 = run_c5(world, rank, local, dev, dist)
         if rank == 0:
@@ -996,6 +1045,36 @@ def main():
             extras["csv_format_1024_instances"] = run_format(world, rank, xh, yh, res["kappa"].cpu().numpy(),
                                                               res["alpha_last"].cpu().numpy(), case, cfg)
     if rank != 0:
+        plan.close()
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    head = {
+        "metric": "PGD outer-iters/sec (N=2000 samples, closed, competition_map1, 1024 alpha-seeds/GPU, min-curv)",
+        "value": round(value, 1),
+        "unit": "PGD outer-iters/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "competition_map1 cones from the reference repo -> reference steps 1-6 (fixture); synthetic alpha-seeds",
+        "config": {"workload": "C2: competition_map1 closed, N=2000, B=1024 alpha-seeds per GPU, min-curvature, "
+                               "14 outer iterations, default cfg::Config", "N": N, "batch_per_gpu": B,
+                   "global_batch": world * B, "parallelism": backend_label(world, backend, same_device, args.full),
+                   "backend": backend if world > 1 else None},
+        "tracks_per_s": round(tracks_per_s, 2),
+        "hip_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"),
+        **({"outputs_dumped": {"dir": args.dump_outputs, "files": dumped}} if dumped is not None else {}),
+    }
+    if not args.full:
+        # a plain run: the headline figure only (everything below is behind --full)
+        print(json.dumps(head), flush=True)
         plan.close()
         if dist is not None:
             dist.barrier()
@@ -1075,7 +1154,7 @@ def main():
         cpu_res = read_cpu_leg(cpu_proc)
     # the drop-in legs (host buffers, host copy threads) once the CPU leg has left the host
     # cores: the reference's caller has them to itself
-    if not args.no_extras:
+    if extras_on:
         extras["c2_pcie_inclusive"] = run_c2_pcie(prob, cfg, B, MO, rank)
         extras["dropin_b1_latency"] = run_dropin(local)
     if cpu_proc is not None:
@@ -1116,24 +1195,7 @@ def main():
             parity["c2_all_instances_vs_oracle"] = c2_full_parity(res, cpu_res["c2_oracle_npz"])
 
     out = {
-        "metric": "PGD outer-iters/sec (N=2000 samples, closed, competition_map1, 1024 alpha-seeds/GPU, min-curv)",
-        "value": round(value, 1),
-        "unit": "PGD outer-iters/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 3),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "competition_map1 cones from the reference repo -> reference steps 1-6 (fixture); synthetic alpha-seeds",
-        "config": {"workload": "C2: competition_map1 closed, N=2000, B=1024 alpha-seeds per GPU, min-curvature, "
-                               "14 outer iterations, default cfg::Config", "N": N, "batch_per_gpu": B,
-                   "global_batch": world * B, "parallelism": backend_label(world, backend, same_device),
-                   "backend": backend if world > 1 else None},
-        "tracks_per_s": round(tracks_per_s, 2),
-        "hip_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"),
+        **head,
         "roofline": roofline,
         "cpu_baseline": cpu,
         "parity": parity if summary_check is None else {**parity, "gather": summary_check},

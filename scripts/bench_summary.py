@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""One-screen summary of a bench.py JSON line (usage: bench_summary.py <bench.json> ...)."""
+"""One-screen summary of a `bench.py --full` JSON line (usage: bench_summary.py <bench.json> ...)."""
 import json, sys
 for path in sys.argv[1:]:
     d = json.load(open(path))
