@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define RL_ABI_VERSION 5
+#define RL_ABI_VERSION 6
 
 /* error codes */
 #define RL_OK          0
@@ -237,7 +237,8 @@ int rl_plan_device_outputs(rl_plan* plan, int32_t which, rl_out* dev_out);
  * framework (e.g. torch tensors for an RCCL gather) receive results without copies. */
 int rl_plan_bind_device_outputs(rl_plan* plan, int32_t which, const rl_out* dev_out);
 /* device time of the last run, in ms, measured with HIP events on the run stream:
- * idx 0 = the whole run, 1 = the min-curvature kernel, 2 = the min-time kernel. */
+ * idx 0 = the whole run, 1 = the min-curvature kernel, 2 = the min-time kernel, 3 = the
+ * selection stage of the last rl_plan_select (score, rank and gather kernels). */
 int rl_plan_kernel_ms(rl_plan* plan, int32_t idx, float* ms);
 /* The batch size the plan's kernel shape is chosen for (rl_kernel_shape's B); 0 = the plan's
  * own B (the default).  Shapes differ in the tree order of the J / decrease / lap sums, so
@@ -250,6 +251,49 @@ int rl_plan_set_shape_batch(rl_plan* plan, int32_t shape_B);
 /* The kernel shape rl_plan_run launches for `mode` (K = 0: the streaming kernel). */
 int rl_plan_shape(rl_plan* plan, int32_t mode, int32_t* K, int32_t* T);
 int rl_plan_destroy(rl_plan* plan);
+
+/* ------------------------------------------------- selection: the best k of a batch
+ * The stage after the optimiser (not in the reference: a multi-start caller's last step).
+ * The B instances of a plan form G = B / group_size contiguous groups; every instance gets
+ * a score, the k best of each group are ranked on the device, and only their rows are
+ * copied into compact buffers and downloaded (G*k rows instead of B).
+ *   score, RL_MODE_MINTIME:  the lap time lap[b] the optimiser wrote.
+ *   score, RL_MODE_MINCURV:  h * sum_i kappa[b][i]^2 with h = L/N (L[b]/N for plans with
+ *                            per-instance lengths), summed in an order fixed by N alone, so
+ *                            its bits do not depend on B, the grouping, k or the kernel shape.
+ *   order: ascending in (isnan(score), score, instance index): scores compare as IEEE
+ *          values (-inf first, +inf before any NaN, -0.0 and +0.0 tie), NaNs rank last,
+ *          equal scores (and NaNs among themselves) rank by the lower index.
+ * Lap-scoring of min-curvature racelines (the reference's debug-dump "min-curv lap") is not
+ * part of this stage: rl_lap_eval evaluates given paths.  rl_optimize_multi and the device
+ * list are not extended: the selection runs on one device. */
+#define RL_SELECT_MAX_K 64
+typedef struct rl_select {
+    int32_t mode;        /* RL_MODE_MINCURV or RL_MODE_MINTIME (exactly one): whose results are ranked */
+    int32_t k;           /* winners per group, 1..min(group_size, RL_SELECT_MAX_K)                      */
+    int32_t group_size;  /* instances per group; 0 = B (one group); B % group_size == 0                 */
+    int32_t _pad;
+} rl_select;
+
+/* Enqueue score -> rank -> gather after the plan's last run, on the stream that run used
+ * (hip_stream NULL; another stream is first made to wait for the run).  Reads the result
+ * arrays in force (after rl_plan_bind_device_outputs: the caller's).  The selection buffers
+ * are plan-owned, allocated at the first call and when G*k grows.  RL_EINVAL before any
+ * device work for: a NULL argument, a mode that is not exactly one of the plan's, k < 1,
+ * k > group_size, k > RL_SELECT_MAX_K, B % group_size != 0, N == 0, a plan never run. */
+int rl_plan_select(rl_plan* plan, const rl_select* sel, void* hip_stream);
+/* Download the last selection (synchronises its stream): index, score [G][k] (index holds
+ * global instance indices, best first; score = the winners' scores); all_scores [B] or NULL;
+ * out: rl_out whose arrays hold G*k rows, row g*k + r = instance index[g][r] (NULL, or NULL
+ * fields, are skipped).  RL_EINVAL before a select, or after a run that followed it. */
+int rl_plan_fetch_selected(rl_plan* plan, int32_t* index, double* score, double* all_scores, rl_out* out);
+/* rl_optimize for `sel->mode` only, without the full download: upload, kernel, select,
+ * download of the G*k rows.  Plans come from rl_optimize's cache; rl_last_call_times reports
+ * the call (rl_last_call_download: 0 groups). */
+int rl_optimize_best(const rl_problem* prob, const rl_cfg* cfg, int32_t n_cfg, const uint64_t* seeds, int32_t B,
+                     const rl_select* sel, int32_t* index, double* score, double* all_scores, rl_out* out);
+/* Rank caller-supplied scores [B] (host in, host out) with the same kernel: index [G][k]. */
+int rl_rank_scores(const double* score, int32_t B, int32_t group_size, int32_t k, int32_t device, int32_t* index);
 
 /* B lap evaluations of given paths: heading/curvature
  * (heading_curv_from_points_generic, ref:595-620) and velocity_profile_forward_backward

@@ -110,6 +110,15 @@ class RlOut(C.Structure):
     ]
 
 
+RL_SELECT_MAX_K = 64
+
+
+class RlSelect(C.Structure):
+    """``rl_select`` — which mode's results are ranked, winners per group, group size (0 = B)."""
+
+    _fields_ = [("mode", C.c_int32), ("k", C.c_int32), ("group_size", C.c_int32), ("_pad", C.c_int32)]
+
+
 OUT_F64 = ("x", "y", "heading", "kappa", "alpha_total", "alpha_last")
 OUT_F64_MT = OUT_F64 + ("v", "ax")
 
@@ -488,6 +497,19 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     if hasattr(lib, "rl_last_call_download"):   # absent only in older experiment builds (A/B bases)
         lib.rl_last_call_download.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         lib.rl_last_call_download.restype = C.c_int
+    if path == LIB_PATH or hasattr(lib, "rl_plan_select"):   # (A/B builds of older sources lack them)
+        lib.rl_plan_select.argtypes = [C.c_void_p, C.POINTER(RlSelect), C.c_void_p]
+        lib.rl_plan_select.restype = C.c_int
+        lib.rl_plan_fetch_selected.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                                               C.POINTER(C.c_double), C.POINTER(RlOut)]
+        lib.rl_plan_fetch_selected.restype = C.c_int
+        lib.rl_optimize_best.argtypes = [C.POINTER(RlProblem), C.POINTER(RlCfg), C.c_int32, C.POINTER(C.c_uint64),
+                                         C.c_int32, C.POINTER(RlSelect), C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                                         C.POINTER(C.c_double), C.POINTER(RlOut)]
+        lib.rl_optimize_best.restype = C.c_int
+        lib.rl_rank_scores.argtypes = [C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                       C.POINTER(C.c_int32)]
+        lib.rl_rank_scores.restype = C.c_int
     if path == LIB_PATH:
         _LIB = lib
     return lib

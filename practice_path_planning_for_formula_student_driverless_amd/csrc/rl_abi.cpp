@@ -23,6 +23,7 @@
 #include "rl_abi.h"
 #include "rl_device.h"
 #include "rl_kernels.h"
+#include "rl_select.h"
 
 namespace {
 
@@ -234,6 +235,18 @@ struct rl_plan {
     bool margin_uniform = false;
     hipEvent_t ev_c = nullptr;
     std::vector<void*> allocs;
+    // selection stage (rl_plan_select): the scores of the last select, its winners and their
+    // rows in compact buffers sized for sel_cap rows; allocated at the first select and again
+    // when G*k outgrows sel_cap.  sel_mode = 0: nothing selected since the last run.
+    double* d_score = nullptr;        // [B] min-curvature scores (min-time ranks mb[1].lap)
+    int32_t* d_index = nullptr;       // [sel_cap]
+    double* d_score_sel = nullptr;    // [sel_cap]
+    ModeBufs selb;                    // compact rows (nx, ny, sb unused)
+    std::vector<void*> sel_allocs;
+    size_t sel_bytes = 0;
+    int sel_cap = 0, sel_mode = 0, sel_G = 0, sel_k = 0;
+    const double* sel_scores = nullptr;   // the [B] scores the last select ranked
+    hipEvent_t ev_sel[2] = {nullptr, nullptr};
 
     template <class T>
     int alloc(T** p, size_t n) {
@@ -248,8 +261,17 @@ struct rl_plan {
 };
 
 namespace {
+// rl_optimize_best's part of a cached call: select after the run and download only the winners
+struct BestArgs {
+    const rl_select* sel;
+    int32_t* index;
+    double* score;
+    double* all_scores;
+    rl_out* out;
+};
 int run_cached(const rl_problem* prob, const rl_cfg* cfg, int32_t n_cfg, const uint64_t* seeds, int32_t B,
-               int32_t modes, const double* centers, const double* Ls, rl_out* out_mc, rl_out* out_mt, float* kms);
+               int32_t modes, const double* centers, const double* Ls, rl_out* out_mc, rl_out* out_mt, float* kms,
+               const BestArgs* best = nullptr);
 }  // namespace
 
 extern "C" {
@@ -378,6 +400,9 @@ int rl_plan_destroy(rl_plan* plan) {
     if (plan->aux_stream) hipStreamSynchronize(plan->aux_stream);
     if (plan->own_stream) hipStreamSynchronize(plan->own_stream);
     for (void* p : plan->allocs) hipFree(p);
+    for (void* p : plan->sel_allocs) hipFree(p);
+    for (auto& e : plan->ev_sel)
+        if (e) hipEventDestroy(e);
     for (auto& e : plan->ev)
         if (e) hipEventDestroy(e);
     for (auto& e : plan->ev_end)
@@ -660,6 +685,7 @@ int rl_plan_run(rl_plan* p, void* hip_stream) {
     if (both) HIPCHK(hipStreamWaitEvent(st, p->ev_end[1], 0));
     HIPCHK(hipEventRecord(p->ev[3], st));
     p->ran = true;
+    p->sel_mode = 0;                                   // an earlier selection is of an earlier run
     return RL_OK;
 }
 
@@ -780,6 +806,7 @@ int rl_plan_run_group(rl_plan* const* plans, int32_t n, void* hip_stream) {
     for (int i = 0; i < n; ++i) {
         HIPCHK(hipEventRecord(plans[i]->ev[3], st));
         plans[i]->ran = true;
+        plans[i]->sel_mode = 0;
     }
     return RL_OK;
 }
@@ -1033,10 +1060,15 @@ int rl_plan_kernel_ms(rl_plan* p, int32_t idx, float* ms) {
     if (!p || !ms || !p->ran) return fail(RL_EINVAL, "plan not run");
     HIPCHK(hipSetDevice(p->device));
     HIPCHK(hipEventSynchronize(p->ev[3]));
-    // idx 0: whole run; 1: min-curv kernel; 2: min-time kernel
+    // idx 0: whole run; 1: min-curv kernel; 2: min-time kernel; 3: the selection stage
     hipEvent_t a, b;
     const bool mc = p->modes & RL_MODE_MINCURV, mt = p->modes & RL_MODE_MINTIME;
     if (idx == 0) { a = p->ev[0]; b = p->ev[3]; }
+    else if (idx == 3 && p->sel_mode) {
+        a = p->ev_sel[0];
+        b = p->ev_sel[1];
+        HIPCHK(hipEventSynchronize(b));
+    }
     else if (idx == 1 && mc) { a = p->ev[1]; b = p->ev_end[0]; }
     else if (idx == 2 && mt) { a = p->ev[2]; b = p->ev_end[1]; }
     else return fail(RL_EINVAL, "kernel index not in this plan");
@@ -1128,6 +1160,196 @@ int rl_plan_device_outputs(rl_plan* p, int32_t which, rl_out* d) {
     d->v = mb.v; d->ax = mb.ax; d->lap = mb.lap;
     d->evals = mb.evals; d->accepts = mb.accepts; d->vpass_sweeps = mb.sweeps;
     return RL_OK;
+}
+
+// ------------------------------------------------------------------- selection
+// The stage after the optimiser (rl_select.hip): score, rank and gather on the device.
+
+// group checks shared by every selection entry point (no device call); *gs = the group size
+static int check_groups(int32_t B, int32_t group_size, int32_t k, int* gs) {
+    if (B < 1) return fail(RL_EINVAL, "select: B must be >= 1");
+    if (group_size < 0) return fail(RL_EINVAL, "select: group_size < 0");
+    const int g = group_size == 0 ? B : group_size;
+    if (g > B || B % g != 0) return fail(RL_EINVAL, "select: B must be a multiple of group_size");
+    if (k < 1) return fail(RL_EINVAL, "select: k must be >= 1");
+    if (k > g) return fail(RL_EINVAL, "select: k exceeds group_size");
+    if (k > RL_SELECT_MAX_K) return fail(RL_EINVAL, "select: k exceeds RL_SELECT_MAX_K (64)");
+    *gs = g;
+    return RL_OK;
+}
+
+static int check_select(const rl_select* sel, int32_t B, int32_t N, int32_t modes, int* gs) {
+    if (!sel) return fail(RL_EINVAL, "select: sel is NULL");
+    if (sel->mode != RL_MODE_MINCURV && sel->mode != RL_MODE_MINTIME)
+        return fail(RL_EINVAL, "select: mode must be exactly one of RL_MODE_MINCURV, RL_MODE_MINTIME");
+    if (!(modes & sel->mode)) return fail(RL_EINVAL, "select: mode is not among the plan's modes");
+    if (int rc = check_groups(B, sel->group_size, sel->k, gs)) return rc;
+    if (N == 0) return fail(RL_EINVAL, "select: N == 0 (nothing to rank)");
+    return RL_OK;
+}
+
+// plan-owned selection buffers for `rows` winners; they count toward dev_bytes
+static int select_alloc(rl_plan* p, int rows) {
+    if (p->d_index && rows <= p->sel_cap) return RL_OK;
+    if (p->last_stream) HIPCHK(hipStreamSynchronize(p->last_stream));   // it may still read the old ones
+    for (void* q : p->sel_allocs) hipFree(q);
+    p->sel_allocs.clear();
+    p->dev_bytes -= p->sel_bytes;
+    p->sel_bytes = 0;
+    p->sel_cap = 0;
+    p->d_score = nullptr;
+    p->d_index = nullptr;
+    p->d_score_sel = nullptr;
+    p->selb = ModeBufs{};
+    bool ok = true;
+    auto get = [&](size_t bytes) -> void* {
+        void* q = nullptr;
+        if (!ok || hipMalloc(&q, std::max<size_t>(bytes, 8)) != hipSuccess) {
+            ok = false;
+            return nullptr;
+        }
+        p->sel_allocs.push_back(q);
+        p->sel_bytes += std::max<size_t>(bytes, 8);
+        return q;
+    };
+    const size_t R = (size_t)rows, RN = R * (size_t)std::max(p->N, 1), mo = (size_t)std::max(p->max_outer, 1);
+    ModeBufs& s = p->selb;
+    p->d_score = (double*)get((size_t)p->B * 8);
+    p->d_index = (int32_t*)get(R * 4);
+    p->d_score_sel = (double*)get(R * 8);
+    double** f64[] = {&s.x, &s.y, &s.heading, &s.kappa, &s.alpha_total, &s.alpha_last, &s.v, &s.ax};
+    for (double** f : f64) *f = (double*)get(RN * 8);
+    s.lap = (double*)get(R * 8);
+    s.evals = (int32_t*)get(R * mo * 4);
+    s.accepts = (int32_t*)get(R * mo * 4);
+    s.sweeps = (int32_t*)get(R * ((size_t)p->max_outer + 1) * 4);
+    p->dev_bytes += p->sel_bytes;
+    if (!ok) return fail(RL_ENOMEM, "hipMalloc (selection buffers) failed");
+    p->sel_cap = rows;
+    return RL_OK;
+}
+
+int rl_plan_select(rl_plan* p, const rl_select* sel, void* hip_stream) {
+    if (!p) return fail(RL_EINVAL, "plan is NULL");
+    int gs = 0;
+    if (int rc = check_select(sel, p->B, p->N, p->modes, &gs)) return rc;
+    if (!p->ran) return fail(RL_EINVAL, "rl_plan_select: the plan has not run");
+    HIPCHK(hipSetDevice(p->device));
+    const int m = sel->mode == RL_MODE_MINTIME ? 1 : 0;
+    const int k = sel->k, G = p->B / gs, rows = G * k;
+    hipStream_t run_st = p->last_stream ? p->last_stream : p->own_stream;
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : run_st;
+    p->sel_mode = 0;
+    if (int rc = select_alloc(p, rows)) return rc;
+    for (auto& e : p->ev_sel)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    if (st != run_st) HIPCHK(hipStreamWaitEvent(st, p->ev[3], 0));
+    p->last_stream = st;
+    HIPCHK(hipEventRecord(p->ev_sel[0], st));
+    const ModeBufs& mb = p->mb[m];
+    hipError_t e = hipSuccess;
+    const double* scores = mb.lap;                     // min-time: the lap the optimiser wrote
+    if (m == 0) {
+        e = rl::launch_score(mb.kappa, p->N, p->B, p->L, p->d_Ls, p->d_score, st);
+        if (e != hipSuccess) return fail(RL_EHIP, std::string("score launch: ") + hipGetErrorString(e));
+        scores = p->d_score;
+    }
+    e = rl::launch_rank(scores, p->B, gs, k, p->d_index, p->d_score_sel, st);
+    if (e != hipSuccess) return fail(RL_EHIP, std::string("rank launch: ") + hipGetErrorString(e));
+    const ModeBufs& sb = p->selb;
+    rl::GatherParams g{};
+    const double* src[rl::RL_SEL_F64] = {mb.x, mb.y, mb.heading, mb.kappa, mb.alpha_total, mb.alpha_last, mb.v, mb.ax};
+    double* dst[rl::RL_SEL_F64] = {sb.x, sb.y, sb.heading, sb.kappa, sb.alpha_total, sb.alpha_last, sb.v, sb.ax};
+    for (int c = 0; c < rl::RL_SEL_F64; ++c) {
+        g.src[c] = src[c];
+        g.dst[c] = dst[c];
+    }
+    g.lap_src = mb.lap; g.lap_dst = sb.lap;
+    g.evals_src = mb.evals; g.evals_dst = sb.evals;
+    g.accepts_src = mb.accepts; g.accepts_dst = sb.accepts;
+    g.sweeps_src = mb.sweeps; g.sweeps_dst = sb.sweeps;
+    g.index = p->d_index;
+    g.N = p->N; g.B = p->B; g.mo = p->max_outer; g.rows = rows;
+    e = rl::launch_gather(g, st);
+    if (e != hipSuccess) return fail(RL_EHIP, std::string("gather launch: ") + hipGetErrorString(e));
+    HIPCHK(hipEventRecord(p->ev_sel[1], st));
+    p->sel_mode = sel->mode;
+    p->sel_G = G;
+    p->sel_k = k;
+    p->sel_scores = scores;
+    return RL_OK;
+}
+
+// the copies that download the last selection of p (out_jobs' order for the rows)
+static void sel_jobs(const rl_plan* p, int32_t* index, double* score, double* all_scores, const rl_out* o,
+                     std::vector<CopyJob>& jobs) {
+    const size_t R = (size_t)p->sel_G * p->sel_k, RN = R * (size_t)p->N, mo = (size_t)p->max_outer;
+    const ModeBufs& sb = p->selb;
+    auto add = [&](void* dst, const void* src, size_t bytes) {
+        if (dst && src && bytes) jobs.push_back({dst, src, bytes});
+    };
+    add(index, p->d_index, R * 4);
+    add(score, p->d_score_sel, R * 8);
+    add(all_scores, p->sel_scores, (size_t)p->B * 8);
+    if (!o) return;
+    add(o->x, sb.x, RN * 8);
+    add(o->y, sb.y, RN * 8);
+    add(o->heading, sb.heading, RN * 8);
+    add(o->kappa, sb.kappa, RN * 8);
+    add(o->alpha_total, sb.alpha_total, RN * 8);
+    add(o->alpha_last, sb.alpha_last, RN * 8);
+    add(o->evals, sb.evals, R * mo * 4);
+    add(o->accepts, sb.accepts, R * mo * 4);
+    if (p->sel_mode == RL_MODE_MINTIME) {
+        add(o->v, sb.v, RN * 8);
+        add(o->ax, sb.ax, RN * 8);
+        add(o->lap, sb.lap, R * 8);
+        add(o->vpass_sweeps, sb.sweeps, R * (mo + 1) * 4);
+    }
+}
+
+int rl_plan_fetch_selected(rl_plan* p, int32_t* index, double* score, double* all_scores, rl_out* out) {
+    if (!p) return fail(RL_EINVAL, "plan is NULL");
+    if (!index || !score) return fail(RL_EINVAL, "rl_plan_fetch_selected: index / score is NULL");
+    if (!p->sel_mode) return fail(RL_EINVAL, "rl_plan_fetch_selected: no selection since the plan's last run");
+    HIPCHK(hipSetDevice(p->device));
+    hipStream_t st = p->last_stream ? p->last_stream : p->own_stream;
+    std::vector<CopyJob> jobs;
+    sel_jobs(p, index, score, all_scores, out, jobs);
+    for (const CopyJob& j : jobs) {
+        hipError_t e = hipMemcpyAsync(j.dst, j.src, j.bytes, hipMemcpyDeviceToHost, st);
+        if (e != hipSuccess) return fail(RL_EHIP, std::string("download: ") + hipGetErrorString(e));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    return RL_OK;
+}
+
+// rank host scores with rl_rank_kernel (rl_select.hip)
+int rl_rank_scores(const double* score, int32_t B, int32_t group_size, int32_t k, int32_t device, int32_t* index) {
+    if (!score || !index) return fail(RL_EINVAL, "rl_rank_scores: score / index is NULL");
+    int gs = 0;
+    if (int rc = check_groups(B, group_size, k, &gs)) return rc;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(RL_ENODEV, "no HIP device");
+    if (device < 0 || device >= ndev) return fail(RL_ENODEV, "device index out of range");
+    HIPCHK(hipSetDevice(device));
+    const size_t R = (size_t)(B / gs) * (size_t)k;
+    double* d_score = nullptr;
+    int32_t* d_index = nullptr;
+    auto done = [&](int code) {
+        if (d_score) hipFree(d_score);
+        if (d_index) hipFree(d_index);
+        return code;
+    };
+    if (hipMalloc((void**)&d_score, (size_t)B * 8) != hipSuccess || hipMalloc((void**)&d_index, R * 4) != hipSuccess)
+        return done(fail(RL_ENOMEM, "rl_rank_scores: hipMalloc failed"));
+    if (hipMemcpy(d_score, score, (size_t)B * 8, hipMemcpyHostToDevice) != hipSuccess)
+        return done(fail(RL_EHIP, "rl_rank_scores: upload"));
+    if (rl::launch_rank(d_score, B, gs, k, d_index, nullptr, nullptr) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+        return done(fail(RL_EHIP, "rl_rank_scores: kernel"));
+    if (hipMemcpy(index, d_index, R * 4, hipMemcpyDeviceToHost) != hipSuccess)
+        return done(fail(RL_EHIP, "rl_rank_scores: download"));
+    return done(RL_OK);
 }
 
 // ------------------------------------------------------------------ plan cache
@@ -1575,8 +1797,12 @@ int download_overlapped(CacheEntry* e, rl_plan* p, const std::vector<CopyJob> (&
 
 // rl_optimize / rl_lap_eval through the plan cache (see above).  kms[0..2]: HIP-event
 // times of the whole run, the min-curvature and the min-time kernel (-1 if not run).
+// best (rl_optimize_best, arguments already checked): no full download (out_mc / out_mt are
+// NULL, so no download jobs, no completion flags, no overlapped path); the selection stage
+// follows the run on the same stream and its G*k rows come back in one staged pass.
 int run_cached(const rl_problem* prob, const rl_cfg* cfg, int32_t n_cfg, const uint64_t* seeds, int32_t B,
-               int32_t modes, const double* centers, const double* Ls, rl_out* out_mc, rl_out* out_mt, float* kms) {
+               int32_t modes, const double* centers, const double* Ls, rl_out* out_mc, rl_out* out_mt, float* kms,
+               const BestArgs* best) {
     const auto t0 = std::chrono::steady_clock::now();
 #ifdef RL_OVL_TRACE
     g_tr = OvlTrace{};
@@ -1657,12 +1883,19 @@ int run_cached(const rl_problem* prob, const rl_cfg* cfg, int32_t n_cfg, const u
     jobs.insert(jobs.end(), jm[1].begin(), jm[1].end());
     // the staging area serves the uploads first, then (after the kernel has started, or
     // stream-ordered after it) the downloads; a reallocation waits for the uploads queued
-    const size_t down_bytes = staged_bytes(jobs);
+    size_t down_bytes = staged_bytes(jobs);
+    if (best) {
+        // the selection's jobs exist only after rl_plan_select: an upper bound of their staging
+        // (16 jobs at most, each rounded up to 256 B), so the buffer is in place before the run
+        const size_t gs = best->sel->group_size ? (size_t)best->sel->group_size : (size_t)B;
+        const size_t R = (size_t)B / gs * (size_t)best->sel->k, mo = (size_t)p->max_outer;
+        down_bytes = 16 * 256 + R * (8 * (size_t)p->N * 8 + 8 + (3 * mo + 1) * 4 + 12) + (size_t)B * 8;
+    }
     if (down_bytes > e->pin_bytes) {
         if (hipStreamSynchronize(p->own_stream) != hipSuccess) return drop(fail(RL_EHIP, "upload sync"));
         if ((rc = ensure_pinned(e, down_bytes))) return drop(rc);
     }
-    const bool overlap = overlap_enabled() && p->N > 0 && B >= 2 && down_bytes >= kOverlapMinBytes;
+    const bool overlap = !best && overlap_enabled() && p->N > 0 && B >= 2 && down_bytes >= kOverlapMinBytes;
     uint32_t epoch = 0;
     if (overlap) {
         if ((rc = ensure_flags(e, B))) return drop(rc);
@@ -1687,7 +1920,13 @@ int run_cached(const rl_problem* prob, const rl_cfg* cfg, int32_t n_cfg, const u
 #endif
     p->done[0] = p->done[1] = nullptr;                 // later runs of this plan signal nothing
     if (rc) return drop(rc);
-    if (overlap) rc = download_overlapped(e, p, jm, epoch);
+    if (best) {
+        if ((rc = rl_plan_select(p, best->sel, nullptr))) return drop(rc);
+        jobs.clear();
+        sel_jobs(p, best->index, best->score, best->all_scores, best->out, jobs);
+        if (staged_bytes(jobs) > e->pin_bytes) return drop(fail(RL_EHIP, "selection staging larger than its bound"));
+        rc = download_staged(e, p->own_stream, jobs, 0);
+    } else if (overlap) rc = download_overlapped(e, p, jm, epoch);
     else rc = download_staged(e, p->own_stream, jobs, 0);
     if (rc) return drop(rc);
     if (hipStreamSynchronize(p->own_stream) != hipSuccess) return drop(fail(RL_EHIP, "stream sync"));
@@ -1721,6 +1960,18 @@ int rl_optimize(const rl_problem* prob, const rl_cfg* cfg, int32_t n_cfg, const 
     int modes = (out_mincurv ? RL_MODE_MINCURV : 0) | (out_mintime ? RL_MODE_MINTIME : 0);
     if (!modes) return fail(RL_EINVAL, "no output requested");
     return run_cached(prob, cfg, n_cfg, seeds, B, modes, nullptr, nullptr, out_mincurv, out_mintime, nullptr);
+}
+
+int rl_optimize_best(const rl_problem* prob, const rl_cfg* cfg, int32_t n_cfg, const uint64_t* seeds, int32_t B,
+                     const rl_select* sel, int32_t* index, double* score, double* all_scores, rl_out* out) {
+    if (!sel || !index || !score) return fail(RL_EINVAL, "rl_optimize_best: sel / index / score is NULL");
+    if (sel->mode != RL_MODE_MINCURV && sel->mode != RL_MODE_MINTIME)
+        return fail(RL_EINVAL, "select: mode must be exactly one of RL_MODE_MINCURV, RL_MODE_MINTIME");
+    if (int rc = check_inputs(prob, cfg, n_cfg, B, sel->mode, nullptr)) return rc;
+    int gs = 0;
+    if (int rc = check_select(sel, B, prob->N, sel->mode, &gs)) return rc;
+    const BestArgs best{sel, index, score, all_scores, out};
+    return run_cached(prob, cfg, n_cfg, seeds, B, sel->mode, nullptr, nullptr, nullptr, nullptr, nullptr, &best);
 }
 
 int rl_last_call_ms(float* kernel_ms, float* call_ms) {

@@ -16,6 +16,8 @@ Reference (``ref`` = /root/reference/src/main.cpp):
 
 Beyond the reference: :func:`optimize_batch` and :class:`Plan` run B
 instances (α-seeds, cfg sweeps) in one launch; that is the product.
+:func:`optimize_best` / :meth:`Plan.select` rank the batch on the GPU and
+return only the k best instances of each group.
 
 Every compute call goes through ``librl.so`` (HIP, gfx950).  With no GPU the
 calls raise :class:`RacelineError` (RL_ENODEV): there is no CPU fallback.
@@ -152,6 +154,83 @@ def optimize_batch(prob: Problem, cfgs, seeds=None, B: Optional[int] = None,
     return out_mc, out_mt
 
 
+# ------------------------------------------------------ best k of a batch
+@dataclass
+class Selected:
+    """The k best instances of each of G groups (rl_plan_select / rl_optimize_best):
+    index [G, k] global instance indices, best first; score [G, k] their scores; scores [B]
+    every instance's score (min-time: the lap; min-curvature: h * sum kappa^2); out: Outputs
+    with G*k rows, row g*k + r = instance index[g, r]."""
+
+    index: np.ndarray
+    score: np.ndarray
+    scores: np.ndarray
+    out: Outputs
+
+
+_MODES = {"mincurv": abi.RL_MODE_MINCURV, "mintime": abi.RL_MODE_MINTIME,
+          abi.RL_MODE_MINCURV: abi.RL_MODE_MINCURV, abi.RL_MODE_MINTIME: abi.RL_MODE_MINTIME}
+
+
+def _check_select(B: int, mode, k: int, group_size) -> tuple:
+    """(mode bit, group size) of a selection over B instances; the C side writes G*k entries
+    into arrays sized from these numbers, so a mismatch is an error here."""
+    if mode not in _MODES:
+        raise ValueError(f"mode must be 'mincurv' or 'mintime', got {mode!r}")
+    if B < 1:
+        raise ValueError(f"B must be >= 1, got {B}")
+    gs = B if group_size in (None, 0) else int(group_size)
+    if gs < 1 or gs > B or B % gs != 0:
+        raise ValueError(f"group_size: B={B} is not a multiple of {gs}")
+    if not 1 <= k <= min(gs, abi.RL_SELECT_MAX_K):
+        raise ValueError(f"k: need 1 <= k <= min(group_size={gs}, {abi.RL_SELECT_MAX_K}), got {k}")
+    return _MODES[mode], gs
+
+
+def _selected_alloc(B: int, N: int, mo: int, mode: int, k: int, gs: int) -> Selected:
+    G = B // gs
+    return Selected(index=np.zeros((G, k), dtype=np.int32), score=np.zeros((G, k)), scores=np.zeros(B),
+                    out=Outputs.alloc(G * k, N, mo, mode == abi.RL_MODE_MINTIME))
+
+
+def optimize_best(prob: Problem, cfgs, seeds=None, B: Optional[int] = None, mode="mintime", k: int = 1,
+                  group_size: Optional[int] = None) -> Selected:
+    """Optimise B instances in `mode` and return only the k best of each group of
+    group_size (None: one group) instances, ranked and compacted on the GPU
+    (rl_optimize_best): G*k rows are downloaded instead of B."""
+    cfg_arr, ncfg = abi.cfg_array(cfgs)
+    if B is None:
+        B = ncfg if ncfg > 1 else (len(seeds) if seeds is not None else 1)
+    _check_batch(B, ncfg, seeds)
+    m, gs = _check_select(B, mode, k, group_size)
+    if prob.N == 0:
+        raise ValueError("optimize_best: N == 0 (nothing to rank)")
+    sel = _selected_alloc(B, prob.N, int(cfg_arr[0].max_outer_iters), m, k, gs)
+    seeds_a = abi.seed_array(seeds)
+    p = prob.as_c()
+    o = sel.out.as_c()
+    s = abi.RlSelect(m, k, gs, 0)
+    _check(_lib().rl_optimize_best(C.byref(p), cfg_arr, ncfg, abi.u64ptr(seeds_a), B, C.byref(s),
+                                   abi.iptr(sel.index), abi.dptr(sel.score), abi.dptr(sel.scores), C.byref(o)))
+    return sel
+
+
+def rank_scores(scores, k: int, group_size: Optional[int] = None, device: int = 0) -> np.ndarray:
+    """index [G, k] of the k best of each group of caller-supplied scores, in the order of
+    rl_plan_select: ascending in (isnan, score, index) (rl_rank_scores, the same kernel)."""
+    sc = np.ascontiguousarray(scores, dtype=np.float64).ravel()
+    B = int(sc.size)
+    if group_size in (None, 0):
+        group_size = B
+    if B < 1 or group_size < 1 or B % group_size != 0:
+        raise ValueError(f"group_size: B={B} is not a multiple of {group_size}")
+    if not 1 <= k <= min(group_size, abi.RL_SELECT_MAX_K):
+        raise ValueError(f"k: need 1 <= k <= min(group_size={group_size}, {abi.RL_SELECT_MAX_K}), got {k}")
+    index = np.zeros((B // group_size, k), dtype=np.int32)
+    _check(_lib().rl_rank_scores(abi.dptr(sc), B, int(group_size), int(k), int(device), abi.iptr(index)))
+    return index
+
+
 class Plan:
     """Device-resident batch (rl_plan_*): inputs uploaded once, run() enqueues
     the optimisation on a HIP stream, fetch() copies results to the host."""
@@ -207,6 +286,26 @@ class Plan:
         c_mt = out_mt.as_c() if out_mt else None
         _check(_lib().rl_plan_fetch(self._h, C.byref(c_mc) if c_mc else None, C.byref(c_mt) if c_mt else None))
         return out_mc, out_mt
+
+    def select(self, mode="mintime", k: int = 1, group_size: Optional[int] = None, stream_ptr: int = 0) -> None:
+        """Enqueue score -> rank -> gather after the last run() (rl_plan_select): the k best
+        instances of each group of group_size (None: all B) in `mode`."""
+        m, gs = _check_select(self.B, mode, k, group_size)
+        s = abi.RlSelect(m, k, gs, 0)
+        self._sel = None
+        _check(_lib().rl_plan_select(self._h, C.byref(s), C.c_void_p(stream_ptr) if stream_ptr else None))
+        self._sel = (m, k, gs)
+
+    def fetch_selected(self) -> Selected:
+        """Download the last select(): indices, scores and the winners' rows (rl_plan_fetch_selected)."""
+        if getattr(self, "_sel", None) is None:
+            raise ValueError("fetch_selected: no select() on this plan")
+        m, k, gs = self._sel
+        sel = _selected_alloc(self.B, self.N, self.max_outer, m, k, gs)
+        o = sel.out.as_c()
+        _check(_lib().rl_plan_fetch_selected(self._h, abi.iptr(sel.index), abi.dptr(sel.score),
+                                             abi.dptr(sel.scores), C.byref(o)))
+        return sel
 
     def device_outputs(self, which: int) -> abi.RlOut:
         d = abi.RlOut()
@@ -653,6 +752,7 @@ def seeds_range(B: int, first: int = 0) -> np.ndarray:
 
 __all__ = ["RacelineError", "MinCurvResult", "MinTimeResult", "Plan", "Problem", "RlCfg", "Outputs",
            "default_cfg", "set_mu", "ring_edges", "polyline_edges", "edges_for", "optimize_batch",
+           "optimize_best", "rank_scores", "Selected",
            "compute_min_curvature_raceline", "compute_min_time_raceline", "compute_raceline_and_save",
            "compute_mintime_and_save", "write_raceline_csvs", "write_mintime_csvs", "load_csv_xy",
            "seeds_range"]
