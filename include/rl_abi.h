@@ -35,6 +35,10 @@ extern "C" {
 #endif
 
 #define RL_ABI_VERSION 6
+/* additions that leave every version-6 caller as it is (rl_abi_minor() reports the library's):
+ *   1  the lap stage: rl_plan_lap, rl_plan_fetch_lap, rl_plan_select_scored,
+ *      rl_optimize_best_scored, rl_path_lengths, rl_plan_kernel_ms indices 4-6 */
+#define RL_ABI_MINOR 1
 
 /* error codes */
 #define RL_OK          0
@@ -238,7 +242,8 @@ int rl_plan_device_outputs(rl_plan* plan, int32_t which, rl_out* dev_out);
 int rl_plan_bind_device_outputs(rl_plan* plan, int32_t which, const rl_out* dev_out);
 /* device time of the last run, in ms, measured with HIP events on the run stream:
  * idx 0 = the whole run, 1 = the min-curvature kernel, 2 = the min-time kernel, 3 = the
- * selection stage of the last rl_plan_select (score, rank and gather kernels). */
+ * selection stage of the last rl_plan_select (score, rank and gather kernels), 4 = the lap
+ * stage of the last rl_plan_lap (5 = its preparation kernel, 6 = its evaluation kernel). */
 int rl_plan_kernel_ms(rl_plan* plan, int32_t idx, float* ms);
 /* The batch size the plan's kernel shape is chosen for (rl_kernel_shape's B); 0 = the plan's
  * own B (the default).  Shapes differ in the tree order of the J / decrease / lap sums, so
@@ -264,8 +269,8 @@ int rl_plan_destroy(rl_plan* plan);
  *   order: ascending in (isnan(score), score, instance index): scores compare as IEEE
  *          values (-inf first, +inf before any NaN, -0.0 and +0.0 tie), NaNs rank last,
  *          equal scores (and NaNs among themselves) rank by the lower index.
- * Lap-scoring of min-curvature racelines (the reference's debug-dump "min-curv lap") is not
- * part of this stage: rl_lap_eval evaluates given paths.  rl_optimize_multi and the device
+ * Min-curvature racelines can also be ranked by their lap time (the reference's debug-dump
+ * "min-curv lap"): the lap stage below and RL_SCORE_LAP.  rl_optimize_multi and the device
  * list are not extended: the selection runs on one device. */
 #define RL_SELECT_MAX_K 64
 typedef struct rl_select {
@@ -294,6 +299,45 @@ int rl_optimize_best(const rl_problem* prob, const rl_cfg* cfg, int32_t n_cfg, c
                      const rl_select* sel, int32_t* index, double* score, double* all_scores, rl_out* out);
 /* Rank caller-supplied scores [B] (host in, host out) with the same kernel: index [G][k]. */
 int rl_rank_scores(const double* score, int32_t B, int32_t group_size, int32_t k, int32_t device, int32_t* index);
+
+/* ------------------------------------------------- lap stage: min-curvature racelines by lap time
+ * The debug dump's "min-curv lap" (ref:1443-1450, 1472-1479) for every instance of a plan, on
+ * the device: the min-curvature raceline's own path length
+ *   L_mc[b] = (((0.0 + d_0) + d_1) + ...),  d_i = hypot(x[i+1]-x[i], y[i+1]-y[i]),
+ * in index order with the closing segment last (closed tracks; N <= 1: 0.0), bit for bit
+ * the reference's path_length; then heading, curvature and velocity_profile_forward_backward
+ * with h = L_mc[b]/N, by the min-time kernel at max_outer_iters = 0, exactly as rl_lap_eval
+ * runs it on the same B paths and lengths (the same kernel shape, so the same bits). */
+#define RL_SCORE_DEFAULT 0   /* lap for min-time, h*sum kappa^2 for min-curvature (rl_plan_select) */
+#define RL_SCORE_LAP     1   /* the lap stage's lap; differs from DEFAULT only for RL_MODE_MINCURV */
+
+/* Enqueue the lap stage after the plan's last run (stream rules of rl_plan_select).  Reads the
+ * min-curvature x, y arrays in force (after rl_plan_bind_device_outputs: the caller's); its
+ * buffers are plan-owned, allocated at the first call.  A later run invalidates the stage.
+ * RL_EINVAL before any device work for: a NULL plan, a plan without RL_MODE_MINCURV, a plan
+ * never run, N == 0. */
+int rl_plan_lap(rl_plan* plan, void* hip_stream);
+/* Download the lap stage (synchronises its stream): out receives heading, kappa (both with
+ * h = L_mc/N), v, ax [B][N], lap [B] and vpass_sweeps [B][1]; its other fields are skipped.
+ * path_len [B] (or NULL) receives L_mc.  RL_EINVAL before a lap stage, or after a run that
+ * followed it. */
+int rl_plan_fetch_lap(rl_plan* plan, rl_out* out, double* path_len);
+/* rl_plan_select with a choice of score.  RL_SCORE_DEFAULT, or any score with
+ * RL_MODE_MINTIME: exactly rl_plan_select.  RL_SCORE_LAP with RL_MODE_MINCURV: runs the lap
+ * stage unless one is valid since the last run, ranks its lap, and gathers the winners: x, y,
+ * heading, kappa, alpha_total, alpha_last, evals, accepts are the optimiser's rows (as the
+ * full download), v, ax, lap and vpass_sweeps [G*k][1] the lap stage's; rl_plan_fetch_selected
+ * then fills those four too.  An unknown score is RL_EINVAL. */
+int rl_plan_select_scored(rl_plan* plan, const rl_select* sel, int32_t score, void* hip_stream);
+/* rl_optimize_best with that score (rl_optimize_best is RL_SCORE_DEFAULT). */
+int rl_optimize_best_scored(const rl_problem* prob, const rl_cfg* cfg, int32_t n_cfg, const uint64_t* seeds, int32_t B,
+                            const rl_select* sel, int32_t score, int32_t* index, double* score_out,
+                            double* all_scores, rl_out* out);
+/* The path lengths L[b] of B paths given as rows x[B][N], y[B][N] (host in, host out), summed
+ * as above by the lap stage's preparation kernel.  RL_EINVAL for a NULL argument, B < 1 or
+ * N < 0; RL_ETOOBIG for N > 1048576. */
+int rl_path_lengths(const double* x, const double* y, int32_t N, int32_t B, int32_t closed,
+                    int32_t device, double* L_out);
 
 /* B lap evaluations of given paths: heading/curvature
  * (heading_curv_from_points_generic, ref:595-620) and velocity_profile_forward_backward
@@ -368,6 +412,7 @@ int rl_corridor(const rl_problem* prob, const rl_cfg* cfg, int32_t device, doubl
 int         rl_device_count(void);
 const char* rl_last_error(void);
 int         rl_abi_version(void);
+int         rl_abi_minor(void);
 /* samples per lane of the THROUGHPUT shape for N (4: N <= 256, 5: N <= 320, 8: N <= 4096;
  * 1 = the streaming kernel), or RL_ETOOBIG.  Batches small enough for a latency shape launch fewer samples per lane:
  * rl_kernel_shape(N, B, mode) reports the shape a launch actually uses. */

@@ -111,6 +111,9 @@ class RlOut(C.Structure):
 
 
 RL_SELECT_MAX_K = 64
+RL_ABI_MINOR = 1
+RL_SCORE_DEFAULT = 0      # lap for min-time, h * sum kappa^2 for min-curvature
+RL_SCORE_LAP = 1          # the lap stage's lap (differs from the default for min-curvature only)
 
 
 class RlSelect(C.Structure):
@@ -510,6 +513,22 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         lib.rl_rank_scores.argtypes = [C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                        C.POINTER(C.c_int32)]
         lib.rl_rank_scores.restype = C.c_int
+    if path == LIB_PATH or hasattr(lib, "rl_plan_lap"):   # (A/B builds of older sources lack them)
+        lib.rl_abi_minor.restype = C.c_int
+        lib.rl_plan_lap.argtypes = [C.c_void_p, C.c_void_p]
+        lib.rl_plan_lap.restype = C.c_int
+        lib.rl_plan_fetch_lap.argtypes = [C.c_void_p, C.POINTER(RlOut), C.POINTER(C.c_double)]
+        lib.rl_plan_fetch_lap.restype = C.c_int
+        lib.rl_plan_select_scored.argtypes = [C.c_void_p, C.POINTER(RlSelect), C.c_int32, C.c_void_p]
+        lib.rl_plan_select_scored.restype = C.c_int
+        lib.rl_optimize_best_scored.argtypes = [C.POINTER(RlProblem), C.POINTER(RlCfg), C.c_int32,
+                                                C.POINTER(C.c_uint64), C.c_int32, C.POINTER(RlSelect), C.c_int32,
+                                                C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                C.POINTER(RlOut)]
+        lib.rl_optimize_best_scored.restype = C.c_int
+        lib.rl_path_lengths.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_int32,
+                                        C.c_int32, C.POINTER(C.c_double)]
+        lib.rl_path_lengths.restype = C.c_int
     if path == LIB_PATH:
         _LIB = lib
     return lib

@@ -24,6 +24,7 @@
 #include "rl_device.h"
 #include "rl_kernels.h"
 #include "rl_select.h"
+#include "rl_lap_stage.h"
 
 namespace {
 
@@ -247,6 +248,20 @@ struct rl_plan {
     int sel_cap = 0, sel_mode = 0, sel_G = 0, sel_k = 0;
     const double* sel_scores = nullptr;   // the [B] scores the last select ranked
     hipEvent_t ev_sel[2] = {nullptr, nullptr};
+    bool sel_lap = false;             // the last select ranked the lap stage's lap (RL_SCORE_LAP)
+    // lap stage (rl_plan_lap): the min-curvature rows packed as per-instance centres, their
+    // own lengths, the plan's cfgs with max_outer_iters = 0, and the result and scratch arrays
+    // of the min-time kernel that evaluates them; allocated at the first rl_plan_lap.
+    // lap_valid: a stage has been queued since the last run.
+    double* d_lap_center = nullptr;   // [B][N][2]
+    double* d_Lmc = nullptr;          // [B]
+    rl_cfg* d_cfg_lap = nullptr;      // [ncfg]
+    ModeBufs lapb;                    // sweeps [B][1]; evals / accepts unused
+    std::vector<void*> lap_allocs;
+    size_t lap_bytes = 0;
+    bool lap_valid = false;
+    hipStream_t lap_stream = nullptr;
+    hipEvent_t ev_lap[3] = {nullptr, nullptr, nullptr};   // start, after the preparation, end
 
     template <class T>
     int alloc(T** p, size_t n) {
@@ -268,6 +283,7 @@ struct BestArgs {
     double* score;
     double* all_scores;
     rl_out* out;
+    int32_t score_kind;               // RL_SCORE_DEFAULT or RL_SCORE_LAP
 };
 int run_cached(const rl_problem* prob, const rl_cfg* cfg, int32_t n_cfg, const uint64_t* seeds, int32_t B,
                int32_t modes, const double* centers, const double* Ls, rl_out* out_mc, rl_out* out_mt, float* kms,
@@ -278,6 +294,7 @@ extern "C" {
 
 const char* rl_last_error(void) { return g_err.c_str(); }
 int rl_abi_version(void) { return RL_ABI_VERSION; }
+int rl_abi_minor(void) { return RL_ABI_MINOR; }
 
 int rl_device_count(void) {
     int n = 0;
@@ -402,6 +419,9 @@ int rl_plan_destroy(rl_plan* plan) {
     for (void* p : plan->allocs) hipFree(p);
     for (void* p : plan->sel_allocs) hipFree(p);
     for (auto& e : plan->ev_sel)
+        if (e) hipEventDestroy(e);
+    for (void* p : plan->lap_allocs) hipFree(p);
+    for (auto& e : plan->ev_lap)
         if (e) hipEventDestroy(e);
     for (auto& e : plan->ev)
         if (e) hipEventDestroy(e);
@@ -686,6 +706,7 @@ int rl_plan_run(rl_plan* p, void* hip_stream) {
     HIPCHK(hipEventRecord(p->ev[3], st));
     p->ran = true;
     p->sel_mode = 0;                                   // an earlier selection is of an earlier run
+    p->lap_valid = false;                              // and so is an earlier lap stage
     return RL_OK;
 }
 
@@ -807,6 +828,7 @@ int rl_plan_run_group(rl_plan* const* plans, int32_t n, void* hip_stream) {
         HIPCHK(hipEventRecord(plans[i]->ev[3], st));
         plans[i]->ran = true;
         plans[i]->sel_mode = 0;
+        plans[i]->lap_valid = false;
     }
     return RL_OK;
 }
@@ -1069,6 +1091,12 @@ int rl_plan_kernel_ms(rl_plan* p, int32_t idx, float* ms) {
         b = p->ev_sel[1];
         HIPCHK(hipEventSynchronize(b));
     }
+    else if (idx >= 4 && idx <= 6 && p->lap_valid) {
+        // 4: the lap stage; 5: its preparation kernel; 6: its evaluation kernel
+        a = p->ev_lap[idx == 6 ? 1 : 0];
+        b = p->ev_lap[idx == 5 ? 1 : 2];
+        HIPCHK(hipEventSynchronize(p->ev_lap[2]));
+    }
     else if (idx == 1 && mc) { a = p->ev[1]; b = p->ev_end[0]; }
     else if (idx == 2 && mt) { a = p->ev[2]; b = p->ev_end[1]; }
     else return fail(RL_EINVAL, "kernel index not in this plan");
@@ -1229,11 +1257,174 @@ static int select_alloc(rl_plan* p, int rows) {
     return RL_OK;
 }
 
-int rl_plan_select(rl_plan* p, const rl_select* sel, void* hip_stream) {
+// ------------------------------------------------------------------- lap stage
+// The debug dump's "min-curv lap" for every instance of a plan (rl_lap_stage.hip):
+// the preparation kernel packs the min-curvature rows and sums their lengths, then the
+// min-time kernel evaluates them at max_outer_iters = 0, as rl_lap_eval launches it.
+
+// plan-owned lap-stage buffers; they count toward dev_bytes
+static int lap_alloc(rl_plan* p) {
+    if (p->d_lap_center) return RL_OK;
+    bool ok = true;
+    auto get = [&](size_t bytes) -> void* {
+        void* q = nullptr;
+        if (!ok || hipMalloc(&q, std::max<size_t>(bytes, 8)) != hipSuccess) {
+            ok = false;
+            return nullptr;
+        }
+        p->lap_allocs.push_back(q);
+        p->lap_bytes += std::max<size_t>(bytes, 8);
+        return q;
+    };
+    const size_t B = (size_t)p->B, BN = B * (size_t)std::max(p->N, 1);
+    ModeBufs& s = p->lapb;
+    double* center = (double*)get(2 * BN * 8);
+    p->d_Lmc = (double*)get(B * 8);
+    p->d_cfg_lap = (rl_cfg*)get((size_t)p->ncfg * sizeof(rl_cfg));
+    double** f64[] = {&s.x, &s.y, &s.heading, &s.kappa, &s.alpha_total, &s.alpha_last, &s.v, &s.ax, &s.nx, &s.ny};
+    for (double** f : f64) *f = (double*)get(BN * 8);
+    s.lap = (double*)get(B * 8);
+    s.sweeps = (int32_t*)get(B * 4);
+    if (p->stream) s.sb.base = (double*)get(BN * rl::RL_STREAM_ARRAYS * 8);
+    p->dev_bytes += p->lap_bytes;
+    if (!ok) {
+        for (void* q : p->lap_allocs) hipFree(q);
+        p->lap_allocs.clear();
+        p->dev_bytes -= p->lap_bytes;
+        p->lap_bytes = 0;
+        p->lapb = ModeBufs{};
+        p->d_Lmc = nullptr;
+        p->d_cfg_lap = nullptr;
+        return fail(RL_ENOMEM, "hipMalloc (lap-stage buffers) failed");
+    }
+    p->d_lap_center = center;
+    return RL_OK;
+}
+
+int rl_plan_lap(rl_plan* p, void* hip_stream) {
     if (!p) return fail(RL_EINVAL, "plan is NULL");
-    int gs = 0;
-    if (int rc = check_select(sel, p->B, p->N, p->modes, &gs)) return rc;
-    if (!p->ran) return fail(RL_EINVAL, "rl_plan_select: the plan has not run");
+    if (!(p->modes & RL_MODE_MINCURV)) return fail(RL_EINVAL, "rl_plan_lap: the plan has no RL_MODE_MINCURV");
+    if (p->N == 0) return fail(RL_EINVAL, "rl_plan_lap: N == 0 (no path)");
+    if (!p->ran) return fail(RL_EINVAL, "rl_plan_lap: the plan has not run");
+    HIPCHK(hipSetDevice(p->device));
+    hipStream_t run_st = p->last_stream ? p->last_stream : p->own_stream;
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : run_st;
+    p->lap_valid = false;
+    if (int rc = lap_alloc(p)) return rc;
+    for (auto& e : p->ev_lap)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    if (st != run_st) HIPCHK(hipStreamWaitEvent(st, p->ev[3], 0));
+    p->last_stream = st;
+    HIPCHK(hipEventRecord(p->ev_lap[0], st));
+    rl::PrepParams q{};
+    q.x = p->mb[0].x;
+    q.y = p->mb[0].y;
+    q.centre = p->d_lap_center;
+    q.L_out = p->d_Lmc;
+    q.cfg_src = p->d_cfg;
+    q.cfg_dst = p->d_cfg_lap;
+    q.N = p->N; q.B = p->B; q.closed = p->closed; q.ncfg = p->ncfg;
+    hipError_t e = rl::launch_path_prep(q, st);
+    if (e != hipSuccess) return fail(RL_EHIP, std::string("path prep launch: ") + hipGetErrorString(e));
+    HIPCHK(hipEventRecord(p->ev_lap[1], st));
+    // rl_lap_eval's launch: per-instance centres and lengths, empty rings, no seeds, no
+    // completion flags, no precomputed corridor
+    const ModeBufs& lb = p->lapb;
+    rl::KParams kp{};
+    kp.center = p->d_lap_center;
+    kp.center_stride = (int64_t)2 * (int64_t)p->N;
+    kp.Ls = p->d_Lmc;
+    for (int r = 0; r < 2; ++r) {                      // (valid addresses, never read: M = 0)
+        kp.ring[r].vtx = (const double2*)p->d_vtx;
+        kp.ring[r].rec = p->d_rec;
+        kp.ring[r].flag = p->d_flag;
+        kp.ring[r].blk = p->d_blk;
+    }
+    kp.cfg = p->d_cfg_lap;
+    kp.x = lb.x; kp.y = lb.y; kp.heading = lb.heading; kp.kappa = lb.kappa;
+    kp.alpha_total = lb.alpha_total; kp.alpha_last = lb.alpha_last;
+    kp.v = lb.v; kp.ax = lb.ax; kp.lap = lb.lap; kp.nx = lb.nx; kp.ny = lb.ny;
+    kp.sweeps = lb.sweeps;
+    kp.N = p->N; kp.ncfg = p->ncfg; kp.B = p->B; kp.closed = p->closed;
+    kp.shape_B = p->shape_B > 0 ? p->shape_B : p->B;
+    kp.L = p->L;
+    e = p->stream ? rl::launch_stream(kp, lb.sb, true, st) : rl::launch_optimize(kp, true, st);
+    if (e != hipSuccess) return fail(RL_EHIP, std::string("lap evaluation launch: ") + hipGetErrorString(e));
+    HIPCHK(hipEventRecord(p->ev_lap[2], st));
+    p->lap_valid = true;
+    p->lap_stream = st;
+    return RL_OK;
+}
+
+int rl_plan_fetch_lap(rl_plan* p, rl_out* out, double* path_len) {
+    if (!p) return fail(RL_EINVAL, "plan is NULL");
+    if (!p->lap_valid) return fail(RL_EINVAL, "rl_plan_fetch_lap: no lap stage since the plan's last run");
+    HIPCHK(hipSetDevice(p->device));
+    hipStream_t st = p->last_stream ? p->last_stream : p->own_stream;
+    if (st != p->lap_stream) HIPCHK(hipStreamWaitEvent(st, p->ev_lap[2], 0));
+    const size_t B = (size_t)p->B, BN = B * (size_t)p->N;
+    const ModeBufs& lb = p->lapb;
+    std::vector<CopyJob> jobs;
+    auto add = [&](void* dst, const void* src, size_t bytes) {
+        if (dst && src && bytes) jobs.push_back({dst, src, bytes});
+    };
+    if (out) {
+        add(out->heading, lb.heading, BN * 8);
+        add(out->kappa, lb.kappa, BN * 8);
+        add(out->v, lb.v, BN * 8);
+        add(out->ax, lb.ax, BN * 8);
+        add(out->lap, lb.lap, B * 8);
+        add(out->vpass_sweeps, lb.sweeps, B * 4);
+    }
+    add(path_len, p->d_Lmc, B * 8);
+    for (const CopyJob& j : jobs) {
+        hipError_t e = hipMemcpyAsync(j.dst, j.src, j.bytes, hipMemcpyDeviceToHost, st);
+        if (e != hipSuccess) return fail(RL_EHIP, std::string("download: ") + hipGetErrorString(e));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    return RL_OK;
+}
+
+// the prep kernel alone on host paths (rl_lap_stage.hip)
+int rl_path_lengths(const double* x, const double* y, int32_t N, int32_t B, int32_t closed, int32_t device,
+                    double* L_out) {
+    if (!x || !y || !L_out) return fail(RL_EINVAL, "rl_path_lengths: x / y / L_out is NULL");
+    if (B < 1 || N < 0) return fail(RL_EINVAL, "rl_path_lengths: B < 1 or N < 0");
+    if (N > rl::RL_STREAM_MAX_N) return fail(RL_ETOOBIG, "rl_path_lengths: N exceeds 1048576");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(RL_ENODEV, "no HIP device");
+    if (device < 0 || device >= ndev) return fail(RL_ENODEV, "device index out of range");
+    HIPCHK(hipSetDevice(device));
+    const size_t bytes = (size_t)B * (size_t)N * 8;
+    double *d_x = nullptr, *d_y = nullptr, *d_L = nullptr;
+    auto done = [&](int code) {
+        if (d_x) hipFree(d_x);
+        if (d_y) hipFree(d_y);
+        if (d_L) hipFree(d_L);
+        return code;
+    };
+    if (hipMalloc((void**)&d_x, std::max<size_t>(bytes, 8)) != hipSuccess ||
+        hipMalloc((void**)&d_y, std::max<size_t>(bytes, 8)) != hipSuccess ||
+        hipMalloc((void**)&d_L, (size_t)B * 8) != hipSuccess)
+        return done(fail(RL_ENOMEM, "rl_path_lengths: hipMalloc failed"));
+    if (bytes && (hipMemcpy(d_x, x, bytes, hipMemcpyHostToDevice) != hipSuccess ||
+                  hipMemcpy(d_y, y, bytes, hipMemcpyHostToDevice) != hipSuccess))
+        return done(fail(RL_EHIP, "rl_path_lengths: upload"));
+    rl::PrepParams q{};
+    q.x = d_x;
+    q.y = d_y;
+    q.L_out = d_L;
+    q.N = N; q.B = B; q.closed = closed ? 1 : 0;
+    if (rl::launch_path_prep(q, nullptr) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+        return done(fail(RL_EHIP, "rl_path_lengths: kernel"));
+    if (hipMemcpy(L_out, d_L, (size_t)B * 8, hipMemcpyDeviceToHost) != hipSuccess)
+        return done(fail(RL_EHIP, "rl_path_lengths: download"));
+    return done(RL_OK);
+}
+
+// rl_plan_select / rl_plan_select_scored (arguments checked).  by_lap: rank the lap stage's
+// lap instead of the min-curvature score, and gather its v, ax, lap and sweeps as well.
+static int select_impl(rl_plan* p, const rl_select* sel, int gs, bool by_lap, void* hip_stream) {
     HIPCHK(hipSetDevice(p->device));
     const int m = sel->mode == RL_MODE_MINTIME ? 1 : 0;
     const int k = sel->k, G = p->B / gs, rows = G * k;
@@ -1244,12 +1435,13 @@ int rl_plan_select(rl_plan* p, const rl_select* sel, void* hip_stream) {
     for (auto& e : p->ev_sel)
         if (!e) HIPCHK(hipEventCreate(&e));
     if (st != run_st) HIPCHK(hipStreamWaitEvent(st, p->ev[3], 0));
+    if (by_lap && st != p->lap_stream) HIPCHK(hipStreamWaitEvent(st, p->ev_lap[2], 0));
     p->last_stream = st;
     HIPCHK(hipEventRecord(p->ev_sel[0], st));
     const ModeBufs& mb = p->mb[m];
     hipError_t e = hipSuccess;
-    const double* scores = mb.lap;                     // min-time: the lap the optimiser wrote
-    if (m == 0) {
+    const double* scores = by_lap ? p->lapb.lap : mb.lap;   // min-time: the lap the optimiser wrote
+    if (m == 0 && !by_lap) {
         e = rl::launch_score(mb.kappa, p->N, p->B, p->L, p->d_Ls, p->d_score, st);
         if (e != hipSuccess) return fail(RL_EHIP, std::string("score launch: ") + hipGetErrorString(e));
         scores = p->d_score;
@@ -1272,12 +1464,46 @@ int rl_plan_select(rl_plan* p, const rl_select* sel, void* hip_stream) {
     g.N = p->N; g.B = p->B; g.mo = p->max_outer; g.rows = rows;
     e = rl::launch_gather(g, st);
     if (e != hipSuccess) return fail(RL_EHIP, std::string("gather launch: ") + hipGetErrorString(e));
+    if (by_lap) {
+        // a second gather: the lap stage's v, ax, lap and sweeps [B][1] of the same winners
+        const ModeBufs& lb = p->lapb;
+        rl::GatherParams h{};
+        h.src[6] = lb.v; h.dst[6] = sb.v;
+        h.src[7] = lb.ax; h.dst[7] = sb.ax;
+        h.lap_src = lb.lap; h.lap_dst = sb.lap;
+        h.sweeps_src = lb.sweeps; h.sweeps_dst = sb.sweeps;
+        h.index = p->d_index;
+        h.N = p->N; h.B = p->B; h.mo = 0; h.rows = rows;
+        e = rl::launch_gather(h, st);
+        if (e != hipSuccess) return fail(RL_EHIP, std::string("gather launch: ") + hipGetErrorString(e));
+    }
     HIPCHK(hipEventRecord(p->ev_sel[1], st));
     p->sel_mode = sel->mode;
+    p->sel_lap = by_lap;
     p->sel_G = G;
     p->sel_k = k;
     p->sel_scores = scores;
     return RL_OK;
+}
+
+int rl_plan_select(rl_plan* p, const rl_select* sel, void* hip_stream) {
+    if (!p) return fail(RL_EINVAL, "plan is NULL");
+    int gs = 0;
+    if (int rc = check_select(sel, p->B, p->N, p->modes, &gs)) return rc;
+    if (!p->ran) return fail(RL_EINVAL, "rl_plan_select: the plan has not run");
+    return select_impl(p, sel, gs, false, hip_stream);
+}
+
+int rl_plan_select_scored(rl_plan* p, const rl_select* sel, int32_t score, void* hip_stream) {
+    if (!p) return fail(RL_EINVAL, "plan is NULL");
+    if (score != RL_SCORE_DEFAULT && score != RL_SCORE_LAP) return fail(RL_EINVAL, "select: unknown score");
+    int gs = 0;
+    if (int rc = check_select(sel, p->B, p->N, p->modes, &gs)) return rc;
+    if (!p->ran) return fail(RL_EINVAL, "rl_plan_select: the plan has not run");
+    const bool by_lap = score == RL_SCORE_LAP && sel->mode == RL_MODE_MINCURV;
+    if (by_lap && !p->lap_valid)
+        if (int rc = rl_plan_lap(p, hip_stream)) return rc;
+    return select_impl(p, sel, gs, by_lap, hip_stream);
 }
 
 // the copies that download the last selection of p (out_jobs' order for the rows)
@@ -1305,6 +1531,11 @@ static void sel_jobs(const rl_plan* p, int32_t* index, double* score, double* al
         add(o->ax, sb.ax, RN * 8);
         add(o->lap, sb.lap, R * 8);
         add(o->vpass_sweeps, sb.sweeps, R * (mo + 1) * 4);
+    } else if (p->sel_lap) {                           // the lap stage's: sweeps [R][1]
+        add(o->v, sb.v, RN * 8);
+        add(o->ax, sb.ax, RN * 8);
+        add(o->lap, sb.lap, R * 8);
+        add(o->vpass_sweeps, sb.sweeps, R * 4);
     }
 }
 
@@ -1921,7 +2152,7 @@ int run_cached(const rl_problem* prob, const rl_cfg* cfg, int32_t n_cfg, const u
     p->done[0] = p->done[1] = nullptr;                 // later runs of this plan signal nothing
     if (rc) return drop(rc);
     if (best) {
-        if ((rc = rl_plan_select(p, best->sel, nullptr))) return drop(rc);
+        if ((rc = rl_plan_select_scored(p, best->sel, best->score_kind, nullptr))) return drop(rc);
         jobs.clear();
         sel_jobs(p, best->index, best->score, best->all_scores, best->out, jobs);
         if (staged_bytes(jobs) > e->pin_bytes) return drop(fail(RL_EHIP, "selection staging larger than its bound"));
@@ -1962,16 +2193,23 @@ int rl_optimize(const rl_problem* prob, const rl_cfg* cfg, int32_t n_cfg, const 
     return run_cached(prob, cfg, n_cfg, seeds, B, modes, nullptr, nullptr, out_mincurv, out_mintime, nullptr);
 }
 
-int rl_optimize_best(const rl_problem* prob, const rl_cfg* cfg, int32_t n_cfg, const uint64_t* seeds, int32_t B,
-                     const rl_select* sel, int32_t* index, double* score, double* all_scores, rl_out* out) {
-    if (!sel || !index || !score) return fail(RL_EINVAL, "rl_optimize_best: sel / index / score is NULL");
+int rl_optimize_best_scored(const rl_problem* prob, const rl_cfg* cfg, int32_t n_cfg, const uint64_t* seeds, int32_t B,
+                            const rl_select* sel, int32_t score, int32_t* index, double* score_out,
+                            double* all_scores, rl_out* out) {
+    if (!sel || !index || !score_out) return fail(RL_EINVAL, "rl_optimize_best: sel / index / score is NULL");
+    if (score != RL_SCORE_DEFAULT && score != RL_SCORE_LAP) return fail(RL_EINVAL, "select: unknown score");
     if (sel->mode != RL_MODE_MINCURV && sel->mode != RL_MODE_MINTIME)
         return fail(RL_EINVAL, "select: mode must be exactly one of RL_MODE_MINCURV, RL_MODE_MINTIME");
     if (int rc = check_inputs(prob, cfg, n_cfg, B, sel->mode, nullptr)) return rc;
     int gs = 0;
     if (int rc = check_select(sel, B, prob->N, sel->mode, &gs)) return rc;
-    const BestArgs best{sel, index, score, all_scores, out};
+    const BestArgs best{sel, index, score_out, all_scores, out, score};
     return run_cached(prob, cfg, n_cfg, seeds, B, sel->mode, nullptr, nullptr, nullptr, nullptr, nullptr, &best);
+}
+
+int rl_optimize_best(const rl_problem* prob, const rl_cfg* cfg, int32_t n_cfg, const uint64_t* seeds, int32_t B,
+                     const rl_select* sel, int32_t* index, double* score, double* all_scores, rl_out* out) {
+    return rl_optimize_best_scored(prob, cfg, n_cfg, seeds, B, sel, RL_SCORE_DEFAULT, index, score, all_scores, out);
 }
 
 int rl_last_call_ms(float* kernel_ms, float* call_ms) {

@@ -41,6 +41,9 @@
 //   --seeds B   optimise B α-seeds in one launch; writes <base>_batch_summary.csv
 //   --best K    with --seeds and --mode mincurv|mintime: also rank the batch on the GPU
 //               (rl_optimize_best, one group) and write <base>_best<r>_raceline.csv, r = 0..K-1
+//   --score lap with --best K --mode mincurv: rank the min-curvature racelines by their lap
+//               time (the lap stage, rl_optimize_best_scored); the lap_time_s column of
+//               <base>_batch_summary.csv then holds every seed's lap
 //   --repeat R  time R launches of the batch; prints outer-iters/s
 //   --device D  HIP device
 //   --devices 0,1,...  shard the --seeds batch over these devices: contiguous instance
@@ -1187,7 +1190,7 @@ static void compute_mintime_and_save(const string& base, const vector<Vec2>& cen
 // B α-seeds in one launch (beyond the reference): one summary row per instance.
 static void batch_and_save(const string& base, const vector<Vec2>& center, double L, bool closed,
                            const vector<Vec2>& inner_from_mids, const vector<Vec2>& outer_from_mids, int B, int modes,
-                           int repeat, int best) {
+                           int repeat, int best, bool score_lap) {
     auto& C = cfg::get();
     SegVec innerE = closed ? edges::ringEdges(inner_from_mids) : edges::polylineEdges(inner_from_mids);
     SegVec outerE = closed ? edges::ringEdges(outer_from_mids) : edges::polylineEdges(outer_from_mids);
@@ -1237,6 +1240,31 @@ static void batch_and_save(const string& base, const vector<Vec2>& center, doubl
                   << " ms -> " << outers * repeat / wall << " PGD outer-iters/s\n";
     }
     if (plan) rl_plan_destroy(plan);
+    // --best K: the K best seeds of the batch, ranked and compacted on the GPU; only their
+    // rows are downloaded.  One file per rank, x,y rows like <base>_raceline.csv.
+    // (--score lap: before the summary, whose lap column is the lap stage's)
+    const size_t N = center.size();
+    vector<int32_t> idx((size_t)std::max(best, 0));
+    vector<double> sc(idx.size()), bx(idx.size() * N), by(idx.size() * N);
+    auto run_best = [&]() {
+        rl_select sel;
+        std::memset(&sel, 0, sizeof(sel));
+        sel.mode = modes;
+        sel.k = best;
+        sel.group_size = 0;
+        rl_out ob;
+        std::memset(&ob, 0, sizeof(ob));
+        ob.x = bx.data();
+        ob.y = by.data();
+        if (score_lap)
+            gpu::check(rl_optimize_best_scored(&pk.prob, &c, 1, seeds.data(), B, &sel, RL_SCORE_LAP, idx.data(),
+                                               sc.data(), lap.data(), &ob),
+                       "rl_optimize_best_scored");
+        else
+            gpu::check(rl_optimize_best(&pk.prob, &c, 1, seeds.data(), B, &sel, idx.data(), sc.data(), nullptr, &ob),
+                       "rl_optimize_best");
+    };
+    if (best > 0 && score_lap) run_best();
     io::Csv fo(base + "_batch_summary.csv");
     fo.f << "seed,lap_time_s,mean_abs_alpha_last,evals_total\n";
     for (int b = 0; b < B; ++b) {
@@ -1244,32 +1272,17 @@ static void batch_and_save(const string& base, const vector<Vec2>& center, doubl
         for (size_t i = 0; i < center.size(); ++i) s += std::fabs(al[b * center.size() + i]);
         long et = 0;
         for (int k = 0; k < C.max_outer_iters; ++k) et += ev[(size_t)b * C.max_outer_iters + k];
-        fo.f << b << "," << (mt ? lap[b] : 0.0) << "," << s / std::max<size_t>(1, center.size()) << "," << et << "\n";
+        fo.f << b << "," << (mt || score_lap ? lap[b] : 0.0) << "," << s / std::max<size_t>(1, center.size()) << "," << et << "\n";
     }
     if (best <= 0) return;
-    // --best K: the K best seeds of the batch, ranked and compacted on the GPU; only their
-    // rows are downloaded.  One file per rank, x,y rows like <base>_raceline.csv.
-    const size_t N = center.size();
-    rl_select sel;
-    std::memset(&sel, 0, sizeof(sel));
-    sel.mode = modes;
-    sel.k = best;
-    sel.group_size = 0;
-    vector<int32_t> idx((size_t)best);
-    vector<double> sc((size_t)best), bx((size_t)best * N), by((size_t)best * N);
-    rl_out ob;
-    std::memset(&ob, 0, sizeof(ob));
-    ob.x = bx.data();
-    ob.y = by.data();
-    gpu::check(rl_optimize_best(&pk.prob, &c, 1, seeds.data(), B, &sel, idx.data(), sc.data(), nullptr, &ob),
-               "rl_optimize_best");
+    if (!score_lap) run_best();
     for (int r = 0; r < best; ++r) {
         io::Csv o(base + "_best" + std::to_string(r) + "_raceline.csv");
         if (!o) throw std::runtime_error("save best raceline failed");
         for (size_t i = 0; i < N; ++i) o.f << bx[r * N + i] << "," << by[r * N + i] << "\n";
         if (C.emit_closed_duplicate && N > 0) o.f << bx[r * N] << "," << by[r * N] << "\n";
     }
-    std::cerr << "[best] " << (mt ? "lap_time_s" : "curvature_score") << " of the " << best << " best of B=" << B << ":";
+    std::cerr << "[best] " << (mt || score_lap ? "lap_time_s" : "curvature_score") << " of the " << best << " best of B=" << B << ":";
     std::cerr << std::setprecision(9);
     for (int r = 0; r < best; ++r) std::cerr << " seed " << seeds[idx[r]] << " = " << sc[r];
     std::cerr << "\n";
@@ -1363,7 +1376,8 @@ int run_pipeline(const string& innerPath, const string& outerPath, const string&
 }
 
 // Steps 7-8 from the reference's step-6 files.
-int run_from_centerline(const string& outPath, double L, double s0, const string& mode, int B, int repeat, int best) {
+int run_from_centerline(const string& outPath, double L, double s0, const string& mode, int B, int repeat, int best,
+                        const string& score) {
     auto& C = cfg::get();
     const string base = io::dropExt(outPath);
     const bool closed_mode = C.is_closed_track;
@@ -1376,6 +1390,20 @@ int run_from_centerline(const string& outPath, double L, double s0, const string
         return 2;
     }
     const vector<Vec2> center_for_opt = opt_input(center, closed_mode);
+    if (!score.empty()) {
+        if (score != "lap" && score != "default") {
+            std::cerr << "[ERR] --score default|lap\n";
+            return 2;
+        }
+        if (best <= 0 || B <= 0) {
+            std::cerr << "[ERR] --score needs --seeds B --best K\n";
+            return 2;
+        }
+        if (score == "lap" && mode != "mincurv") {
+            std::cerr << "[ERR] --score lap needs --mode mincurv (the min-time score is the lap already)\n";
+            return 2;
+        }
+    }
     if (B > 0) {
         const int modes = mode == "mincurv" ? RL_MODE_MINCURV
                                             : mode == "mintime" ? RL_MODE_MINTIME : RL_MODE_MINCURV | RL_MODE_MINTIME;
@@ -1387,7 +1415,8 @@ int run_from_centerline(const string& outPath, double L, double s0, const string
             std::cerr << "[ERR] --best K: K <= min(B, " << RL_SELECT_MAX_K << ")\n";
             return 2;
         }
-        pipeline::batch_and_save(base, center_for_opt, L, closed_mode, inner, outer, B, modes, repeat, best);
+        pipeline::batch_and_save(base, center_for_opt, L, closed_mode, inner, outer, B, modes, repeat, best,
+                                 score == "lap");
         return 0;
     }
     auto t0 = Clock::now();
@@ -1408,6 +1437,7 @@ int main(int argc, char** argv) {
     double L = NAN, s0 = 0.0;
     string mode = "both", stop_after;
     int B = 0, repeat = 0, best = 0;
+    string score;
     try {
         for (int i = 1; i < argc; ++i) {
             const string a = argv[i];
@@ -1423,6 +1453,7 @@ int main(int argc, char** argv) {
             else if (a == "--seeds") B = std::stoi(next());
             else if (a == "--repeat") repeat = std::stoi(next());
             else if (a == "--best") best = std::stoi(next());
+            else if (a == "--score") score = next();
             else if (a == "--device") gpu::device = std::stoi(next());
             else if (a == "--devices") {
                 std::stringstream ss(next());
@@ -1439,11 +1470,12 @@ int main(int argc, char** argv) {
             std::cerr << "Usage: " << argv[0] << " inner.csv outer.csv centerline.csv [--set key=value ...]"
                       << " [--mode mincurv|mintime|both] [--stop-after centerline]\n"
                       << "       " << argv[0]
-                      << " centerline.csv [--L v] [--s0 v] [--open] [--mode m] [--seeds B] [--repeat R] [--best K]\n";
+                      << " centerline.csv [--L v] [--s0 v] [--open] [--mode m] [--seeds B] [--repeat R] [--best K]\n"
+                      << "         [--score lap]   with --best K --mode mincurv: rank by the lap stage's lap time\n";
             return 1;
         }
         if (pos.size() == 3) return run_pipeline(pos[0], pos[1], pos[2], mode, stop_after == "centerline");
-        return run_from_centerline(pos[0], L, s0, mode, B, repeat, best);
+        return run_from_centerline(pos[0], L, s0, mode, B, repeat, best, score);
     } catch (const std::exception& e) {
         std::cerr << "[ERR] " << e.what() << "\n";
         return 3;

@@ -159,7 +159,8 @@ def optimize_batch(prob: Problem, cfgs, seeds=None, B: Optional[int] = None,
 class Selected:
     """The k best instances of each of G groups (rl_plan_select / rl_optimize_best):
     index [G, k] global instance indices, best first; score [G, k] their scores; scores [B]
-    every instance's score (min-time: the lap; min-curvature: h * sum kappa^2); out: Outputs
+    every instance's score (min-time: the lap; min-curvature: h * sum kappa^2, or the lap
+    stage's lap with score="lap"); out: Outputs
     with G*k rows, row g*k + r = instance index[g, r]."""
 
     index: np.ndarray
@@ -187,17 +188,34 @@ def _check_select(B: int, mode, k: int, group_size) -> tuple:
     return _MODES[mode], gs
 
 
-def _selected_alloc(B: int, N: int, mo: int, mode: int, k: int, gs: int) -> Selected:
+_SCORES = {"default": abi.RL_SCORE_DEFAULT, "lap": abi.RL_SCORE_LAP,
+           abi.RL_SCORE_DEFAULT: abi.RL_SCORE_DEFAULT, abi.RL_SCORE_LAP: abi.RL_SCORE_LAP}
+
+
+def _check_score(score, mode_bit: int) -> bool:
+    """True if the selection ranks the lap stage's lap (score 'lap' on min-curvature results)."""
+    if score not in _SCORES:
+        raise ValueError(f"score must be 'default' or 'lap', got {score!r}")
+    return _SCORES[score] == abi.RL_SCORE_LAP and mode_bit == abi.RL_MODE_MINCURV
+
+
+def _selected_alloc(B: int, N: int, mo: int, mode: int, k: int, gs: int, lap: bool = False) -> Selected:
     G = B // gs
-    return Selected(index=np.zeros((G, k), dtype=np.int32), score=np.zeros((G, k)), scores=np.zeros(B),
-                    out=Outputs.alloc(G * k, N, mo, mode == abi.RL_MODE_MINTIME))
+    out = Outputs.alloc(G * k, N, mo, mode == abi.RL_MODE_MINTIME)
+    if lap:                     # a min-curvature selection by lap: the lap stage's v, ax, lap, sweeps [G*k, 1]
+        out.v, out.ax = np.zeros((G * k, N)), np.zeros((G * k, N))
+        out.lap, out.vpass_sweeps = np.zeros(G * k), np.zeros((G * k, 1), dtype=np.int32)
+    return Selected(index=np.zeros((G, k), dtype=np.int32), score=np.zeros((G, k)), scores=np.zeros(B), out=out)
 
 
 def optimize_best(prob: Problem, cfgs, seeds=None, B: Optional[int] = None, mode="mintime", k: int = 1,
-                  group_size: Optional[int] = None) -> Selected:
+                  group_size: Optional[int] = None, score="default") -> Selected:
     """Optimise B instances in `mode` and return only the k best of each group of
     group_size (None: one group) instances, ranked and compacted on the GPU
-    (rl_optimize_best): G*k rows are downloaded instead of B."""
+    (rl_optimize_best): G*k rows are downloaded instead of B.  score: "default" (the lap
+    for min-time, h * sum kappa^2 for min-curvature) or "lap": min-curvature racelines are
+    ranked by the lap time of the lap stage (rl_optimize_best_scored), whose v, ax, lap and
+    vpass_sweeps [G*k, 1] then come back with the winners' rows."""
     cfg_arr, ncfg = abi.cfg_array(cfgs)
     if B is None:
         B = ncfg if ncfg > 1 else (len(seeds) if seeds is not None else 1)
@@ -205,14 +223,38 @@ def optimize_best(prob: Problem, cfgs, seeds=None, B: Optional[int] = None, mode
     m, gs = _check_select(B, mode, k, group_size)
     if prob.N == 0:
         raise ValueError("optimize_best: N == 0 (nothing to rank)")
-    sel = _selected_alloc(B, prob.N, int(cfg_arr[0].max_outer_iters), m, k, gs)
+    by_lap = _check_score(score, m)
+    sel = _selected_alloc(B, prob.N, int(cfg_arr[0].max_outer_iters), m, k, gs, by_lap)
     seeds_a = abi.seed_array(seeds)
     p = prob.as_c()
     o = sel.out.as_c()
     s = abi.RlSelect(m, k, gs, 0)
-    _check(_lib().rl_optimize_best(C.byref(p), cfg_arr, ncfg, abi.u64ptr(seeds_a), B, C.byref(s),
-                                   abi.iptr(sel.index), abi.dptr(sel.score), abi.dptr(sel.scores), C.byref(o)))
+    if _SCORES[score] == abi.RL_SCORE_DEFAULT:
+        _check(_lib().rl_optimize_best(C.byref(p), cfg_arr, ncfg, abi.u64ptr(seeds_a), B, C.byref(s),
+                                       abi.iptr(sel.index), abi.dptr(sel.score), abi.dptr(sel.scores), C.byref(o)))
+    else:
+        _check(_lib().rl_optimize_best_scored(C.byref(p), cfg_arr, ncfg, abi.u64ptr(seeds_a), B, C.byref(s),
+                                              _SCORES[score], abi.iptr(sel.index), abi.dptr(sel.score),
+                                              abi.dptr(sel.scores), C.byref(o)))
     return sel
+
+
+def path_lengths(x, y, closed: bool, device: int = 0) -> np.ndarray:
+    """L [B]: the debug dump's path_length (ref:1443-1448) of B paths given as rows x [B, N],
+    y [B, N], summed on the GPU in the reference's order (rl_path_lengths): L[b] equals
+    path_length(column_stack(x[b], y[b]), closed) bit for bit."""
+    X = np.ascontiguousarray(x, dtype=np.float64)
+    Y = np.ascontiguousarray(y, dtype=np.float64)
+    if X.ndim == 1:
+        X, Y = X[None], Y[None]
+    if X.ndim != 2 or X.shape != Y.shape or X.shape[0] < 1:
+        raise ValueError(f"path_lengths: x and y must be [B, N] arrays of one shape, got {X.shape} and {Y.shape}")
+    B, N = X.shape
+    L = np.zeros(B)
+    if N == 0:                              # (no row to point at)
+        X = Y = np.zeros((B, 1))
+    _check(_lib().rl_path_lengths(abi.dptr(X), abi.dptr(Y), N, B, 1 if closed else 0, int(device), abi.dptr(L)))
+    return L
 
 
 def rank_scores(scores, k: int, group_size: Optional[int] = None, device: int = 0) -> np.ndarray:
@@ -287,21 +329,45 @@ class Plan:
         _check(_lib().rl_plan_fetch(self._h, C.byref(c_mc) if c_mc else None, C.byref(c_mt) if c_mt else None))
         return out_mc, out_mt
 
-    def select(self, mode="mintime", k: int = 1, group_size: Optional[int] = None, stream_ptr: int = 0) -> None:
+    def lap(self, stream_ptr: int = 0) -> None:
+        """Enqueue the lap stage after the last run() (rl_plan_lap): every min-curvature
+        raceline's own path length, then heading, curvature and the velocity profile with
+        h = path length / N -- the debug dump's "min-curv lap" for the whole batch."""
+        _check(_lib().rl_plan_lap(self._h, C.c_void_p(stream_ptr) if stream_ptr else None))
+
+    def fetch_lap(self):
+        """Download the last lap(): (Outputs, path_len [B]).  The Outputs hold heading, kappa,
+        v, ax, lap and vpass_sweeps [B, 1] as lap_eval returns them; x, y and the alphas are
+        not part of the stage and stay zero."""
+        out = Outputs.alloc(self.B, self.N, 0, True)
+        path_len = np.zeros(self.B)
+        o = out.as_c()
+        _check(_lib().rl_plan_fetch_lap(self._h, C.byref(o), abi.dptr(path_len)))
+        return out, path_len
+
+    def select(self, mode="mintime", k: int = 1, group_size: Optional[int] = None, stream_ptr: int = 0,
+               score="default") -> None:
         """Enqueue score -> rank -> gather after the last run() (rl_plan_select): the k best
-        instances of each group of group_size (None: all B) in `mode`."""
+        instances of each group of group_size (None: all B) in `mode`.  score="lap" ranks
+        min-curvature racelines by the lap stage's lap (rl_plan_select_scored; runs lap()
+        first unless one is valid since the last run)."""
         m, gs = _check_select(self.B, mode, k, group_size)
+        by_lap = _check_score(score, m)
         s = abi.RlSelect(m, k, gs, 0)
+        st = C.c_void_p(stream_ptr) if stream_ptr else None
         self._sel = None
-        _check(_lib().rl_plan_select(self._h, C.byref(s), C.c_void_p(stream_ptr) if stream_ptr else None))
-        self._sel = (m, k, gs)
+        if _SCORES[score] == abi.RL_SCORE_DEFAULT:
+            _check(_lib().rl_plan_select(self._h, C.byref(s), st))
+        else:
+            _check(_lib().rl_plan_select_scored(self._h, C.byref(s), _SCORES[score], st))
+        self._sel = (m, k, gs, by_lap)
 
     def fetch_selected(self) -> Selected:
         """Download the last select(): indices, scores and the winners' rows (rl_plan_fetch_selected)."""
         if getattr(self, "_sel", None) is None:
             raise ValueError("fetch_selected: no select() on this plan")
-        m, k, gs = self._sel
-        sel = _selected_alloc(self.B, self.N, self.max_outer, m, k, gs)
+        m, k, gs, by_lap = self._sel
+        sel = _selected_alloc(self.B, self.N, self.max_outer, m, k, gs, by_lap)
         o = sel.out.as_c()
         _check(_lib().rl_plan_fetch_selected(self._h, abi.iptr(sel.index), abi.dptr(sel.score),
                                              abi.dptr(sel.scores), C.byref(o)))
@@ -752,7 +818,7 @@ def seeds_range(B: int, first: int = 0) -> np.ndarray:
 
 __all__ = ["RacelineError", "MinCurvResult", "MinTimeResult", "Plan", "Problem", "RlCfg", "Outputs",
            "default_cfg", "set_mu", "ring_edges", "polyline_edges", "edges_for", "optimize_batch",
-           "optimize_best", "rank_scores", "Selected",
+           "optimize_best", "rank_scores", "Selected", "path_lengths", "path_length", "lap_eval",
            "compute_min_curvature_raceline", "compute_min_time_raceline", "compute_raceline_and_save",
            "compute_mintime_and_save", "write_raceline_csvs", "write_mintime_csvs", "load_csv_xy",
            "seeds_range"]
