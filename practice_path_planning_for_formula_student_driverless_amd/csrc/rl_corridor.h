@@ -3,7 +3,7 @@
 //   minDistanceToSegments_global ref:501-512, safe_ray ref:694-699,
 //   corridor blocks ref:701-711 / 749-756.
 //
-// Rings arrive as an ENTRY STREAM (built by rl_abi.cpp make_ring): the vertices of
+// Rings arrive as an ENTRY STREAM (built by rl_host.h make_ring): the vertices of
 // each chain of segments in order, padded to blocks of 32 entries; entry v carries
 // the record of the segment that ENDS at v (flag bit set) or a dummy (chain start,
 // padding).  For CK samples (P, n) per lane:
@@ -74,7 +74,7 @@ typedef __attribute__((address_space(4))) const float cflt;
 // measured slower on every configuration, then removed)
 
 // Block culling. Entries come in blocks of RL_BLK. The host gives each block a circle (C, R)
-// that contains both endpoints of every segment ending in the block (rl_abi.cpp
+// that contains both endpoints of every segment ending in the block (rl_host.h
 // make_ring), so every point of those segments lies within R of C.
 //  * Ray filter: |n x (V - C)| <= |n| R for every such vertex V. If the centre's side
 //    value satisfies |c_C| > R(1+1e-9) + 2 dl, every endpoint's computed side value is

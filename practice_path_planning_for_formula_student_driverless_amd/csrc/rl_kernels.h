@@ -1,4 +1,4 @@
-// rl_kernels.h — launch interface between the C-ABI (rl_abi.cpp) and the
+// rl_kernels.h — launch interface between the C-ABI (rl_plan.cpp and its siblings) and the
 // gfx950 kernels (rl_kernels.hip).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -26,13 +26,13 @@ struct KParams {
     int32_t shape_B;           // batch size the kernel shape is chosen for (pick_shape; >= 1)
     int64_t center_stride;     // doubles between instances' centres (0: shared)
     double L, veh_width;
-    // Instance completion flags (rl_optimize's overlapped download, rl_abi.cpp run_cached):
+    // Instance completion flags (rl_optimize's overlapped download, rl_cache.cpp run_cached):
     // nullptr, or [B] words in coherent pinned host memory; instance b stores `epoch` into
     // done[b] once every result word of b has reached memory (signal_done below)
     uint32_t* done;
     uint32_t epoch;
     // Outer iteration 0's corridor bounds [N] (lo, hi), computed once for the whole batch by
-    // rl_corridor_kernel on the shared centre line (rl_abi.cpp rl_plan_run), or nullptr: the
+    // rl_corridor_kernel on the shared centre line (rl_plan.cpp rl_plan_run), or nullptr: the
     // first corridor is the same for every instance of a batch (P = centre, guard = the
     // problem's veh_width * 0.5 + the cfg's margin), so the instances load it instead of each
     // casting it again

@@ -1,6 +1,6 @@
 // rl_lap_stage.h — launch interface of the lap stage's preparation kernel
 // (rl_lap_stage.hip): the result rows of a plan become the inputs of a lap evaluation
-// (rl_abi.cpp rl_plan_lap, rl_path_lengths).  Not part of the public ABI.
+// (rl_stages.cpp rl_plan_lap, rl_abi.cpp rl_path_lengths).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

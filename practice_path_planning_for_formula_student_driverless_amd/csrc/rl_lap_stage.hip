@@ -1,7 +1,7 @@
 // rl_lap_stage.hip — the lap stage's preparation kernel: the SoA result rows
 // x[b][.], y[b][.] of a plan become the inputs of a lap evaluation, the interleaved path
 // [B][N][2] and its own length L_mc[b], without leaving the device.  The evaluation itself
-// is the min-time kernel at max_outer_iters = 0 (rl_abi.cpp rl_plan_lap), launched as
+// is the min-time kernel at max_outer_iters = 0 (rl_stages.cpp rl_plan_lap), launched as
 // rl_lap_eval launches it; this file holds no second v-pass.
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -347,7 +347,7 @@ struct MinWaves {
 // exact-multiple version carries no partial-chunk bookkeeping).  One workgroup runs instance b
 // of the launch p; the kernels below call it with their own (p, b).
 #ifndef RL_PRIO
-// wave priority by progress (rl_kernels.h progress_prio): build.py sets 1 for the throughput
+// wave priority by progress (rl_kernels.h progress_prio): build.py sets 3 for the throughput
 // shapes' translation units (two or more instances per CU); 0 keeps the issue order
 #define RL_PRIO 0
 #endif

@@ -1,6 +1,6 @@
 // rl_select.h — launch interface of the selection stage (rl_select.hip): score the
 // instances of a batch, rank them per group and gather the winners' rows, all on the
-// device (rl_abi.cpp rl_plan_select, rl_rank_scores).  Not part of the public ABI.
+// device (rl_stages.cpp rl_plan_select, rl_abi.cpp rl_rank_scores).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,0 +1,252 @@
+// rl_stages.cpp — C-ABI implementation, part 3: the stages that follow a plan's run on the
+// device.  Selection (rl_select.hip): score, rank and gather.  Lap stage (rl_lap_stage.hip,
+// DESIGN §3i): the debug dump's "min-curv lap" for every instance of a plan.
+#include "rl_host.h"
+
+using namespace rl;
+
+int rl::check_groups(int32_t B, int32_t group_size, int32_t k, int* gs) {
+    if (B < 1) return fail(RL_EINVAL, "select: B must be >= 1");
+    if (group_size < 0) return fail(RL_EINVAL, "select: group_size < 0");
+    const int g = group_size == 0 ? B : group_size;
+    if (g > B || B % g != 0) return fail(RL_EINVAL, "select: B must be a multiple of group_size");
+    if (k < 1) return fail(RL_EINVAL, "select: k must be >= 1");
+    if (k > g) return fail(RL_EINVAL, "select: k exceeds group_size");
+    if (k > RL_SELECT_MAX_K) return fail(RL_EINVAL, "select: k exceeds RL_SELECT_MAX_K (64)");
+    *gs = g;
+    return RL_OK;
+}
+
+int rl::check_select(const rl_select* sel, int32_t B, int32_t N, int32_t modes, int* gs) {
+    if (!sel) return fail(RL_EINVAL, "select: sel is NULL");
+    if (sel->mode != RL_MODE_MINCURV && sel->mode != RL_MODE_MINTIME)
+        return fail(RL_EINVAL, "select: mode must be exactly one of RL_MODE_MINCURV, RL_MODE_MINTIME");
+    if (!(modes & sel->mode)) return fail(RL_EINVAL, "select: mode is not among the plan's modes");
+    if (int rc = check_groups(B, sel->group_size, sel->k, gs)) return rc;
+    if (N == 0) return fail(RL_EINVAL, "select: N == 0 (nothing to rank)");
+    return RL_OK;
+}
+
+// the copies of index / score / all_scores, then the winners' rows: the mode's own arrays,
+// or (a min-curvature selection by lap) the lap stage's v, ax, lap and sweeps [R][1] as well
+void rl::sel_jobs(const rl_plan* p, int32_t* index, double* score, double* all_scores, const rl_out* o,
+                  std::vector<CopyJob>& jobs) {
+    const size_t R = (size_t)p->sel_G * p->sel_k, mo = (size_t)p->max_outer;
+    add_job(jobs, index, p->d_index, R * 4);
+    add_job(jobs, score, p->d_score_sel, R * 8);
+    add_job(jobs, all_scores, p->sel_scores, (size_t)p->B * 8);
+    const bool mt = p->sel_mode == RL_MODE_MINTIME;
+    field_jobs(o, p->selb, {R, (size_t)p->N, mo, mt ? mo + 1 : 1}, mt || p->sel_lap, false, jobs);
+}
+
+namespace {
+
+// plan-owned selection buffers for `rows` winners; they count toward dev_bytes()
+int select_alloc(rl_plan* p, int rows) {
+    if (p->d_index && rows <= p->sel_cap) return RL_OK;
+    if (p->last_stream) HIPCHK(hipStreamSynchronize(p->last_stream));   // it may still read the old ones
+    DevArena& a = p->sel_mem;
+    a.release();
+    p->sel_cap = 0;
+    p->selb = ModeBufs{};
+    const size_t R = (size_t)rows, mo = (size_t)p->max_outer;
+    p->d_score = a.get<double>((size_t)p->B);
+    p->d_index = a.get<int32_t>(R);
+    p->d_score_sel = a.get<double>(R);
+    alloc_fields(a, p->selb, {R, (size_t)std::max(p->N, 1), std::max<size_t>(mo, 1), mo + 1}, true);
+    if (!a.ok()) return fail(RL_ENOMEM, "hipMalloc (selection buffers) failed");
+    p->sel_cap = rows;
+    return RL_OK;
+}
+
+// plan-owned lap-stage buffers; they count toward dev_bytes()
+int lap_alloc(rl_plan* p) {
+    if (p->d_lap_center) return RL_OK;
+    DevArena& a = p->lap_mem;
+    const size_t B = (size_t)p->B, N = (size_t)std::max(p->N, 1), BN = B * N;
+    ModeBufs& s = p->lapb;
+    double* center = a.get<double>(2 * BN);
+    p->d_Lmc = a.get<double>(B);
+    p->d_cfg_lap = a.get<rl_cfg>((size_t)p->ncfg);
+    alloc_fields(a, s, {B, N, 0, 1}, true);            // no outer iteration: no evals / accepts
+    s.nx = a.get<double>(BN);
+    s.ny = a.get<double>(BN);
+    if (p->stream) s.sb.base = a.get<double>(BN * rl::RL_STREAM_ARRAYS);
+    if (!a.ok()) {
+        a.release();
+        p->lapb = ModeBufs{};
+        p->d_Lmc = nullptr;
+        p->d_cfg_lap = nullptr;
+        return fail(RL_ENOMEM, "hipMalloc (lap-stage buffers) failed");
+    }
+    p->d_lap_center = center;
+    return RL_OK;
+}
+
+// rl_plan_select / rl_plan_select_scored (arguments checked).  by_lap: rank the lap stage's
+// lap instead of the min-curvature score, and gather its v, ax, lap and sweeps as well.
+int select_impl(rl_plan* p, const rl_select* sel, int gs, bool by_lap, void* hip_stream) {
+    HIPCHK(hipSetDevice(p->device));
+    const int m = sel->mode == RL_MODE_MINTIME ? 1 : 0;
+    const int k = sel->k, G = p->B / gs, rows = G * k;
+    hipStream_t run_st = p->run_stream();
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : run_st;
+    p->sel_mode = 0;
+    if (int rc = select_alloc(p, rows)) return rc;
+    for (auto& e : p->ev_sel)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    if (st != run_st) HIPCHK(hipStreamWaitEvent(st, p->ev[3], 0));
+    if (by_lap && st != p->lap_stream) HIPCHK(hipStreamWaitEvent(st, p->ev_lap[2], 0));
+    p->last_stream = st;
+    HIPCHK(hipEventRecord(p->ev_sel[0], st));
+    const ModeBufs& mb = p->mb[m];
+    hipError_t e = hipSuccess;
+    const double* scores = by_lap ? p->lapb.lap : mb.lap;   // min-time: the lap the optimiser wrote
+    if (m == 0 && !by_lap) {
+        e = rl::launch_score(mb.kappa, p->N, p->B, p->L, p->d_Ls, p->d_score, st);
+        if (e != hipSuccess) return fail(RL_EHIP, std::string("score launch: ") + hipGetErrorString(e));
+        scores = p->d_score;
+    }
+    e = rl::launch_rank(scores, p->B, gs, k, p->d_index, p->d_score_sel, st);
+    if (e != hipSuccess) return fail(RL_EHIP, std::string("rank launch: ") + hipGetErrorString(e));
+    const ModeBufs& sb = p->selb;
+    rl::GatherParams g{};
+    int c = 0;                                         // the [B][N] arrays, in kOutFields order
+    for (const OutField& f : kOutFields)
+        if (f.shape == F_ROW_N) {
+            g.src[c] = mb.*f.b64;
+            g.dst[c++] = sb.*f.b64;
+        }
+    g.lap_src = mb.lap; g.lap_dst = sb.lap;
+    g.evals_src = mb.evals; g.evals_dst = sb.evals;
+    g.accepts_src = mb.accepts; g.accepts_dst = sb.accepts;
+    g.sweeps_src = mb.sweeps; g.sweeps_dst = sb.sweeps;
+    g.index = p->d_index;
+    g.N = p->N; g.B = p->B; g.mo = p->max_outer; g.rows = rows;
+    e = rl::launch_gather(g, st);
+    if (e != hipSuccess) return fail(RL_EHIP, std::string("gather launch: ") + hipGetErrorString(e));
+    if (by_lap) {
+        // a second gather: the lap stage's v, ax, lap and sweeps [B][1] of the same winners
+        const ModeBufs& lb = p->lapb;
+        rl::GatherParams h{};
+        h.src[6] = lb.v; h.dst[6] = sb.v;
+        h.src[7] = lb.ax; h.dst[7] = sb.ax;
+        h.lap_src = lb.lap; h.lap_dst = sb.lap;
+        h.sweeps_src = lb.sweeps; h.sweeps_dst = sb.sweeps;
+        h.index = p->d_index;
+        h.N = p->N; h.B = p->B; h.mo = 0; h.rows = rows;
+        e = rl::launch_gather(h, st);
+        if (e != hipSuccess) return fail(RL_EHIP, std::string("gather launch: ") + hipGetErrorString(e));
+    }
+    HIPCHK(hipEventRecord(p->ev_sel[1], st));
+    p->sel_mode = sel->mode;
+    p->sel_lap = by_lap;
+    p->sel_G = G;
+    p->sel_k = k;
+    p->sel_scores = scores;
+    return RL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// The preparation kernel packs the min-curvature rows and sums their lengths, then the
+// min-time kernel evaluates them at max_outer_iters = 0, as rl_lap_eval launches it.
+int rl_plan_lap(rl_plan* p, void* hip_stream) {
+    if (!p) return fail(RL_EINVAL, "plan is NULL");
+    if (!(p->modes & RL_MODE_MINCURV)) return fail(RL_EINVAL, "rl_plan_lap: the plan has no RL_MODE_MINCURV");
+    if (p->N == 0) return fail(RL_EINVAL, "rl_plan_lap: N == 0 (no path)");
+    if (!p->ran) return fail(RL_EINVAL, "rl_plan_lap: the plan has not run");
+    HIPCHK(hipSetDevice(p->device));
+    hipStream_t run_st = p->run_stream();
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : run_st;
+    p->lap_valid = false;
+    if (int rc = lap_alloc(p)) return rc;
+    for (auto& e : p->ev_lap)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    if (st != run_st) HIPCHK(hipStreamWaitEvent(st, p->ev[3], 0));
+    p->last_stream = st;
+    HIPCHK(hipEventRecord(p->ev_lap[0], st));
+    rl::PrepParams q{};
+    q.x = p->mb[0].x;
+    q.y = p->mb[0].y;
+    q.centre = p->d_lap_center;
+    q.L_out = p->d_Lmc;
+    q.cfg_src = p->d_cfg;
+    q.cfg_dst = p->d_cfg_lap;
+    q.N = p->N; q.B = p->B; q.closed = p->closed; q.ncfg = p->ncfg;
+    hipError_t e = rl::launch_path_prep(q, st);
+    if (e != hipSuccess) return fail(RL_EHIP, std::string("path prep launch: ") + hipGetErrorString(e));
+    HIPCHK(hipEventRecord(p->ev_lap[1], st));
+    // rl_lap_eval's launch: per-instance centres and lengths, empty rings, no seeds, no
+    // completion flags, no precomputed corridor
+    const ModeBufs& lb = p->lapb;
+    rl::KParams kp{};
+    kp.center = p->d_lap_center;
+    kp.center_stride = (int64_t)2 * (int64_t)p->N;
+    kp.Ls = p->d_Lmc;
+    DevRing none;                                      // (valid addresses, never read: M = 0)
+    none.vtx = p->ring.vtx; none.rec = p->ring.rec; none.flag = p->ring.flag; none.blk = p->ring.blk;
+    none.fill(kp.ring, 0, 0);
+    kp.cfg = p->d_cfg_lap;
+    set_bufs(kp, lb);
+    kp.N = p->N; kp.ncfg = p->ncfg; kp.B = p->B; kp.closed = p->closed;
+    kp.shape_B = p->shape_batch();
+    kp.L = p->L;
+    e = p->stream ? rl::launch_stream(kp, lb.sb, true, st) : rl::launch_optimize(kp, true, st);
+    if (e != hipSuccess) return fail(RL_EHIP, std::string("lap evaluation launch: ") + hipGetErrorString(e));
+    HIPCHK(hipEventRecord(p->ev_lap[2], st));
+    p->lap_valid = true;
+    p->lap_stream = st;
+    return RL_OK;
+}
+
+int rl_plan_fetch_lap(rl_plan* p, rl_out* out, double* path_len) {
+    if (!p) return fail(RL_EINVAL, "plan is NULL");
+    if (!p->lap_valid) return fail(RL_EINVAL, "rl_plan_fetch_lap: no lap stage since the plan's last run");
+    HIPCHK(hipSetDevice(p->device));
+    hipStream_t st = p->run_stream();
+    if (st != p->lap_stream) HIPCHK(hipStreamWaitEvent(st, p->ev_lap[2], 0));
+    std::vector<CopyJob> jobs;
+    field_jobs(out, p->lapb, {(size_t)p->B, (size_t)p->N, 0, 1}, true, true, jobs);
+    add_job(jobs, path_len, p->d_Lmc, (size_t)p->B * 8);
+    if (int rc = queue_downloads(jobs, st)) return rc;
+    HIPCHK(hipStreamSynchronize(st));
+    return RL_OK;
+}
+
+int rl_plan_select(rl_plan* p, const rl_select* sel, void* hip_stream) {
+    if (!p) return fail(RL_EINVAL, "plan is NULL");
+    int gs = 0;
+    if (int rc = check_select(sel, p->B, p->N, p->modes, &gs)) return rc;
+    if (!p->ran) return fail(RL_EINVAL, "rl_plan_select: the plan has not run");
+    return select_impl(p, sel, gs, false, hip_stream);
+}
+
+int rl_plan_select_scored(rl_plan* p, const rl_select* sel, int32_t score, void* hip_stream) {
+    if (!p) return fail(RL_EINVAL, "plan is NULL");
+    if (score != RL_SCORE_DEFAULT && score != RL_SCORE_LAP) return fail(RL_EINVAL, "select: unknown score");
+    int gs = 0;
+    if (int rc = check_select(sel, p->B, p->N, p->modes, &gs)) return rc;
+    if (!p->ran) return fail(RL_EINVAL, "rl_plan_select: the plan has not run");
+    const bool by_lap = score == RL_SCORE_LAP && sel->mode == RL_MODE_MINCURV;
+    if (by_lap && !p->lap_valid)
+        if (int rc = rl_plan_lap(p, hip_stream)) return rc;
+    return select_impl(p, sel, gs, by_lap, hip_stream);
+}
+
+int rl_plan_fetch_selected(rl_plan* p, int32_t* index, double* score, double* all_scores, rl_out* out) {
+    if (!p) return fail(RL_EINVAL, "plan is NULL");
+    if (!index || !score) return fail(RL_EINVAL, "rl_plan_fetch_selected: index / score is NULL");
+    if (!p->sel_mode) return fail(RL_EINVAL, "rl_plan_fetch_selected: no selection since the plan's last run");
+    HIPCHK(hipSetDevice(p->device));
+    hipStream_t st = p->run_stream();
+    std::vector<CopyJob> jobs;
+    sel_jobs(p, index, score, all_scores, out, jobs);
+    if (int rc = queue_downloads(jobs, st)) return rc;
+    HIPCHK(hipStreamSynchronize(st));
+    return RL_OK;
+}
+
+}  // extern "C"

@@ -49,6 +49,19 @@ def test_library_exports_every_declared_symbol():
     assert set(declared_functions()) <= exported
 
 
+def test_build_lists_name_every_source():
+    """build.KERNEL_SRCS / KERNEL_DEPS name files that exist, and every source or header under
+    csrc/ is a dependency: a header left out would defeat the staleness check silently."""
+    import glob
+    from practice_path_planning_for_formula_student_driverless_amd import build
+    for rel in build.KERNEL_SRCS + build.KERNEL_DEPS:
+        assert os.path.isfile(os.path.join(build.PKG, rel)), rel
+    assert set(build.KERNEL_SRCS) <= set(build.KERNEL_DEPS)
+    on_disk = {os.path.relpath(p, build.PKG).replace(os.sep, "/") for ext in ("h", "inc", "hip", "cpp")
+               for p in glob.glob(os.path.join(build.PKG, "csrc", "**", "*." + ext), recursive=True)}
+    assert on_disk and on_disk <= set(build.KERNEL_DEPS), sorted(on_disk - set(build.KERNEL_DEPS))
+
+
 def test_struct_layouts_match_c():
     probe = r'''
 #include <stdio.h>
