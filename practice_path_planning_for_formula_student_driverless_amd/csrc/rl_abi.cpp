@@ -23,7 +23,7 @@ int rl_device_count(void) {
 int rl_kernel_variant(int32_t N) {
     if (N > rl::RL_STREAM_MAX_N) return RL_ETOOBIG;
     if (use_stream(N)) return 1;
-    int k = rl::pick_k(N);
+    const int k = rl::fit_shape(rl::THR_SHAPES, N).K;
     return k < 0 ? RL_ETOOBIG : k;
 }
 

@@ -295,7 +295,7 @@ __device__ __forceinline__ void ring_rays(const RingDesc& R, const double (&qx)[
 //      lower bound |q_k - mid| - half_len already exceeds the running minimum md_k
 //      cannot lower it (std::min keeps the first of equal values), so only the others
 //      get the exact reference distance.
-template <int CK, bool TIGHT = true, bool PRUNE = true>
+template <int CK, bool TIGHT = true>
 __device__ __forceinline__ void ring_mindist(const RingDesc& R, const double (&qx)[CK], const double (&qy)[CK],
                                              const bool (&need)[CK], const double (&rad)[CK], double (&md)[CK]) {
     cu32* F = as_cu32(R.flag);
@@ -392,7 +392,7 @@ __device__ __forceinline__ void ring_mindist(const RingDesc& R, const double (&q
 #pragma unroll
             for (int k = 0; k < CK; ++k) {
                 const double ex = qx[k] - mx, ey = qy[k] - my, lim = md[k] + hr;
-                const bool may = h && need[k] && (!PRUNE || !(ex * ex + ey * ey > lim * lim));
+                const bool may = h && need[k] && !(ex * ex + ey * ey > lim * lim);
                 if (may) {
                     RL_CNT(7, 1);                                 // exact distance evaluations (lane)
                     md[k] = smin(md[k], seg_dist_exact(x0, y0, sx, sy, dn, qx[k], qy[k]));
@@ -431,7 +431,7 @@ struct NoStamp {
     __device__ __forceinline__ void operator()(int) const {}
 };
 // the fallback searches and the bounds from both rings' ray results (bp/bn/ub2 [ring][k])
-template <int CK, bool TIGHT, bool PRUNE, class Stamp>
+template <int CK, bool TIGHT, class Stamp>
 __device__ __forceinline__ void corridor_finish(const RingDesc& Ri, const RingDesc& Ro, const double (&qx)[CK],
                                                 const double (&qy)[CK], const bool (&act)[CK], double guard,
                                                 double (&bp)[2][CK], double (&bn)[2][CK], double (&ub2)[2][CK],
@@ -466,7 +466,7 @@ __device__ __forceinline__ void corridor_finish(const RingDesc& Ri, const RingDe
             const double lim = sqrt(ub2[r][k]) * (1.0 + 1e-9) + 1e-12;   // >= the true minimum
             rad[k] = fmin(lim, rad[k] * (1.0 + 1e-9) + 1e-12);
         }
-        ring_mindist<CK, TIGHT, PRUNE>(R, qx, qy, need, rad, md[r]);
+        ring_mindist<CK, TIGHT>(R, qx, qy, need, rad, md[r]);
     }
     stamp(10);
 #pragma unroll
@@ -491,7 +491,7 @@ __device__ __forceinline__ void corridor_finish(const RingDesc& Ri, const RingDe
     }
 }
 
-template <int CK, bool TIGHT = true, bool PRUNE = true, class Stamp = NoStamp>
+template <int CK, bool TIGHT = true, class Stamp = NoStamp>
 __device__ __forceinline__ void corridor_bounds(const RingDesc& Ri, const RingDesc& Ro, const double (&qx)[CK],
                                                 const double (&qy)[CK], const double (&ux)[CK],
                                                 const double (&uy)[CK], const bool (&act)[CK], double guard,
@@ -501,7 +501,7 @@ __device__ __forceinline__ void corridor_bounds(const RingDesc& Ri, const RingDe
     stamp(8);
     ring_rays<CK>(Ro, qx, qy, ux, uy, act, bp[1], bn[1], ub2[1]);
     stamp(9);
-    corridor_finish<CK, TIGHT, PRUNE>(Ri, Ro, qx, qy, act, guard, bp, bn, ub2, lo, hi, stamp);
+    corridor_finish<CK, TIGHT>(Ri, Ro, qx, qy, act, guard, bp, bn, ub2, lo, hi, stamp);
 }
 
 

@@ -61,9 +61,6 @@ struct VConst {
     int32_t _pad;
 };
 
-#ifndef RL_VC_UNI
-#define RL_VC_UNI 1      // v-pass constants in SGPRs (A/B knob)
-#endif
 // the v-pass constants as wave-uniform values (SGPR pairs) rather than per-lane VGPR copies
 // of the LDS table: the register-resident relaxations hold 3 x Cr doubles per lane already
 __device__ __forceinline__ VConst vconst_uniform(const VConst& s) {
@@ -88,9 +85,6 @@ __device__ __forceinline__ VConst vconst_uniform(const VConst& s) {
 // min(a_res, acc_cap) bit for bit.
 __device__ __forceinline__ bool power_never_binds(double Pmax, double mass, double kFd, double Fr, double v_cap,
                                                   double acc_cap) {
-#if defined(RL_PWF) && RL_PWF == 0
-    return false;                    // A/B knob: always evaluate the power limit
-#endif
     if (!(Pmax > 0.0) || !(mass > 0.0) || !(v_cap > 1e-6) || !(kFd >= 0.0) || !(Fr >= 0.0)) return false;
     if (!(Pmax < 1e300) || !(mass < 1e300) || !(v_cap < 1e150) || !(kFd < 1e300) || !(Fr < 1e300)) return false;
     if (!(acc_cap < 1e8) || !(acc_cap > -1e300)) return false;
@@ -118,7 +112,7 @@ __device__ __forceinline__ double vmin_f64(double a, double b) {
 
 // The v-pass steps below sit on the velocity profile's serial dependency chain (each
 // step needs the previous one's value), so their latency, not their throughput, sets the
-// v-pass time.  RL_VSTEP_FAST (A/B knob) shortens that chain without changing a bit:
+// v-pass time.  These forms shorten that chain without changing a bit:
 //  * std::max(0.0, x) as v_max_f64(+0, x): equal for every x that is not a signalling NaN
 //    (x > 0: x; x = +0, -0, < 0, -inf or a quiet NaN: +0 both ways); one instruction
 //    instead of a compare and two selects;
@@ -131,18 +125,9 @@ __device__ __forceinline__ double vmin_f64(double a, double b) {
 // A signalling-NaN cap would make v_min_f64 return a quiet NaN where the select form
 // returns the other operand, so the caps are loaded canonicalised (vs_cap: a signalling
 // NaN quieted, every other value unchanged, zero signs included).
-#ifndef RL_VSTEP_FAST
-#define RL_VSTEP_FAST 1
-#endif
-#if RL_VSTEP_FAST
 __device__ __forceinline__ double vs_cap(double x) { return __builtin_canonicalize(x); }
 __device__ __forceinline__ double vs_max0(double x) { return vmax_f64(0.0, x); }
 __device__ __forceinline__ double vs_min(double a, double b) { return vmin_f64(a, b); }
-#else
-__device__ __forceinline__ double vs_cap(double x) { return x; }
-__device__ __forceinline__ double vs_max0(double x) { return smax(0.0, x); }
-__device__ __forceinline__ double vs_min(double a, double b) { return smin(a, b); }
-#endif
 
 // forward step of velocity_profile_forward_backward (ref:829-833):
 //   a_acc = ax_max_at(v,k).first ; return sqrt(max(0, v*v + 2*a_acc*h))
@@ -150,20 +135,12 @@ __device__ __forceinline__ double vstep_fwd(const VConst& c, double vi, double k
     double alat = vi * vi * fabs(ki);
     double a_res = sqrt(vs_max0(c.a_total2 - alat * alat));
     double a_acc = vs_min(a_res, c.acc_cap);
-#if defined(RL_PW_BRANCH) && RL_PW_BRANCH == 0
-    if (true) {
-#else
-    if (!__builtin_amdgcn_readfirstlane(c.pw_free)) {
-#endif   // uniform per instance (power_never_binds)
+    if (!__builtin_amdgcn_readfirstlane(c.pw_free)) {   // uniform per instance (power_never_binds)
         double Fd = c.kFd * vi * vi;
-#if RL_VSTEP_FAST
         // evaluated unconditionally and selected: as the arm of a branch its two divisions ran
         // after the a_res chain instead of beside it (a discarded value has no effect)
         const double ap = c.Pmax / (c.mass * vi) - (Fd + c.Fr) / c.mass;
         double a_power = (c.Pmax > 0 && vi > 1e-6) ? ap : 1e9;
-#else
-        double a_power = (c.Pmax > 0 && vi > 1e-6) ? (c.Pmax / (c.mass * vi) - (Fd + c.Fr) / c.mass) : 1e9;
-#endif
         a_acc = vs_min(a_acc, a_power);     // std::min({a_res, cap, a_power}) ref:818
     }
     a_acc = vs_max0(a_acc);

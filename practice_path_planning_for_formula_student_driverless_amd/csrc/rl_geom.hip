@@ -140,13 +140,7 @@ __global__ __launch_bounds__(256) void rl_corridor_kernel(CorrParams c) {
 }
 
 #ifdef RL_COUNT
-int debug_counts_geom(unsigned long long* host, int reset) {
-    if (reset) {
-        unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        return hipMemcpyToSymbol(HIP_SYMBOL(rl_dbg_count), z, sizeof(z)) == hipSuccess ? 0 : -3;
-    }
-    return hipMemcpyFromSymbol(host, HIP_SYMBOL(rl_dbg_count), sizeof(unsigned long long) * 8) == hipSuccess ? 0 : -3;
-}
+int debug_counts_geom(unsigned long long* host, int reset) { return read_counts(rl_dbg_count, host, reset); }
 #endif
 
 hipError_t launch_corridor(const CorrParams& c, hipStream_t st) {

@@ -97,39 +97,58 @@ constexpr int RL_STREAM_ARRAYS = 15;
 constexpr int RL_REG_MAX_N = 4096;          // register-resident kernel covers N <= 4096
 constexpr int RL_STREAM_MAX_N = 1 << 20;
 
-// samples per lane for N (4, 5 or 8) of the throughput shapes, or -1 if N exceeds the
-// register-resident kernel
-int pick_k(int N);
 // (K samples per lane, T lanes per instance) of a register-resident launch
 struct Shape {
     int K, T;
 };
-// Latency shapes (rl_kernels_lat.hip) by N: one instance spread over a whole CU, for
-// batches that leave most of the GPU idle (build knobs for A/B timing).  Above N = 2048
-// the throughput shape (8, 512) already spreads an instance over 8 waves (a 1024-lane
-// shape would be capped at 128 VGPRs and spill).
-#ifndef RL_LAT1_K
-#define RL_LAT1_K 1      // N <= 256: (1, 256)
+inline bool operator==(const Shape& a, const Shape& b) { return a.K == b.K && a.T == b.T; }
+
+// Variant for 1024 < N <= 2048 (the C2/C3 tracks): RL_MID_K samples per lane, RL_MID_T lanes
+// per instance.  Build-time knobs so variants can be A/B-timed.
+#ifndef RL_MID_K
+#define RL_MID_K 8
 #endif
-#ifndef RL_LAT2_K
-#define RL_LAT2_K 1      // N <= 512: (1, 512), 8 waves (A/B: testday3 N=261 2.20 -> 1.75 ms vs (2, 256))
+#ifndef RL_MID_T
+#define RL_MID_T 256
 #endif
-#ifndef RL_LAT3_K
-#define RL_LAT3_K 2      // N <= 1024: (2, 512)
+// min-time at 1024 < N <= 2048: the extra γ² state favours 4 samples per lane
+#ifndef RL_MIDMT_K
+#define RL_MIDMT_K 4
 #endif
-// RL_LAT_FIT: for N <= 512 one sample per lane on just enough waves, T = max(128, N rounded
-// up to 64): fewer waves make the evaluation's barrier and cross-wave sum cheaper (A/B:
-// testday3 N=261 (1, 512) -> (1, 320) 1.76 -> 1.68 ms min-curv, 2.25 -> 2.16 ms min-time;
-// 0 keeps the RL_LAT1_K / RL_LAT2_K table)
-#ifndef RL_LAT_FIT
-#define RL_LAT_FIT 1
+#ifndef RL_MIDMT_T
+#define RL_MIDMT_T 512
 #endif
-inline Shape lat_shape(int N) {
-    if (RL_LAT_FIT && N <= 512) return {1, N <= 128 ? 128 : (N + 63) / 64 * 64};
-    if (N <= 256) return {RL_LAT1_K, 256 / RL_LAT1_K};
-    if (N <= 512) return {RL_LAT2_K, 512 / RL_LAT2_K};
-    if (N <= 1024) return {RL_LAT3_K, 1024 / RL_LAT3_K};
-    if (N <= 2048) return {4, 512};
+
+// The shape tables.  A row (K, T) serves N <= K * T and the first row that fits is taken
+// (fit_shape); X(K, T) is expanded once per row, for the tables here and for the launch
+// dispatch of the translation unit that instantiates the rows (rl_optimize_body.h
+// RL_LAUNCH_IF).
+// Throughput shapes (rl_kernels.hip; every batch that fills the GPU): one wave per instance
+// up to N = 512.  (5, 64) for 256 < N <= 320 (testday1/3 of the bundled tracks): 5 samples per
+// lane instead of 8, 0 B scratch and two waves per SIMD in both modes.  C4
+// (scripts/ab_c4_single.py, profiles/r05/ab_c4_s5.log): those plans alone min-time 4.16 / 4.59
+// -> 3.32 / 3.74 ms, min-curv 3.64 / 3.97 -> 3.07 / 3.36 ms; the concurrent sweep 17.55 ->
+// 16.42 ms, bit-exact.  XMID: the row that min-time leaves for (RL_MIDMT_K, RL_MIDMT_T) below
+// two instances per CU (pick_shape).
+#define RL_SHAPES_THR(X, XMID) X(4, 64) X(5, 64) X(8, 64) X(8, 128) XMID(RL_MID_K, RL_MID_T) X(8, 512)
+// Latency shapes (rl_kernels_lat.hip): one instance spread over a whole CU, while the batch
+// needs at most one wave per SIMD in them (B x T/64 <= 4 x CUs) -- the drop-in use, one track
+// per call (ref:1347, 1397).  Up to N = 512 one sample per lane on just enough waves: fewer
+// waves make the evaluation's barrier and cross-wave sum cheaper (testday3 N=261 (2, 256) ->
+// (1, 512) 2.20 -> 1.75 ms, (1, 512) -> (1, 320) 1.76 -> 1.68 ms min-curv, 2.25 -> 2.16 ms
+// min-time).  The table ends with the (4, 512) shape of rl_kernels_mid.hip; above N = 2048 the
+// throughput shape (8, 512) already spreads an instance over 8 waves (a 1024-lane shape would
+// be capped at 128 VGPRs and spill).
+#define RL_SHAPES_LAT(X) X(1, 128) X(1, 192) X(1, 256) X(1, 320) X(1, 384) X(1, 448) X(1, 512) X(2, 512)
+#define RL_SHAPE_MID4(X) X(4, 512)
+#define RL_SHAPE_ROW(K_, T_) {K_, T_},
+constexpr Shape THR_SHAPES[] = {RL_SHAPES_THR(RL_SHAPE_ROW, RL_SHAPE_ROW)};
+constexpr Shape LAT_SHAPES[] = {RL_SHAPES_LAT(RL_SHAPE_ROW) RL_SHAPE_MID4(RL_SHAPE_ROW)};
+// the first row of a table that holds N samples, {-1, -1} if none does
+template <int R>
+inline Shape fit_shape(const Shape (&rows)[R], int N) {
+    for (const Shape& s : rows)
+        if (N <= s.K * s.T) return s;
     return {-1, -1};
 }
 // the shape launch_optimize uses for N samples and a batch of B instances on a device with
@@ -144,14 +163,14 @@ bool group_shape(const Shape& s);
 // all ragged (N % K != 0) or none, one mode: rl_kernels_group.hip
 hipError_t launch_optimize_group(const KGroup& g, const Shape& s, bool closed, bool ragged, bool mintime,
                                  hipStream_t st);
-// the launches of the latency shapes lat_shape(p.N) and of every (4, 512) shape (also the
-// min-time shape for 1024 < N <= 2048 below two instances per CU), rl_kernels_lat.hip
-hipError_t launch_optimize_lat(const KParams& p, bool mintime, hipStream_t st);
-// the (4, 512) launches (1024 < N <= 2048), rl_kernels_mid.hip
-hipError_t launch_optimize_mid(const KParams& p, bool mintime, hipStream_t st);
+// the launch of shape s if it is a latency shape (LAT_SHAPES; (4, 512) is also the min-time
+// shape for 1024 < N <= 2048 below two instances per CU), rl_kernels_lat.hip
+hipError_t launch_optimize_lat(const KParams& p, const Shape& s, bool mintime, hipStream_t st);
+// the (4, 512) launches, rl_kernels_mid.hip
+hipError_t launch_optimize_mid(const KParams& p, const Shape& s, bool mintime, hipStream_t st);
 // large-N variant: one workgroup of stream_threads() threads per instance, state in HBM
 hipError_t launch_stream(const KParams& p, const StreamBufs& sb, bool mintime, hipStream_t st);
-// threads per instance of the streaming kernel (its build knob RL_STS, 1024 by default)
+// threads per instance of the streaming kernel (1024)
 int stream_threads();
 // step 6 geometry (rl_geom.hip): spline knots [5][nk] per axis (s,a,b,c,d), rows [Kmax+dup][9]
 struct GeomParams {
@@ -179,12 +198,27 @@ hipError_t launch_corridor(const CorrParams& c, hipStream_t st);
 int format_rows(const double* table, int64_t rows, int cols, char* out, uint64_t cap, uint64_t* offs,
                 uint64_t* total, hipStream_t st);
 #ifdef RL_STAMPS
+// diagnostic builds: the first nblocks rows of a translation unit's per-phase cycle totals
+template <class Sym>
+inline int read_stamps(const Sym& stamps, unsigned long long* host, int nblocks) {
+    if (nblocks > 16384) nblocks = 16384;
+    return hipMemcpyFromSymbol(host, HIP_SYMBOL(stamps), sizeof(unsigned long long) * 16 * nblocks) == hipSuccess ? 0 : -3;
+}
 int debug_stamps(unsigned long long* host, int nblocks);
 int debug_stamps_stream(unsigned long long* host, int nblocks);
 int debug_stamps_lat(unsigned long long* host, int nblocks);
 int debug_stamps_mid(unsigned long long* host, int nblocks);
 #endif
 #ifdef RL_COUNT
+// diagnostic builds: a translation unit's eight corridor counters, or (reset) zero them
+template <class Sym>
+inline int read_counts(const Sym& counts, unsigned long long* host, int reset) {
+    if (reset) {
+        unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        return hipMemcpyToSymbol(HIP_SYMBOL(counts), z, sizeof(z)) == hipSuccess ? 0 : -3;
+    }
+    return hipMemcpyFromSymbol(host, HIP_SYMBOL(counts), sizeof(unsigned long long) * 8) == hipSuccess ? 0 : -3;
+}
 int debug_counts(unsigned long long* host, int reset);
 int debug_counts_geom(unsigned long long* host, int reset);
 int debug_counts_reg(unsigned long long* host, int reset);

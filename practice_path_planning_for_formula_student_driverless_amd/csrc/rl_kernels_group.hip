@@ -31,7 +31,7 @@ static hipError_t launch_gk(const KGroup& g, bool closed, bool ragged, bool mt, 
 }
 
 bool group_shape(const Shape& s) {
-    return s.T == 64 && (s.K == 4 || s.K == 5 || s.K == 8);
+    return s.T == 64 && s == fit_shape(THR_SHAPES, s.K * s.T);   // a one-wave row of the throughput table
 }
 
 hipError_t launch_optimize_group(const KGroup& g, const Shape& s, bool closed, bool ragged, bool mintime,

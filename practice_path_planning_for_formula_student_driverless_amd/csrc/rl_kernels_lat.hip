@@ -16,51 +16,15 @@
 
 namespace rl {
 
-template <int K, int T, bool CL, bool MT>
-static hipError_t launch_lat_t(const KParams& p, hipStream_t st) {
-    if constexpr (K > 1) {
-        if (p.N % K) {
-            hipLaunchKernelGGL((rl_optimize_kernel<K, T, CL, MT, true>), dim3(p.B), dim3(T), 0, st, p);
-            return hipGetLastError();
-        }
-    }
-    hipLaunchKernelGGL((rl_optimize_kernel<K, T, CL, MT, false>), dim3(p.B), dim3(T), 0, st, p);
-    return hipGetLastError();
-}
-template <int K, int T>
-static hipError_t launch_lat_kt(const KParams& p, bool mt, hipStream_t st) {
-    static_assert(T % 64 == 0 && T <= 512, "latency shape");
-    if (p.closed) return mt ? launch_lat_t<K, T, true, true>(p, st) : launch_lat_t<K, T, true, false>(p, st);
-    return mt ? launch_lat_t<K, T, false, true>(p, st) : launch_lat_t<K, T, false, false>(p, st);
-}
-
 #ifdef RL_STAMPS
 // diagnostic builds: this translation unit's copy of the per-phase cycle totals
-int debug_stamps_lat(unsigned long long* host, int nblocks) {
-    if (nblocks > 16384) nblocks = 16384;
-    return hipMemcpyFromSymbol(host, HIP_SYMBOL(rl_dbg_stamps), sizeof(unsigned long long) * 16 * nblocks) == hipSuccess ? 0 : -3;
-}
+int debug_stamps_lat(unsigned long long* host, int nblocks) { return read_stamps(rl_dbg_stamps, host, nblocks); }
 #endif
 
-hipError_t launch_optimize_lat(const KParams& p, bool mintime, hipStream_t st) {
-    if (p.N <= 0 || p.N > 2048) return hipErrorInvalidValue;
-#if RL_LAT_FIT
-    if (p.N <= 512) {
-        switch (lat_shape(p.N).T) {
-            case 128: return launch_lat_kt<1, 128>(p, mintime, st);
-            case 192: return launch_lat_kt<1, 192>(p, mintime, st);
-            case 256: return launch_lat_kt<1, 256>(p, mintime, st);
-            case 320: return launch_lat_kt<1, 320>(p, mintime, st);
-            case 384: return launch_lat_kt<1, 384>(p, mintime, st);
-            case 448: return launch_lat_kt<1, 448>(p, mintime, st);
-            default: return launch_lat_kt<1, 512>(p, mintime, st);
-        }
-    }
-#endif
-    if (p.N <= 256) return launch_lat_kt<RL_LAT1_K, 256 / RL_LAT1_K>(p, mintime, st);
-    if (p.N <= 512) return launch_lat_kt<RL_LAT2_K, 512 / RL_LAT2_K>(p, mintime, st);
-    if (p.N <= 1024) return launch_lat_kt<RL_LAT3_K, 1024 / RL_LAT3_K>(p, mintime, st);
-    return launch_optimize_mid(p, mintime, st);       // (4, 512): rl_kernels_mid.hip
+hipError_t launch_optimize_lat(const KParams& p, const Shape& s, bool mintime, hipStream_t st) {
+    if (p.N <= 0 || p.N > s.K * s.T) return hipErrorInvalidValue;
+    RL_SHAPES_LAT(RL_LAUNCH_IF)
+    return launch_optimize_mid(p, s, mintime, st);       // (4, 512): rl_kernels_mid.hip
 }
 
 }  // namespace rl

@@ -7,28 +7,15 @@
 
 namespace rl {
 
-template <bool CL, bool MT>
-static hipError_t launch_mid_t(const KParams& p, hipStream_t st) {
-    if (p.N % 4) {
-        hipLaunchKernelGGL((rl_optimize_kernel<4, 512, CL, MT, true>), dim3(p.B), dim3(512), 0, st, p);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL((rl_optimize_kernel<4, 512, CL, MT, false>), dim3(p.B), dim3(512), 0, st, p);
-    return hipGetLastError();
-}
-
 #ifdef RL_STAMPS
 // diagnostic builds: this translation unit's copy of the per-phase cycle totals
-int debug_stamps_mid(unsigned long long* host, int nblocks) {
-    if (nblocks > 16384) nblocks = 16384;
-    return hipMemcpyFromSymbol(host, HIP_SYMBOL(rl_dbg_stamps), sizeof(unsigned long long) * 16 * nblocks) == hipSuccess ? 0 : -3;
-}
+int debug_stamps_mid(unsigned long long* host, int nblocks) { return read_stamps(rl_dbg_stamps, host, nblocks); }
 #endif
 
-hipError_t launch_optimize_mid(const KParams& p, bool mintime, hipStream_t st) {
+hipError_t launch_optimize_mid(const KParams& p, const Shape& s, bool mintime, hipStream_t st) {
     if (p.N <= 1024 || p.N > 2048) return hipErrorInvalidValue;
-    if (p.closed) return mintime ? launch_mid_t<true, true>(p, st) : launch_mid_t<true, false>(p, st);
-    return mintime ? launch_mid_t<false, true>(p, st) : launch_mid_t<false, false>(p, st);
+    RL_SHAPE_MID4(RL_LAUNCH_IF)
+    return hipErrorInvalidValue;
 }
 
 }  // namespace rl

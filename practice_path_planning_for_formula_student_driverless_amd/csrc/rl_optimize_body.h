@@ -46,9 +46,9 @@ namespace rl {
 #define RL_CK 2
 #endif
 constexpr int CK = (RL_CK < 8 ? RL_CK : 8);   // corridor sub-chunk (samples per ring pass)
-#ifndef RL_MD_TIGHT
-#define RL_MD_TIGHT 0    // fallback search: nearest-midpoint radius pass (rl_corridor.h ring_mindist; A/B: +0.8% C2 here, -21% C5 in the streaming kernel)
-#endif
+// The fallback search's nearest-midpoint radius pass (rl_corridor.h ring_mindist, TIGHT) is
+// off in this kernel (corridor_bounds<CKK, false>): it measured +0.8 % on C2 here and -21 % on
+// C5 in the streaming kernel, which keeps it.
 // v-pass: in-wave relaxation rounds between two cross-wave exchanges (barriers), per shape.
 // A/B (scripts/ab_variants.py, caps 1 (= one barrier per round), 2, 4, 8, 16): the (4, 512)
 // latency shape gains 5 % from 8-16 rounds; the (8, 256) throughput shape at two instances
@@ -65,9 +65,6 @@ struct VpRounds {
     static constexpr int value = (T == 64) ? 0x7fffffff
                                  : ((K == 4 && T == 512) || K <= 2 || T >= 1024) ? RL_VP_ROUNDS : 1;
 };
-#ifndef RL_MD_PRUNE
-#define RL_MD_PRUNE 1    // fallback search: running-minimum pruning in the exact walk
-#endif
 
 // Diagnostic build only (-DRL_STAMPS=1): per-phase s_memtime totals of each
 // workgroup's wave 0, written to a device array no other code reads.
@@ -219,17 +216,13 @@ __device__ __forceinline__ void put(double (&a)[K], int idx, double v) {
     }
 }
 
-// v-pass warm starts (min-time, see vpass): 0 off, 1 multi-wave shapes only, 2 every
-// min-time shape.  In the one-wave (K, 64) throughput shapes (C1/C4) the in-wave rounds are
+// v-pass warm starts (min-time, see vpass): the multi-wave shapes only.  In the one-wave (K, 64) throughput shapes (C1/C4) the in-wave rounds are
 // cheap DPP steps and the starts leave the kernel time as it is, while their 2 KB table
 // costs LDS granules that concurrent plans share (C4 min-time 8.7 -> 11.9 ms wall at equal
 // kernel times, scripts/ab_c4_single.py, profiles/r05/ab_c4_lds.log)
-#ifndef RL_WARM
-#define RL_WARM 1
-#endif
 template <int T, bool MT>
 struct WarmStart {
-    static constexpr bool value = MT && (RL_WARM == 2 || (RL_WARM == 1 && T > 64));
+    static constexpr bool value = MT && T > 64;
 };
 
 // min-time: warm start of the v-pass relaxations, per thread the incoming value its chunk
@@ -278,24 +271,11 @@ struct alignas(16) Smem : PubTab<T / 64>, WarmTab<T, WARM> {
 };
 
 // --------------------------------------------------------------- the kernel
-// Variant for 1024 < N <= 2048 (the C2/C3 tracks): RL_MID_K samples per lane,
-// RL_MID_T lanes per instance, RL_MID_W waves per SIMD requested from the
-// register allocator.  Build-time knobs so variants can be A/B-timed.
-#ifndef RL_MID_K
-#define RL_MID_K 8
-#endif
-#ifndef RL_MID_T
-#define RL_MID_T 256
-#endif
+// Waves per SIMD requested from the register allocator for the (RL_MID_K, RL_MID_T) and
+// (RL_MIDMT_K, RL_MIDMT_T) shapes of 1024 < N <= 2048 (rl_kernels.h).  Build-time knobs so
+// variants can be A/B-timed.
 #ifndef RL_MID_W
 #define RL_MID_W 2
-#endif
-// min-time at 1024 < N <= 2048: the extra γ² state favours 4 samples per lane
-#ifndef RL_MIDMT_K
-#define RL_MIDMT_K 4
-#endif
-#ifndef RL_MIDMT_T
-#define RL_MIDMT_T 512
 #endif
 #ifndef RL_MIDMT_W
 #define RL_MIDMT_W 2
@@ -327,13 +307,10 @@ struct alignas(16) Smem : PubTab<T / 64>, WarmTab<T, WARM> {
 
 // latency shapes (rl_kernels_lat.hip: K <= 2, or 1024 lanes): one instance per CU, so one
 // wave per SIMD may use the whole register file (1024 lanes need 4 per SIMD regardless)
-#ifndef RL_LAT_W
-#define RL_LAT_W 1
-#endif
 // waves per SIMD to keep resident (caps the register budget the compiler may use)
 template <int K, int T, bool MT>
 struct MinWaves {
-    static constexpr int value = (K <= 2 || T >= 1024)                   ? RL_LAT_W
+    static constexpr int value = (K <= 2 || T >= 1024)                   ? 1
                                  : (K == RL_MID_K && T == RL_MID_T)       ? RL_MID_W
                                  : (K == RL_MIDMT_K && T == RL_MIDMT_T) ? RL_MIDMT_W
                                  : (T >= 512)                           ? 1
@@ -394,5 +371,34 @@ __global__ __launch_bounds__(T, (MinWaves<K, T, MT>::value)) void rl_optimize_gr
         if (i < g.n && blk >= g.start[i]) j = i;
     rl_optimize_body<K, T, CLOSED, MT, RAGGED>(g.p[j], blk - g.start[j]);
 }
+
+// ------------------------------------------------------------------ launcher
+// One persistent launch of shape (K, T), one workgroup per instance: the ragged form if N % K
+// leaves a partial chunk (K = 1 has none), fanned out over the boundary (closed / open) by the
+// <K, T, MT> form and over boundary and mode by the <K, T> form.  A translation unit
+// instantiates the kernels of exactly the shapes it calls these with.
+template <int K, int T, bool CL, bool MT>
+static hipError_t launch_shape(const KParams& p, hipStream_t st) {
+    if constexpr (K > 1) {
+        if (p.N % K) {
+            hipLaunchKernelGGL((rl_optimize_kernel<K, T, CL, MT, true>), dim3(p.B), dim3(T), 0, st, p);
+            return hipGetLastError();
+        }
+    }
+    hipLaunchKernelGGL((rl_optimize_kernel<K, T, CL, MT, false>), dim3(p.B), dim3(T), 0, st, p);
+    return hipGetLastError();
+}
+template <int K, int T, bool MT>
+static hipError_t launch_shape(const KParams& p, hipStream_t st) {
+    return p.closed ? launch_shape<K, T, true, MT>(p, st) : launch_shape<K, T, false, MT>(p, st);
+}
+template <int K, int T>
+static hipError_t launch_shape(const KParams& p, bool mt, hipStream_t st) {
+    if (p.closed) return mt ? launch_shape<K, T, true, true>(p, st) : launch_shape<K, T, true, false>(p, st);
+    return mt ? launch_shape<K, T, false, true>(p, st) : launch_shape<K, T, false, false>(p, st);
+}
+// a row of a launch dispatch over a shape list of rl_kernels.h: launch s if it is (K_, T_)
+#define RL_LAUNCH_IF(K_, T_) \
+    if (s == Shape{K_, T_}) return launch_shape<K_, T_>(p, mintime, st);
 
 }  // namespace rl

@@ -141,26 +141,15 @@
     // the parity of the evaluation's one barrier), with the same expressions the owners
     // use.  One barrier per evaluation instead of two: in a one-instance launch the
     // barrier and its LDS round trip, not the arithmetic, set the latency.
-#ifndef RL_GHOST
-#define RL_GHOST 1
-#endif
-#ifndef RL_GHOST_KMAX
-#define RL_GHOST_KMAX 2      // ghost samples for K <= this (A/B knob)
-#endif
-    constexpr bool GHOST = RL_GHOST && NW > 1 && K <= RL_GHOST_KMAX;
+    constexpr int GHOST_KMAX = 2;      // ghost samples for K <= this
+    constexpr bool GHOST = NW > 1 && K <= GHOST_KMAX;
     // min-time latency shapes: the v-pass on one wave beside the corridor (VSPLIT, see vpass1w)
-#ifndef RL_VSPLIT
-#define RL_VSPLIT 1
-#endif
-    constexpr bool VSPLIT = RL_VSPLIT && MT && K == 1 && NW >= 2 && T <= 512;
+    constexpr bool VSPLIT = MT && K == 1 && NW >= 2 && T <= 512;
     // Speculative gradient (latency shapes): every trial's gradient is evaluated before its
     // Armijo test (the bundled tracks accept 120 of 122-137 trials per outer iteration), so
     // the gradient's LDS reads and arithmetic run beside the J/decrease sums instead of
     // after them.  A rejected trial's gradient is discarded; nothing else changes.
-#ifndef RL_SPEC_GRAD
-#define RL_SPEC_GRAD 1
-#endif
-    constexpr bool SPEC = RL_SPEC_GRAD && GHOST;
+    constexpr bool SPEC = GHOST;
     constexpr int KT = K * T;
     __shared__ double gq[GHOST ? 2 * 3 * KT : 1];      // [parity][q1 | q2 | D1α][sample]
     __shared__ double gred[GHOST ? 2 * 2 * NW : 1];    // [parity][J | decrease][wave]
@@ -309,10 +298,10 @@
             } else {
 #ifdef RL_STAMPS
             RL_STAMP(7);
-            corridor_bounds<CKK, RL_MD_TIGHT != 0, RL_MD_PRUNE != 0>(p.ring[0], p.ring[1], qx, qy, ux, uy, act, guard,
+            corridor_bounds<CKK, false>(p.ring[0], p.ring[1], qx, qy, ux, uy, act, guard,
                                                                       lc, hc, [&](int s) { RL_STAMP(s); });
 #else
-            corridor_bounds<CKK, RL_MD_TIGHT != 0, RL_MD_PRUNE != 0>(p.ring[0], p.ring[1], qx, qy, ux, uy, act, guard,
+            corridor_bounds<CKK, false>(p.ring[0], p.ring[1], qx, qy, ux, uy, act, guard,
                                                                       lc, hc);
 #endif
             }
@@ -365,7 +354,7 @@
     auto same_bits = [](double a, double b) RL_AI -> bool { return __double_as_longlong(a) == __double_as_longlong(b); };
     // returns sweeps executed; padding samples hold ka=0, v=+inf (never bind)
     auto vpass = [&](const double (&ka)[K], double (&v)[K]) RL_AI -> int {
-        const VConst vc = RL_VC_UNI ? vconst_uniform(sm.vc) : sm.vc;
+        const VConst vc = vconst_uniform(sm.vc);
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             double kk = fabs(ka[k]);
@@ -551,7 +540,7 @@
     __shared__ double vsv[VSPLIT ? T : 1];
     double vwg[4] = {INFINITY, INFINITY, INFINITY, INFINITY};   // warm starts (the v-pass wave's lanes)
     auto vpass1w = [&]() RL_AI -> int {
-        const VConst vc = RL_VC_UNI ? vconst_uniform(sm.vc) : sm.vc;
+        const VConst vc = vconst_uniform(sm.vc);
         const int b0 = lane * KP;
         const int c1 = min(KP, max(0, N - b0));
         double ka1[KP], v[KP];
@@ -747,28 +736,19 @@
     double q1[K], q2[K], a1v[K];                    // gradient stencil inputs of the last evaluation
     // Min-curv keeps A1, A2, N0 of its own samples in registers from lin-geom on (the single
     // gradient array left the room: 247 VGPRs, no scratch) and reads only W from LDS per
-    // evaluation.  A/B (build knob RL_A12_REG = 0 / 1 / 2: none / A1,A2 / A1,A2,N0 in
-    // registers): C2 8.81 / 8.71 / 8.69 ms, bit-exact.  Min-time has no room (γ²), nor has
+    // evaluation.  Measured (none / A1,A2 / A1,A2,N0 in registers): C2 8.81 / 8.71 / 8.69 ms, bit-exact.  Min-time has no room (γ²), nor has
     // the open K = 8 min-curv kernel (its boundary stencils: scratch 100 -> 172 B/lane, the
     // open C2-shaped run 21.4 -> 25.0 ms).
-#ifndef RL_A12_REG
-#define RL_A12_REG 2
-#endif
-#ifndef RL_A12_MT
-// min-time, shapes of 256+ lanes: 0 none, 1 N0, 2 A1+A2, 3 all three in registers.  2: C3
-// (B = 4096, (8, 256)) min-time 39.19 -> 38.77 ms at 32 B/lane of scratch outside the loop,
-// B = 256 ((4, 512)) 7.50 -> 7.34 ms, bit-exact (profiles/r05/ab_c3_a12mt.log)
-#define RL_A12_MT 2
-#endif
+    // Min-time, closed shapes of 256+ lanes: A1 and A2 in registers (of none, N0, A1+A2, all
+    // three).  C3 (B = 4096, (8, 256)) min-time 39.19 -> 38.77 ms at 32 B/lane of scratch
+    // outside the loop, B = 256 ((4, 512)) 7.50 -> 7.34 ms, bit-exact
+    // (profiles/r05/ab_c3_a12mt.log)
     // The latency shapes (K <= 2 samples per lane, registers to spare) hold all four
     // coefficients in registers: no LDS read on the evaluation's dependency chain
-#ifndef RL_LAT_COEF_REG
-#define RL_LAT_COEF_REG 1
-#endif
-    constexpr bool ALLR = RL_LAT_COEF_REG && K <= 2;
-    constexpr bool A12R = ALLR || (RL_A12_REG && !MT && (CLOSED || K < 8)) || (MT && CLOSED && T >= 256 && (RL_A12_MT & 2));   // (A1, A2) in registers instead of LDS
-    constexpr bool N0R = ALLR || (A12R && !MT && RL_A12_REG >= 2) || (MT && CLOSED && T >= 256 && (RL_A12_MT & 1));            // and N0
-    constexpr bool WR = ALLR;                                                                                   // and W
+    constexpr bool ALLR = K <= 2;
+    constexpr bool A12R = ALLR || (!MT && (CLOSED || K < 8)) || (MT && CLOSED && T >= 256);   // (A1, A2) in registers instead of LDS
+    constexpr bool N0R = ALLR || (A12R && !MT);                                                // and N0
+    constexpr bool WR = ALLR;                                                                  // and W
     double A1r[K], A2r[K], N0r[K], Wr[K];
 
     // One evaluation (eval_cost_grad_frozen ref:654-675 / _timeweighted ref:866-895)
@@ -865,9 +845,7 @@
             rv = trial ? tR : cR;
         } else {
             xpub(0, a);
-#ifndef RL_PROBE_NOB1       // timing probe only (wrong results): the trial halo's barrier removed
             if constexpr (NW > 1) __syncthreads();
-#endif
             xget(0, a, lv, rv);
         }
         const double pJ = eval_part(a, lv, rv);
@@ -1214,12 +1192,7 @@
         for (int k = 0; k < K; ++k)
             zb_lane |= (__double_as_longlong(lo[k]) == (long long)0x8000000000000000ull) ||
                        (hi[k] == 0.0 && k < cnt);
-#ifdef RL_PROBE_NOZB      // timing probe only (zero signs may differ): every clamp as maxNum/minNum
-        const bool zb = false;
-        (void)zb_lane;
-#else
         const bool zb = __builtin_amdgcn_ballot_w64(zb_lane) != 0;
-#endif
         double step = step_init;
         // trial vector std::min(hi, std::max(lo, cur - step*grad)) (ref:731)
         auto project = [&](const double (&cur)[K], const double (&g)[K], double (&nxt)[K]) RL_AI {
@@ -1234,13 +1207,8 @@
                 for (int k = 0; k < K; ++k) nxt[k] = smin(hi[k], smax(lo[k], ai[k]));   // the select forms
             }
             if constexpr (GHOST) {               // the neighbour samples' trial values
-#ifdef RL_PROBE_NOZB
-                tL = vmin_f64(hiL, vmax_f64(loL, cL - step * gL));
-                tR = vmin_f64(hiR, vmax_f64(loR, cR - step * gR));
-#else
                 tL = smin(hiL, smax(loL, cL - step * gL));
                 tR = smin(hiR, smax(loR, cR - step * gR));
-#endif
             }
         };
         double dec;

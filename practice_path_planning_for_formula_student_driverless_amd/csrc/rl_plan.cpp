@@ -231,8 +231,7 @@ int rl_plan_run(rl_plan* p, void* hip_stream) {
     const int first_m = (p->modes & RL_MODE_MINCURV) ? 0 : 1;
     bool pre0 = p->N > 0 && p->max_outer > 0 && p->center_stride == 0 && p->margin_uniform && p->B >= 2;
     if (pre0 && !p->stream) {
-        const rl::Shape s = rl::pick_shape(p->N, sB, first_m == 1, cus), lat = rl::lat_shape(p->N);
-        pre0 = !(s.K == lat.K && s.T == lat.T);
+        pre0 = !(rl::pick_shape(p->N, sB, first_m == 1, cus) == rl::fit_shape(rl::LAT_SHAPES, p->N));
     }
     if (pre0) {
         const char* e = std::getenv("RL_CORRIDOR0");

@@ -37,23 +37,15 @@ namespace rl {
 namespace {
 // threads per instance (C5 A/B: 1024 -> 32.5 ms, 512 -> 38.3 ms, 256 -> 36.7 ms;
 // profiles/r01/ab_c5_stream_wg.log)
-#ifndef RL_STS
-#define RL_STS 1024
-#endif
-constexpr int TS = RL_STS;        // threads per instance
+constexpr int TS = 1024;          // threads per instance
 constexpr int NWS = TS / 64;
 
 // The lane's first index of a strided pass, opaque to the optimiser: its addresses (array
 // base + 8·tid for each of the ~20 state arrays) are then formed inside the pass instead of
 // being hoisted to the kernel's start as 64-bit per-lane pointers live across every outer
 // iteration -- at the 128-VGPR budget of 1024 threads those were spilled and reloaded
-#ifndef RL_S_OPQ
-#define RL_S_OPQ 1
-#endif
 __device__ __forceinline__ int opq(int x) {
-#if RL_S_OPQ
     asm volatile("" : "+v"(x));
-#endif
     return x;
 }
 
@@ -62,17 +54,11 @@ __device__ __forceinline__ int opq(int x) {
 // offset (an SGPR) and the lane's byte offset i*8 (one VGPR shared by every array indexed by i).
 // As plain pointers each array's 64-bit base held an SGPR pair for the whole kernel (30 of its
 // 106 SGPRs for these 15 arrays) and the kernel spilled SGPRs to VGPR lanes, VGPRs to scratch.
-// Offsets stay below 2^31: 15 * N * 8 B with N <= RL_STREAM_MAX_N.  A/B knob: 0 = pointers.
-#ifndef RL_S_BUF
-#define RL_S_BUF 1
-#endif
-#ifndef RL_S_BUF_OPQ
-#define RL_S_BUF_OPQ 1
-#endif
+// Offsets stay below 2^31: 15 * N * 8 B with N <= RL_STREAM_MAX_N.
 typedef unsigned int u32x2_s __attribute__((ext_vector_type(2)));
 struct BufArr {
     __amdgpu_buffer_rsrc_t r;
-    int so;                     // byte offset of the array within the instance's resource
+    int so;                     // N*8: the byte size of one array of the instance's resource
     struct Ref {
         __amdgpu_buffer_rsrc_t r;
         int so, vo;
@@ -87,13 +73,9 @@ struct BufArr {
         __device__ __forceinline__ Ref& operator+=(double v) { return *this = (double)*this + v; }
     };
     __device__ __forceinline__ Ref operator[](int i) const {
-#if RL_S_BUF_OPQ
         int n8 = so;            // (so holds N*8 and k: field k's offset formed at each access)
         asm volatile("" : "+s"(n8));
         return Ref{r, k * n8, i * 8};
-#else
-        return Ref{r, so, i * 8};
-#endif
     }
     int k;
 };
@@ -117,41 +99,22 @@ __device__ __forceinline__ double wave_sum_s(double x) {
     return (readlane_s(x, 0) + readlane_s(x, 16)) + (readlane_s(x, 32) + readlane_s(x, 48));
 }
 
-// backtracking trials evaluated per pass over the state once the first trial of an
-// inner iteration is rejected (both optimisers)
 // corridor samples per lane in the streaming kernel (C5 A/B: 1 -> 36.0 ms, 2 -> 32.4 ms,
 // 4 -> 41.6 ms; scripts/ab_c5.py)
-#ifndef RL_SFUSE
-#define RL_SFUSE 1       // lin-geom (and min-time curvature) in the normals pass (A/B knob)
-#endif
-#ifndef RL_SVP_REG
-#define RL_SVP_REG 1     // register-resident v-pass for RL_SVP_MIN <= ceil(N/1024) <= RL_SVP_MAX (A/B knob)
-#endif
-#ifndef RL_SVP_MIN
-#define RL_SVP_MIN 5
-#endif
-#ifndef RL_SVP_MAX
-#define RL_SVP_MAX 12
-#endif
 #ifndef RL_SCK
 #define RL_SCK 2
 #endif
-#ifndef RL_BT_FIRST
-#define RL_BT_FIRST 1    // the first trial of an inner iteration joins a batch (its vectors stored)
-#endif
+// backtracking trials evaluated per pass over the state once the first trial of an
+// inner iteration is rejected (both optimisers).  The first trial itself is adaptive
+// (`first_batch` in the kernel): it joins a batch exactly when the instance's previous first
+// trial was rejected (the all-rejected regime of C5, E_k = 21), and is evaluated alone
+// otherwise (the accepting regime, where a batch's three extra steps are wasted work).
+// Uniform per instance; exact either way (a batched step is bit-identical to a lone trial).
 #ifndef RL_BT_BATCH
 #define RL_BT_BATCH 4
 #endif
-#ifndef RL_BT_FIRST_MT
-#define RL_BT_FIRST_MT 0 // min-time: the first trial joins a batch as well (A/B knob)
-#endif
-// adaptive first trial: it joins a batch exactly when the instance's previous first trial was
-// rejected (the all-rejected regime of C5, E_k = 21), and is evaluated alone otherwise (the
-// accepting regime, where a batch's three extra steps are wasted work).  Uniform per
-// instance; exact either way (a batched step is bit-identical to a lone trial).
-#ifndef RL_BT_ADAPT
-#define RL_BT_ADAPT 1
-#endif
+// register-resident v-pass (vpass_reg) for SVP_MIN <= ceil(N/1024) <= SVP_MAX samples per thread
+constexpr int SVP_MIN = 5, SVP_MAX = 12;
 constexpr int RED_SLOTS = 3 * RL_BT_BATCH > 4 ? 3 * RL_BT_BATCH : 4;
 
 struct SSmem {
@@ -164,7 +127,7 @@ struct SSmem {
     // sweep, [2] / [3] the same for the backward sweeps (+inf: none yet)
     double vg[4][TS];
     double bc[4];
-    double* pp[7];    // the instance's output arrays X .. KA (RL_S_PLDS), read where used
+    double* pp[7];    // the instance's output arrays X .. KA (PPT), read where used
     VConst vc;        // v-pass constants (read at the start of each v pass: no registers held)
     int ctr;          // corridor work queue: next chunk of 64*RL_SCK samples
 };
@@ -211,13 +174,11 @@ __device__ unsigned long long rl_dbg_stamps_s[16384][16];
 #define RL_SSTAMP(slot) do {} while (0)
 #endif
 
-// the output arrays' bases: 0 pointers held for the whole kernel, 1 all seven in an LDS table
-// read where used, 2 X, Y, NX, NY held (every pass reads them) and alpha_total, alpha_last,
-// kappa from the table (once-per-outer passes).  C5 A/B (profiles/r05/ab_c5_scratch.log):
-// min-time scratch 112 / 64 / 32 B/lane, 32.3 / 32.7 / 32.2 ms (round-5 head 160 B/lane, 32.3)
-#ifndef RL_S_PLDS
-#define RL_S_PLDS 2
-#endif
+// the output arrays' bases: X, Y, NX, NY held (every pass reads them) and alpha_total,
+// alpha_last, kappa from an LDS table read where used (once-per-outer passes).  Measured on C5
+// against all seven held for the whole kernel and all seven in the table
+// (profiles/r05/ab_c5_scratch.log): min-time scratch 112 / 64 / 32 B/lane, 32.3 / 32.7 /
+// 32.2 ms (round-5 head 160 B/lane, 32.3)
 // a uniform pointer read from LDS, as an SGPR pair
 template <class T>
 __device__ __forceinline__ T* unip(T* q) {
@@ -225,28 +186,13 @@ __device__ __forceinline__ T* unip(T* q) {
     const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)u), hi = __builtin_amdgcn_readfirstlane((uint32_t)(u >> 32));
     return (T*)(((uint64_t)hi << 32) | lo);
 }
-#if RL_S_PLDS == 2
 #define PPT(k) ((k) < 4 ? PL4[(k) & 3] : unip(sm.pp[(k)]))
-#elif RL_S_PLDS
-#define PPT(k) (unip(sm.pp[(k)]))
-#else
-#define PPT(k) (((double* const[]){X, Y, NX, NY, ATOT, ALAST, KA})[(k)])
-#endif
 
 template <bool CLOSED, bool MT>
-// RL_STS_MINW: minimum waves per SIMD the register budget must allow (0: the compiler's
-// choice for TS), e.g. TS = 512 with 4 keeps two instances co-resident per CU (A/B knob)
-#ifndef RL_STS_MINW
-#define RL_STS_MINW 0
-#endif
-#if RL_STS_MINW
-__global__ __launch_bounds__(TS, RL_STS_MINW) void rl_stream_kernel(KParams p, StreamBufs sb) {
-#else
 __global__ __launch_bounds__(TS) void rl_stream_kernel(KParams p, StreamBufs sb) {
-#endif
     __shared__ SSmem sm;
-    // the register-resident v-pass's curvatures (RL_SVP_MAX samples per thread; vpass_reg)
-    __shared__ double ska[MT && RL_SVP_REG ? RL_SVP_MAX * TS + RL_SVP_MAX : 1];
+    // the register-resident v-pass's curvatures (SVP_MAX samples per thread; vpass_reg)
+    __shared__ double ska[MT ? SVP_MAX * TS + SVP_MAX : 1];
 #ifdef RL_STAMPS
     unsigned long long st_acc[16] = {};
     unsigned long long st_last = __builtin_amdgcn_s_memtime();
@@ -267,39 +213,18 @@ __global__ __launch_bounds__(TS) void rl_stream_kernel(KParams p, StreamBufs sb)
     const double lam = C.lambda_smooth, lam2 = uni(2.0 * lam);
 
     const size_t off = (size_t)b * (size_t)N;
-#if RL_S_PLDS
     // the output arrays' bases in LDS, read where they are used: held for the whole kernel they
-    // sat in VGPR pairs (no SGPRs left) and were spilled (RL_S_PLDS above)
+    // sat in VGPR pairs (no SGPRs left) and were spilled (PPT above)
     if (tid == 0) {
         sm.pp[0] = p.x + off; sm.pp[1] = p.y + off; sm.pp[2] = p.nx + off; sm.pp[3] = p.ny + off;
         sm.pp[4] = p.alpha_total + off; sm.pp[5] = p.alpha_last + off; sm.pp[6] = p.kappa + off;
     }
     __syncthreads();
-#if RL_S_PLDS == 2
     double* const PL4[4] = {p.x + off, p.y + off, p.nx + off, p.ny + off};   // (the corridor's, held)
-#endif
-#else
-    double* __restrict__ X = p.x + off;
-    double* __restrict__ Y = p.y + off;
-    double* __restrict__ NX = p.nx + off;
-    double* __restrict__ NY = p.ny + off;
-    double* __restrict__ ATOT = p.alpha_total + off;
-    double* __restrict__ ALAST = p.alpha_last + off;
-    double* __restrict__ KA = p.kappa + off;          // κ scratch, final output at the end
-#endif
     // the streaming state ([B][15][N], StreamBufs); al / an swap roles on every accepted step
-#if RL_S_BUF
     const __amdgpu_buffer_rsrc_t srs = __builtin_amdgcn_make_buffer_rsrc(
         sb.base + (size_t)b * RL_STREAM_ARRAYS * (size_t)N, (short)0, RL_STREAM_ARRAYS * N * 8, 0x00020000);
-#if RL_S_BUF_OPQ
     auto sfield = [&](int k) { return BufArr{srs, N * 8, k}; };
-#else
-    auto sfield = [&](int k) { return BufArr{srs, k * N * 8, k}; };
-#endif
-#else
-    double* const sinst = sb.base + (size_t)b * RL_STREAM_ARRAYS * (size_t)N;
-    auto sfield = [&](int k) -> double* __restrict__ { return sinst + (size_t)k * N; };
-#endif
     const auto AL = sfield(0), AN = sfield(1), GR = sfield(2), LO = sfield(3), HI = sfield(4);
     const auto CA1 = sfield(5), CA2 = sfield(6), CN0 = sfield(7), CW = sfield(8);
     const auto Q1 = sfield(9), Q2 = sfield(10), D1 = sfield(11), G2 = sfield(12), V = sfield(13), VS = sfield(14);
@@ -342,10 +267,9 @@ __global__ __launch_bounds__(TS) void rl_stream_kernel(KParams p, StreamBufs sb)
         if (!(n < 1e-15)) { ox = vx / n; oy = vy / n; }
         PPT(2)[i] = ox;
         PPT(3)[i] = oy;
-#if RL_SFUSE
         // precompute_lin_geom_generic (ref:622-651) at i in the same pass over P: it needs
-        // only this sample's normal, so the later lin-geom pass (and, for min-time, the
-        // curvature pass, ref:595-620) need not read P and n again
+        // only this sample's normal, so no separate lin-geom pass (nor, for min-time,
+        // curvature pass, ref:595-620) has to read P and n again
         double xp, yp, xpp, ypp;
         deriv(i, xp, yp, xpp, ypp);
         CA1[i] = ox * ypp - oy * xpp;
@@ -355,7 +279,6 @@ __global__ __launch_bounds__(TS) void rl_stream_kernel(KParams p, StreamBufs sb)
         const double d = pow15(smax(1e-12, xp * xp + yp * yp));
         CW[i] = 1.0 / d;
         if (MT) PPT(6)[i] = n0 / d;
-#endif
     };
     // corridor (ref:694-711 / 749-756) at sample i via the per-lane candidate scan
     auto corridor_at = [&](int i, double guard) {
@@ -438,7 +361,7 @@ __global__ __launch_bounds__(TS) void rl_stream_kernel(KParams p, StreamBufs sb)
     // min-time run 5-15 % slower at every round cap tried -- one barrier per round stays)
     auto vpass = [&]() -> int {
         const int r0 = opq(r0_), r1 = opq(r1_);   // (opaque: addresses formed per pass, see opq)
-        const VConst vc = RL_VC_UNI ? vconst_uniform(sm.vc) : sm.vc;
+        const VConst vc = vconst_uniform(sm.vc);
         for (int i = r0; i < r1; ++i) {
             double kk = fabs(PPT(6)[i]);
             V[i] = smin(C.v_cap_mps, sqrt(C.a_lat_max / smax(kk, C.kappa_eps)));   // ref:787-794
@@ -521,7 +444,7 @@ __global__ __launch_bounds__(TS) void rl_stream_kernel(KParams p, StreamBufs sb)
         return sweeps;
     };
 
-    // Register-resident v-pass for Cr = CR samples per thread (RL_SVP_MIN <= Cr <= RL_SVP_MAX,
+    // Register-resident v-pass for Cr = CR samples per thread (SVP_MIN <= Cr <= SVP_MAX,
     // e.g. C5's N = 10000: Cr = 10).  The chunk's κ, its values and the pass-start values stay
     // in registers for the whole v pass (the memory path above reloads them from HBM in every
     // relaxation round), and a re-evaluated chunk stops at the first value that repeats bit for
@@ -534,7 +457,7 @@ __global__ __launch_bounds__(TS) void rl_stream_kernel(KParams p, StreamBufs sb)
     // directly and V, which only the weights would read, is not
     auto vpass_reg = [&](auto crc, bool g2) -> int {
         constexpr int CR = decltype(crc)::value;
-        const VConst vc = RL_VC_UNI ? vconst_uniform(sm.vc) : sm.vc;
+        const VConst vc = vconst_uniform(sm.vc);
         // (opaque: the chunk's addresses are formed here, not hoisted out of the outer loop
         // as per-lane pointers for every instantiated CR, which were spilled)
         const int rb = opq(r0_);
@@ -686,14 +609,13 @@ __global__ __launch_bounds__(TS) void rl_stream_kernel(KParams p, StreamBufs sb)
     // g2_done: the register path wrote G2 itself (requested by g2)
     auto vpass_any = [&](bool g2, bool& g2_done) -> int {
         g2_done = false;
-        if (RL_SVP_REG) {
-            switch (Cr) {
-#define RL_SVP_CASE(n) case n: if (n >= RL_SVP_MIN && n <= RL_SVP_MAX) { g2_done = g2; return vpass_reg(std::integral_constant<int, n>(), g2); } break;
-                RL_SVP_CASE(5) RL_SVP_CASE(6) RL_SVP_CASE(7) RL_SVP_CASE(8)
-                RL_SVP_CASE(9) RL_SVP_CASE(10) RL_SVP_CASE(11) RL_SVP_CASE(12)
+        static_assert(SVP_MIN == 5 && SVP_MAX == 12, "one case per Cr");
+        switch (Cr) {
+#define RL_SVP_CASE(n) case n: g2_done = g2; return vpass_reg(std::integral_constant<int, n>(), g2);
+            RL_SVP_CASE(5) RL_SVP_CASE(6) RL_SVP_CASE(7) RL_SVP_CASE(8)
+            RL_SVP_CASE(9) RL_SVP_CASE(10) RL_SVP_CASE(11) RL_SVP_CASE(12)
 #undef RL_SVP_CASE
-                default: break;
-            }
+            default: break;
         }
         return vpass();
     };
@@ -705,7 +627,7 @@ __global__ __launch_bounds__(TS) void rl_stream_kernel(KParams p, StreamBufs sb)
         PPT(4)[i] = 0.0; PPT(5)[i] = 0.0; AL[i] = 0.0;   // (the gradient needs no zeroing: each outer
     }                                                     // iteration's first evaluation writes it first)
     const int MO = C.max_outer_iters;
-    bool first_batch = RL_BT_ADAPT ? false : (RL_BT_FIRST && (!MT || RL_BT_FIRST_MT));
+    bool first_batch = false;   // (adaptive first trial: RL_BT_BATCH above)
     auto al_p = AL;
     auto an_p = AN;
     RL_SSTAMP(0);
@@ -791,7 +713,7 @@ __global__ __launch_bounds__(TS) void rl_stream_kernel(KParams p, StreamBufs sb)
         __syncthreads();
 #endif
         RL_SSTAMP(1);
-        if ((MT && !RL_SFUSE) || outer == MO) {
+        if (outer == MO) {
             for (int i = opq(tid); i < N; i += TS) {                    // ref:595-620
                 double xp, yp, xpp, ypp;
                 deriv(i, xp, yp, xpp, ypp);
@@ -831,17 +753,6 @@ __global__ __launch_bounds__(TS) void rl_stream_kernel(KParams p, StreamBufs sb)
         RL_SSTAMP(2);
         if (outer == MO) break;
 
-        if (!RL_SFUSE) {
-            for (int i = opq(tid); i < N; i += TS) {                    // ref:622-651
-                double xp, yp, xpp, ypp;
-                deriv(i, xp, yp, xpp, ypp);
-                const double nx = PPT(2)[i], ny = PPT(3)[i];
-                CA1[i] = nx * ypp - ny * xpp;
-                CA2[i] = xp * ny - yp * nx;
-                CN0[i] = xp * ypp - yp * xpp;
-                CW[i] = 1.0 / pow15(smax(1e-12, xp * xp + yp * yp));
-            }
-        }
         __syncthreads();
         RL_SSTAMP(3);
 
@@ -972,7 +883,7 @@ __global__ __launch_bounds__(TS) void rl_stream_kernel(KParams p, StreamBufs sb)
             bool accepted = false;
             int bt = 0;
             while (bt < 20) {
-                // (fixed rules measured before RL_BT_ADAPT: the first trial in a batch for min-curv
+                // (fixed rules measured before the adaptive first trial: the first trial in a batch for min-curv
                 // only, C5 27.8 -> 26.4 ms; min-time 67.2 -> 69.8 ms)
                 if (MB > 1 && (first_batch || bt > 0)) {
                     const bool kept = bt == 0;             // step 0's vectors are stored by the pass
@@ -991,7 +902,7 @@ __global__ __launch_bounds__(TS) void rl_stream_kernel(KParams p, StreamBufs sb)
                     bool stop = false;
                     for (int j = 0; j < m; ++j) {
                         ++evals;
-                        if (RL_BT_ADAPT && kept && j == 0) first_batch = !(Jn[0] <= J + C.armijo_c * dn[0]);
+                        if (kept && j == 0) first_batch = !(Jn[0] <= J + C.armijo_c * dn[0]);
                         if (Jn[j] <= J + C.armijo_c * dn[j]) {
                             if (!(kept && j == 0)) materialize(st[j]);
                             const auto t = al_p; al_p = an_p; an_p = t;
@@ -1014,7 +925,7 @@ __global__ __launch_bounds__(TS) void rl_stream_kernel(KParams p, StreamBufs sb)
                 const bool keep = (bt == 0);
                 const double Jn = eval_trial(step, keep, dec);
                 ++evals;
-                if (RL_BT_ADAPT && keep) first_batch = !(Jn <= J + C.armijo_c * dec);
+                if (keep) first_batch = !(Jn <= J + C.armijo_c * dec);
                 if (Jn <= J + C.armijo_c * dec) {
                     if (!keep) materialize(step);
                     const auto t = al_p; al_p = an_p; an_p = t;       // α := α_trial (uniform swap)
@@ -1047,19 +958,10 @@ __global__ __launch_bounds__(TS) void rl_stream_kernel(KParams p, StreamBufs sb)
 }
 
 #ifdef RL_COUNT
-int debug_counts(unsigned long long* host, int reset) {
-    if (reset) {
-        unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        return hipMemcpyToSymbol(HIP_SYMBOL(rl_dbg_count), z, sizeof(z)) == hipSuccess ? 0 : -3;
-    }
-    return hipMemcpyFromSymbol(host, HIP_SYMBOL(rl_dbg_count), sizeof(unsigned long long) * 8) == hipSuccess ? 0 : -3;
-}
+int debug_counts(unsigned long long* host, int reset) { return read_counts(rl_dbg_count, host, reset); }
 #endif
 #ifdef RL_STAMPS
-int debug_stamps_stream(unsigned long long* host, int nblocks) {
-    if (nblocks > 16384) nblocks = 16384;
-    return hipMemcpyFromSymbol(host, HIP_SYMBOL(rl_dbg_stamps_s), sizeof(unsigned long long) * 16 * nblocks) == hipSuccess ? 0 : -3;
-}
+int debug_stamps_stream(unsigned long long* host, int nblocks) { return read_stamps(rl_dbg_stamps_s, host, nblocks); }
 #endif
 
 template <bool CL, bool MT>

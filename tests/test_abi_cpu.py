@@ -140,7 +140,7 @@ def test_kernel_shape_table():
     """Throughput shapes for batches that fill the GPU, latency shapes (one instance over a
     CU) while the batch needs at most one wave per SIMD in them (256 CUs assumed here)."""
     MC, MT = abi.RL_MODE_MINCURV, abi.RL_MODE_MINTIME
-    # K = 1 on just enough waves up to N = 512 (RL_LAT_FIT)
+    # K = 1 on just enough waves up to N = 512
     assert abi.kernel_shape(1, 1, MC) == (1, 128)
     assert abi.kernel_shape(128, 1, MC) == (1, 128)
     assert abi.kernel_shape(187, 1, MT) == (1, 192)
@@ -162,6 +162,39 @@ def test_kernel_shape_table():
     assert abi.kernel_shape(2000, 4096, MT) == (8, 256)
     assert abi.kernel_shape(4096, 1, MC) == (8, 512)
     assert abi.kernel_shape(10000, 1, MC) == (0, 1024)
+
+
+SHAPE_NS = [1, 127, 128, 129, 191, 192, 193, 255, 256, 257, 319, 320, 321, 383, 384, 385, 447, 448, 449, 511, 512, 513,
+            1023, 1024, 1025, 2047, 2048, 2049, 4095, 4096, 4097, 1 << 20, (1 << 20) + 1]
+SHAPE_BS = [1, 128, 129, 170, 171, 204, 205, 255, 256, 257, 511, 512, 513, 1023, 1024, 1025, 4096]
+
+
+def kernel_shape_record(lib, setenv, delenv):
+    """rl_kernel_variant(N) and rl_kernel_shape(N, B, mode) as [rc, K, T] over every boundary of
+    the shape tables and its neighbours, with RL_LAT_SHAPES unset and "0" (no device needed: 256
+    CUs are assumed without one, and the MI355X has 256)."""
+    rec = {"N": SHAPE_NS, "B": SHAPE_BS, "variant": [lib.rl_kernel_variant(n) for n in SHAPE_NS], "shape": {}}
+    for env in ("unset", "0"):
+        setenv("RL_LAT_SHAPES", "0") if env == "0" else delenv("RL_LAT_SHAPES", raising=False)
+        for mode, name in ((abi.RL_MODE_MINCURV, "mincurv"), (abi.RL_MODE_MINTIME, "mintime")):
+            rows = []
+            for n in SHAPE_NS:
+                row = []
+                for b in SHAPE_BS:
+                    k, t = C.c_int32(-9), C.c_int32(-9)
+                    row.append([lib.rl_kernel_shape(n, b, mode, C.byref(k), C.byref(t)), k.value, t.value])
+                rows.append(row)
+            rec["shape"][env + "/" + name] = rows
+    return rec
+
+
+def test_kernel_shapes_equal_recorded_table(monkeypatch):
+    """The (K, T) dispatch over (N, B, mode, RL_LAT_SHAPES) equals tests/golden/kernel_shapes.json,
+    recorded from the library before the shape tables were merged into one."""
+    import json
+    with open(os.path.join(REPO, "tests", "golden", "kernel_shapes.json")) as f:
+        want = json.load(f)
+    assert kernel_shape_record(abi.load_library(), monkeypatch.setenv, monkeypatch.delenv) == want
 
 
 def test_plan_cache_queries_without_a_call():
