@@ -412,123 +412,79 @@ def u64ptr(a: Optional[np.ndarray]):
     return a.ctypes.data_as(C.POINTER(C.c_uint64))
 
 
+_P = C.POINTER
+_PROB, _CFG, _OUT, _SEL = _P(RlProblem), _P(RlCfg), _P(RlOut), _P(RlSelect)
+_F64, _F32, _I32, _I64, _U64 = _P(C.c_double), _P(C.c_float), _P(C.c_int32), _P(C.c_int64), _P(C.c_uint64)
+_BATCH = [_PROB, _CFG, C.c_int32, _U64, C.c_int32]       # problem, cfgs, ncfg, seeds, B
+_BEST = [_I32, _F64, _F64, _OUT]                          # index, score, scores, the winners' rows
+
+# every function of rl_abi.h (ABI 6.1): (name, restype, argtypes); argtypes None = not declared
+DECLS = [
+    ("rl_optimize", C.c_int, _BATCH + [_OUT, _OUT]),
+    ("rl_cfg_default", None, [_CFG]),
+    ("rl_cfg_set_mu", None, [_CFG, C.c_double]),
+    ("rl_ring_segments", C.c_int, [_F64, C.c_int32, C.c_int32, _F64]),
+    ("rl_seed_value", C.c_double, [C.c_uint64, C.c_int32, C.c_double]),
+    ("rl_plan_create", C.c_int, [_P(C.c_void_p), C.c_int32] + _BATCH + [C.c_int32]),
+    ("rl_plan_run", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("rl_plan_run_group", C.c_int, [_P(C.c_void_p), C.c_int32, C.c_void_p]),
+    ("rl_plan_fetch", C.c_int, [C.c_void_p, _OUT, _OUT]),
+    ("rl_plan_device_outputs", C.c_int, [C.c_void_p, C.c_int32, _OUT]),
+    ("rl_plan_bind_device_outputs", C.c_int, [C.c_void_p, C.c_int32, _OUT]),
+    ("rl_plan_kernel_ms", C.c_int, [C.c_void_p, C.c_int32, _F32]),
+    ("rl_plan_destroy", C.c_int, [C.c_void_p]),
+    ("rl_plan_set_shape_batch", C.c_int, [C.c_void_p, C.c_int32]),
+    ("rl_plan_shape", C.c_int, [C.c_void_p, C.c_int32, _I32, _I32]),
+    ("rl_device_count", C.c_int, None),
+    ("rl_last_error", C.c_char_p, None),
+    ("rl_abi_version", C.c_int, None),
+    ("rl_abi_minor", C.c_int, None),
+    ("rl_kernel_variant", C.c_int, [C.c_int32]),
+    ("rl_kernel_shape", C.c_int, [C.c_int32, C.c_int32, C.c_int32, _I32, _I32]),
+    ("rl_geom", C.c_int, [_P(RlGeomProblem), _CFG, C.c_int32, _F64, _F32]),
+    ("rl_corridor", C.c_int, [_PROB, _CFG, C.c_int32, _F64, _F64]),
+    ("rl_lap_eval", C.c_int, [_F64, _F64, C.c_int32, C.c_int32, C.c_int32, _CFG, C.c_int32, C.c_int32, _OUT, _F32]),
+    ("rl_format_csv", C.c_int, [_F64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, _I64, _I64]),
+    ("rl_optimize_multi", C.c_int, _BATCH + [_I32, C.c_int32, _OUT, _OUT]),
+    ("rl_last_call_ms", C.c_int, [_F32, _F32]),
+    ("rl_release_plan_cache", C.c_int, []),
+    ("rl_last_call_times", C.c_int, [_F32] * 4),
+    ("rl_plan_cache_info", C.c_int, [_I32, _I64, _I64]),
+    ("rl_last_call_download", C.c_int, [_I32, _I32]),
+    ("rl_plan_select", C.c_int, [C.c_void_p, _SEL, C.c_void_p]),
+    ("rl_plan_fetch_selected", C.c_int, [C.c_void_p] + _BEST),
+    ("rl_optimize_best", C.c_int, _BATCH + [_SEL] + _BEST),
+    ("rl_rank_scores", C.c_int, [_F64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _I32]),
+    ("rl_plan_lap", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("rl_plan_fetch_lap", C.c_int, [C.c_void_p, _OUT, _F64]),
+    ("rl_plan_select_scored", C.c_int, [C.c_void_p, _SEL, C.c_int32, C.c_void_p]),
+    ("rl_optimize_best_scored", C.c_int, _BATCH + [_SEL, C.c_int32] + _BEST),
+    ("rl_path_lengths", C.c_int, [_F64, _F64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F64]),
+]
+
+
 def declare_optimize(fn) -> None:
-    fn.restype = C.c_int
-    fn.argtypes = [C.POINTER(RlProblem), C.POINTER(RlCfg), C.c_int32, C.POINTER(C.c_uint64),
-                   C.c_int32, C.POINTER(RlOut), C.POINTER(RlOut)]
+    """rl_optimize's signature (the oracle's oracle_optimize shares it)."""
+    fn.restype, fn.argtypes = DECLS[0][1], DECLS[0][2]
 
 
 _LIB = None
 
 
 def load_library(path: str = LIB_PATH) -> C.CDLL:
-    """Load librl.so (the HIP path).  Raises if it is missing: there is no fallback."""
+    """Load librl.so (the HIP path).  Raises if it is missing: there is no fallback; a library
+    that lacks a function of DECLS raises AttributeError naming it."""
     global _LIB
     if _LIB is not None and path == LIB_PATH:
         return _LIB
     if not os.path.exists(path):
         raise RuntimeError(f"librl.so not built at {path}: run `python -c 'import __graft_entry__ as g; g.build()'`")
     lib = C.CDLL(path)
-    declare_optimize(lib.rl_optimize)
-    lib.rl_cfg_default.argtypes = [C.POINTER(RlCfg)]
-    lib.rl_cfg_default.restype = None
-    lib.rl_cfg_set_mu.argtypes = [C.POINTER(RlCfg), C.c_double]
-    lib.rl_cfg_set_mu.restype = None
-    lib.rl_ring_segments.argtypes = [C.POINTER(C.c_double), C.c_int32, C.c_int32, C.POINTER(C.c_double)]
-    lib.rl_ring_segments.restype = C.c_int
-    lib.rl_seed_value.argtypes = [C.c_uint64, C.c_int32, C.c_double]
-    lib.rl_seed_value.restype = C.c_double
-    lib.rl_plan_create.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(RlProblem), C.POINTER(RlCfg),
-                                   C.c_int32, C.POINTER(C.c_uint64), C.c_int32, C.c_int32]
-    lib.rl_plan_create.restype = C.c_int
-    lib.rl_plan_run.argtypes = [C.c_void_p, C.c_void_p]
-    lib.rl_plan_run.restype = C.c_int
-    if path == LIB_PATH or hasattr(lib, "rl_plan_run_group"):   # (A/B builds of older sources lack it)
-        lib.rl_plan_run_group.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_void_p]
-        lib.rl_plan_run_group.restype = C.c_int
-    lib.rl_plan_fetch.argtypes = [C.c_void_p, C.POINTER(RlOut), C.POINTER(RlOut)]
-    lib.rl_plan_fetch.restype = C.c_int
-    lib.rl_plan_device_outputs.argtypes = [C.c_void_p, C.c_int32, C.POINTER(RlOut)]
-    lib.rl_plan_device_outputs.restype = C.c_int
-    lib.rl_plan_bind_device_outputs.argtypes = [C.c_void_p, C.c_int32, C.POINTER(RlOut)]
-    lib.rl_plan_bind_device_outputs.restype = C.c_int
-    lib.rl_plan_kernel_ms.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_float)]
-    lib.rl_plan_kernel_ms.restype = C.c_int
-    lib.rl_plan_destroy.argtypes = [C.c_void_p]
-    lib.rl_plan_destroy.restype = C.c_int
-    if hasattr(lib, "rl_plan_set_shape_batch"):   # absent only in older experiment builds (A/B bases)
-        lib.rl_plan_set_shape_batch.argtypes = [C.c_void_p, C.c_int32]
-        lib.rl_plan_set_shape_batch.restype = C.c_int
-        lib.rl_plan_shape.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-        lib.rl_plan_shape.restype = C.c_int
-    lib.rl_device_count.restype = C.c_int
-    lib.rl_last_error.restype = C.c_char_p
-    lib.rl_abi_version.restype = C.c_int
-    lib.rl_kernel_variant.argtypes = [C.c_int32]
-    lib.rl_kernel_variant.restype = C.c_int
-    if hasattr(lib, "rl_kernel_shape"):     # absent only in older experiment builds (A/B bases)
-        lib.rl_kernel_shape.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-        lib.rl_kernel_shape.restype = C.c_int
-    lib.rl_geom.argtypes = [C.POINTER(RlGeomProblem), C.POINTER(RlCfg), C.c_int32, C.POINTER(C.c_double),
-                            C.POINTER(C.c_float)]
-    lib.rl_geom.restype = C.c_int
-    if hasattr(lib, "rl_corridor"):      # absent only in older experiment builds (A/B bases)
-        lib.rl_corridor.argtypes = [C.POINTER(RlProblem), C.POINTER(RlCfg), C.c_int32, C.POINTER(C.c_double),
-                                    C.POINTER(C.c_double)]
-        lib.rl_corridor.restype = C.c_int
-    lib.rl_lap_eval.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_int32,
-                                C.POINTER(RlCfg), C.c_int32, C.c_int32, C.POINTER(RlOut), C.POINTER(C.c_float)]
-    lib.rl_lap_eval.restype = C.c_int
-    lib.rl_format_csv.argtypes = [C.POINTER(C.c_double), C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
-                                  C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    lib.rl_format_csv.restype = C.c_int
-    if hasattr(lib, "rl_optimize_multi"):   # absent only in older experiment builds (A/B bases)
-        lib.rl_optimize_multi.argtypes = [C.POINTER(RlProblem), C.POINTER(RlCfg), C.c_int32, C.POINTER(C.c_uint64),
-                                          C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(RlOut),
-                                          C.POINTER(RlOut)]
-        lib.rl_optimize_multi.restype = C.c_int
-    if hasattr(lib, "rl_last_call_ms"):     # absent only in older experiment builds (A/B bases)
-        lib.rl_last_call_ms.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float)]
-        lib.rl_last_call_ms.restype = C.c_int
-        lib.rl_release_plan_cache.argtypes = []
-        lib.rl_release_plan_cache.restype = C.c_int
-    if hasattr(lib, "rl_last_call_times"):  # absent only in older experiment builds (A/B bases)
-        lib.rl_last_call_times.argtypes = [C.POINTER(C.c_float)] * 4
-        lib.rl_last_call_times.restype = C.c_int
-        lib.rl_plan_cache_info.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-        lib.rl_plan_cache_info.restype = C.c_int
-    if hasattr(lib, "rl_last_call_download"):   # absent only in older experiment builds (A/B bases)
-        lib.rl_last_call_download.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-        lib.rl_last_call_download.restype = C.c_int
-    if path == LIB_PATH or hasattr(lib, "rl_plan_select"):   # (A/B builds of older sources lack them)
-        lib.rl_plan_select.argtypes = [C.c_void_p, C.POINTER(RlSelect), C.c_void_p]
-        lib.rl_plan_select.restype = C.c_int
-        lib.rl_plan_fetch_selected.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double),
-                                               C.POINTER(C.c_double), C.POINTER(RlOut)]
-        lib.rl_plan_fetch_selected.restype = C.c_int
-        lib.rl_optimize_best.argtypes = [C.POINTER(RlProblem), C.POINTER(RlCfg), C.c_int32, C.POINTER(C.c_uint64),
-                                         C.c_int32, C.POINTER(RlSelect), C.POINTER(C.c_int32), C.POINTER(C.c_double),
-                                         C.POINTER(C.c_double), C.POINTER(RlOut)]
-        lib.rl_optimize_best.restype = C.c_int
-        lib.rl_rank_scores.argtypes = [C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                       C.POINTER(C.c_int32)]
-        lib.rl_rank_scores.restype = C.c_int
-    if path == LIB_PATH or hasattr(lib, "rl_plan_lap"):   # (A/B builds of older sources lack them)
-        lib.rl_abi_minor.restype = C.c_int
-        lib.rl_plan_lap.argtypes = [C.c_void_p, C.c_void_p]
-        lib.rl_plan_lap.restype = C.c_int
-        lib.rl_plan_fetch_lap.argtypes = [C.c_void_p, C.POINTER(RlOut), C.POINTER(C.c_double)]
-        lib.rl_plan_fetch_lap.restype = C.c_int
-        lib.rl_plan_select_scored.argtypes = [C.c_void_p, C.POINTER(RlSelect), C.c_int32, C.c_void_p]
-        lib.rl_plan_select_scored.restype = C.c_int
-        lib.rl_optimize_best_scored.argtypes = [C.POINTER(RlProblem), C.POINTER(RlCfg), C.c_int32,
-                                                C.POINTER(C.c_uint64), C.c_int32, C.POINTER(RlSelect), C.c_int32,
-                                                C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double),
-                                                C.POINTER(RlOut)]
-        lib.rl_optimize_best_scored.restype = C.c_int
-        lib.rl_path_lengths.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_int32,
-                                        C.c_int32, C.POINTER(C.c_double)]
-        lib.rl_path_lengths.restype = C.c_int
+    for name, restype, argtypes in DECLS:
+        fn = getattr(lib, name)
+        fn.restype = restype
+        if argtypes is not None:
+            fn.argtypes = argtypes
     if path == LIB_PATH:
         _LIB = lib
     return lib

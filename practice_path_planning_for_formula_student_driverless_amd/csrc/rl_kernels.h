@@ -126,7 +126,7 @@ inline bool operator==(const Shape& a, const Shape& b) { return a.K == b.K && a.
 // Throughput shapes (rl_kernels.hip; every batch that fills the GPU): one wave per instance
 // up to N = 512.  (5, 64) for 256 < N <= 320 (testday1/3 of the bundled tracks): 5 samples per
 // lane instead of 8, 0 B scratch and two waves per SIMD in both modes.  C4
-// (scripts/ab_c4_single.py, profiles/r05/ab_c4_s5.log): those plans alone min-time 4.16 / 4.59
+// (scripts/ab.py time c4, profiles/r05/ab_c4_s5.log): those plans alone min-time 4.16 / 4.59
 // -> 3.32 / 3.74 ms, min-curv 3.64 / 3.97 -> 3.07 / 3.36 ms; the concurrent sweep 17.55 ->
 // 16.42 ms, bit-exact.  XMID: the row that min-time leaves for (RL_MIDMT_K, RL_MIDMT_T) below
 // two instances per CU (pick_shape).

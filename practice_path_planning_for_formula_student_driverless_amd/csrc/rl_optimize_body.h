@@ -50,7 +50,7 @@ constexpr int CK = (RL_CK < 8 ? RL_CK : 8);   // corridor sub-chunk (samples per
 // off in this kernel (corridor_bounds<CKK, false>): it measured +0.8 % on C2 here and -21 % on
 // C5 in the streaming kernel, which keeps it.
 // v-pass: in-wave relaxation rounds between two cross-wave exchanges (barriers), per shape.
-// A/B (scripts/ab_variants.py, caps 1 (= one barrier per round), 2, 4, 8, 16): the (4, 512)
+// A/B (scripts/ab.py time, caps 1 (= one barrier per round), 2, 4, 8, 16): the (4, 512)
 // latency shape gains 5 % from 8-16 rounds; the (8, 256) throughput shape at two instances
 // per CU loses 1-3 % with any cap above 1 (a chain that reaches a wave edge waits for the
 // slowest wave's rounds), so it keeps one barrier per round; single-wave instances need
@@ -219,7 +219,7 @@ __device__ __forceinline__ void put(double (&a)[K], int idx, double v) {
 // v-pass warm starts (min-time, see vpass): the multi-wave shapes only.  In the one-wave (K, 64) throughput shapes (C1/C4) the in-wave rounds are
 // cheap DPP steps and the starts leave the kernel time as it is, while their 2 KB table
 // costs LDS granules that concurrent plans share (C4 min-time 8.7 -> 11.9 ms wall at equal
-// kernel times, scripts/ab_c4_single.py, profiles/r05/ab_c4_lds.log)
+// kernel times, scripts/ab.py time c4, profiles/r05/ab_c4_lds.log)
 template <int T, bool MT>
 struct WarmStart {
     static constexpr bool value = MT && T > 64;
@@ -282,7 +282,7 @@ struct alignas(16) Smem : PubTab<T / 64>, WarmTab<T, WARM> {
 #endif
 
 // single-wave (4, 64) variant (N <= 256: the bundled tracks, C1/C4) per mode.  A/B on
-// C4-shaped plans (scripts/ab_c4.py, kernel-time sum): 4 waves/SIMD (128 VGPRs) spilled
+// C4-shaped plans (scripts/ab.py time c4t, kernel-time sum): 4 waves/SIMD (128 VGPRs) spilled
 // 148 B/lane (min-curv) and 596 B/lane (min-time); 2 waves/SIMD: 61.9 -> 51.1 ms
 #ifndef RL_SMALL_W
 #define RL_SMALL_W 2

@@ -100,7 +100,7 @@ __device__ __forceinline__ double wave_sum_s(double x) {
 }
 
 // corridor samples per lane in the streaming kernel (C5 A/B: 1 -> 36.0 ms, 2 -> 32.4 ms,
-// 4 -> 41.6 ms; scripts/ab_c5.py)
+// 4 -> 41.6 ms; scripts/ab.py time c5)
 #ifndef RL_SCK
 #define RL_SCK 2
 #endif

@@ -44,13 +44,18 @@ VARIANTS = {
     "prio3": {"RL_PRIO": 3, "_tu": {"csrc/rl_kernels.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-maxocc"],
                                     "csrc/rl_kernels_group.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-maxocc"]}},   # end-weighted levels
     "prio_s": {"RL_PRIO": 1, "RL_SPRIO": 1},   # and in the streaming kernel
-    "stamps": {"RL_STAMPS": 1},          # diagnostic (scripts/stamps.py); not A/B-timed
-    "stamps_eval": {"RL_STAMPS": 1, "RL_STAMPS_EVAL": 1},   # + the latency evaluation's phases (scripts/stamps_lat.py)
-    "count": {"RL_COUNT": 1},            # diagnostic (scripts/counts_c5.py); not A/B-timed
+    "stamps": {"RL_STAMPS": 1},          # diagnostic (scripts/ab.py stamps); not A/B-timed
+    "stamps_eval": {"RL_STAMPS": 1, "RL_STAMPS_EVAL": 1},   # + the latency evaluation's phases (scripts/ab.py stamps lat --variant stamps_eval)
+    "count": {"RL_COUNT": 1},            # diagnostic (scripts/ab.py counts); not A/B-timed
 }
 if __name__ == "__main__":
-    names = sys.argv[1:] or [n for n in VARIANTS if n not in ("stamps", "count")]
+    # usage: build_variants.py [NAME | ALIAS=NAME ...]   (ALIAS=NAME: the variant NAME built as librl_ALIAS.so)
+    names = sys.argv[1:] or [n for n in VARIANTS if n not in ("stamps", "stamps_eval", "count")]
+    jobs = [(a.split("=")[0], a.split("=")[-1]) for a in names]
+    for _, name in jobs:
+        if name not in VARIANTS:
+            sys.exit(f"build_variants.py: no variant {name!r}; known: {', '.join(VARIANTS)}")
     import shutil; shutil.rmtree(os.path.join(B.LIB_DIR, "variants"), ignore_errors=True)
     with ThreadPoolExecutor(4) as ex:
-        for p in ex.map(lambda n: B.build_variant(n, VARIANTS[n]), names):
+        for p in ex.map(lambda j: B.build_variant(j[0], VARIANTS[j[1]]), jobs):
             print("built", p)

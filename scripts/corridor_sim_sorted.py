@@ -21,7 +21,7 @@ Paths: C5's problem (the N = 10000 oval), seeds 1 and 7.  The kernel's 14 corrid
 (outers 0..13) see two paths: the centre line (outer 0), then the path the seeded first
 outer iteration left, which no later outer moves (its corridor collapses: every trial is
 rejected, E_k = 21) -- the CPU oracle run with max_outer_iters = 1 gives it.  Ground truth
-for `natural`: the RL_COUNT counters of the GPU kernel per pass (scripts/counts_c5_outer.py,
+for `natural`: the RL_COUNT counters of the GPU kernel per pass (scripts/ab.py counts c5 --outer 1,2,14,
 profiles/r06/corridor_counts_c5_per_pass.log): first pass 0.177 and later passes 0.500 as
 logged, i.e. 0.354 and 0.999 once the counters' denominator is corrected (they counted 4
 block slots per 32-entry word, the blocks-of-8 figure, against 2 at blocks of 16; fixed in

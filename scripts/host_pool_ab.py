@@ -5,7 +5,6 @@ and pool off, and into reused outputs; interleaved rounds, call ms (wall) and ke
 (the library's own HIP events), medians.  One pooled call after the rounds is compared with
 the reused-output call bit for bit (a compare between timed calls would idle the GPU).
 usage: python scripts/host_pool_ab.py [rounds]"""
-import ctypes as C
 import json
 import os
 import sys
@@ -13,28 +12,21 @@ import time
 
 import numpy as np
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-sys.path.insert(0, os.path.join(REPO, "tests"))
-import oracle_lib as O  # noqa: E402
-from practice_path_planning_for_formula_student_driverless_amd import abi, raceline  # noqa: E402
+import ab
+from practice_path_planning_for_formula_student_driverless_amd import abi, raceline
 
 
 def main():
     rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 6
-    lib = abi.load_library()
-    case = O.load_case("cmap1_n2000")
-    prob, cfg = O.case_problem(case), O.case_cfg(case)
+    lib = ab.load_library()
+    prob, cfg = ab.load("cmap1_n2000")
     B = 1024
     seeds = np.arange(B, dtype=np.uint64)
     pool = abi.HOST_POOL
     cap = pool.cap
     keep = raceline.optimize_batch(prob, cfg, seeds, B, mintime=False)
 
-    def kms():
-        run, k, call = C.c_float(), C.c_float(), C.c_float()
-        lib.rl_last_call_times(C.byref(run), C.byref(k), None, C.byref(call))
-        return k.value
+    kms = lambda: ab.last_call_kernel_ms(lib)   # noqa: E731
 
     same = [True]
 
@@ -62,16 +54,8 @@ def main():
         raceline.optimize_batch(prob, cfg, seeds, B, mintime=False, out=keep)
         return (time.perf_counter() - t0) * 1e3, kms()
 
-    cases = {"pool": pooled, "no_pool": no_pool, "reused": reused}
-    res = {k: [] for k in cases}
-    for f in cases.values():
-        f()
-        f()
-    for _ in range(rounds):
-        for k, f in cases.items():
-            # two calls per case: the second follows one of its own kind
-            f()
-            res[k].append(f())
+    # two calls per case: the second follows one of its own kind
+    res = ab.interleave({"pool": pooled, "no_pool": no_pool, "reused": reused}, rounds, repeat=2)
     pooled(check=True)
     out = {k: {"call_ms": round(float(np.median([c for c, _ in v])), 3),
                "kernel_ms": round(float(np.median([k_ for _, k_ in v])), 3),

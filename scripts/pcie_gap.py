@@ -1,47 +1,33 @@
 """Why is C2's kernel slower inside rl_optimize (host buffers, the drop-in path) than in the
-device-resident plan the bench times?    The same C2 launch (B=1024,
-min-curv) timed five ways, the optimiser kernel alone from its own HIP events:
+device-resident plan the bench times?  The same C2 launch (B=1024, min-curv), the optimiser
+kernel alone from its own HIP events:
   plan_b2b     rl_plan_run back to back, no host work between launches
   plan_sleep   rl_plan_run with a 3.5 ms host sleep between launches (the time rl_optimize
                spends copying results into the caller's buffers)
   plan_spin    the same gap spent busy-waiting on the host
   plan_copy    rl_plan_run + rl_plan_fetch into fresh host arrays each time
   optimize     rl_optimize (plan cache hit, pinned staging, threaded host copies)
-Run under rocprofv3 --kernel-trace the kernel durations can be read per launch too."""
-import ctypes as C
+  gap sweep    kernel ms against the GPU idle gap before each launch (0 .. 4 ms of host spin,
+               interleaved): the drop-in call pays the gapped figure
+Run under rocprofv3 --kernel-trace the kernel durations can be read per launch too.
+usage: python scripts/pcie_gap.py [reps]"""
 import json
-import os
 import sys
 import time
 
 import numpy as np
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-sys.path.insert(0, os.path.join(REPO, "tests"))
-import oracle_lib as O  # noqa: E402
+import ab
+from practice_path_planning_for_formula_student_driverless_amd import abi, raceline
 
-from practice_path_planning_for_formula_student_driverless_amd import abi, raceline  # noqa: E402
-
-lib = abi.load_library()
-case = O.load_case("cmap1_n2000")
-prob, cfg = O.case_problem(case), O.case_cfg(case)
+lib = ab.load_library()
+prob, cfg = ab.load("cmap1_n2000")
 B = 1024
 seeds = np.arange(B, dtype=np.uint64)
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 6
-res = {}
-plan = raceline.Plan(prob, cfg, seeds=seeds, B=B, modes=abi.RL_MODE_MINCURV)
+plan = ab.make_plans(lib, ab.WORKLOADS["c2"], B)[0]
 plan.run()
 plan.kernel_ms(1)
-
-
-def timed_plan(gap):
-    ms = []
-    for _ in range(reps):
-        plan.run()
-        ms.append(plan.kernel_ms(1))      # waits for the run
-        gap()
-    return ms
 
 
 def spin(s):
@@ -50,10 +36,27 @@ def spin(s):
         pass
 
 
-res["plan_b2b"] = timed_plan(lambda: None)
-res["plan_sleep"] = timed_plan(lambda: time.sleep(0.0035))
-res["plan_spin"] = timed_plan(lambda: spin(0.0035))
-res["plan_copy"] = timed_plan(lambda: plan.fetch())
+def after(gap):
+    def f():
+        plan.run()
+        k = plan.kernel_ms(1)      # waits for the run
+        gap()
+        return k
+    return f
+
+
+def before(ms):
+    def f():
+        spin(ms * 1e-3)
+        plan.run()
+        return plan.kernel_ms(1)
+    return f
+
+
+res = {k: [after(g)() for _ in range(reps)] for k, g in (
+    ("plan_b2b", lambda: None), ("plan_sleep", lambda: time.sleep(0.0035)), ("plan_spin", lambda: spin(0.0035)),
+    ("plan_copy", plan.fetch))}
+gaps = ab.interleave({str(g): before(g) for g in (0.0, 0.05, 0.2, 0.5, 1.0, 2.0, 4.0)}, reps)
 plan.close()
 raceline.optimize_batch(prob, cfg, seeds, B, mintime=False)
 ms, calls = [], []
@@ -62,10 +65,10 @@ for _ in range(reps):
     out = raceline.optimize_batch(prob, cfg, seeds, B, mintime=False)
     calls.append(1e3 * (time.perf_counter() - t0))
     del out
-    run, kmc, cm = C.c_float(), C.c_float(), C.c_float()
-    lib.rl_last_call_times(C.byref(run), C.byref(kmc), None, C.byref(cm))
-    ms.append(kmc.value)
+    ms.append(ab.last_call_kernel_ms(lib))
 res["optimize"] = ms
 res["optimize_call_ms"] = calls
 print(json.dumps({k: [round(x, 3) for x in v] for k, v in res.items()}))
 print(json.dumps({k: round(float(np.median(v)), 3) for k, v in res.items()}), flush=True)
+print(json.dumps({"kernel_ms_by_gap_ms": {g: ab.med_min_max(v)["median"] for g, v in gaps.items()},
+                  "min": {g: ab.med_min_max(v)["min"] for g, v in gaps.items()}}), flush=True)

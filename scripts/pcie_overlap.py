@@ -11,12 +11,8 @@ import time
 
 import numpy as np
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-sys.path.insert(0, os.path.join(REPO, "tests"))
-
-import oracle_lib as O  # noqa: E402
-from practice_path_planning_for_formula_student_driverless_amd import abi, raceline  # noqa: E402
+import ab
+from practice_path_planning_for_formula_student_driverless_amd import abi, raceline
 
 
 def main():
@@ -24,10 +20,9 @@ def main():
     B = int(sys.argv[2]) if len(sys.argv) > 2 else 1024
     reps = int(sys.argv[3]) if len(sys.argv) > 3 else 7
     mt = len(sys.argv) > 4 and sys.argv[4] == "both"
-    lib = abi.load_library(os.environ.get("PCIE_LIB", abi.LIB_PATH))
+    lib = ab.load_library(os.environ.get("PCIE_LIB", abi.LIB_PATH))
     raceline._lib = lambda: lib          # (a variant build, e.g. the RL_OVL_TRACE one)
-    c = O.load_case(case)
-    prob, cfg = O.case_problem(c), O.case_cfg(c)
+    prob, cfg = ab.load(case)
     MO = int(cfg.max_outer_iters)
     seeds = np.arange(B, dtype=np.uint64)
     res = {"1": [], "0": []}

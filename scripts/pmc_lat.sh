@@ -2,7 +2,7 @@
 # Latency / instruction-fetch PMC passes (one counter group per run, kernel trace only) over
 # a command (default: the C5 corridor-dominated run).  usage: scripts/pmc_lat.sh <outdir> [cmd...]
 out=${1:-gpurun_out/lat}; shift
-cmd=${*:-"python scripts/run_phase.py C5 --only"}
+cmd=${*:-"python scripts/ab.py run c5 --inner 0 --launches 3"}
 mkdir -p "$out"
 export TMPDIR=/tmp
 passes=(

@@ -1,4 +1,6 @@
-"""Report for scripts/pmc_split.py: counters per PGD evaluation per wave."""
+"""Report for `scripts/ab.py run c2 --inner default,0 --launches 1` under rocprofv3 --pmc (dispatch 1 = the
+default cfg, dispatch 2 = max_inner_iters 0; argv: the profile directory, the file with the command's output):
+counters per PGD evaluation per wave."""
 import csv, glob, json, sys
 from collections import defaultdict
 d = sys.argv[1]
