@@ -21,8 +21,10 @@
 //     per-wave LDS edge table; an evaluation costs two workgroup barriers;
 //   * J, Jsm and the Armijo decrease are reduced per wave then across waves in
 //     a fixed order, so the accept/backtrack decision is uniform;
-//   * outer-level state (P, n, α_total, α_last) lives in the instance's slice of
-//     the result arrays in HBM and is touched once per outer iteration;
+//   * outer-level state (P, n, α_total) lives in the instance's slice of the
+//     result arrays in HBM and is touched once per outer iteration; P and n cross
+//     to the corridor scan's mapping through the LDS coefficient area, and α_last
+//     is stored by the last update only;
 //   * the serial v(s) recurrence runs as an exact chunked relaxation: every
 //     thread recomputes its chunk from the pass-start values with the value its
 //     neighbour published, until no published value changes; the fixed point

@@ -205,27 +205,44 @@
             xpp = (sub2x(px[k + 3], px[k + 2]) + px[k + 1]) / hh; ypp = (sub2x(py[k + 3], py[k + 2]) + py[k + 1]) / hh;
         }
     };
-    // normals_from_points_generic ref:581-593, own valid samples -> NX/NY
-    auto normals = [&]() RL_AI {
+    // The path and its normals cross from the owners' mapping (K adjacent samples per lane) to
+    // the corridor scan's (64*CKK adjacent samples per wave) once per outer iteration.  They
+    // take the LDS coefficient area, which is free from the last evaluation's barrier until
+    // lin-geom fills it: slot k*T+t of coef[0] holds (x, y) of sample t*K+k and the same slot
+    // of coef[1] its normal; the scan replaces (x, y) of a sample with its bounds.  The global
+    // stores of x, y and the normals stay (outputs, and what lin-geom, the final pass and
+    // the next update read much later), but nothing waits for them.  Not for VSPLIT, whose
+    // curvature needs the path's halo of 2 (normals_kappa).
+    constexpr bool LDSX = !VSPLIT;
+    // normals_from_points_generic ref:581-593 of the own samples xs, ys (k < cnt valid): the
+    // two neighbour samples from the owners' slots (after a barrier), the normals -> NX/NY and
+    // coef[1]
+    auto normals = [&](const double (&xs)[K], const double (&ys)[K]) RL_AI {
         if (!active) return;
-        double px[K + 4], py[K + 4];
-        loadP(px, py);
+        const double2* pxy = &sm.u.coef[0][0][0];
+        double2* pn = &sm.u.coef[1][0][0];
         const int bs = opaque(base);     // per-phase addresses (nothing hoisted across the PGD loop)
+        const int jl = wrapj(bs - 1), jr = wrapj(bs + cnt);
+        const double2 pl = pxy[(jl % K) * T + jl / K], pr = pxy[(jr % K) * T + jr / K];
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             const int i = bs + k;
+            const double xm = (k > 0) ? xs[k > 0 ? k - 1 : 0] : pl.x, ym = (k > 0) ? ys[k > 0 ? k - 1 : 0] : pl.y;
+            double xn = pr.x, yn = pr.y;                     // sample i+1: the next own one, if any
+            if (k + 1 < K && (!RAGGED || k + 1 < cnt)) { xn = xs[k + 1 < K ? k + 1 : k]; yn = ys[k + 1 < K ? k + 1 : k]; }
             double tx, ty;
             if (N == 1) { tx = 1; ty = 0; }
-            else if (CLOSED) { tx = (px[k + 3] - px[k + 1]) * 0.5; ty = (py[k + 3] - py[k + 1]) * 0.5; }
-            else if (i == 0) { tx = px[k + 3] - px[k + 2]; ty = py[k + 3] - py[k + 2]; }
-            else if (i == N - 1) { tx = px[k + 2] - px[k + 1]; ty = py[k + 2] - py[k + 1]; }
-            else { tx = (px[k + 3] - px[k + 1]) * 0.5; ty = (py[k + 3] - py[k + 1]) * 0.5; }
+            else if (CLOSED) { tx = (xn - xm) * 0.5; ty = (yn - ym) * 0.5; }
+            else if (i == 0) { tx = xn - xs[k]; ty = yn - ys[k]; }
+            else if (i == N - 1) { tx = xs[k] - xm; ty = ys[k] - ym; }
+            else { tx = (xn - xm) * 0.5; ty = (yn - ym) * 0.5; }
             if (sqrt(tx * tx + ty * ty) < 1e-15) { tx = 1; ty = 0; }
             double vx = -ty, vy = tx;
             double n = sqrt(vx * vx + vy * vy);              // geom::normalize ref:132
             double ox = 0, oy = 0;
             if (!(n < 1e-15)) { ox = vx / n; oy = vy / n; }
             if (k < cnt) { NX[i] = ox; NY[i] = oy; }
+            pn[k * T + tid] = make_double2(ox, oy);
         }
     };
     // normals (as `normals`) and the curvature of heading_curv_from_points_generic
@@ -285,7 +302,12 @@
 #pragma unroll
             for (int k = 0; k < CKK; ++k) {
                 const int i = min(i0 + k, N - 1);
-                qx[k] = X[i]; qy[k] = Y[i]; ux[k] = NX[i]; uy[k] = NY[i];
+                if constexpr (LDSX) {    // the owners' slots (a clamped tail lane reads with its wave, before any bounds land)
+                    const double2 q = bnd[(i % K) * T + i / K], u = sm.u.coef[1][i % K][i / K];
+                    qx[k] = q.x; qy[k] = q.y; ux[k] = u.x; uy[k] = u.y;
+                } else {
+                    qx[k] = X[i]; qy[k] = Y[i]; ux[k] = NX[i]; uy[k] = NY[i];
+                }
                 act[k] = i0 + k < N;
             }
             if (pre) {
@@ -944,39 +966,65 @@
     // driver: compute_min_curvature_raceline ref:683-764 /
     //         compute_min_time_raceline ref:905-1052
     // ======================================================================
+    const int MO = C.max_outer_iters;
+    // alpha_total and alpha_last keep their zeros (ref:720 / 937) only if nothing iterates:
+    // otherwise the first update stores 0.0 + alpha and the last one alpha_last (below), and
+    // nothing reads either column before that
     if (active) {                                                // P := center
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             if (k < cnt) {
                 X[base + k] = CEN[2 * (base + k)];
                 Y[base + k] = CEN[2 * (base + k) + 1];
-                ATOT[base + k] = 0.0;
-                ALAST[base + k] = 0.0;
+                if (MO == 0) {
+                    ATOT[base + k] = 0.0;
+                    ALAST[base + k] = 0.0;
+                }
             }
         }
     }
 #pragma unroll
     for (int k = 0; k < K; ++k) { al[k] = 0.0; gr[k] = 0.0; G2[k] = 0.0; }
 
-    const int MO = C.max_outer_iters;
     RL_STAMP(0);
     for (int outer = 0;; ++outer) {
 #if RL_PRIO
         progress_prio(outer, MO, RL_PRIO);               // (tail balance: rl_kernels.h, build.py)
 #endif
+        double xs[K], ys[K];                             // P of the own samples (LDSX; 0 beyond cnt)
+#pragma unroll
+        for (int k = 0; k < K; ++k) { xs[k] = 0.0; ys[k] = 0.0; }
+        if (LDSX && outer == 0 && active) {              // P = center (stored above)
+            const int bu = opaque(base);
+#pragma unroll
+            for (int k = 0; k < K; ++k)
+                if (k < cnt) { xs[k] = CEN[2 * (bu + k)]; ys[k] = CEN[2 * (bu + k) + 1]; }
+        }
         if (outer > 0 && active) {
             const int bu = opaque(base);
-            // update (ref:743-746 / 1027-1030): alpha_last, P += n*alpha, alpha_accum
+            // update (ref:743-746 / 1027-1030): alpha_last, P += n*alpha, alpha_accum.
+            // alpha_last is an output only (ref:763 / 1050): the last update's alone is stored.
+            // alpha_accum starts from 0.0 (ref:720), so the first update adds to that constant
+            // instead of to a stored zero: the same sum, 0.0 + (-0.0) = +0.0 included
+            const bool last_upd = outer == MO, first_upd = outer == 1;   // (uniform)
 #pragma unroll
             for (int k = 0; k < K; ++k) {
                 if (k < cnt) {
                     const int i = bu + k;
-                    ALAST[i] = al[k];
-                    X[i] += NX[i] * al[k];
-                    Y[i] += NY[i] * al[k];
-                    ATOT[i] += al[k];
+                    if (last_upd) ALAST[i] = al[k];
+                    xs[k] = X[i] + NX[i] * al[k];
+                    ys[k] = Y[i] + NY[i] * al[k];
+                    X[i] = xs[k];
+                    Y[i] = ys[k];
+                    double at = 0.0;
+                    if (!first_upd) at = ATOT[i];
+                    ATOT[i] = at + al[k];
                 }
             }
+        }
+        if (LDSX && outer < MO) {        // the path into the owners' slots (see `normals`)
+#pragma unroll
+            for (int k = 0; k < K; ++k) sm.u.coef[0][k][tid] = make_double2(xs[k], ys[k]);
         }
 #pragma unroll
         for (int k = 0; k < K; ++k) { al[k] = 0.0; gr[k] = 0.0; }   // ref:757 / 1041
@@ -1012,10 +1060,13 @@
                 vsv[tid] = ka[0];
                 ka_done = true;
             } else {
-                normals();
+                normals(xs, ys);
             }
             __syncthreads();
             if constexpr (!VSPLIT) {                             // (VSPLIT: beside the v-pass below)
+#if defined(RL_STAMPS) && !defined(RL_STAMPS_EVAL)
+                RL_STAMP(11);                                    // (normals and their barrier; 7: the scan's loads)
+#endif
                 corridor(guard, pre, lo, hi);
                 seed_alpha();
             }

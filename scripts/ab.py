@@ -360,11 +360,12 @@ def time_workload(libs: dict, wl: Workload, B: int = None, modes=None, rounds: i
 # slot names of the RL_STAMPS builds, once per kernel family (16 slots of cycles per block)
 _BODY = ["setup", "corridor tail (combine, LDS, seed)", "mt: kappa / v-pass / gamma", "lin-geom", "PGD loop", "update", "final",
          "normals + corridor loads", "corridor: inner-ring rays", "corridor: outer-ring rays", "corridor: fallback search"]
+_NORMALS = ["normals + their barrier (slot 7: the scan's loads alone)"]
 STAMP_SLOTS = {
-    "reg": _BODY,
-    "mid": _BODY,
+    "reg": _BODY + _NORMALS,
+    "mid": _BODY + _NORMALS,
     # VSPLIT (min-time, K = 1): slots 12-15 are other waves' cycles, or counted in 7-10 already
-    "lat": _BODY + ["vsplit: join wait + collect (wave 0)", "vsplit: v-pass wave's v-pass [not in the sum]",
+    "lat": _BODY + ["normals + their barrier / vsplit: join wait + collect (wave 0)", "vsplit: v-pass wave's v-pass [not in the sum]",
                     "vsplit: wave 0 scan [in 7-10]", "vsplit: wave 1 scan [not in the sum]", "vsplit: wave 2 scan [not in the sum]"],
     # RL_STAMPS_EVAL (variant stamps_eval): the evaluation's phases, slot 4 = the rest of the loop
     "eval": _BODY + ["pgd: projection", "pgd: stencil+partials", "pgd: wave sum", "pgd: barrier+block sum", "pgd: gradient"],

@@ -1,6 +1,6 @@
 #!/bin/bash
 # rocprofv3 PMC passes over the C2 bench workload (counters in separate passes, kernel
-# trace only; no sys/runtime trace).  usage: scripts/pmc.sh <outdir>
+# trace only; no sys/runtime trace).  usage: [PMC_ONLY="3 4"] [PMC_CMD=...] scripts/pmc.sh <outdir>
 # Summarise with: python scripts/pmc_summary.py <outdir>
 out=${1:-gpurun_out/pmc}
 mkdir -p "$out"
@@ -12,9 +12,11 @@ passes=(
   "FETCH_SIZE"
   "WRITE_SIZE"
 )
+only=${PMC_ONLY:-"1 2 3 4"}      # the passes to take, e.g. PMC_ONLY="3 4": the traffic counters alone
 i=0
 for p in "${passes[@]}"; do
   i=$((i + 1))
+  case " $only " in *" $i "*) ;; *) continue ;; esac
   echo "=== pass $i: $p"
   timeout -k 10 240 rocprofv3 --pmc $p --kernel-trace -d "$out/p$i" -o run --output-format csv -- $cmd > "$out/p$i.log" 2>&1
   rc=$?
