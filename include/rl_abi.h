@@ -243,7 +243,8 @@ int rl_plan_bind_device_outputs(rl_plan* plan, int32_t which, const rl_out* dev_
 /* device time of the last run, in ms, measured with HIP events on the run stream:
  * idx 0 = the whole run, 1 = the min-curvature kernel, 2 = the min-time kernel, 3 = the
  * selection stage of the last rl_plan_select (score, rank and gather kernels), 4 = the lap
- * stage of the last rl_plan_lap (5 = its preparation kernel, 6 = its evaluation kernel). */
+ * stage of the last rl_plan_lap (5 = its preparation kernel, 6 = its evaluation kernel), 7 =
+ * the trajectory stage of the last rl_plan_trajectory. */
 int rl_plan_kernel_ms(rl_plan* plan, int32_t idx, float* ms);
 /* The batch size the plan's kernel shape is chosen for (rl_kernel_shape's B); 0 = the plan's
  * own B (the default).  Shapes differ in the tree order of the J / decrease / lap sums, so
@@ -339,6 +340,64 @@ int rl_optimize_best_scored(const rl_problem* prob, const rl_cfg* cfg, int32_t n
 int rl_path_lengths(const double* x, const double* y, int32_t N, int32_t B, int32_t closed,
                     int32_t device, double* L_out);
 
+/* ------------------------------------------------- trajectory stage: racelines by time
+ * What a controller tracks is the state at every control tick, not at every h metres.  The
+ * stage after the optimiser, the lap stage and the selection, on the device: for one row
+ * (x, y, heading, kappa, v, ax of N samples, step h, closed or open), in fp64 without
+ * contraction,
+ *   stamps  t_0 = 0,  t_{i+1} = t_i + h / max(1e-6, v_i)  for i = 0 .. N-1, added serially in
+ *           index order (the reference's lap loop, ref:854-860); S = closed ? N : N-1 segments,
+ *           segment i from sample i to sample j = (i+1) mod N;  T = t_S  (N == 0, and an open
+ *           row of one sample: T = 0)
+ *   ticks   tau_m = (double)m * dt,  M = min(M_cap, #{m : tau_m < T})  (strict);  T NaN or
+ *           infinite: M = 0
+ *   segment of a tick: the i in [0, S) with t_i <= tau_m < t_{i+1};  u = (tau_m - t_i) / (t_{i+1} - t_i)
+ *   s = ((double)i + u) * h;  x = x_i + u*(x_j - x_i), and y, v, kappa likewise;
+ *   heading = psi_i + u*d, d = psi_j - psi_i, less 2*pi if d > pi, plus 2*pi if d < -pi;
+ *   ax = ax_i (constant on a segment, ref:858).
+ * raceline.trajectory_host states the same in NumPy; the kernel equals it bit for bit.
+ * For closed rows T is the reference's lap summed serially; the optimiser's own `lap` sums the
+ * same terms as a tree and may differ from T in the last bits (by at most (N+2)*2^-52
+ * relative).  The stamp order is the contract, as the order of L_mc is for the lap stage.
+ * This is an addition to ABI 6.1 that leaves RL_ABI_MINOR as it is: callers discover it
+ * through rl_abi_features(). */
+typedef struct rl_traj {      /* caller-allocated; [R][M_cap] unless noted; NULL fields skipped */
+    double *s, *x, *y, *heading, *kappa, *v, *ax;
+    double *stamps;           /* [R][N+1] */
+    double *T;                /* [R] */
+    int32_t *count;           /* [R]  = M; ticks m >= count[r] of row r are unspecified */
+} rl_traj;
+#define RL_TRAJ_ALL 0         /* R = B: output row r is instance r */
+#define RL_TRAJ_SELECTED 1    /* R = G*k: output row g*k + r is instance index[g][r] of the plan's valid selection */
+#define RL_TRAJ_MAX_TICKS 1048576
+
+/* Enqueue the stage after the plan's last run (stream rules of rl_plan_select; a later run
+ * invalidates it).  mode RL_MODE_MINTIME reads the min-time rows in force (after
+ * rl_plan_bind_device_outputs: the caller's) with h = L/N (L[b]/N for per-instance lengths).
+ * mode RL_MODE_MINCURV reads the optimiser's x, y and the lap stage's heading, kappa, v, ax
+ * with h = L_mc[b]/N, and runs rl_plan_lap first unless a lap stage is valid since the last
+ * run.  rows RL_TRAJ_SELECTED resamples only the winners of the plan's valid selection, which
+ * must be of the same mode.  The buffers are plan-owned (they count toward the plan cache's
+ * budget), allocated at the first call and when R or M_cap grows.  rl_plan_kernel_ms index 7
+ * is the stage.  RL_EINVAL before any device work for: a NULL plan, a mode that is not exactly
+ * one of the plan's, dt not finite or <= 0, M_cap < 1 or > RL_TRAJ_MAX_TICKS, N == 0, an unknown
+ * `rows`, a plan never run, RL_TRAJ_SELECTED without a valid selection of `mode`. */
+int rl_plan_trajectory(rl_plan* plan, int32_t mode, int32_t rows, double dt, int32_t M_cap, void* hip_stream);
+/* Download the last trajectory stage (synchronises its stream) into the non-NULL fields of
+ * out.  RL_EINVAL before a stage, or after a run that followed it. */
+int rl_plan_fetch_trajectory(rl_plan* plan, rl_traj* out);
+/* rl_optimize_best_scored, then the trajectories of the winners (RL_TRAJ_SELECTED), with the
+ * winners' rows and trajectories downloaded in one pass: traj holds G*k rows. */
+int rl_optimize_best_trajectory(const rl_problem* prob, const rl_cfg* cfg, int32_t n_cfg, const uint64_t* seeds, int32_t B,
+                                const rl_select* sel, int32_t score, int32_t* index, double* score_out,
+                                double* all_scores, rl_out* out, double dt, int32_t M_cap, rl_traj* traj);
+/* The trajectories of B given rows [B][N] with steps h [B] (host in, host out; R = B) by the
+ * same kernel.  N == 0 gives T = 0 and count = 0.  RL_EINVAL for a NULL input or out, B < 1,
+ * N < 0, a bad dt or M_cap; RL_ETOOBIG for N > 1048576. */
+int rl_trajectory(const double* x, const double* y, const double* heading, const double* kappa,
+                  const double* v, const double* ax, const double* h, int32_t N, int32_t B,
+                  int32_t closed, double dt, int32_t M_cap, int32_t device, rl_traj* out);
+
 /* B lap evaluations of given paths: heading/curvature
  * (heading_curv_from_points_generic, ref:595-620) and velocity_profile_forward_backward
  * (ref:782-862) with h = L[b]/N on path b — the min-time driver's final step
@@ -413,6 +472,9 @@ int         rl_device_count(void);
 const char* rl_last_error(void);
 int         rl_abi_version(void);
 int         rl_abi_minor(void);
+/* additions since the last minor, one bit each (a library without this function has none) */
+#define RL_FEATURE_TRAJECTORY 1   /* bit 0: the trajectory stage */
+int         rl_abi_features(void);
 /* samples per lane of the THROUGHPUT shape for N (4: N <= 256, 5: N <= 320, 8: N <= 4096;
  * 1 = the streaming kernel), or RL_ETOOBIG.  Batches small enough for a latency shape launch fewer samples per lane:
  * rl_kernel_shape(N, B, mode) reports the shape a launch actually uses. */

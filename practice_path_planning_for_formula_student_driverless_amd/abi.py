@@ -122,6 +122,20 @@ class RlSelect(C.Structure):
     _fields_ = [("mode", C.c_int32), ("k", C.c_int32), ("group_size", C.c_int32), ("_pad", C.c_int32)]
 
 
+RL_FEATURE_TRAJECTORY = 1  # rl_abi_features() bit 0: the trajectory stage
+RL_TRAJ_ALL = 0            # one trajectory per instance
+RL_TRAJ_SELECTED = 1       # one per winner of the plan's valid selection
+RL_TRAJ_MAX_TICKS = 1 << 20
+TRAJ_COLS = ("s", "x", "y", "heading", "kappa", "v", "ax")
+
+
+class RlTraj(C.Structure):
+    """``rl_traj`` — caller-allocated trajectory arrays: the columns [R][M_cap], stamps [R][N+1],
+    T [R], count [R]; NULL fields are skipped."""
+
+    _fields_ = [(n, C.POINTER(C.c_double)) for n in TRAJ_COLS + ("stamps", "T")] + [("count", C.POINTER(C.c_int32))]
+
+
 OUT_F64 = ("x", "y", "heading", "kappa", "alpha_total", "alpha_last")
 OUT_F64_MT = OUT_F64 + ("v", "ax")
 
@@ -462,6 +476,16 @@ DECLS = [
     ("rl_path_lengths", C.c_int, [_F64, _F64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F64]),
 ]
 
+# additions that leave RL_ABI_MINOR as it is (rl_abi_features() names them); bound like DECLS
+_TRAJ = _P(RlTraj)
+DECLS_EXT = [
+    ("rl_abi_features", C.c_int, []),
+    ("rl_plan_trajectory", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_void_p]),
+    ("rl_plan_fetch_trajectory", C.c_int, [C.c_void_p, _TRAJ]),
+    ("rl_optimize_best_trajectory", C.c_int, _BATCH + [_SEL, C.c_int32] + _BEST + [C.c_double, C.c_int32, _TRAJ]),
+    ("rl_trajectory", C.c_int, [_F64] * 7 + [C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32, _TRAJ]),
+]
+
 
 def declare_optimize(fn) -> None:
     """rl_optimize's signature (the oracle's oracle_optimize shares it)."""
@@ -473,14 +497,17 @@ _LIB = None
 
 def load_library(path: str = LIB_PATH) -> C.CDLL:
     """Load librl.so (the HIP path).  Raises if it is missing: there is no fallback; a library
-    that lacks a function of DECLS raises AttributeError naming it."""
+    that lacks a function of DECLS or DECLS_EXT raises AttributeError naming it."""
     global _LIB
     if _LIB is not None and path == LIB_PATH:
         return _LIB
     if not os.path.exists(path):
         raise RuntimeError(f"librl.so not built at {path}: run `python -c 'import __graft_entry__ as g; g.build()'`")
     lib = C.CDLL(path)
-    for name, restype, argtypes in DECLS:
+    # a library built from an earlier revision (RL_LIB: A/B against a parent) has no
+    # rl_abi_features and none of DECLS_EXT; one that has it must have them all
+    ext = DECLS_EXT if hasattr(lib, "rl_abi_features") else []
+    for name, restype, argtypes in DECLS + ext:
         fn = getattr(lib, name)
         fn.restype = restype
         if argtypes is not None:

@@ -11,6 +11,7 @@ extern "C" {
 const char* rl_last_error(void) { return g_err.c_str(); }
 int rl_abi_version(void) { return RL_ABI_VERSION; }
 int rl_abi_minor(void) { return RL_ABI_MINOR; }
+int rl_abi_features(void) { return RL_FEATURE_TRAJECTORY; }
 
 int rl_device_count(void) {
     int n = 0;
@@ -276,6 +277,50 @@ int rl_path_lengths(const double* x, const double* y, int32_t N, int32_t B, int3
         return fail(RL_EHIP, "rl_path_lengths: kernel");
     if (hipMemcpy(L_out, d_L, (size_t)B * 8, hipMemcpyDeviceToHost) != hipSuccess)
         return fail(RL_EHIP, "rl_path_lengths: download");
+    return RL_OK;
+}
+
+// the trajectory kernel alone on host rows (rl_trajectory.hip): output row b is row b
+int rl_trajectory(const double* x, const double* y, const double* heading, const double* kappa, const double* v,
+                  const double* ax, const double* h, int32_t N, int32_t B, int32_t closed, double dt, int32_t M_cap,
+                  int32_t device, rl_traj* out) {
+    if (!x || !y || !heading || !kappa || !v || !ax || !h || !out)
+        return fail(RL_EINVAL, "rl_trajectory: an input row, h or out is NULL");
+    if (B < 1 || N < 0) return fail(RL_EINVAL, "rl_trajectory: B < 1 or N < 0");
+    if (int rc = check_traj(dt, M_cap)) return rc;
+    if (N > rl::RL_STREAM_MAX_N) return fail(RL_ETOOBIG, "rl_trajectory: N exceeds 1048576");
+    if (int rc = select_device(device)) return rc;
+    const size_t BN = (size_t)B * (size_t)N, BM = (size_t)B * (size_t)M_cap;
+    DevArena mem;
+    const double* in[6] = {x, y, heading, kappa, v, ax};
+    double* d_in[6];
+    for (auto& d : d_in) d = mem.get<double>(BN);
+    double* d_h = mem.get<double>((size_t)B);
+    rl::TrajParams q{};
+    for (auto& c : q.out) c = mem.get<double>(BM);
+    q.stamps = mem.get<double>((size_t)B * ((size_t)N + 1));
+    q.T = mem.get<double>((size_t)B);
+    q.count = mem.get<int32_t>((size_t)B);
+    if (!mem.ok()) return fail(RL_ENOMEM, "rl_trajectory: hipMalloc failed");
+    for (int c = 0; c < 6; ++c)
+        if (BN && hipMemcpy(d_in[c], in[c], BN * 8, hipMemcpyHostToDevice) != hipSuccess)
+            return fail(RL_EHIP, "rl_trajectory: upload");
+    if (hipMemcpy(d_h, h, (size_t)B * 8, hipMemcpyHostToDevice) != hipSuccess) return fail(RL_EHIP, "rl_trajectory: upload");
+    q.x = d_in[0]; q.y = d_in[1]; q.heading = d_in[2]; q.kappa = d_in[3]; q.v = d_in[4]; q.ax = d_in[5];
+    q.h = d_h;
+    q.dt = dt;
+    q.N = N; q.B = B; q.R = B; q.closed = closed ? 1 : 0; q.M_cap = M_cap;
+    if (rl::launch_trajectory(q, nullptr) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+        return fail(RL_EHIP, "rl_trajectory: kernel");
+    double* const dst[rl::TRAJ_COLS] = {out->s, out->x, out->y, out->heading, out->kappa, out->v, out->ax};
+    std::vector<CopyJob> jobs;
+    for (int c = 0; c < rl::TRAJ_COLS; ++c) add_job(jobs, dst[c], q.out[c], BM * 8);
+    add_job(jobs, out->stamps, q.stamps, (size_t)B * ((size_t)N + 1) * 8);
+    add_job(jobs, out->T, q.T, (size_t)B * 8);
+    add_job(jobs, out->count, q.count, (size_t)B * 4);
+    for (const CopyJob& j : jobs)
+        if (hipMemcpy(j.dst, j.src, j.bytes, hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(RL_EHIP, "rl_trajectory: download");
     return RL_OK;
 }
 

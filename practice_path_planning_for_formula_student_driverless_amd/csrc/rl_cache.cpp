@@ -462,6 +462,10 @@ struct BestArgs {
     double* all_scores;
     rl_out* out;
     int32_t score_kind;               // RL_SCORE_DEFAULT or RL_SCORE_LAP
+    // rl_optimize_best_trajectory: the winners' trajectories too (traj nullptr: none)
+    double traj_dt = 0.0;
+    int32_t traj_M = 0;
+    rl_traj* traj = nullptr;
 };
 
 // rl_optimize / rl_lap_eval through the plan cache (see above), on the calling thread's
@@ -561,6 +565,9 @@ int run_cached(const rl_problem* prob, const rl_cfg* cfg, int32_t n_cfg, const u
         const size_t gs = best->sel->group_size ? (size_t)best->sel->group_size : (size_t)B;
         const size_t R = (size_t)B / gs * (size_t)best->sel->k, mo = (size_t)p->max_outer;
         down_bytes = 16 * 256 + R * (8 * (size_t)p->N * 8 + 8 + (3 * mo + 1) * 4 + 12) + (size_t)B * 8;
+        // and of the trajectory's jobs: 7 columns, the stamps, T and count
+        if (best->traj)
+            down_bytes += 10 * 256 + R * (((size_t)TRAJ_COLS * (size_t)best->traj_M + (size_t)p->N + 2) * 8 + 4);
     }
     if (down_bytes > e->pin_bytes) {
         if (hipStreamSynchronize(p->own_stream) != hipSuccess) return drop(fail(RL_EHIP, "upload sync"));
@@ -593,8 +600,11 @@ int run_cached(const rl_problem* prob, const rl_cfg* cfg, int32_t n_cfg, const u
     if (rc) return drop(rc);
     if (best) {
         if ((rc = rl_plan_select_scored(p, best->sel, best->score_kind, nullptr))) return drop(rc);
+        if (best->traj && (rc = rl_plan_trajectory(p, best->sel->mode, RL_TRAJ_SELECTED, best->traj_dt, best->traj_M, nullptr)))
+            return drop(rc);
         jobs.clear();
         sel_jobs(p, best->index, best->score, best->all_scores, best->out, jobs);
+        if (best->traj) traj_jobs(p, best->traj, jobs);
         if (staged_bytes(jobs) > e->pin_bytes) return drop(fail(RL_EHIP, "selection staging larger than its bound"));
         rc = download_staged(e, p->own_stream, jobs, 0);
     } else if (overlap) rc = download_overlapped(e, p, jm, epoch);
@@ -644,6 +654,24 @@ int rl_optimize_best_scored(const rl_problem* prob, const rl_cfg* cfg, int32_t n
     int gs = 0;
     if (int rc = check_select(sel, B, prob->N, sel->mode, &gs)) return rc;
     const BestArgs best{sel, index, score_out, all_scores, out, score};
+    return run_cached(prob, cfg, n_cfg, seeds, B, sel->mode, nullptr, nullptr, nullptr, nullptr, nullptr, &best);
+}
+
+int rl_optimize_best_trajectory(const rl_problem* prob, const rl_cfg* cfg, int32_t n_cfg, const uint64_t* seeds, int32_t B,
+                                const rl_select* sel, int32_t score, int32_t* index, double* score_out,
+                                double* all_scores, rl_out* out, double dt, int32_t M_cap, rl_traj* traj) {
+    if (!sel || !index || !score_out || !traj) return fail(RL_EINVAL, "rl_optimize_best_trajectory: sel / index / score / traj is NULL");
+    if (score != RL_SCORE_DEFAULT && score != RL_SCORE_LAP) return fail(RL_EINVAL, "select: unknown score");
+    if (sel->mode != RL_MODE_MINCURV && sel->mode != RL_MODE_MINTIME)
+        return fail(RL_EINVAL, "select: mode must be exactly one of RL_MODE_MINCURV, RL_MODE_MINTIME");
+    if (int rc = check_traj(dt, M_cap)) return rc;
+    if (int rc = check_inputs(prob, cfg, n_cfg, B, sel->mode, nullptr)) return rc;
+    int gs = 0;
+    if (int rc = check_select(sel, B, prob->N, sel->mode, &gs)) return rc;
+    BestArgs best{sel, index, score_out, all_scores, out, score};
+    best.traj_dt = dt;
+    best.traj_M = M_cap;
+    best.traj = traj;
     return run_cached(prob, cfg, n_cfg, seeds, B, sel->mode, nullptr, nullptr, nullptr, nullptr, nullptr, &best);
 }
 

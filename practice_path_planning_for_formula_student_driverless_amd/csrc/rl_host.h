@@ -18,6 +18,7 @@
 #include "rl_kernels.h"
 #include "rl_select.h"
 #include "rl_lap_stage.h"
+#include "rl_trajectory.h"
 
 namespace rl {
 
@@ -434,6 +435,17 @@ struct rl_plan {
     bool lap_valid = false;
     hipStream_t lap_stream = nullptr;
     hipEvent_t ev_lap[3] = {nullptr, nullptr, nullptr};   // start, after the preparation, end
+    // trajectory stage (rl_plan_trajectory): the columns [traj_R][traj_M], the stamps
+    // [traj_R][N + 1], T and count [traj_R] of the last stage, in buffers sized for traj_cap_R
+    // rows of traj_cap_M ticks; allocated at the first stage and again when either grows.
+    // traj_R = 0: no stage since the last run.
+    double* traj_col[rl::TRAJ_COLS] = {};
+    double* traj_stamps = nullptr;
+    double* traj_T = nullptr;
+    int32_t* traj_count = nullptr;
+    rl::DevArena traj_mem;
+    int traj_cap_R = 0, traj_cap_M = 0, traj_R = 0, traj_M = 0;
+    hipEvent_t ev_traj[2] = {nullptr, nullptr};
 
     template <class T>
     int alloc(T** p, size_t n) {
@@ -442,7 +454,7 @@ struct rl_plan {
     }
     int nomem() const { return rl::fail(RL_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(mem.err)); }
     // device memory held (plan cache budget)
-    size_t dev_bytes() const { return mem.bytes + sel_mem.bytes + lap_mem.bytes; }
+    size_t dev_bytes() const { return mem.bytes + sel_mem.bytes + lap_mem.bytes + traj_mem.bytes; }
     // the stream of the last run or stage
     hipStream_t run_stream() const { return last_stream ? last_stream : own_stream; }
     // the batch size the kernel shape is chosen for
@@ -473,5 +485,9 @@ int check_select(const rl_select* sel, int32_t B, int32_t N, int32_t modes, int*
 // the copies that download the last selection of p (out_jobs' order for the rows)
 void sel_jobs(const rl_plan* p, int32_t* index, double* score, double* all_scores, const rl_out* o,
               std::vector<CopyJob>& jobs);
+// argument checks shared by every trajectory entry point (no device call)
+int check_traj(double dt, int32_t M_cap);
+// the copies that download the last trajectory stage of p into the non-NULL fields of t
+void traj_jobs(const rl_plan* p, const rl_traj* t, std::vector<CopyJob>& jobs);
 
 }  // namespace rl

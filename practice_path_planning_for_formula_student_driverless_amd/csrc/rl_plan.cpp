@@ -190,6 +190,9 @@ int rl_plan_destroy(rl_plan* plan) {
     plan->lap_mem.release();
     for (auto& e : plan->ev_lap)
         if (e) hipEventDestroy(e);
+    plan->traj_mem.release();
+    for (auto& e : plan->ev_traj)
+        if (e) hipEventDestroy(e);
     for (auto& e : plan->ev)
         if (e) hipEventDestroy(e);
     for (auto& e : plan->ev_end)
@@ -287,6 +290,7 @@ int rl_plan_run(rl_plan* p, void* hip_stream) {
     p->ran = true;
     p->sel_mode = 0;                                   // an earlier selection is of an earlier run
     p->lap_valid = false;                              // and so is an earlier lap stage
+    p->traj_R = 0;                                     // and an earlier trajectory stage
     return RL_OK;
 }
 
@@ -409,6 +413,7 @@ int rl_plan_run_group(rl_plan* const* plans, int32_t n, void* hip_stream) {
         plans[i]->ran = true;
         plans[i]->sel_mode = 0;
         plans[i]->lap_valid = false;
+        plans[i]->traj_R = 0;
     }
     return RL_OK;
 }
@@ -431,6 +436,11 @@ int rl_plan_kernel_ms(rl_plan* p, int32_t idx, float* ms) {
         a = p->ev_lap[idx == 6 ? 1 : 0];
         b = p->ev_lap[idx == 5 ? 1 : 2];
         HIPCHK(hipEventSynchronize(p->ev_lap[2]));
+    }
+    else if (idx == 7 && p->traj_R) {
+        a = p->ev_traj[0];
+        b = p->ev_traj[1];
+        HIPCHK(hipEventSynchronize(b));
     }
     else if (idx == 1 && mc) { a = p->ev[1]; b = p->ev_end[0]; }
     else if (idx == 2 && mt) { a = p->ev[2]; b = p->ev_end[1]; }

@@ -1,6 +1,7 @@
 // rl_stages.cpp — C-ABI implementation, part 3: the stages that follow a plan's run on the
 // device.  Selection (rl_select.hip): score, rank and gather.  Lap stage (rl_lap_stage.hip,
-// DESIGN §3i): the debug dump's "min-curv lap" for every instance of a plan.
+// DESIGN §3i): the debug dump's "min-curv lap" for every instance of a plan.  Trajectory
+// stage (rl_trajectory.hip): time stamps and the state at every control tick.
 #include "rl_host.h"
 
 using namespace rl;
@@ -39,7 +40,48 @@ void rl::sel_jobs(const rl_plan* p, int32_t* index, double* score, double* all_s
     field_jobs(o, p->selb, {R, (size_t)p->N, mo, mt ? mo + 1 : 1}, mt || p->sel_lap, false, jobs);
 }
 
+int rl::check_traj(double dt, int32_t M_cap) {
+    if (!std::isfinite(dt) || !(dt > 0.0)) return fail(RL_EINVAL, "trajectory: dt must be finite and > 0");
+    if (M_cap < 1 || M_cap > RL_TRAJ_MAX_TICKS) return fail(RL_EINVAL, "trajectory: M_cap must be 1..1048576");
+    return RL_OK;
+}
+
+// the columns in rl_traj's order (TrajParams::out's), then stamps, T and count
+void rl::traj_jobs(const rl_plan* p, const rl_traj* t, std::vector<CopyJob>& jobs) {
+    if (!t) return;
+    const size_t R = (size_t)p->traj_R, col = R * (size_t)p->traj_M * 8;
+    double* const dst[TRAJ_COLS] = {t->s, t->x, t->y, t->heading, t->kappa, t->v, t->ax};
+    for (int c = 0; c < TRAJ_COLS; ++c) add_job(jobs, dst[c], p->traj_col[c], col);
+    add_job(jobs, t->stamps, p->traj_stamps, R * ((size_t)p->N + 1) * 8);
+    add_job(jobs, t->T, p->traj_T, R * 8);
+    add_job(jobs, t->count, p->traj_count, R * 4);
+}
+
 namespace {
+
+// plan-owned trajectory buffers for R rows of M ticks; they count toward dev_bytes()
+int traj_alloc(rl_plan* p, int R, int M) {
+    if (p->traj_stamps && R <= p->traj_cap_R && M <= p->traj_cap_M) return RL_OK;
+    if (p->last_stream) HIPCHK(hipStreamSynchronize(p->last_stream));   // it may still write the old ones
+    DevArena& a = p->traj_mem;
+    a.release();
+    R = std::max(R, p->traj_cap_R);
+    M = std::max(M, p->traj_cap_M);
+    p->traj_cap_R = p->traj_cap_M = 0;
+    p->traj_stamps = nullptr;
+    for (auto& c : p->traj_col) c = a.get<double>((size_t)R * (size_t)M);
+    double* stamps = a.get<double>((size_t)R * ((size_t)p->N + 1));
+    p->traj_T = a.get<double>((size_t)R);
+    p->traj_count = a.get<int32_t>((size_t)R);
+    if (!a.ok()) {
+        a.release();
+        return fail(RL_ENOMEM, "hipMalloc (trajectory buffers) failed");
+    }
+    p->traj_stamps = stamps;
+    p->traj_cap_R = R;
+    p->traj_cap_M = M;
+    return RL_OK;
+}
 
 // plan-owned selection buffers for `rows` winners; they count toward dev_bytes()
 int select_alloc(rl_plan* p, int rows) {
@@ -244,6 +286,74 @@ int rl_plan_fetch_selected(rl_plan* p, int32_t* index, double* score, double* al
     hipStream_t st = p->run_stream();
     std::vector<CopyJob> jobs;
     sel_jobs(p, index, score, all_scores, out, jobs);
+    if (int rc = queue_downloads(jobs, st)) return rc;
+    HIPCHK(hipStreamSynchronize(st));
+    return RL_OK;
+}
+
+// One launch of rl_trajectory_kernel over the rows in force: the min-time optimiser's, or the
+// min-curvature optimiser's x, y with the lap stage's heading, kappa, v, ax and lengths.
+int rl_plan_trajectory(rl_plan* p, int32_t mode, int32_t rows, double dt, int32_t M_cap, void* hip_stream) {
+    if (!p) return fail(RL_EINVAL, "plan is NULL");
+    if (mode != RL_MODE_MINCURV && mode != RL_MODE_MINTIME)
+        return fail(RL_EINVAL, "trajectory: mode must be exactly one of RL_MODE_MINCURV, RL_MODE_MINTIME");
+    if (!(p->modes & mode)) return fail(RL_EINVAL, "trajectory: mode is not among the plan's modes");
+    if (int rc = check_traj(dt, M_cap)) return rc;
+    if (p->N == 0) return fail(RL_EINVAL, "trajectory: N == 0 (no row)");
+    if (rows != RL_TRAJ_ALL && rows != RL_TRAJ_SELECTED) return fail(RL_EINVAL, "trajectory: unknown rows");
+    if (!p->ran) return fail(RL_EINVAL, "rl_plan_trajectory: the plan has not run");
+    const bool selected = rows == RL_TRAJ_SELECTED;
+    if (selected && p->sel_mode != mode)
+        return fail(RL_EINVAL, "rl_plan_trajectory: no selection of this mode since the plan's last run");
+    const bool mc = mode == RL_MODE_MINCURV;
+    p->traj_R = 0;
+    if (mc && !p->lap_valid)
+        if (int rc = rl_plan_lap(p, hip_stream)) return rc;
+    HIPCHK(hipSetDevice(p->device));
+    const int R = selected ? p->sel_G * p->sel_k : p->B;
+    hipStream_t run_st = p->run_stream();
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : run_st;
+    if (int rc = traj_alloc(p, R, M_cap)) return rc;
+    for (auto& e : p->ev_traj)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    if (st != run_st) {
+        HIPCHK(hipStreamWaitEvent(st, p->ev[3], 0));
+        if (selected) HIPCHK(hipStreamWaitEvent(st, p->ev_sel[1], 0));
+    }
+    if (mc && st != p->lap_stream) HIPCHK(hipStreamWaitEvent(st, p->ev_lap[2], 0));
+    p->last_stream = st;
+    HIPCHK(hipEventRecord(p->ev_traj[0], st));
+    const ModeBufs& mb = p->mb[mc ? 0 : 1];
+    const ModeBufs& src = mc ? p->lapb : mb;
+    rl::TrajParams q{};
+    q.x = mb.x; q.y = mb.y;
+    q.heading = src.heading; q.kappa = src.kappa; q.v = src.v; q.ax = src.ax;
+    q.Ls = mc ? p->d_Lmc : p->d_Ls;
+    q.L = p->L;
+    q.index = selected ? p->d_index : nullptr;
+    for (int c = 0; c < TRAJ_COLS; ++c) q.out[c] = p->traj_col[c];
+    q.stamps = p->traj_stamps;
+    q.T = p->traj_T;
+    q.count = p->traj_count;
+    q.dt = dt;
+    q.N = p->N; q.B = p->B; q.R = R; q.closed = p->closed; q.M_cap = M_cap;
+    const hipError_t e = rl::launch_trajectory(q, st);
+    if (e != hipSuccess) return fail(RL_EHIP, std::string("trajectory launch: ") + hipGetErrorString(e));
+    HIPCHK(hipEventRecord(p->ev_traj[1], st));
+    p->traj_R = R;
+    p->traj_M = M_cap;
+    return RL_OK;
+}
+
+int rl_plan_fetch_trajectory(rl_plan* p, rl_traj* out) {
+    if (!p) return fail(RL_EINVAL, "plan is NULL");
+    if (!out) return fail(RL_EINVAL, "rl_plan_fetch_trajectory: out is NULL");
+    if (!p->traj_R) return fail(RL_EINVAL, "rl_plan_fetch_trajectory: no trajectory stage since the plan's last run");
+    HIPCHK(hipSetDevice(p->device));
+    hipStream_t st = p->run_stream();
+    HIPCHK(hipStreamWaitEvent(st, p->ev_traj[1], 0));   // (a later stage may have moved to another stream)
+    std::vector<CopyJob> jobs;
+    traj_jobs(p, out, jobs);
     if (int rc = queue_downloads(jobs, st)) return rc;
     HIPCHK(hipStreamSynchronize(st));
     return RL_OK;

@@ -41,6 +41,9 @@
 //   --seeds B   optimise B α-seeds in one launch; writes <base>_batch_summary.csv
 //   --best K    with --seeds and --mode mincurv|mintime: also rank the batch on the GPU
 //               (rl_optimize_best, one group) and write <base>_best<r>_raceline.csv, r = 0..K-1
+//   --trajectory-dt DT [--trajectory-cap M]  with --best K: also resample the K winners on the
+//               GPU at ticks of DT seconds, at most M (4096) each (rl_optimize_best_trajectory),
+//               and write <base>_trajectory_<r>.csv: t,s,x,y,heading_rad,curvature,v_mps,ax_mps2
 //   --score lap with --best K --mode mincurv: rank the min-curvature racelines by their lap
 //               time (the lap stage, rl_optimize_best_scored); the lap_time_s column of
 //               <base>_batch_summary.csv then holds every seed's lap
@@ -1190,7 +1193,7 @@ static void compute_mintime_and_save(const string& base, const vector<Vec2>& cen
 // B α-seeds in one launch (beyond the reference): one summary row per instance.
 static void batch_and_save(const string& base, const vector<Vec2>& center, double L, bool closed,
                            const vector<Vec2>& inner_from_mids, const vector<Vec2>& outer_from_mids, int B, int modes,
-                           int repeat, int best, bool score_lap) {
+                           int repeat, int best, bool score_lap, double traj_dt, int traj_cap) {
     auto& C = cfg::get();
     SegVec innerE = closed ? edges::ringEdges(inner_from_mids) : edges::polylineEdges(inner_from_mids);
     SegVec outerE = closed ? edges::ringEdges(outer_from_mids) : edges::polylineEdges(outer_from_mids);
@@ -1246,6 +1249,12 @@ static void batch_and_save(const string& base, const vector<Vec2>& center, doubl
     const size_t N = center.size();
     vector<int32_t> idx((size_t)std::max(best, 0));
     vector<double> sc(idx.size()), bx(idx.size() * N), by(idx.size() * N);
+    // --trajectory-dt: the winners' trajectories, resampled on the GPU in the same call
+    const bool want_traj = traj_dt > 0.0 && best > 0;
+    const size_t RM = want_traj ? idx.size() * (size_t)traj_cap : 0;
+    vector<double> tcol[7];
+    for (auto& col : tcol) col.resize(RM);
+    vector<int32_t> tcount(want_traj ? idx.size() : 0);
     auto run_best = [&]() {
         rl_select sel;
         std::memset(&sel, 0, sizeof(sel));
@@ -1256,7 +1265,17 @@ static void batch_and_save(const string& base, const vector<Vec2>& center, doubl
         std::memset(&ob, 0, sizeof(ob));
         ob.x = bx.data();
         ob.y = by.data();
-        if (score_lap)
+        if (want_traj) {
+            rl_traj tj;
+            std::memset(&tj, 0, sizeof(tj));
+            tj.s = tcol[0].data(); tj.x = tcol[1].data(); tj.y = tcol[2].data(); tj.heading = tcol[3].data();
+            tj.kappa = tcol[4].data(); tj.v = tcol[5].data(); tj.ax = tcol[6].data();
+            tj.count = tcount.data();
+            gpu::check(rl_optimize_best_trajectory(&pk.prob, &c, 1, seeds.data(), B, &sel,
+                                                   score_lap ? RL_SCORE_LAP : RL_SCORE_DEFAULT, idx.data(), sc.data(),
+                                                   score_lap ? lap.data() : nullptr, &ob, traj_dt, traj_cap, &tj),
+                       "rl_optimize_best_trajectory");
+        } else if (score_lap)
             gpu::check(rl_optimize_best_scored(&pk.prob, &c, 1, seeds.data(), B, &sel, RL_SCORE_LAP, idx.data(),
                                                sc.data(), lap.data(), &ob),
                        "rl_optimize_best_scored");
@@ -1281,6 +1300,23 @@ static void batch_and_save(const string& base, const vector<Vec2>& center, doubl
         if (!o) throw std::runtime_error("save best raceline failed");
         for (size_t i = 0; i < N; ++i) o.f << bx[r * N + i] << "," << by[r * N + i] << "\n";
         if (C.emit_closed_duplicate && N > 0) o.f << bx[r * N] << "," << by[r * N] << "\n";
+    }
+    // <base>_trajectory_<r>.csv: one row per tick of winner r, the numbers formatted on the GPU
+    for (int r = 0; want_traj && r < best; ++r) {
+        const int64_t rows = tcount[r];
+        vector<double> tab((size_t)rows * 8);
+        for (int64_t m = 0; m < rows; ++m) {
+            tab[(size_t)m * 8] = (double)m * traj_dt;
+            for (int cc = 0; cc < 7; ++cc) tab[(size_t)m * 8 + 1 + cc] = tcol[cc][(size_t)r * traj_cap + (size_t)m];
+        }
+        vector<char> text((size_t)rows * 8 * 22 + 1);
+        int64_t len = 0;
+        gpu::check(rl_format_csv(tab.data(), rows, 8, gpu::device, text.data(), (int64_t)text.size(), &len, nullptr),
+                   "rl_format_csv");
+        io::Csv o(base + "_trajectory_" + std::to_string(r) + ".csv");
+        if (!o) throw std::runtime_error("save trajectory failed");
+        o.f << "t,s,x,y,heading_rad,curvature,v_mps,ax_mps2\n";
+        o.f.write(text.data(), (std::streamsize)len);
     }
     std::cerr << "[best] " << (mt || score_lap ? "lap_time_s" : "curvature_score") << " of the " << best << " best of B=" << B << ":";
     std::cerr << std::setprecision(9);
@@ -1377,7 +1413,7 @@ int run_pipeline(const string& innerPath, const string& outerPath, const string&
 
 // Steps 7-8 from the reference's step-6 files.
 int run_from_centerline(const string& outPath, double L, double s0, const string& mode, int B, int repeat, int best,
-                        const string& score) {
+                        const string& score, double traj_dt, int traj_cap) {
     auto& C = cfg::get();
     const string base = io::dropExt(outPath);
     const bool closed_mode = C.is_closed_track;
@@ -1404,6 +1440,17 @@ int run_from_centerline(const string& outPath, double L, double s0, const string
             return 2;
         }
     }
+    if (traj_dt != 0.0 || traj_cap != 0) {
+        if (best <= 0 || B <= 0) {
+            std::cerr << "[ERR] --trajectory-dt needs --seeds B --best K\n";
+            return 2;
+        }
+        if (traj_cap == 0) traj_cap = 4096;
+        if (!(traj_dt > 0.0) || !std::isfinite(traj_dt) || traj_cap < 1 || traj_cap > RL_TRAJ_MAX_TICKS) {
+            std::cerr << "[ERR] --trajectory-dt DT > 0 [--trajectory-cap M, 1.." << RL_TRAJ_MAX_TICKS << "]\n";
+            return 2;
+        }
+    }
     if (B > 0) {
         const int modes = mode == "mincurv" ? RL_MODE_MINCURV
                                             : mode == "mintime" ? RL_MODE_MINTIME : RL_MODE_MINCURV | RL_MODE_MINTIME;
@@ -1416,7 +1463,7 @@ int run_from_centerline(const string& outPath, double L, double s0, const string
             return 2;
         }
         pipeline::batch_and_save(base, center_for_opt, L, closed_mode, inner, outer, B, modes, repeat, best,
-                                 score == "lap");
+                                 score == "lap", traj_dt, traj_cap);
         return 0;
     }
     auto t0 = Clock::now();
@@ -1438,6 +1485,8 @@ int main(int argc, char** argv) {
     string mode = "both", stop_after;
     int B = 0, repeat = 0, best = 0;
     string score;
+    double traj_dt = 0.0;
+    int traj_cap = 0;
     try {
         for (int i = 1; i < argc; ++i) {
             const string a = argv[i];
@@ -1454,6 +1503,8 @@ int main(int argc, char** argv) {
             else if (a == "--repeat") repeat = std::stoi(next());
             else if (a == "--best") best = std::stoi(next());
             else if (a == "--score") score = next();
+            else if (a == "--trajectory-dt") traj_dt = std::stod(next());
+            else if (a == "--trajectory-cap") traj_cap = std::stoi(next());
             else if (a == "--device") gpu::device = std::stoi(next());
             else if (a == "--devices") {
                 std::stringstream ss(next());
@@ -1471,11 +1522,12 @@ int main(int argc, char** argv) {
                       << " [--mode mincurv|mintime|both] [--stop-after centerline]\n"
                       << "       " << argv[0]
                       << " centerline.csv [--L v] [--s0 v] [--open] [--mode m] [--seeds B] [--repeat R] [--best K]\n"
-                      << "         [--score lap]   with --best K --mode mincurv: rank by the lap stage's lap time\n";
+                      << "         [--score lap]   with --best K --mode mincurv: rank by the lap stage's lap time\n"
+                      << "         [--trajectory-dt DT [--trajectory-cap M]]   with --best K: the winners at ticks of DT s\n";
             return 1;
         }
         if (pos.size() == 3) return run_pipeline(pos[0], pos[1], pos[2], mode, stop_after == "centerline");
-        return run_from_centerline(pos[0], L, s0, mode, B, repeat, best, score);
+        return run_from_centerline(pos[0], L, s0, mode, B, repeat, best, score, traj_dt, traj_cap);
     } catch (const std::exception& e) {
         std::cerr << "[ERR] " << e.what() << "\n";
         return 3;

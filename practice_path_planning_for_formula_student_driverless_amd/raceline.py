@@ -18,6 +18,9 @@ Beyond the reference: :func:`optimize_batch` and :class:`Plan` run B
 instances (α-seeds, cfg sweeps) in one launch; that is the product.
 :func:`optimize_best` / :meth:`Plan.select` rank the batch on the GPU and
 return only the k best instances of each group.
+:func:`best_trajectory` / :meth:`Plan.trajectory` resample racelines on the GPU into what a
+controller tracks, the state at every control tick; :func:`trajectory_host` is their
+specification in NumPy.
 
 Every compute call goes through ``librl.so`` (HIP, gfx950).  With no GPU the
 calls raise :class:`RacelineError` (RL_ENODEV): there is no CPU fallback.
@@ -239,6 +242,176 @@ def optimize_best(prob: Problem, cfgs, seeds=None, B: Optional[int] = None, mode
     return sel
 
 
+# ------------------------------------------------- trajectories: racelines by time
+TRAJ_HEADER = "t,s,x,y,heading_rad,curvature,v_mps,ax_mps2\n"
+
+
+@dataclass
+class Trajectory:
+    """Time-stamped trajectories of R rows (rl_traj): the state at the ticks tau_m = m * dt.
+    s, x, y, heading, kappa, v, ax [R, M_cap]; stamps [R, N + 1] (t_i: when the car is at
+    sample i); T [R] (closed rows: the lap, summed serially); count [R]: row r holds count[r]
+    ticks, the entries after them are unspecified."""
+
+    s: np.ndarray
+    x: np.ndarray
+    y: np.ndarray
+    heading: np.ndarray
+    kappa: np.ndarray
+    v: np.ndarray
+    ax: np.ndarray
+    stamps: np.ndarray
+    T: np.ndarray
+    count: np.ndarray
+    dt: float
+
+    @classmethod
+    def alloc(cls, R: int, N: int, m_cap: int, dt: float) -> "Trajectory":
+        cols = {n: np.zeros((R, m_cap)) for n in abi.TRAJ_COLS}
+        return cls(**cols, stamps=np.zeros((R, N + 1)), T=np.zeros(R), count=np.zeros(R, dtype=np.int32), dt=float(dt))
+
+    def as_c(self) -> abi.RlTraj:
+        t = abi.RlTraj()
+        for n in abi.TRAJ_COLS + ("stamps", "T"):
+            setattr(t, n, _ptr(getattr(self, n), np.float64, n))
+        t.count = _ptr(self.count, np.int32, "count")
+        return t
+
+    def row(self, r: int) -> dict:
+        """The ticks of row r: t [count[r]] = m * dt and the seven columns' first count[r] entries."""
+        m = int(self.count[r])
+        out = {"t": np.arange(m, dtype=np.float64) * self.dt}
+        for n in abi.TRAJ_COLS:
+            out[n] = getattr(self, n)[r, :m]
+        return out
+
+    def table(self, r: int) -> np.ndarray:
+        """[count[r], 8]: the rows of <base>_trajectory_<r>.csv (TRAJ_HEADER's columns)."""
+        t = self.row(r)
+        return np.stack([t[n] for n in ("t",) + abi.TRAJ_COLS], axis=1)
+
+
+def _ptr(a: np.ndarray, dtype, name: str):
+    """C pointer to a; the library reads and writes whole arrays through it, so anything but a
+    C-contiguous array of `dtype` is an error here."""
+    if not isinstance(a, np.ndarray) or a.dtype != dtype or not a.flags.c_contiguous:
+        raise ValueError(f"{name}: need a C-contiguous {np.dtype(dtype).name} array")
+    return a.ctypes.data_as(C.POINTER(C.c_int32 if dtype == np.int32 else C.c_double))
+
+
+def _traj_rows(x, y, heading, kappa, v, ax, h) -> tuple:
+    """The six rows as [B, N] float64 arrays of one shape and h as [B]."""
+    rows = [np.ascontiguousarray(a, dtype=np.float64) for a in (x, y, heading, kappa, v, ax)]
+    if rows[0].ndim == 1:
+        rows = [a[None] if a.ndim == 1 else a for a in rows]
+    shape = rows[0].shape
+    if len(shape) != 2 or shape[0] < 1 or any(a.shape != shape for a in rows):
+        raise ValueError(f"trajectory: x, y, heading, kappa, v, ax must be [B, N] arrays of one shape, got "
+                         f"{[a.shape for a in rows]}")
+    hs = np.asarray(h, dtype=np.float64)
+    if hs.ndim > 1 or (hs.ndim == 1 and hs.shape[0] != shape[0]):
+        raise ValueError(f"trajectory: h must be a number or [B={shape[0]}] array, got shape {hs.shape}")
+    return rows, np.ascontiguousarray(np.broadcast_to(hs, (shape[0],)))
+
+
+def _check_ticks(dt, m_cap) -> None:
+    if not (np.isfinite(dt) and dt > 0):
+        raise ValueError(f"dt must be finite and > 0, got {dt}")
+    if not 1 <= int(m_cap) <= abi.RL_TRAJ_MAX_TICKS:
+        raise ValueError(f"m_cap must be 1..{abi.RL_TRAJ_MAX_TICKS}, got {m_cap}")
+
+
+def trajectory_host(x, y, heading, kappa, v, ax, h, closed: bool, dt: float, m_cap: int) -> Trajectory:
+    """The specification of the trajectory stage (include/rl_abi.h) in NumPy; the
+    kernel equals it bit for bit.  Rows [B, N] (or one row [N]), h a number or [B].  Per row:
+    stamps t = cumsum([0, h / smax(1e-6, v_i) ...]) (np.cumsum adds serially in index order),
+    T = t[S] with S = N segments (closed) or N - 1 (open); ticks tau_m = m * dt, M = min(m_cap,
+    #{tau_m < T}) (0 for a NaN or infinite T); segment i = searchsorted(t, tau, "right") - 1,
+    u = (tau - t_i) / (t_{i+1} - t_i); the columns interpolate between samples i and
+    j = (i + 1) mod N, the heading along the shorter arc, ax constant on the segment."""
+    rows, hs = _traj_rows(x, y, heading, kappa, v, ax, h)
+    _check_ticks(dt, m_cap)
+    B, N = rows[0].shape
+    m_cap, closed, dt = int(m_cap), bool(closed), float(dt)
+    out = Trajectory.alloc(B, N, m_cap, dt)
+    tau_all = np.arange(m_cap, dtype=np.float64) * dt
+    S = N if closed else N - 1
+    for b in range(B):
+        X, Y, P, K, V, A = (a[b] for a in rows)
+        hb = hs[b]
+        with np.errstate(all="ignore"):
+            inc = hb / np.where(1e-6 < V, V, 1e-6)                 # smax(1e-6, v): (1e-6 < v) ? v : 1e-6
+            t = np.cumsum(np.concatenate(([0.0], inc)))            # t_0 = 0, t_{i+1} = t_i + inc_i
+            out.stamps[b] = t
+            T = t[S] if N > 0 else 0.0
+            out.T[b] = T
+            M = int(np.count_nonzero(tau_all < T)) if np.isfinite(T) else 0
+            out.count[b] = M
+            if M == 0:
+                continue
+            tau = tau_all[:M]
+            i = np.clip(np.searchsorted(t[:S + 1], tau, side="right") - 1, 0, S - 1)
+            j = (i + 1) % N
+            u = (tau - t[i]) / (t[i + 1] - t[i])
+            d = P[j] - P[i]
+            d = np.where(d > np.pi, d - 2.0 * np.pi, np.where(d < -np.pi, d + 2.0 * np.pi, d))
+            out.s[b, :M] = (i.astype(np.float64) + u) * hb
+            out.x[b, :M] = X[i] + u * (X[j] - X[i])
+            out.y[b, :M] = Y[i] + u * (Y[j] - Y[i])
+            out.heading[b, :M] = P[i] + u * d
+            out.kappa[b, :M] = K[i] + u * (K[j] - K[i])
+            out.v[b, :M] = V[i] + u * (V[j] - V[i])
+            out.ax[b, :M] = A[i]
+    return out
+
+
+def trajectory(x, y, heading, kappa, v, ax, h, closed: bool, dt: float, m_cap: int, device: int = 0) -> Trajectory:
+    """trajectory_host on the GPU (rl_trajectory): the trajectories of B given rows [B, N] (or
+    one row [N]) with steps h (a number or [B]), row r of the result from row r."""
+    rows, hs = _traj_rows(x, y, heading, kappa, v, ax, h)
+    _check_ticks(dt, m_cap)
+    B, N = rows[0].shape
+    out = Trajectory.alloc(B, N, int(m_cap), dt)
+    if N == 0:                              # (no row to point at)
+        rows = [np.zeros((B, 1))] * 6
+    t = out.as_c()
+    _check(_lib().rl_trajectory(*[_ptr(a, np.float64, "row") for a in rows], _ptr(hs, np.float64, "h"), N, B,
+                                1 if closed else 0, float(dt), int(m_cap), int(device), C.byref(t)))
+    return out
+
+
+_TRAJ_ROWS = {"all": abi.RL_TRAJ_ALL, "selected": abi.RL_TRAJ_SELECTED}
+
+
+def best_trajectory(prob: Problem, cfgs, seeds=None, B: Optional[int] = None, mode="mintime", k: int = 1,
+                    group_size: Optional[int] = None, score="default", dt: float = 0.05, m_cap: int = 1024):
+    """optimize_best, then the winners' trajectories at ticks of dt seconds, at most m_cap per
+    winner, resampled on the GPU and downloaded with the winners' rows in one pass
+    (rl_optimize_best_trajectory).  Returns (Selected, Trajectory): row g*k + r of both is
+    instance index[g, r].  A min-curvature trajectory takes v, ax, heading and curvature from
+    the lap stage, whatever the score."""
+    cfg_arr, ncfg = abi.cfg_array(cfgs)
+    if B is None:
+        B = ncfg if ncfg > 1 else (len(seeds) if seeds is not None else 1)
+    _check_batch(B, ncfg, seeds)
+    m, gs = _check_select(B, mode, k, group_size)
+    if prob.N == 0:
+        raise ValueError("best_trajectory: N == 0 (nothing to rank)")
+    by_lap = _check_score(score, m)
+    _check_ticks(dt, m_cap)
+    sel = _selected_alloc(B, prob.N, int(cfg_arr[0].max_outer_iters), m, k, gs, by_lap)
+    traj = Trajectory.alloc((B // gs) * k, prob.N, int(m_cap), dt)
+    seeds_a = abi.seed_array(seeds)
+    p = prob.as_c()
+    o = sel.out.as_c()
+    t = traj.as_c()
+    s = abi.RlSelect(m, k, gs, 0)
+    _check(_lib().rl_optimize_best_trajectory(C.byref(p), cfg_arr, ncfg, abi.u64ptr(seeds_a), B, C.byref(s),
+                                              _SCORES[score], abi.iptr(sel.index), abi.dptr(sel.score),
+                                              abi.dptr(sel.scores), C.byref(o), float(dt), int(m_cap), C.byref(t)))
+    return sel, traj
+
+
 def path_lengths(x, y, closed: bool, device: int = 0) -> np.ndarray:
     """L [B]: the debug dump's path_length (ref:1443-1448) of B paths given as rows x [B, N],
     y [B, N], summed on the GPU in the reference's order (rl_path_lengths): L[b] equals
@@ -372,6 +545,34 @@ class Plan:
         _check(_lib().rl_plan_fetch_selected(self._h, abi.iptr(sel.index), abi.dptr(sel.score),
                                              abi.dptr(sel.scores), C.byref(o)))
         return sel
+
+    def trajectory(self, mode="mintime", dt: float = 0.05, m_cap: int = 1024, rows="all", stream_ptr: int = 0) -> None:
+        """Enqueue the trajectory stage after the last run() (rl_plan_trajectory): the state at
+        the ticks m * dt, at most m_cap per row, of every instance (rows="all") or of the
+        winners of the last select() of the same mode (rows="selected").  Min-curvature rows
+        take heading, curvature, v and ax from the lap stage (run first unless one is valid)."""
+        if mode not in _MODES:
+            raise ValueError(f"mode must be 'mincurv' or 'mintime', got {mode!r}")
+        if rows not in _TRAJ_ROWS:
+            raise ValueError(f"rows must be 'all' or 'selected', got {rows!r}")
+        self._traj = None
+        _check(_lib().rl_plan_trajectory(self._h, _MODES[mode], _TRAJ_ROWS[rows], float(dt), int(m_cap),
+                                         C.c_void_p(stream_ptr) if stream_ptr else None))
+        sel = getattr(self, "_sel", None)
+        R = self.B if rows == "all" else (self.B // sel[2]) * sel[1]
+        self._traj = (R, int(m_cap), float(dt))
+
+    def fetch_trajectory(self) -> Trajectory:
+        """Download the last trajectory() (rl_plan_fetch_trajectory)."""
+        if getattr(self, "_traj", None) is None:
+            t = abi.RlTraj()                # (the library's own answer: no stage on this plan)
+            _check(_lib().rl_plan_fetch_trajectory(self._h, C.byref(t)))
+            raise ValueError("fetch_trajectory: no trajectory() on this plan")
+        R, m_cap, dt = self._traj
+        out = Trajectory.alloc(R, self.N, m_cap, dt)
+        t = out.as_c()
+        _check(_lib().rl_plan_fetch_trajectory(self._h, C.byref(t)))
+        return out
 
     def device_outputs(self, which: int) -> abi.RlOut:
         d = abi.RlOut()
@@ -821,4 +1022,4 @@ __all__ = ["RacelineError", "MinCurvResult", "MinTimeResult", "Plan", "Problem",
            "optimize_best", "rank_scores", "Selected", "path_lengths", "path_length", "lap_eval",
            "compute_min_curvature_raceline", "compute_min_time_raceline", "compute_raceline_and_save",
            "compute_mintime_and_save", "write_raceline_csvs", "write_mintime_csvs", "load_csv_xy",
-           "seeds_range"]
+           "seeds_range", "Trajectory", "trajectory", "trajectory_host", "best_trajectory"]

@@ -5,7 +5,9 @@
 
 Every .hip file of build.KERNEL_SRCS is compiled in both trees to device assembly with
 build.HIPCC, build.HIP_FLAGS and that source's build.TU_FLAGS (plus the extra flags given),
-and the two listings are compared as whole files.  Exit status 0: all byte-identical.
+and the two listings are compared as whole files.  A source that only one tree has (a new
+kernel in a translation unit of its own) is reported and not compared.  Exit status 0: every
+source both trees have is byte-identical.
 Needs no GPU.  A refactor that must not change the kernels is checked with this.
 """
 from __future__ import annotations
@@ -23,9 +25,12 @@ PKG_NAME = os.path.basename(build.PKG)
 SRCS = [s for s in build.KERNEL_SRCS if s.endswith(".hip")]
 
 
-def listing(tree: str, src: str, extra=()) -> bytes:
-    """Device assembly of one source of one tree (the tree's own include directory)."""
+def listing(tree: str, src: str, extra=()):
+    """Device assembly of one source of one tree (the tree's own include directory); None if
+    the tree has no such source."""
     tree = os.path.abspath(tree)
+    if not os.path.isfile(os.path.join(tree, PKG_NAME, src)):
+        return None
     flags = ["-I" + os.path.join(tree, "include") if f == "-I" + build.INCLUDE else f for f in build.HIP_FLAGS]
     with tempfile.TemporaryDirectory() as tmp:
         out = os.path.join(tmp, "dev.s")
@@ -44,9 +49,10 @@ def main(argv) -> int:
     jobs = [(t, s) for s in SRCS for t in trees]
     with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 1)) as ex:
         asm = dict(zip(jobs, ex.map(lambda j: listing(j[0], j[1], extra), jobs)))
-    differ = [s for s in SRCS if asm[(trees[0], s)] != asm[(trees[1], s)]]
+    only = [s for s in SRCS if (asm[(trees[0], s)] is None) != (asm[(trees[1], s)] is None)]
+    differ = [s for s in SRCS if s not in only and asm[(trees[0], s)] != asm[(trees[1], s)]]
     for s in SRCS:
-        print(("DIFFER     " if s in differ else "identical  ") + s)
+        print(("one tree   " if s in only else "DIFFER     " if s in differ else "identical  ") + s)
     return 1 if differ else 0
 
 
