@@ -244,7 +244,8 @@ int rl_plan_bind_device_outputs(rl_plan* plan, int32_t which, const rl_out* dev_
  * idx 0 = the whole run, 1 = the min-curvature kernel, 2 = the min-time kernel, 3 = the
  * selection stage of the last rl_plan_select (score, rank and gather kernels), 4 = the lap
  * stage of the last rl_plan_lap (5 = its preparation kernel, 6 = its evaluation kernel), 7 =
- * the trajectory stage of the last rl_plan_trajectory. */
+ * the trajectory stage of the last rl_plan_trajectory, 8 = the horizon stage of the last
+ * rl_plan_horizon. */
 int rl_plan_kernel_ms(rl_plan* plan, int32_t idx, float* ms);
 /* The batch size the plan's kernel shape is chosen for (rl_kernel_shape's B); 0 = the plan's
  * own B (the default).  Shapes differ in the tree order of the J / decrease / lap sums, so
@@ -398,6 +399,78 @@ int rl_trajectory(const double* x, const double* y, const double* heading, const
                   const double* v, const double* ax, const double* h, int32_t N, int32_t B,
                   int32_t closed, double dt, int32_t M_cap, int32_t device, rl_traj* out);
 
+/* ------------------------------------------------- horizon stage: look-ahead from a pose
+ * A controller asks every 10-50 ms: "I am at (px, py); where on the raceline is that, and what
+ * are the next M ticks from there?"  The stage after a trajectory stage, as often as the
+ * caller likes without another run: each of Q query poses is located on one row of that stage
+ * (an exact nearest point on the polyline, optionally within a window of segments around a
+ * hint) and up to M_cap ticks are resampled from the located time on, dt apart; on a closed
+ * row they run on across the start line.  Only the poses go up; only the ticks and the
+ * location come down.  In fp64 without contraction, with smax(a,b) = (a<b)?b:a and
+ * smin(a,b) = (b<a)?b:a; one row is the trajectory stage's: samples x, y, psi, kappa, v, ax [N],
+ * step h, stamps t[0..N], T = t_S, S = closed ? N : N-1 segments, segment i from sample i to
+ * j = (i+1) mod N:
+ *   candidates  seg_hint = -1: every i in [0, S).  Hint g, window W >= 0, closed row:
+ *           (g + k) mod S for k = -W .. W, and all of [0, S) if 2W+1 >= S.  Open row:
+ *           max(0, g-W) .. min(S-1, g+W).
+ *   distance of pose p to candidate i:  dx = x_j - x_i, dy = y_j - y_i, wx = px - x_i,
+ *           wy = py - y_i, dd = dx*dx + dy*dy, c = wx*dx + wy*dy,
+ *           u = dd > 0 ? smin(1.0, smax(0.0, c/dd)) : 0.0, rx = wx - u*dx, ry = wy - u*dy,
+ *           D = rx*rx + ry*ry
+ *   winner  the candidate least in the order (isnan(D), D, i): the lowest segment index wins a
+ *           tie.  A NaN winner, or S = 0: seg = -1 and count = 0, nothing else is specified.
+ *   location  seg = i, u, dist2 = D;  e = (dx*wy - dy*wx) < 0 ? -sqrt(D) : sqrt(D), the lateral
+ *           offset, left of the direction of travel positive;  t0 = t_i + u*(t_{i+1} - t_i);
+ *           s0 = ((double)i + u)*h
+ *   ticks   tau_m = t0 + (double)m*dt.  Open rows: count = min(M_cap, #{m : tau_m < T}), wrap
+ *           count c = 0, w = tau_m.  Closed rows: count = M_cap if T is finite and > 0, else 0;
+ *           c = floor(tau_m / T), w = tau_m - c*T (two roundings), then at most one fix-up each
+ *           way: w < 0: w += T, c -= 1; else w >= T: w -= T, c += 1 (c stays a double).
+ *   segment of a tick: i = clip(#{k <= S : t_k <= w} - 1, 0, S-1), the trajectory stage's
+ *           bisection on w;  u_m = (w - t_i)/(t_{i+1} - t_i)
+ *   columns s = ((c*(double)S + (double)i) + u_m)*h (monotone across laps; for c = 0 the bits
+ *           of the trajectory stage's s); x, y, heading (shorter arc), kappa, v, ax: the
+ *           trajectory stage's expressions with u_m.
+ * raceline.horizon_host states the same in NumPy; the kernel equals it bit for bit.  These are
+ * additions to ABI 6.1 that leave RL_ABI_MINOR as it is: RL_FEATURE_HORIZON announces them. */
+typedef struct rl_hzn_query {
+    const double*  pose_xy;   /* [Q][2] host */
+    const int32_t* row;       /* [Q] row of the plan's trajectory stage (of B for rl_horizon); NULL: 0 */
+    const int32_t* seg_hint;  /* [Q], -1 = every segment; NULL: all -1 */
+    int32_t Q, window, M_cap, _pad;
+    double  dt;
+} rl_hzn_query;
+
+typedef struct rl_hzn {       /* caller-allocated; NULL fields skipped */
+    double *s, *x, *y, *heading, *kappa, *v, *ax;   /* [Q][M_cap]; ticks m >= count[q] are unspecified */
+    double *u, *t0, *s0, *e, *dist2;                /* [Q] */
+    int32_t *seg, *count;                           /* [Q] */
+} rl_hzn;
+
+#define RL_HZN_MAX_QUERIES 65536
+
+/* Enqueue the stage after the plan's last trajectory stage, whose rows, stamps and T it reads
+ * (stream rules of rl_plan_select).  It may be repeated with other poses without a run or a
+ * trajectory stage in between, and leaves the trajectory stage as it is; a later rl_plan_run or
+ * rl_plan_trajectory invalidates it.  The buffers are plan-owned (they count toward the plan
+ * cache's budget) and grow with Q and M_cap.  pose_xy, row and seg_hint are read before the
+ * call returns.  rl_plan_kernel_ms index 8 is the stage.  RL_EINVAL before any device work for:
+ * a NULL plan, query or pose_xy, Q < 1 or > RL_HZN_MAX_QUERIES, window < 0, dt not finite or
+ * <= 0, M_cap < 1 or > RL_TRAJ_MAX_TICKS, a row outside the stage's [0, R), a hint outside
+ * [-1, S), a plan with no valid trajectory stage, and a trajectory stage whose source rows have
+ * been replaced since (a selection after a stage of RL_TRAJ_SELECTED, a lap stage after a
+ * stage of RL_MODE_MINCURV). */
+int rl_plan_horizon(rl_plan* plan, const rl_hzn_query* query, void* hip_stream);
+/* Download the last horizon stage (synchronises its stream) into the non-NULL fields of out.
+ * RL_EINVAL before a stage, or after a run or trajectory stage that followed it. */
+int rl_plan_fetch_horizon(rl_plan* plan, rl_hzn* out);
+/* The horizons of poses on B given rows [B][N] with steps h [B] (host in, host out): the
+ * trajectory kernel for the stamps, then the horizon kernel.  RL_EINVAL for a NULL input, query
+ * or out, B < 1, N < 1 and the query errors above with R = B; RL_ETOOBIG for N > 1048576. */
+int rl_horizon(const double* x, const double* y, const double* heading, const double* kappa,
+               const double* v, const double* ax, const double* h, int32_t N, int32_t B,
+               int32_t closed, const rl_hzn_query* query, int32_t device, rl_hzn* out);
+
 /* B lap evaluations of given paths: heading/curvature
  * (heading_curv_from_points_generic, ref:595-620) and velocity_profile_forward_backward
  * (ref:782-862) with h = L[b]/N on path b — the min-time driver's final step
@@ -474,6 +547,7 @@ int         rl_abi_version(void);
 int         rl_abi_minor(void);
 /* additions since the last minor, one bit each (a library without this function has none) */
 #define RL_FEATURE_TRAJECTORY 1   /* bit 0: the trajectory stage */
+#define RL_FEATURE_HORIZON 2      /* bit 1: the horizon stage */
 int         rl_abi_features(void);
 /* samples per lane of the THROUGHPUT shape for N (4: N <= 256, 5: N <= 320, 8: N <= 4096;
  * 1 = the streaming kernel), or RL_ETOOBIG.  Batches small enough for a latency shape launch fewer samples per lane:

@@ -136,6 +136,25 @@ class RlTraj(C.Structure):
     _fields_ = [(n, C.POINTER(C.c_double)) for n in TRAJ_COLS + ("stamps", "T")] + [("count", C.POINTER(C.c_int32))]
 
 
+RL_FEATURE_HORIZON = 2     # rl_abi_features() bit 1: the horizon stage
+RL_HZN_MAX_QUERIES = 65536
+HZN_LOC = ("u", "t0", "s0", "e", "dist2")
+
+
+class RlHznQuery(C.Structure):
+    """``rl_hzn_query`` — Q poses [Q][2] with their rows and segment hints (NULL: row 0, no hint)."""
+
+    _fields_ = [("pose_xy", C.POINTER(C.c_double)), ("row", C.POINTER(C.c_int32)), ("seg_hint", C.POINTER(C.c_int32)),
+                ("Q", C.c_int32), ("window", C.c_int32), ("M_cap", C.c_int32), ("_pad", C.c_int32), ("dt", C.c_double)]
+
+
+class RlHzn(C.Structure):
+    """``rl_hzn`` — caller-allocated horizon arrays: the columns [Q][M_cap], u, t0, s0, e, dist2 [Q],
+    seg and count [Q]; NULL fields are skipped."""
+
+    _fields_ = [(n, C.POINTER(C.c_double)) for n in TRAJ_COLS + HZN_LOC] + [(n, C.POINTER(C.c_int32)) for n in ("seg", "count")]
+
+
 OUT_F64 = ("x", "y", "heading", "kappa", "alpha_total", "alpha_last")
 OUT_F64_MT = OUT_F64 + ("v", "ax")
 
@@ -486,6 +505,14 @@ DECLS_EXT = [
     ("rl_trajectory", C.c_int, [_F64] * 7 + [C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32, _TRAJ]),
 ]
 
+# the horizon stage: bound only in a library whose rl_abi_features() has RL_FEATURE_HORIZON
+_HZN, _HZNQ = _P(RlHzn), _P(RlHznQuery)
+DECLS_HZN = [
+    ("rl_plan_horizon", C.c_int, [C.c_void_p, _HZNQ, C.c_void_p]),
+    ("rl_plan_fetch_horizon", C.c_int, [C.c_void_p, _HZN]),
+    ("rl_horizon", C.c_int, [_F64] * 7 + [C.c_int32, C.c_int32, C.c_int32, _HZNQ, C.c_int32, _HZN]),
+]
+
 
 def declare_optimize(fn) -> None:
     """rl_optimize's signature (the oracle's oracle_optimize shares it)."""
@@ -497,7 +524,8 @@ _LIB = None
 
 def load_library(path: str = LIB_PATH) -> C.CDLL:
     """Load librl.so (the HIP path).  Raises if it is missing: there is no fallback; a library
-    that lacks a function of DECLS or DECLS_EXT raises AttributeError naming it."""
+    that lacks a function of DECLS or DECLS_EXT raises AttributeError naming it, and so does
+    one that announces RL_FEATURE_HORIZON and lacks a function of DECLS_HZN."""
     global _LIB
     if _LIB is not None and path == LIB_PATH:
         return _LIB
@@ -507,11 +535,16 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     # a library built from an earlier revision (RL_LIB: A/B against a parent) has no
     # rl_abi_features and none of DECLS_EXT; one that has it must have them all
     ext = DECLS_EXT if hasattr(lib, "rl_abi_features") else []
-    for name, restype, argtypes in DECLS + ext:
-        fn = getattr(lib, name)
-        fn.restype = restype
-        if argtypes is not None:
-            fn.argtypes = argtypes
+    def bind(decls):
+        for name, restype, argtypes in decls:
+            fn = getattr(lib, name)
+            fn.restype = restype
+            if argtypes is not None:
+                fn.argtypes = argtypes
+
+    bind(DECLS + ext)
+    if ext and lib.rl_abi_features() & RL_FEATURE_HORIZON:
+        bind(DECLS_HZN)
     if path == LIB_PATH:
         _LIB = lib
     return lib

@@ -19,6 +19,7 @@
 #include "rl_select.h"
 #include "rl_lap_stage.h"
 #include "rl_trajectory.h"
+#include "rl_horizon.h"
 
 namespace rl {
 
@@ -446,6 +447,23 @@ struct rl_plan {
     rl::DevArena traj_mem;
     int traj_cap_R = 0, traj_cap_M = 0, traj_R = 0, traj_M = 0;
     hipEvent_t ev_traj[2] = {nullptr, nullptr};
+    // horizon stage (rl_plan_horizon): it reads the last trajectory stage through traj_q, that
+    // stage's launch parameters, which stay valid while traj_R != 0 and the rows they point at
+    // are those the stamps were made from: traj_sel_epoch / traj_lap_epoch are sel_epoch /
+    // lap_epoch (counted up by every selection / lap stage) at that launch.  The queries go up
+    // and the results come down as one packed block each (hzn_in, hzn_out), through one pinned
+    // host block (hzn_pin); all three grow with Q and M_cap.  hzn_Q = 0: no stage since the
+    // last run or trajectory stage.
+    rl::TrajParams traj_q{};
+    int traj_mode = 0;
+    uint32_t sel_epoch = 0, lap_epoch = 0, traj_sel_epoch = 0, traj_lap_epoch = 0;
+    char* hzn_in = nullptr;
+    char* hzn_out = nullptr;
+    char* hzn_pin = nullptr;
+    size_t hzn_in_cap = 0, hzn_out_cap = 0, hzn_pin_cap = 0;
+    rl::DevArena hzn_mem;
+    int hzn_Q = 0, hzn_M = 0;
+    hipEvent_t ev_hzn[2] = {nullptr, nullptr};            // after the upload, after the kernel
 
     template <class T>
     int alloc(T** p, size_t n) {
@@ -454,7 +472,7 @@ struct rl_plan {
     }
     int nomem() const { return rl::fail(RL_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(mem.err)); }
     // device memory held (plan cache budget)
-    size_t dev_bytes() const { return mem.bytes + sel_mem.bytes + lap_mem.bytes + traj_mem.bytes; }
+    size_t dev_bytes() const { return mem.bytes + sel_mem.bytes + lap_mem.bytes + traj_mem.bytes + hzn_mem.bytes; }
     // the stream of the last run or stage
     hipStream_t run_stream() const { return last_stream ? last_stream : own_stream; }
     // the batch size the kernel shape is chosen for
@@ -489,5 +507,19 @@ void sel_jobs(const rl_plan* p, int32_t* index, double* score, double* all_score
 int check_traj(double dt, int32_t M_cap);
 // the copies that download the last trajectory stage of p into the non-NULL fields of t
 void traj_jobs(const rl_plan* p, const rl_traj* t, std::vector<CopyJob>& jobs);
+// argument checks shared by the horizon entry points (no device call): the queries against a
+// trajectory stage of R rows of N samples
+int check_hzn(const rl_hzn_query* q, int32_t R, int32_t N, int32_t closed);
+// the packed blocks of a horizon stage of Q queries and M ticks: the queries are poses [Q][2],
+// rows [Q], hints [Q]; the results the columns [Q][M] in rl_hzn's order, then u, t0, s0, e,
+// dist2 [Q], then seg, count [Q]
+inline size_t hzn_in_bytes(size_t Q) { return Q * 24; }
+inline size_t hzn_out_bytes(size_t Q, size_t M) { return ((size_t)TRAJ_COLS * Q * M + (size_t)HZN_LOC * Q) * 8 + 2 * Q * 4; }
+// fill the queries' block (host) from q
+void hzn_pack(const rl_hzn_query* q, char* block);
+// the launch parameters of q on the blocks `in` and `out` (device)
+HznParams hzn_params(const TrajParams& src, const rl_hzn_query* q, char* in, char* out);
+// copy a results' block (host) into the non-NULL fields of o
+void hzn_unpack(const char* block, size_t Q, size_t M, const rl_hzn* o);
 
 }  // namespace rl

@@ -193,6 +193,10 @@ int rl_plan_destroy(rl_plan* plan) {
     plan->traj_mem.release();
     for (auto& e : plan->ev_traj)
         if (e) hipEventDestroy(e);
+    plan->hzn_mem.release();
+    if (plan->hzn_pin) hipHostFree(plan->hzn_pin);
+    for (auto& e : plan->ev_hzn)
+        if (e) hipEventDestroy(e);
     for (auto& e : plan->ev)
         if (e) hipEventDestroy(e);
     for (auto& e : plan->ev_end)
@@ -291,6 +295,7 @@ int rl_plan_run(rl_plan* p, void* hip_stream) {
     p->sel_mode = 0;                                   // an earlier selection is of an earlier run
     p->lap_valid = false;                              // and so is an earlier lap stage
     p->traj_R = 0;                                     // and an earlier trajectory stage
+    p->hzn_Q = 0;                                      // and the horizon stage that read it
     return RL_OK;
 }
 
@@ -414,6 +419,7 @@ int rl_plan_run_group(rl_plan* const* plans, int32_t n, void* hip_stream) {
         plans[i]->sel_mode = 0;
         plans[i]->lap_valid = false;
         plans[i]->traj_R = 0;
+        plans[i]->hzn_Q = 0;
     }
     return RL_OK;
 }
@@ -440,6 +446,11 @@ int rl_plan_kernel_ms(rl_plan* p, int32_t idx, float* ms) {
     else if (idx == 7 && p->traj_R) {
         a = p->ev_traj[0];
         b = p->ev_traj[1];
+        HIPCHK(hipEventSynchronize(b));
+    }
+    else if (idx == 8 && p->hzn_Q && p->traj_R) {
+        a = p->ev_hzn[0];
+        b = p->ev_hzn[1];
         HIPCHK(hipEventSynchronize(b));
     }
     else if (idx == 1 && mc) { a = p->ev[1]; b = p->ev_end[0]; }

@@ -2,6 +2,8 @@
 // device.  Selection (rl_select.hip): score, rank and gather.  Lap stage (rl_lap_stage.hip,
 // DESIGN §3i): the debug dump's "min-curv lap" for every instance of a plan.  Trajectory
 // stage (rl_trajectory.hip): time stamps and the state at every control tick.
+// Horizon stage (rl_horizon.hip): poses located on that stage's rows, and the next
+// ticks from there.
 #include "rl_host.h"
 
 using namespace rl;
@@ -57,7 +59,93 @@ void rl::traj_jobs(const rl_plan* p, const rl_traj* t, std::vector<CopyJob>& job
     add_job(jobs, t->count, p->traj_count, R * 4);
 }
 
+int rl::check_hzn(const rl_hzn_query* q, int32_t R, int32_t N, int32_t closed) {
+    if (!q || !q->pose_xy) return fail(RL_EINVAL, "horizon: the query or its pose_xy is NULL");
+    if (q->Q < 1 || q->Q > RL_HZN_MAX_QUERIES) return fail(RL_EINVAL, "horizon: Q must be 1..65536");
+    if (q->window < 0) return fail(RL_EINVAL, "horizon: window < 0");
+    if (int rc = check_traj(q->dt, q->M_cap)) return rc;
+    if (N < 1) return fail(RL_EINVAL, "horizon: N == 0 (no row)");
+    const int32_t S = closed ? N : N - 1;
+    for (int32_t k = 0; k < q->Q; ++k) {
+        const int32_t r = q->row ? q->row[k] : 0, g = q->seg_hint ? q->seg_hint[k] : -1;
+        if (r < 0 || r >= R) return fail(RL_EINVAL, "horizon: a row outside the trajectory stage's [0, R)");
+        if (g < -1 || g >= S) return fail(RL_EINVAL, "horizon: a seg_hint outside [-1, S)");
+    }
+    return RL_OK;
+}
+
+void rl::hzn_pack(const rl_hzn_query* q, char* block) {
+    const size_t Q = (size_t)q->Q;
+    std::memcpy(block, q->pose_xy, Q * 16);
+    int32_t* row = (int32_t*)(block + Q * 16);
+    int32_t* hint = row + Q;
+    for (size_t k = 0; k < Q; ++k) {
+        row[k] = q->row ? q->row[k] : 0;
+        hint[k] = q->seg_hint ? q->seg_hint[k] : -1;
+    }
+}
+
+HznParams rl::hzn_params(const TrajParams& src, const rl_hzn_query* q, char* in, char* out) {
+    const size_t Q = (size_t)q->Q, M = (size_t)q->M_cap;
+    HznParams h{};
+    h.src = src;
+    h.pose = (const double*)in;
+    h.row = (const int32_t*)(in + Q * 16);
+    h.hint = h.row + Q;
+    double* d = (double*)out;
+    for (auto& c : h.out) { c = d; d += Q * M; }
+    for (auto& c : h.loc) { c = d; d += Q; }
+    h.seg = (int32_t*)d;
+    h.count = h.seg + Q;
+    h.dt = q->dt;
+    h.Q = q->Q; h.window = q->window; h.M_cap = q->M_cap;
+    return h;
+}
+
+void rl::hzn_unpack(const char* block, size_t Q, size_t M, const rl_hzn* o) {
+    double* const col[TRAJ_COLS] = {o->s, o->x, o->y, o->heading, o->kappa, o->v, o->ax};
+    double* const loc[HZN_LOC] = {o->u, o->t0, o->s0, o->e, o->dist2};
+    const char* src = block;
+    for (double* c : col) {
+        if (c) std::memcpy(c, src, Q * M * 8);
+        src += Q * M * 8;
+    }
+    for (double* c : loc) {
+        if (c) std::memcpy(c, src, Q * 8);
+        src += Q * 8;
+    }
+    if (o->seg) std::memcpy(o->seg, src, Q * 4);
+    if (o->count) std::memcpy(o->count, src + Q * 4, Q * 4);
+}
+
 namespace {
+
+// plan-owned horizon blocks for Q queries of M ticks; the device blocks count toward dev_bytes()
+int hzn_alloc(rl_plan* p, size_t Q, size_t M) {
+    const size_t in = hzn_in_bytes(Q), out = hzn_out_bytes(Q, M);
+    if (p->hzn_in && in <= p->hzn_in_cap && out <= p->hzn_out_cap) return RL_OK;
+    if (p->last_stream) HIPCHK(hipStreamSynchronize(p->last_stream));   // it may still use the old ones
+    DevArena& a = p->hzn_mem;
+    a.release();
+    if (p->hzn_pin) hipHostFree(p->hzn_pin);
+    p->hzn_in = p->hzn_out = p->hzn_pin = nullptr;
+    const size_t in_cap = std::max(in, p->hzn_in_cap), out_cap = std::max(out, p->hzn_out_cap);
+    p->hzn_in_cap = p->hzn_out_cap = p->hzn_pin_cap = 0;
+    char* d_in = a.get<char>(in_cap);
+    char* d_out = a.get<char>(out_cap);
+    void* pin = nullptr;
+    if (!a.ok() || hipHostMalloc(&pin, std::max(in_cap, out_cap), hipHostMallocDefault) != hipSuccess) {
+        a.release();
+        return fail(RL_ENOMEM, "allocation of the horizon buffers failed");
+    }
+    p->hzn_in = d_in;
+    p->hzn_out = d_out;
+    p->hzn_pin = (char*)pin;
+    p->hzn_in_cap = in_cap;
+    p->hzn_out_cap = out_cap;
+    p->hzn_pin_cap = std::max(in_cap, out_cap);
+    return RL_OK;
+}
 
 // plan-owned trajectory buffers for R rows of M ticks; they count toward dev_bytes()
 int traj_alloc(rl_plan* p, int R, int M) {
@@ -134,6 +222,7 @@ int select_impl(rl_plan* p, const rl_select* sel, int gs, bool by_lap, void* hip
     hipStream_t run_st = p->run_stream();
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : run_st;
     p->sel_mode = 0;
+    ++p->sel_epoch;                                    // d_index and the compact rows change
     if (int rc = select_alloc(p, rows)) return rc;
     for (auto& e : p->ev_sel)
         if (!e) HIPCHK(hipEventCreate(&e));
@@ -204,6 +293,7 @@ int rl_plan_lap(rl_plan* p, void* hip_stream) {
     hipStream_t run_st = p->run_stream();
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : run_st;
     p->lap_valid = false;
+    ++p->lap_epoch;                                    // the stage's rows are written again
     if (int rc = lap_alloc(p)) return rc;
     for (auto& e : p->ev_lap)
         if (!e) HIPCHK(hipEventCreate(&e));
@@ -307,6 +397,7 @@ int rl_plan_trajectory(rl_plan* p, int32_t mode, int32_t rows, double dt, int32_
         return fail(RL_EINVAL, "rl_plan_trajectory: no selection of this mode since the plan's last run");
     const bool mc = mode == RL_MODE_MINCURV;
     p->traj_R = 0;
+    p->hzn_Q = 0;                                      // a horizon stage read the stage before this one
     if (mc && !p->lap_valid)
         if (int rc = rl_plan_lap(p, hip_stream)) return rc;
     HIPCHK(hipSetDevice(p->device));
@@ -342,6 +433,10 @@ int rl_plan_trajectory(rl_plan* p, int32_t mode, int32_t rows, double dt, int32_
     HIPCHK(hipEventRecord(p->ev_traj[1], st));
     p->traj_R = R;
     p->traj_M = M_cap;
+    p->traj_q = q;                                     // what the horizon stage reads
+    p->traj_mode = mode;
+    p->traj_sel_epoch = p->sel_epoch;
+    p->traj_lap_epoch = p->lap_epoch;
     return RL_OK;
 }
 
@@ -356,6 +451,56 @@ int rl_plan_fetch_trajectory(rl_plan* p, rl_traj* out) {
     traj_jobs(p, out, jobs);
     if (int rc = queue_downloads(jobs, st)) return rc;
     HIPCHK(hipStreamSynchronize(st));
+    return RL_OK;
+}
+
+// One launch of rl_horizon_kernel on the last trajectory stage: the queries go up in one
+// block, through the plan's pinned block, ahead of the kernel on the same stream.
+int rl_plan_horizon(rl_plan* p, const rl_hzn_query* query, void* hip_stream) {
+    if (!p) return fail(RL_EINVAL, "plan is NULL");
+    if (!query) return fail(RL_EINVAL, "horizon: the query or its pose_xy is NULL");
+    if (!p->traj_R) return fail(RL_EINVAL, "rl_plan_horizon: no trajectory stage since the plan's last run");
+    if (int rc = check_hzn(query, p->traj_R, p->N, p->closed)) return rc;
+    if (p->traj_q.index && p->traj_sel_epoch != p->sel_epoch)
+        return fail(RL_EINVAL, "rl_plan_horizon: a selection has replaced the winners the trajectory stage read");
+    if (p->traj_mode == RL_MODE_MINCURV && p->traj_lap_epoch != p->lap_epoch)
+        return fail(RL_EINVAL, "rl_plan_horizon: a lap stage has rewritten the rows the trajectory stage read");
+    HIPCHK(hipSetDevice(p->device));
+    hipStream_t run_st = p->run_stream();
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : run_st;
+    // the last stage's upload may still read the pinned block
+    if (p->hzn_Q) HIPCHK(hipEventSynchronize(p->ev_hzn[0]));
+    p->hzn_Q = 0;
+    const size_t Q = (size_t)query->Q, M = (size_t)query->M_cap;
+    if (int rc = hzn_alloc(p, Q, M)) return rc;
+    for (auto& e : p->ev_hzn)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    if (st != run_st) HIPCHK(hipStreamWaitEvent(st, p->ev_traj[1], 0));
+    p->last_stream = st;
+    hzn_pack(query, p->hzn_pin);
+    HIPCHK(hipMemcpyAsync(p->hzn_in, p->hzn_pin, hzn_in_bytes(Q), hipMemcpyHostToDevice, st));
+    HIPCHK(hipEventRecord(p->ev_hzn[0], st));
+    const rl::HznParams h = hzn_params(p->traj_q, query, p->hzn_in, p->hzn_out);
+    const hipError_t e = rl::launch_horizon(h, st);
+    if (e != hipSuccess) return fail(RL_EHIP, std::string("horizon launch: ") + hipGetErrorString(e));
+    HIPCHK(hipEventRecord(p->ev_hzn[1], st));
+    p->hzn_Q = query->Q;
+    p->hzn_M = query->M_cap;
+    return RL_OK;
+}
+
+int rl_plan_fetch_horizon(rl_plan* p, rl_hzn* out) {
+    if (!p) return fail(RL_EINVAL, "plan is NULL");
+    if (!out) return fail(RL_EINVAL, "rl_plan_fetch_horizon: out is NULL");
+    if (!p->hzn_Q || !p->traj_R)
+        return fail(RL_EINVAL, "rl_plan_fetch_horizon: no horizon stage since the plan's last run or trajectory stage");
+    HIPCHK(hipSetDevice(p->device));
+    hipStream_t st = p->run_stream();
+    HIPCHK(hipStreamWaitEvent(st, p->ev_hzn[1], 0));    // (a later stage may have moved to another stream)
+    const size_t Q = (size_t)p->hzn_Q, M = (size_t)p->hzn_M;
+    HIPCHK(hipMemcpyAsync(p->hzn_pin, p->hzn_out, hzn_out_bytes(Q, M), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    hzn_unpack(p->hzn_pin, Q, M, out);
     return RL_OK;
 }
 

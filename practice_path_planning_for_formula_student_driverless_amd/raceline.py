@@ -21,6 +21,9 @@ return only the k best instances of each group.
 :func:`best_trajectory` / :meth:`Plan.trajectory` resample racelines on the GPU into what a
 controller tracks, the state at every control tick; :func:`trajectory_host` is their
 specification in NumPy.
+:func:`horizon` / :meth:`Plan.horizon` locate poses on those trajectories' rows and resample
+the next ticks from there, across the start line on a closed track; :func:`horizon_host` is
+their specification in NumPy.
 
 Every compute call goes through ``librl.so`` (HIP, gfx950).  With no GPU the
 calls raise :class:`RacelineError` (RL_ENODEV): there is no CPU fallback.
@@ -412,6 +415,204 @@ def best_trajectory(prob: Problem, cfgs, seeds=None, B: Optional[int] = None, mo
     return sel, traj
 
 
+# ------------------------------------------------- horizons: look-ahead from the car's pose
+@dataclass
+class Horizon:
+    """The horizons of Q query poses (rl_hzn).  Location [Q]: seg (the segment the pose lies
+    nearest to, -1: none), u (the foot's parameter on it), dist2 (squared distance), e (lateral
+    offset, left of travel positive), t0 and s0 (the foot's time and arc length on the row);
+    count [Q] ticks at t0 + m * dt in s, x, y, heading, kappa, v, ax [Q, M_cap], the entries
+    after them unspecified.  On a closed row the ticks run on across the start line and s keeps
+    growing."""
+
+    s: np.ndarray
+    x: np.ndarray
+    y: np.ndarray
+    heading: np.ndarray
+    kappa: np.ndarray
+    v: np.ndarray
+    ax: np.ndarray
+    u: np.ndarray
+    t0: np.ndarray
+    s0: np.ndarray
+    e: np.ndarray
+    dist2: np.ndarray
+    seg: np.ndarray
+    count: np.ndarray
+    dt: float
+
+    @classmethod
+    def alloc(cls, Q: int, m_cap: int, dt: float) -> "Horizon":
+        cols = {n: np.zeros((Q, m_cap)) for n in abi.TRAJ_COLS}
+        loc = {n: np.zeros(Q) for n in abi.HZN_LOC}
+        return cls(**cols, **loc, seg=np.zeros(Q, dtype=np.int32), count=np.zeros(Q, dtype=np.int32), dt=float(dt))
+
+    def as_c(self) -> abi.RlHzn:
+        t = abi.RlHzn()
+        for n in abi.TRAJ_COLS + abi.HZN_LOC:
+            setattr(t, n, _ptr(getattr(self, n), np.float64, n))
+        t.seg = _ptr(self.seg, np.int32, "seg")
+        t.count = _ptr(self.count, np.int32, "count")
+        return t
+
+    def row(self, q: int) -> dict:
+        """The ticks of query q: t [count[q]] = t0[q] + m * dt and the seven columns' first count[q] entries."""
+        m = int(self.count[q])
+        out = {"t": self.t0[q] + np.arange(m, dtype=np.float64) * self.dt}
+        for n in abi.TRAJ_COLS:
+            out[n] = getattr(self, n)[q, :m]
+        return out
+
+    def table(self, q: int) -> np.ndarray:
+        """[count[q], 8]: TRAJ_HEADER's columns for query q."""
+        t = self.row(q)
+        return np.stack([t[n] for n in ("t",) + abi.TRAJ_COLS], axis=1)
+
+
+def _hzn_query(poses, row, seg_hint, window, dt, m_cap) -> tuple:
+    """The query as arrays: poses [Q, 2] float64, row and seg_hint [Q] int32 or None."""
+    P = np.ascontiguousarray(poses, dtype=np.float64)
+    if P.ndim == 1 and P.shape[0] == 2:
+        P = P[None]
+    if P.ndim != 2 or P.shape[1] != 2 or not 1 <= P.shape[0] <= abi.RL_HZN_MAX_QUERIES:
+        raise ValueError(f"horizon: poses must be [Q, 2] with 1 <= Q <= {abi.RL_HZN_MAX_QUERIES}, got shape {P.shape}")
+    Q = P.shape[0]
+
+    def ints(a, name):
+        if a is None:
+            return None
+        a = np.asarray(a)
+        if a.ndim == 0:
+            a = np.broadcast_to(a, (Q,))
+        if a.shape != (Q,) or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError(f"horizon: {name} must be an integer or [Q={Q}] integers, got {a.dtype} {a.shape}")
+        return np.ascontiguousarray(a, dtype=np.int32)
+
+    if int(window) != window or window < 0 or window >= 2 ** 31:
+        raise ValueError(f"horizon: window must be an integer >= 0, got {window}")
+    _check_ticks(dt, m_cap)
+    return P, ints(row, "row"), ints(seg_hint, "seg_hint")
+
+
+def _hzn_c(P, rw, hint, window, dt, m_cap) -> abi.RlHznQuery:
+    return abi.RlHznQuery(_ptr(P, np.float64, "poses"), None if rw is None else _ptr(rw, np.int32, "row"),
+                          None if hint is None else _ptr(hint, np.int32, "seg_hint"), P.shape[0], int(window),
+                          int(m_cap), 0, float(dt))
+
+
+def horizon_host(x, y, heading, kappa, v, ax, h, closed: bool, poses, row=None, seg_hint=None, window: int = 0,
+                 dt: float = 0.05, m_cap: int = 64, stamps=None) -> Horizon:
+    """The specification of the horizon stage (include/rl_abi.h) in NumPy; the kernel
+    equals it bit for bit.  Rows [B, N] (or one row [N]) with steps h as for trajectory_host,
+    whose stamps they get unless `stamps` [B, N + 1] gives them (a plan's, as fetched).  Pose q
+    [Q, 2] is located on row[q] (None: row 0) among all S segments (seg_hint None or -1) or the
+    segments within `window` of seg_hint[q], around the start line on a closed row; the winner
+    is the least (isnan(D), D, i).  Then up to m_cap ticks at t0 + m * dt: open rows stop
+    before T, closed rows wrap modulo T and count the laps in s."""
+    rows, hs = _traj_rows(x, y, heading, kappa, v, ax, h)
+    P, rw, hint = _hzn_query(poses, row, seg_hint, window, dt, m_cap)
+    B, N = rows[0].shape
+    if N < 1:
+        raise ValueError("horizon: N == 0 (no row)")
+    Q, closed, dt, m_cap, W = P.shape[0], bool(closed), float(dt), int(m_cap), int(window)
+    S = N if closed else N - 1
+    rw = np.zeros(Q, dtype=np.int32) if rw is None else rw
+    hint = np.full(Q, -1, dtype=np.int32) if hint is None else hint
+    if np.any(rw < 0) or np.any(rw >= B):
+        raise ValueError(f"horizon: row outside [0, {B})")
+    if np.any(hint < -1) or np.any(hint >= S):
+        raise ValueError(f"horizon: seg_hint outside [-1, {S})")
+    with np.errstate(all="ignore"):
+        if stamps is None:
+            inc = hs[:, None] / np.where(1e-6 < rows[4], rows[4], 1e-6)
+            stamps = np.cumsum(np.concatenate((np.zeros((B, 1)), inc), axis=1), axis=1)
+        else:
+            stamps = np.ascontiguousarray(stamps, dtype=np.float64).reshape(-1, N + 1)
+            if stamps.shape[0] != B:
+                raise ValueError(f"horizon: stamps must be [B={B}, N + 1], got {stamps.shape}")
+    out = Horizon.alloc(Q, m_cap, dt)
+    out.seg[:] = -1
+    steps = np.arange(m_cap, dtype=np.float64)
+    fS = np.float64(S)
+    for k in range(Q):
+        if S < 1:
+            continue
+        X, Y, PSI, K, V, A = (a[rw[k]] for a in rows)
+        t, hb, px, py, g = stamps[rw[k]], hs[rw[k]], P[k, 0], P[k, 1], int(hint[k])
+        T = t[S]
+        if g < 0 or (closed and 2 * W + 1 >= S):
+            cand = np.arange(S)
+        elif closed:
+            cand = (g + np.arange(-W, W + 1)) % S
+        else:
+            cand = np.arange(max(0, g - W), min(S - 1, g + W) + 1)
+        with np.errstate(all="ignore"):
+            i = cand
+            j = (i + 1) % N
+            dx, dy, wx, wy = X[j] - X[i], Y[j] - Y[i], px - X[i], py - Y[i]
+            dd = dx * dx + dy * dy
+            c = wx * dx + wy * dy
+            ratio = c / dd
+            lo = np.where(0.0 < ratio, ratio, 0.0)                  # smax(0.0, c/dd)
+            u = np.where(dd > 0.0, np.where(lo < 1.0, lo, 1.0), 0.0)  # smin(1.0, .)
+            rx, ry = wx - u * dx, wy - u * dy
+            D = rx * rx + ry * ry
+            nan = np.isnan(D)
+            win = np.lexsort((i, np.where(nan, 0.0, D), nan))[0]    # least (isnan(D), D, i)
+            if nan[win]:
+                continue
+            i0, u0, D0 = int(i[win]), u[win], D[win]
+            root = np.sqrt(D0)
+            t0 = t[i0] + u0 * (t[i0 + 1] - t[i0])
+            out.seg[k], out.u[k], out.dist2[k], out.t0[k] = i0, u0, D0, t0
+            out.e[k] = -root if dx[win] * wy[win] - dy[win] * wx[win] < 0.0 else root
+            out.s0[k] = (np.float64(i0) + u0) * hb
+            tau = t0 + steps * dt
+            if closed:
+                M = m_cap if np.isfinite(T) and T > 0.0 else 0
+                lap = np.floor(tau / T)
+                w = tau - lap * T
+                neg = w < 0.0
+                over = ~neg & (w >= T)
+                w, lap = np.where(neg, w + T, np.where(over, w - T, w)), np.where(neg, lap - 1.0, np.where(over, lap + 1.0, lap))
+            else:
+                M = int(np.count_nonzero(tau < T))                  # (monotone in m: the kernel bisects)
+                lap, w = np.zeros(m_cap), tau
+            out.count[k] = M
+            if M == 0:
+                continue
+            w, lap = w[:M], lap[:M]
+            i = np.clip(np.searchsorted(t[:S + 1], w, side="right") - 1, 0, S - 1)
+            j = (i + 1) % N
+            um = (w - t[i]) / (t[i + 1] - t[i])
+            d = PSI[j] - PSI[i]
+            d = np.where(d > np.pi, d - 2.0 * np.pi, np.where(d < -np.pi, d + 2.0 * np.pi, d))
+            out.s[k, :M] = ((lap * fS + i.astype(np.float64)) + um) * hb
+            out.x[k, :M] = X[i] + um * (X[j] - X[i])
+            out.y[k, :M] = Y[i] + um * (Y[j] - Y[i])
+            out.heading[k, :M] = PSI[i] + um * d
+            out.kappa[k, :M] = K[i] + um * (K[j] - K[i])
+            out.v[k, :M] = V[i] + um * (V[j] - V[i])
+            out.ax[k, :M] = A[i]
+    return out
+
+
+def horizon(x, y, heading, kappa, v, ax, h, closed: bool, poses, row=None, seg_hint=None, window: int = 0,
+            dt: float = 0.05, m_cap: int = 64, device: int = 0) -> Horizon:
+    """horizon_host on the GPU (rl_horizon): the trajectory kernel stamps the B given rows, then
+    the horizon kernel answers the Q poses; row[q] counts the given rows."""
+    rows, hs = _traj_rows(x, y, heading, kappa, v, ax, h)
+    P, rw, hint = _hzn_query(poses, row, seg_hint, window, dt, m_cap)
+    B, N = rows[0].shape
+    if N < 1:
+        raise ValueError("horizon: N == 0 (no row)")
+    out = Horizon.alloc(P.shape[0], int(m_cap), dt)
+    qc, oc = _hzn_c(P, rw, hint, window, dt, m_cap), out.as_c()
+    _check(_lib().rl_horizon(*[_ptr(a, np.float64, "row") for a in rows], _ptr(hs, np.float64, "h"), N, B,
+                             1 if closed else 0, C.byref(qc), int(device), C.byref(oc)))
+    return out
+
+
 def path_lengths(x, y, closed: bool, device: int = 0) -> np.ndarray:
     """L [B]: the debug dump's path_length (ref:1443-1448) of B paths given as rows x [B, N],
     y [B, N], summed on the GPU in the reference's order (rl_path_lengths): L[b] equals
@@ -572,6 +773,31 @@ class Plan:
         out = Trajectory.alloc(R, self.N, m_cap, dt)
         t = out.as_c()
         _check(_lib().rl_plan_fetch_trajectory(self._h, C.byref(t)))
+        return out
+
+    def horizon(self, poses, row=None, seg_hint=None, window: int = 0, dt: float = 0.05, m_cap: int = 64,
+                stream_ptr: int = 0) -> None:
+        """Enqueue the horizon stage after the last trajectory() (rl_plan_horizon): locate the
+        poses [Q, 2] on rows of that stage (row[q], None: row 0; within `window` segments of
+        seg_hint[q], None or -1: anywhere) and resample up to m_cap ticks from there, dt apart,
+        across the start line on a closed track.  As often as the caller likes without another
+        run(); the trajectory stage stays as it is."""
+        P, rw, hint = _hzn_query(poses, row, seg_hint, window, dt, m_cap)
+        self._hzn = None
+        qc = _hzn_c(P, rw, hint, window, dt, m_cap)
+        _check(_lib().rl_plan_horizon(self._h, C.byref(qc), C.c_void_p(stream_ptr) if stream_ptr else None))
+        self._hzn = (P.shape[0], int(m_cap), float(dt))
+
+    def fetch_horizon(self) -> Horizon:
+        """Download the last horizon() (rl_plan_fetch_horizon)."""
+        if getattr(self, "_hzn", None) is None:
+            t = abi.RlHzn()                 # (the library's own answer: no stage on this plan)
+            _check(_lib().rl_plan_fetch_horizon(self._h, C.byref(t)))
+            raise ValueError("fetch_horizon: no horizon() on this plan")
+        Q, m_cap, dt = self._hzn
+        out = Horizon.alloc(Q, m_cap, dt)
+        t = out.as_c()
+        _check(_lib().rl_plan_fetch_horizon(self._h, C.byref(t)))
         return out
 
     def device_outputs(self, which: int) -> abi.RlOut:
