@@ -245,7 +245,7 @@ int rl_plan_bind_device_outputs(rl_plan* plan, int32_t which, const rl_out* dev_
  * selection stage of the last rl_plan_select (score, rank and gather kernels), 4 = the lap
  * stage of the last rl_plan_lap (5 = its preparation kernel, 6 = its evaluation kernel), 7 =
  * the trajectory stage of the last rl_plan_trajectory, 8 = the horizon stage of the last
- * rl_plan_horizon. */
+ * rl_plan_horizon, 9 = the rejoin stage of the last rl_plan_rejoin. */
 int rl_plan_kernel_ms(rl_plan* plan, int32_t idx, float* ms);
 /* The batch size the plan's kernel shape is chosen for (rl_kernel_shape's B); 0 = the plan's
  * own B (the default).  Shapes differ in the tree order of the J / decrease / lap sums, so
@@ -471,6 +471,98 @@ int rl_horizon(const double* x, const double* y, const double* heading, const do
                const double* v, const double* ax, const double* h, int32_t N, int32_t B,
                int32_t closed, const rl_hzn_query* query, int32_t device, rl_hzn* out);
 
+/* ------------------------------------------------- rejoin stage: a reachable profile from the car's speed
+ * The horizon stage's ticks carry the row's own v and ax, the flying-lap profile.  A car that is
+ * not on that profile (a standing start, a slow corner exit, a late brake) cannot follow them.
+ * This stage takes the car's speed v0 and one rl_cfg, the car's limits now (they may differ from
+ * the planning cfg), marches the reachable speed nearest the row's from the located point until
+ * it meets the row's, and resamples the ticks along that profile; after the merge they are the
+ * row's own.  In fp64 without contraction, smax / smin and the row as for the horizon stage:
+ *   ax_max_at(cfg, w, k) -> (a_acc, a_brk), the reference's lambda (ref:797-824):
+ *           alat = w*w*fabs(k);  a_total = use_total_ge_lat ? smax(a_total_max, a_lat_max) : a_total_max;
+ *           a_res = sqrt(smax(0.0, a_total*a_total - alat*alat));
+ *           Fd = 0.5*rho_air*Cd*A_front_m2*w*w;  Fr = mass_kg*9.81*c_rr;
+ *           a_power = (P_max_W > 0 && w > 1e-6) ? (P_max_W/(mass_kg*w) - (Fd + Fr)/mass_kg) : 1e9;
+ *           a_acc = smax(0.0, smin(smin(a_res, a_long_acc_cap), a_power));
+ *           a_brk = smax(0.0, smin(a_res, a_long_brake_cap) + (Fd + Fr)/mass_kg)
+ *           (a_total*a_total, 0.5*rho_air*Cd*A_front_m2 and mass_kg*9.81*c_rr are evaluated once,
+ *           left to right)
+ *   locate  the horizon stage's candidates, distance, winner and location, with the same seg_hint
+ *           and window: seg = i, u, e, dist2, t0, s0.  A NaN winner, or S = 0: seg = -1,
+ *           count = 0, merge_node = -1, nothing else is specified.
+ *   nodes   node 0 is the located point: kappa_0 = kappa_i + u*(kappa_j - kappa_i),
+ *           r_0 = v_i + u*(v_j - v_i), d_0 = (1.0 - u)*h.  Node k >= 1 is sample n_k = i + k
+ *           (unwrapped; row index n_k mod N on a closed row): kappa_k, r_k that sample's kappa
+ *           and v, d_k = h.  K_lim = min(K_cap, closed ? N : N-1-i).
+ *   march   serial, in index order: w_0 = v0, tt_0 = 0.0.  If w_0 == r_0: K* = 0.  Otherwise for
+ *           k = 0, 1, ...:  (a_acc, a_brk) = ax_max_at(cfg, w_k, kappa_k);
+ *           up = sqrt(smax(0.0, w_k*w_k + (2.0*a_acc)*d_k));
+ *           dn = sqrt(smax(0.0, w_k*w_k - (2.0*a_brk)*d_k));
+ *           w_{k+1} = smin(up, smax(dn, r_{k+1}))   (the reachable speed nearest the row's);
+ *           tt_{k+1} = tt_k + (2.0*d_k)/smax(1e-6, w_k + w_{k+1})   (exact for constant
+ *           acceleration, finite from standstill).  The first k+1 with w_{k+1} == r_{k+1} is the
+ *           merge node K*; none by K_lim: K* = -1.  K_end = K* >= 0 ? K* : K_lim.
+ *           overspeed = #{k in [0, K_end] : w_k > r_k}.
+ *   merge   c0 = floor(n_K* / N), j* = n_K* - c0*N, t_ref = (K* == 0) ? t0 : t[j*];
+ *           t_merge = tt_{K_end} (the time marched);
+ *           t_loss = tt_K* - (((double)c0*T + t_ref) - t0), the time lost against the row's own
+ *           schedule (a quiet NaN when K* = -1).  From standstill at sample 0, T + t_loss is the
+ *           standing-start lap.
+ *   ticks   tau_m = (double)m*dt, counted from the car.  M1 = #{m < M_cap : tau_m < tt_{K_end}}
+ *           ticks lie on the march: k = the node with tt_k <= tau_m < tt_{k+1} (bisection:
+ *           a = 0, e = K_end; while e - a > 1: mid = a + (e-a)/2; tt_mid <= tau_m ? a = mid : e = mid),
+ *           u_m = (tau_m - tt_k)/(tt_{k+1} - tt_k); x, y, heading (shorter arc) and kappa are
+ *           interpolated with u_m between the node values (node 0's: the trajectory stage's
+ *           expressions with u; its kappa is kappa_0); v = w_k + u_m*(w_{k+1} - w_k);
+ *           ax = d_k > 0 ? (w_{k+1}*w_{k+1} - w_k*w_k)/(2.0*d_k) : 0.0;
+ *           s = s_k + u_m*(s_{k+1} - s_k), s_0 = s0, s_k = (double)n_k*h.
+ *           Not merged: count = M1.  Merged: tick m >= M1 has the row time
+ *           w_ref = t_ref + (tau_m - tt_K*); the horizon stage's wrap (c, w of w_ref), bisection
+ *           and columns follow, with the lap count c0 + c in its s.  Open rows:
+ *           count = M1 + #{M1 <= m < M_cap : w_ref < T}; closed rows: count = M_cap if T is
+ *           finite and > 0, else M1.
+ * A pose with v0 == r_0 therefore reproduces the horizon stage bit for bit.
+ * raceline.rejoin_host states the same in NumPy; the kernel equals it bit for bit.  These are
+ * additions to ABI 6.1 that leave RL_ABI_MINOR as it is: RL_FEATURE_REJOIN announces them. */
+#define RL_RJN_MAX_NODES 1024
+typedef struct rl_rjn_query {
+    const double*  pose_xy;   /* [Q][2] host */
+    const int32_t* row;       /* [Q] row of the plan's trajectory stage (of B for rl_rejoin); NULL: 0 */
+    const int32_t* seg_hint;  /* [Q], -1 = every segment; NULL: all -1 */
+    int32_t Q, window, M_cap, _pad;
+    double  dt;
+    const double*  v0;        /* [Q] the car's speed, finite and >= 0 */
+    const rl_cfg*  cfg;       /* one: the car's limits now */
+    int32_t K_cap, _pad2;     /* march nodes, 1..RL_RJN_MAX_NODES */
+} rl_rjn_query;
+
+typedef struct rl_rjn {       /* caller-allocated; NULL fields skipped */
+    double *s, *x, *y, *heading, *kappa, *v, *ax;   /* [Q][M_cap]; ticks m >= count[q] are unspecified */
+    double *u, *t0, *s0, *e, *dist2;                /* [Q] */
+    int32_t *seg, *count;                           /* [Q] */
+    int32_t *merge_node, *overspeed;                /* [Q] */
+    double *t_merge, *t_loss;                       /* [Q] */
+    double *node_v, *node_t;                        /* [Q][K_cap+1] w_k, tt_k; entries past K_end are unspecified;
+                                                       downloaded only when asked for */
+} rl_rjn;
+
+/* Enqueue the stage after the plan's last trajectory stage: rl_plan_horizon's stream, validity
+ * and invalidation rules.  It leaves the trajectory stage, the last horizon stage and the
+ * results untouched; its buffers are plan-owned (they count toward the plan cache's budget) and
+ * grow with Q, M_cap and K_cap.  The query's arrays and cfg are read before the call returns.
+ * rl_plan_kernel_ms index 9 is the stage.  RL_EINVAL before any device work for: every error
+ * of rl_plan_horizon, a NULL cfg or v0, a v0[q] that is not finite or is < 0, K_cap < 1 or
+ * > RL_RJN_MAX_NODES. */
+int rl_plan_rejoin(rl_plan* plan, const rl_rjn_query* query, void* hip_stream);
+/* Download the last rejoin stage (synchronises its stream) into the non-NULL fields of out.
+ * RL_EINVAL before a stage, or after a run or trajectory stage that followed it. */
+int rl_plan_fetch_rejoin(rl_plan* plan, rl_rjn* out);
+/* The same on B given rows [B][N] with steps h [B] (host in, host out): the trajectory kernel
+ * for the stamps, then the rejoin kernel.  Errors as rl_horizon's, and the query errors above. */
+int rl_rejoin(const double* x, const double* y, const double* heading, const double* kappa,
+              const double* v, const double* ax, const double* h, int32_t N, int32_t B,
+              int32_t closed, const rl_rjn_query* query, int32_t device, rl_rjn* out);
+
 /* B lap evaluations of given paths: heading/curvature
  * (heading_curv_from_points_generic, ref:595-620) and velocity_profile_forward_backward
  * (ref:782-862) with h = L[b]/N on path b — the min-time driver's final step
@@ -548,6 +640,7 @@ int         rl_abi_minor(void);
 /* additions since the last minor, one bit each (a library without this function has none) */
 #define RL_FEATURE_TRAJECTORY 1   /* bit 0: the trajectory stage */
 #define RL_FEATURE_HORIZON 2      /* bit 1: the horizon stage */
+#define RL_FEATURE_REJOIN 4       /* bit 2: the rejoin stage */
 int         rl_abi_features(void);
 /* samples per lane of the THROUGHPUT shape for N (4: N <= 256, 5: N <= 320, 8: N <= 4096;
  * 1 = the streaming kernel), or RL_ETOOBIG.  Batches small enough for a latency shape launch fewer samples per lane:

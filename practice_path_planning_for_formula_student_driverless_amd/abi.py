@@ -155,6 +155,29 @@ class RlHzn(C.Structure):
     _fields_ = [(n, C.POINTER(C.c_double)) for n in TRAJ_COLS + HZN_LOC] + [(n, C.POINTER(C.c_int32)) for n in ("seg", "count")]
 
 
+RL_FEATURE_REJOIN = 4      # rl_abi_features() bit 2: the rejoin stage
+RL_RJN_MAX_NODES = 1024
+RJN_SCAL = ("t_merge", "t_loss")
+RJN_INTS = ("seg", "count", "merge_node", "overspeed")
+RJN_NODES = ("node_v", "node_t")
+
+
+class RlRjnQuery(C.Structure):
+    """``rl_rjn_query`` — ``rl_hzn_query`` plus the car's speeds v0 [Q], one ``rl_cfg`` (the car's
+    limits now) and the number of march nodes K_cap."""
+
+    _fields_ = RlHznQuery._fields_ + [("v0", C.POINTER(C.c_double)), ("cfg", C.POINTER(RlCfg)), ("K_cap", C.c_int32),
+                                      ("_pad2", C.c_int32)]
+
+
+class RlRjn(C.Structure):
+    """``rl_rjn`` — ``rl_hzn`` plus merge_node, overspeed, t_merge, t_loss [Q] and the optional
+    march nodes node_v, node_t [Q][K_cap + 1]; NULL fields are skipped."""
+
+    _fields_ = (RlHzn._fields_ + [(n, C.POINTER(C.c_int32)) for n in RJN_INTS[2:]] +
+                [(n, C.POINTER(C.c_double)) for n in RJN_SCAL + RJN_NODES])
+
+
 OUT_F64 = ("x", "y", "heading", "kappa", "alpha_total", "alpha_last")
 OUT_F64_MT = OUT_F64 + ("v", "ax")
 
@@ -513,6 +536,14 @@ DECLS_HZN = [
     ("rl_horizon", C.c_int, [_F64] * 7 + [C.c_int32, C.c_int32, C.c_int32, _HZNQ, C.c_int32, _HZN]),
 ]
 
+# the rejoin stage: bound only in a library whose rl_abi_features() has RL_FEATURE_REJOIN
+_RJN, _RJNQ = _P(RlRjn), _P(RlRjnQuery)
+DECLS_RJN = [
+    ("rl_plan_rejoin", C.c_int, [C.c_void_p, _RJNQ, C.c_void_p]),
+    ("rl_plan_fetch_rejoin", C.c_int, [C.c_void_p, _RJN]),
+    ("rl_rejoin", C.c_int, [_F64] * 7 + [C.c_int32, C.c_int32, C.c_int32, _RJNQ, C.c_int32, _RJN]),
+]
+
 
 def declare_optimize(fn) -> None:
     """rl_optimize's signature (the oracle's oracle_optimize shares it)."""
@@ -525,7 +556,8 @@ _LIB = None
 def load_library(path: str = LIB_PATH) -> C.CDLL:
     """Load librl.so (the HIP path).  Raises if it is missing: there is no fallback; a library
     that lacks a function of DECLS or DECLS_EXT raises AttributeError naming it, and so does
-    one that announces RL_FEATURE_HORIZON and lacks a function of DECLS_HZN."""
+    one that announces RL_FEATURE_HORIZON / RL_FEATURE_REJOIN and lacks a function of DECLS_HZN /
+    DECLS_RJN."""
     global _LIB
     if _LIB is not None and path == LIB_PATH:
         return _LIB
@@ -545,6 +577,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     bind(DECLS + ext)
     if ext and lib.rl_abi_features() & RL_FEATURE_HORIZON:
         bind(DECLS_HZN)
+    if ext and lib.rl_abi_features() & RL_FEATURE_REJOIN:
+        bind(DECLS_RJN)
     if path == LIB_PATH:
         _LIB = lib
     return lib

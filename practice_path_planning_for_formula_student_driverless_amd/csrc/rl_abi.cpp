@@ -11,7 +11,7 @@ extern "C" {
 const char* rl_last_error(void) { return g_err.c_str(); }
 int rl_abi_version(void) { return RL_ABI_VERSION; }
 int rl_abi_minor(void) { return RL_ABI_MINOR; }
-int rl_abi_features(void) { return RL_FEATURE_TRAJECTORY | RL_FEATURE_HORIZON; }
+int rl_abi_features(void) { return RL_FEATURE_TRAJECTORY | RL_FEATURE_HORIZON | RL_FEATURE_REJOIN; }
 
 int rl_device_count(void) {
     int n = 0;
@@ -367,6 +367,52 @@ int rl_horizon(const double* x, const double* y, const double* heading, const do
     if (hipMemcpy(block.data(), d_res, hzn_out_bytes(Q, M), hipMemcpyDeviceToHost) != hipSuccess)
         return fail(RL_EHIP, "rl_horizon: download");
     hzn_unpack(block.data(), Q, M, out);
+    return RL_OK;
+}
+
+// rl_horizon's route with the rejoin kernel (rl_rejoin.hip) in the horizon kernel's place
+int rl_rejoin(const double* x, const double* y, const double* heading, const double* kappa, const double* v,
+              const double* ax, const double* h, int32_t N, int32_t B, int32_t closed, const rl_rjn_query* query,
+              int32_t device, rl_rjn* out) {
+    if (!x || !y || !heading || !kappa || !v || !ax || !h || !query || !out)
+        return fail(RL_EINVAL, "rl_rejoin: an input row, h, the query or out is NULL");
+    if (B < 1 || N < 0) return fail(RL_EINVAL, "rl_rejoin: B < 1 or N < 0");
+    if (N > rl::RL_STREAM_MAX_N) return fail(RL_ETOOBIG, "rl_rejoin: N exceeds 1048576");
+    if (int rc = check_rjn(query, B, N, closed ? 1 : 0)) return rc;
+    if (int rc = select_device(device)) return rc;
+    const size_t BN = (size_t)B * (size_t)N, Q = (size_t)query->Q, M = (size_t)query->M_cap, K = (size_t)query->K_cap;
+    DevArena mem;
+    const double* in[6] = {x, y, heading, kappa, v, ax};
+    double* d_in[6];
+    for (auto& d : d_in) d = mem.get<double>(BN);
+    double* d_h = mem.get<double>((size_t)B);
+    rl::TrajParams q{};
+    for (auto& c : q.out) c = mem.get<double>((size_t)B);
+    q.stamps = mem.get<double>((size_t)B * ((size_t)N + 1));
+    q.T = mem.get<double>((size_t)B);
+    q.count = mem.get<int32_t>((size_t)B);
+    char* d_qry = mem.get<char>(rjn_in_bytes(Q));
+    char* d_res = mem.get<char>(rjn_out_bytes(Q, M, K));
+    if (!mem.ok()) return fail(RL_ENOMEM, "rl_rejoin: hipMalloc failed");
+    std::vector<char> block(std::max(rjn_in_bytes(Q), rjn_out_bytes(Q, M, K)));
+    rjn_pack(query, block.data());
+    for (int c = 0; c < 6; ++c)
+        if (hipMemcpy(d_in[c], in[c], BN * 8, hipMemcpyHostToDevice) != hipSuccess) return fail(RL_EHIP, "rl_rejoin: upload");
+    if (hipMemcpy(d_h, h, (size_t)B * 8, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_qry, block.data(), rjn_in_bytes(Q), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(RL_EHIP, "rl_rejoin: upload");
+    q.x = d_in[0]; q.y = d_in[1]; q.heading = d_in[2]; q.kappa = d_in[3]; q.v = d_in[4]; q.ax = d_in[5];
+    q.h = d_h;
+    q.dt = query->dt;
+    q.N = N; q.B = B; q.R = B; q.closed = closed ? 1 : 0; q.M_cap = 1;
+    if (rl::launch_trajectory(q, nullptr) != hipSuccess) return fail(RL_EHIP, "rl_rejoin: trajectory kernel");
+    const rl::RjnParams rp = rjn_params(q, query, d_qry, d_res);
+    if (rl::launch_rejoin(rp, nullptr) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+        return fail(RL_EHIP, "rl_rejoin: kernel");
+    const bool nodes = out->node_v || out->node_t;
+    if (hipMemcpy(block.data(), d_res, nodes ? rjn_out_bytes(Q, M, K) : rjn_head_bytes(Q, M), hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(RL_EHIP, "rl_rejoin: download");
+    rjn_unpack(block.data(), Q, M, K, out);
     return RL_OK;
 }
 

@@ -28,36 +28,6 @@
 
 namespace rl {
 
-constexpr int HZN_THREADS = 256;
-// order keys of D: a D that is not NaN is >= +0, so its bits order as it does; every NaN takes
-// one key above +inf's (the index then decides among them); a lane without a candidate loses
-// every comparison
-constexpr uint64_t HZN_KEY_NAN = 0x7ff8000000000000ull;
-constexpr uint64_t HZN_KEY_NONE = ~0ull;
-constexpr uint32_t HZN_IDX_NONE = 0xffffffffu;
-
-__device__ __forceinline__ bool key_less(uint64_t ka, uint32_t ia, uint64_t kb, uint32_t ib) {
-    return ka < kb || (ka == kb && ia < ib);
-}
-
-// the pose's nearest point on one segment: its parameter u and squared distance D
-struct Foot {
-    double dx, dy, wx, wy, u, D;
-};
-__device__ __forceinline__ Foot foot(double xi, double yi, double xj, double yj, double px, double py) {
-    Foot f;
-    f.dx = xj - xi;
-    f.dy = yj - yi;
-    f.wx = px - xi;
-    f.wy = py - yi;
-    const double dd = f.dx * f.dx + f.dy * f.dy;
-    const double c = f.wx * f.dx + f.wy * f.dy;
-    f.u = dd > 0.0 ? smin(1.0, smax(0.0, c / dd)) : 0.0;
-    const double rx = f.wx - f.u * f.dx, ry = f.wy - f.u * f.dy;
-    f.D = rx * rx + ry * ry;
-    return f;
-}
-
 // One workgroup per query.  The lanes stride over the candidates and each keeps its least
 // (key, index); the wave folds its 64 with an xor butterfly, the waves meet in LDS and every
 // lane reads all slots (rl_rank_kernel's scheme).  The same barrier publishes the stamps of a
@@ -93,59 +63,9 @@ __global__ __launch_bounds__(HZN_THREADS) void rl_horizon_kernel(HznParams p) {
         for (int i = tid; i <= N; i += HZN_THREADS) s_t[i] = tg[i];
     const double px = p.pose[2 * (size_t)k], py = p.pose[2 * (size_t)k + 1];
 
-    // the candidates are lo + c, c in [0, C), taken mod S on a closed row (lo > -S, lo + C < 2S)
-    const int g = p.hint ? p.hint[k] : -1;
-    const int64_t W = p.window;
-    int lo = 0, C = S;
-    if (g >= 0) {
-        if (q.closed) {
-            if (2 * W + 1 < (int64_t)S) {
-                lo = g % S - (int)W;
-                C = 2 * (int)W + 1;
-            }
-        } else {
-            const int64_t a = (int64_t)g - W, e = (int64_t)g + W;
-            lo = (int)(a < 0 ? 0 : a);
-            C = (int)(e > S - 1 ? S - 1 : e) - lo + 1;         // <= 0 for a hint past the row: no candidate
-        }
-    }
-    uint64_t bk = HZN_KEY_NONE;
-    uint32_t bi = HZN_IDX_NONE;
-    for (int c = tid; c < C; c += HZN_THREADS) {
-        int i = lo + c;
-        if (i < 0) i += S;
-        else if (i >= S) i -= S;
-        const int j = i + 1 < N ? i + 1 : 0;
-        const double D = foot(x[i], y[i], x[j], y[j], px, py).D;
-        const uint64_t key = D != D ? HZN_KEY_NAN : (uint64_t)__double_as_longlong(D);
-        if (key_less(key, (uint32_t)i, bk, bi)) {
-            bk = key;
-            bi = (uint32_t)i;
-        }
-    }
-    for (int o = 32; o; o >>= 1) {
-        const uint64_t ok = __shfl_xor(bk, o, 64);
-        const uint32_t oi = __shfl_xor(bi, o, 64);
-        if (key_less(ok, oi, bk, bi)) {
-            bk = ok;
-            bi = oi;
-        }
-    }
-    if ((tid & 63) == 0) {
-        s_key[tid >> 6] = bk;
-        s_idx[tid >> 6] = bi;
-    }
-    __syncthreads();
-    bk = s_key[0];
-    bi = s_idx[0];
-    for (int w = 1; w < HZN_THREADS / 64; ++w) {
-        const uint64_t ok = s_key[w];
-        const uint32_t oi = s_idx[w];
-        if (key_less(ok, oi, bk, bi)) {
-            bk = ok;
-            bi = oi;
-        }
-    }
+    const HznWin win = hzn_locate(p, k, tid, x, y, px, py, s_key, s_idx);
+    const uint64_t bk = win.key;
+    const uint32_t bi = win.idx;
     if (bk >= HZN_KEY_NAN || bi >= (uint32_t)S) {  // a NaN winner, or no candidate at all
         if (tid == 0) {
             p.seg[k] = -1;
@@ -187,45 +107,11 @@ __global__ __launch_bounds__(HZN_THREADS) void rl_horizon_kernel(HznParams p) {
     __syncthreads();
     const double t0 = s_t0;
     const int M = s_count;
-    const double* psi = q.heading + off;
-    const double* kap = q.kappa + off;
-    const double* v = q.v + off;
-    const double* ax = q.ax + off;
+    const HznRow row{x, y, q.heading + off, q.kappa + off, q.v + off, q.ax + off};
     const size_t orow = (size_t)k * (size_t)p.M_cap;
     for (int m = tid; m < M; m += HZN_THREADS) {
-        const double tau = t0 + (double)m * p.dt;
-        double c = 0.0, w = tau;
-        if (q.closed) {
-            c = floor(tau / T);
-            w = tau - c * T;
-            if (w < 0.0) {
-                w += T;
-                c -= 1.0;
-            } else if (w >= T) {
-                w -= T;
-                c += 1.0;
-            }
-        }
-        int a = 0, e = S;                          // t_a <= w < t_e on a sorted row; clipped otherwise
-        while (e - a > 1) {
-            const int mid = a + ((e - a) >> 1);
-            if (stamp(mid) <= w) a = mid;
-            else e = mid;
-        }
-        const int i = a, jn = i + 1 < N ? i + 1 : 0;
-        const double ta = stamp(i), tb = stamp(i + 1);
-        const double u = (w - ta) / (tb - ta);
-        const double xi = x[i], yi = y[i], vi = v[i], ki = kap[i], pi = psi[i];
-        double d = psi[jn] - pi;
-        if (d > M_PI) d -= 2.0 * M_PI;
-        else if (d < -M_PI) d += 2.0 * M_PI;
-        p.out[0][orow + m] = ((c * (double)S + (double)i) + u) * h;
-        p.out[1][orow + m] = xi + u * (x[jn] - xi);
-        p.out[2][orow + m] = yi + u * (y[jn] - yi);
-        p.out[3][orow + m] = pi + u * d;
-        p.out[4][orow + m] = ki + u * (kap[jn] - ki);
-        p.out[5][orow + m] = vi + u * (v[jn] - vi);
-        p.out[6][orow + m] = ax[i];
+        const HznLap l = hzn_wrap(q.closed, T, t0 + (double)m * p.dt);
+        hzn_columns(p, row, stamp, N, S, h, l.c, l.w, orow + m);
     }
 }
 

@@ -20,6 +20,7 @@
 #include "rl_lap_stage.h"
 #include "rl_trajectory.h"
 #include "rl_horizon.h"
+#include "rl_rejoin.h"
 
 namespace rl {
 
@@ -464,6 +465,16 @@ struct rl_plan {
     rl::DevArena hzn_mem;
     int hzn_Q = 0, hzn_M = 0;
     hipEvent_t ev_hzn[2] = {nullptr, nullptr};            // after the upload, after the kernel
+    // rejoin stage (rl_plan_rejoin): the horizon stage's scheme with blocks of its own (rjn_in,
+    // rjn_out, rjn_pin), so that the last horizon stage stays fetchable; they grow with Q, M_cap
+    // and K_cap.  rjn_Q = 0: no stage since the last run or trajectory stage.
+    char* rjn_in = nullptr;
+    char* rjn_out = nullptr;
+    char* rjn_pin = nullptr;
+    size_t rjn_in_cap = 0, rjn_out_cap = 0;
+    rl::DevArena rjn_mem;
+    int rjn_Q = 0, rjn_M = 0, rjn_K = 0;
+    hipEvent_t ev_rjn[2] = {nullptr, nullptr};            // after the upload, after the kernel
 
     template <class T>
     int alloc(T** p, size_t n) {
@@ -472,7 +483,7 @@ struct rl_plan {
     }
     int nomem() const { return rl::fail(RL_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(mem.err)); }
     // device memory held (plan cache budget)
-    size_t dev_bytes() const { return mem.bytes + sel_mem.bytes + lap_mem.bytes + traj_mem.bytes + hzn_mem.bytes; }
+    size_t dev_bytes() const { return mem.bytes + sel_mem.bytes + lap_mem.bytes + traj_mem.bytes + hzn_mem.bytes + rjn_mem.bytes; }
     // the stream of the last run or stage
     hipStream_t run_stream() const { return last_stream ? last_stream : own_stream; }
     // the batch size the kernel shape is chosen for
@@ -521,5 +532,21 @@ void hzn_pack(const rl_hzn_query* q, char* block);
 HznParams hzn_params(const TrajParams& src, const rl_hzn_query* q, char* in, char* out);
 // copy a results' block (host) into the non-NULL fields of o
 void hzn_unpack(const char* block, size_t Q, size_t M, const rl_hzn* o);
+// argument checks shared by the rejoin entry points (no device call): check_hzn's, then v0, cfg
+// and K_cap
+int check_rjn(const rl_rjn_query* q, int32_t R, int32_t N, int32_t closed);
+// the packed blocks of a rejoin stage of Q queries, M ticks and K = K_cap nodes: the queries are
+// poses [Q][2], v0 [Q], rows [Q], hints [Q]; the results the columns [Q][M] in rl_rjn's order,
+// then u, t0, s0, e, dist2, t_merge, t_loss [Q], then seg, count, merge_node, overspeed [Q] (the
+// head, always downloaded), then node_v, node_t [Q][K + 1]
+inline size_t rjn_in_bytes(size_t Q) { return Q * 32; }
+inline size_t rjn_head_bytes(size_t Q, size_t M) {
+    return ((size_t)TRAJ_COLS * Q * M + (size_t)(HZN_LOC + RJN_SCAL) * Q) * 8 + 4 * Q * 4;
+}
+inline size_t rjn_out_bytes(size_t Q, size_t M, size_t K) { return rjn_head_bytes(Q, M) + 2 * Q * (K + 1) * 8; }
+void rjn_pack(const rl_rjn_query* q, char* block);
+RjnParams rjn_params(const TrajParams& src, const rl_rjn_query* q, char* in, char* out);
+// copy a results' block (host) into the non-NULL fields of o
+void rjn_unpack(const char* block, size_t Q, size_t M, size_t K, const rl_rjn* o);
 
 }  // namespace rl

@@ -197,6 +197,10 @@ int rl_plan_destroy(rl_plan* plan) {
     if (plan->hzn_pin) hipHostFree(plan->hzn_pin);
     for (auto& e : plan->ev_hzn)
         if (e) hipEventDestroy(e);
+    plan->rjn_mem.release();
+    if (plan->rjn_pin) hipHostFree(plan->rjn_pin);
+    for (auto& e : plan->ev_rjn)
+        if (e) hipEventDestroy(e);
     for (auto& e : plan->ev)
         if (e) hipEventDestroy(e);
     for (auto& e : plan->ev_end)
@@ -296,6 +300,7 @@ int rl_plan_run(rl_plan* p, void* hip_stream) {
     p->lap_valid = false;                              // and so is an earlier lap stage
     p->traj_R = 0;                                     // and an earlier trajectory stage
     p->hzn_Q = 0;                                      // and the horizon stage that read it
+    p->rjn_Q = 0;                                      // and the rejoin stage
     return RL_OK;
 }
 
@@ -420,6 +425,7 @@ int rl_plan_run_group(rl_plan* const* plans, int32_t n, void* hip_stream) {
         plans[i]->lap_valid = false;
         plans[i]->traj_R = 0;
         plans[i]->hzn_Q = 0;
+        plans[i]->rjn_Q = 0;
     }
     return RL_OK;
 }
@@ -451,6 +457,11 @@ int rl_plan_kernel_ms(rl_plan* p, int32_t idx, float* ms) {
     else if (idx == 8 && p->hzn_Q && p->traj_R) {
         a = p->ev_hzn[0];
         b = p->ev_hzn[1];
+        HIPCHK(hipEventSynchronize(b));
+    }
+    else if (idx == 9 && p->rjn_Q && p->traj_R) {
+        a = p->ev_rjn[0];
+        b = p->ev_rjn[1];
         HIPCHK(hipEventSynchronize(b));
     }
     else if (idx == 1 && mc) { a = p->ev[1]; b = p->ev_end[0]; }

@@ -1,0 +1,265 @@
+// rl_rejoin.hip — the rejoin stage's kernel: "I am at (px, py) doing v0, with these
+// limits: what can I drive for the next M ticks, where do I rejoin the plan, and what did that
+// cost?"  The horizon stage's query (rl_horizon.hip, §3l) with a speed and one rl_cfg.  Per
+// query, in fp64 without contraction:
+//     locate: §3l's candidates, distance, winner and location: seg = i, u, e, dist2, t0, s0
+//     nodes: node 0 the located point (kappa_0, r_0 interpolated with u, d_0 = (1.0 - u)*h),
+//         node k >= 1 sample n_k = i + k (row index n_k mod N), d_k = h;
+//         K_lim = min(K_cap, closed ? N : N - 1 - i)
+//     march (serial): w_0 = v0, tt_0 = 0.0; w_0 == r_0: K* = 0.  Else for k = 0, 1, ..:
+//         (a_acc, a_brk) = ax_max_at(cfg, w_k, kappa_k)
+//         up = sqrt(smax(0.0, w_k*w_k + (2.0*a_acc)*d_k)), dn = sqrt(smax(0.0, w_k*w_k - (2.0*a_brk)*d_k))
+//         w_{k+1} = smin(up, smax(dn, r_{k+1})), tt_{k+1} = tt_k + (2.0*d_k)/smax(1e-6, w_k + w_{k+1})
+//         the first k + 1 with w_{k+1} == r_{k+1} is K*; none by K_lim: K* = -1; K_end = K* >= 0 ? K* : K_lim
+//     merge: c0 = floor(n_K* / N), j* = n_K* - c0*N, t_ref = K* == 0 ? t0 : t[j*],
+//         t_merge = tt_{K_end}, t_loss = tt_K* - (((double)c0*T + t_ref) - t0) (NaN when K* = -1)
+//     ticks: tau_m = (double)m*dt.  M1 = #{m < M_cap : tau_m < tt_{K_end}} of them lie between the
+//         nodes k, k + 1 with tt_k <= tau_m < tt_{k+1}, u_m = (tau_m - tt_k)/(tt_{k+1} - tt_k), the
+//         columns interpolated between the node values, v between w_k and w_{k+1}, ax constant.
+//         Merged rows go on at the row time t_ref + (tau_m - tt_K*) with §3l's wrap, bisection and
+//         columns, c0 laps added to the count in s.
+// raceline.rejoin_host states the same in NumPy, and the two agree bit for bit.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "rl_device.h"
+#include "rl_rejoin.h"
+
+namespace rl {
+
+// ax_max_at (ref:797-824) with the constant prefixes of RjnCfg, in the reference's operation
+// order and its select forms of std::max / std::min
+struct AxMax {
+    double acc, brk;
+};
+__device__ __forceinline__ AxMax ax_max_at(const RjnCfg& c, double vi, double ki) {
+    const double alat = vi * vi * fabs(ki);
+    const double a_res = sqrt(smax(0.0, c.a_total2 - alat * alat));
+    const double Fd = c.kFd * vi * vi;
+    const double a_power = (c.Pmax > 0 && vi > 1e-6) ? (c.Pmax / (c.mass * vi) - (Fd + c.Fr) / c.mass) : 1e9;
+    AxMax r;
+    r.acc = smax(0.0, smin(smin(a_res, c.acc_cap), a_power));
+    r.brk = smax(0.0, smin(a_res, c.brk_cap) + (Fd + c.Fr) / c.mass);
+    return r;
+}
+
+// position, heading, curvature and arc length of a march node
+struct Node {
+    double x, y, psi, kap, s;
+};
+
+// One workgroup per query, in the horizon kernel's steps with a march in the middle.  The locate
+// is hzn_locate; its barrier also publishes the stamps of a row of N <= TRAJ_LDS_N samples.
+// All lanes then stage kappa_k and r_k of the nodes k <= K_lim into LDS; lane 0 marches over
+// them, writes w_k and tt_k beside them and hands K*, K_end, the counts and the merge time over
+// through LDS; all lanes stride over the ticks (consecutive lanes, consecutive ticks) and over
+// the nodes' w, tt for node_v, node_t.  No atomics: every output element has one writer.
+// LDS: the stamps (32 776 B) and four node arrays (4 x 8 200 B).
+__global__ __launch_bounds__(HZN_THREADS) void rl_rejoin_kernel(RjnParams rp) {
+    __shared__ double s_t[TRAJ_LDS_N + 1];
+    __shared__ double s_kap[RJN_MAX_NODES + 1];
+    __shared__ double s_r[RJN_MAX_NODES + 1];
+    __shared__ double s_w[RJN_MAX_NODES + 1];
+    __shared__ double s_tt[RJN_MAX_NODES + 1];
+    __shared__ uint64_t s_key[HZN_THREADS / 64];
+    __shared__ uint32_t s_idx[HZN_THREADS / 64];
+    __shared__ double s_tref;
+    __shared__ int s_kstar, s_kend, s_m1, s_count;
+    const HznParams& p = rp.hz;
+    const TrajParams& q = p.src;
+    const int k = blockIdx.x, tid = threadIdx.x, N = q.N;
+    const int S = q.closed ? N : N - 1;
+    const int r = p.row ? p.row[k] : 0;
+    int b = -1;
+    if (r >= 0 && r < q.R) b = q.index ? q.index[r] : r;
+    if (b < 0 || b >= q.B || S < 1) {             // no row, or a row without a segment
+        if (tid == 0) {
+            p.seg[k] = -1;
+            p.count[k] = 0;
+            rp.merge_node[k] = -1;
+        }
+        return;
+    }
+    const size_t off = (size_t)b * (size_t)N;
+    const HznRow row{q.x + off, q.y + off, q.heading + off, q.kappa + off, q.v + off, q.ax + off};
+    const double* tg = q.stamps + (size_t)r * ((size_t)N + 1);
+    const bool lds = N <= TRAJ_LDS_N;
+    if (lds)
+        for (int i = tid; i <= N; i += HZN_THREADS) s_t[i] = tg[i];
+    const double px = p.pose[2 * (size_t)k], py = p.pose[2 * (size_t)k + 1];
+
+    const HznWin win = hzn_locate(p, k, tid, row.x, row.y, px, py, s_key, s_idx);
+    if (win.key >= HZN_KEY_NAN || win.idx >= (uint32_t)S) {  // a NaN winner, or no candidate at all
+        if (tid == 0) {
+            p.seg[k] = -1;
+            p.count[k] = 0;
+            rp.merge_node[k] = -1;
+        }
+        return;
+    }
+    auto stamp = [&](int i) { return lds ? s_t[i] : tg[i]; };
+    const double h = q.h ? q.h[b] : (q.Ls ? q.Ls[b] : q.L) / (double)N;
+    const double T = q.T[r];
+    // the located point, by every lane: node 0 needs it in the tick phase
+    const int i0 = (int)win.idx, j0 = i0 + 1 < N ? i0 + 1 : 0;
+    const Foot f = foot(row.x[i0], row.y[i0], row.x[j0], row.y[j0], px, py);
+    const double ta0 = stamp(i0);
+    const double t0 = ta0 + f.u * (stamp(i0 + 1) - ta0);
+    const double d0 = (1.0 - f.u) * h;
+    const int room = q.closed ? N : N - 1 - i0;   // >= 1: i0 < S
+    const int K_lim = rp.K_cap < room ? rp.K_cap : room;
+    auto sample = [&](int kk) {                    // row index of node kk >= 1 (i0 + kk < 2N)
+        const int n = i0 + kk;
+        return n >= N ? n - N : n;
+    };
+    for (int kk = tid; kk <= K_lim; kk += HZN_THREADS) {
+        if (kk == 0) {
+            const double ki = row.kap[i0], vi = row.v[i0];
+            s_kap[0] = ki + f.u * (row.kap[j0] - ki);
+            s_r[0] = vi + f.u * (row.v[j0] - vi);
+        } else {
+            const int n = sample(kk);
+            s_kap[kk] = row.kap[n];
+            s_r[kk] = row.v[n];
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double w = rp.v0[k], tt = 0.0;
+        int ks = -1, over = 0;
+        s_w[0] = w;
+        s_tt[0] = 0.0;
+        if (w == s_r[0]) {
+            ks = 0;
+        } else {
+            over += w > s_r[0];
+            for (int kk = 0; kk < K_lim; ++kk) {
+                const double d = kk == 0 ? d0 : h;
+                const AxMax a = ax_max_at(rp.cfg, w, s_kap[kk]);
+                const double up = sqrt(smax(0.0, w * w + (2.0 * a.acc) * d));
+                const double dn = sqrt(smax(0.0, w * w - (2.0 * a.brk) * d));
+                const double rn = s_r[kk + 1];
+                const double wn = smin(up, smax(dn, rn));
+                tt = tt + (2.0 * d) / smax(1e-6, w + wn);
+                s_w[kk + 1] = wn;
+                s_tt[kk + 1] = tt;
+                w = wn;
+                if (wn == rn) {
+                    ks = kk + 1;
+                    break;
+                }
+                over += wn > rn;
+            }
+        }
+        const int kend = ks >= 0 ? ks : K_lim;
+        const double tte = s_tt[kend];
+        const int nk = i0 + (ks >= 0 ? ks : 0), c0 = nk >= N ? 1 : 0;
+        const double tref = ks == 0 ? t0 : stamp(nk - c0 * N);
+        int a = 0, e = p.M_cap;                    // the first m with !(tau_m < tt_{K_end})
+        while (a < e) {
+            const int mid = a + ((e - a) >> 1);
+            if ((double)mid * p.dt < tte) a = mid + 1;
+            else e = mid;
+        }
+        const int m1 = a;
+        int cnt = m1;
+        if (ks >= 0) {
+            if (q.closed) {
+                if (__builtin_isfinite(T) && T > 0.0) cnt = p.M_cap;
+            } else {
+                e = p.M_cap;                       // the first m >= M1 whose row time is not < T
+                while (a < e) {
+                    const int mid = a + ((e - a) >> 1);
+                    if (tref + ((double)mid * p.dt - tte) < T) a = mid + 1;
+                    else e = mid;
+                }
+                cnt = a;
+            }
+        }
+        const double root = sqrt(f.D);
+        p.seg[k] = i0;
+        p.count[k] = cnt;
+        p.loc[0][k] = f.u;
+        p.loc[1][k] = t0;
+        p.loc[2][k] = ((double)i0 + f.u) * h;
+        p.loc[3][k] = (f.dx * f.wy - f.dy * f.wx) < 0.0 ? -root : root;
+        p.loc[4][k] = f.D;
+        rp.merge_node[k] = ks;
+        rp.overspeed[k] = over;
+        rp.scal[0][k] = tte;
+        rp.scal[1][k] = ks >= 0 ? tte - (((double)c0 * T + tref) - t0) : __longlong_as_double(0x7ff8000000000000ll);
+        s_tref = tref;
+        s_kstar = ks;
+        s_kend = kend;
+        s_m1 = m1;
+        s_count = cnt;
+    }
+    __syncthreads();
+    const int kend = s_kend, m1 = s_m1, M = s_count;
+    const int c0 = (s_kstar > 0 && i0 + s_kstar >= N) ? 1 : 0;
+    const double tref = s_tref, tte = s_tt[kend];
+    const size_t nrow = (size_t)k * ((size_t)rp.K_cap + 1);
+    for (int kk = tid; kk <= kend; kk += HZN_THREADS) {
+        rp.node_v[nrow + kk] = s_w[kk];
+        rp.node_t[nrow + kk] = s_tt[kk];
+    }
+    auto node = [&](int kk) {
+        Node n;
+        if (kk == 0) {
+            const double xi = row.x[i0], yi = row.y[i0], pi = row.psi[i0];
+            double d = row.psi[j0] - pi;
+            if (d > M_PI) d -= 2.0 * M_PI;
+            else if (d < -M_PI) d += 2.0 * M_PI;
+            n.x = xi + f.u * (row.x[j0] - xi);
+            n.y = yi + f.u * (row.y[j0] - yi);
+            n.psi = pi + f.u * d;
+            n.s = ((double)i0 + f.u) * h;
+        } else {
+            const int j = sample(kk);
+            n.x = row.x[j];
+            n.y = row.y[j];
+            n.psi = row.psi[j];
+            n.s = (double)(i0 + kk) * h;
+        }
+        n.kap = s_kap[kk];
+        return n;
+    };
+    const size_t orow = (size_t)k * (size_t)p.M_cap;
+    for (int m = tid; m < M; m += HZN_THREADS) {
+        const double tau = (double)m * p.dt;
+        const size_t o = orow + m;
+        if (m < m1) {
+            int a = 0, e = kend;                   // tt_a <= tau < tt_e
+            while (e - a > 1) {
+                const int mid = a + ((e - a) >> 1);
+                if (s_tt[mid] <= tau) a = mid;
+                else e = mid;
+            }
+            const double ta = s_tt[a], tb = s_tt[a + 1], wa = s_w[a], wb = s_w[a + 1];
+            const double u = (tau - ta) / (tb - ta);
+            const double d = a == 0 ? d0 : h;
+            const Node A = node(a), B = node(a + 1);
+            double dp = B.psi - A.psi;
+            if (dp > M_PI) dp -= 2.0 * M_PI;
+            else if (dp < -M_PI) dp += 2.0 * M_PI;
+            p.out[0][o] = A.s + u * (B.s - A.s);
+            p.out[1][o] = A.x + u * (B.x - A.x);
+            p.out[2][o] = A.y + u * (B.y - A.y);
+            p.out[3][o] = A.psi + u * dp;
+            p.out[4][o] = A.kap + u * (B.kap - A.kap);
+            p.out[5][o] = wa + u * (wb - wa);
+            p.out[6][o] = d > 0.0 ? (wb * wb - wa * wa) / (2.0 * d) : 0.0;
+        } else {
+            const HznLap l = hzn_wrap(q.closed, T, tref + (tau - tte));
+            hzn_columns(p, row, stamp, N, S, h, (double)c0 + l.c, l.w, o);
+        }
+    }
+}
+
+hipError_t launch_rejoin(const RjnParams& p, hipStream_t st) {
+    hipLaunchKernelGGL(rl_rejoin_kernel, dim3((unsigned)p.hz.Q), dim3(HZN_THREADS), 0, st, p);
+    return hipGetLastError();
+}
+
+}  // namespace rl

@@ -44,6 +44,9 @@
 //   --trajectory-dt DT [--trajectory-cap M]  with --best K: also resample the K winners on the
 //               GPU at ticks of DT seconds, at most M (4096) each (rl_optimize_best_trajectory),
 //               and write <base>_trajectory_<r>.csv: t,s,x,y,heading_rad,curvature,v_mps,ax_mps2
+//   --start-speed V  with --best K --mode mintime --trajectory-dt DT: also the winners' ticks from
+//               sample 0 at speed V along the reachable speed profile (rl_rejoin), in
+//               <base>_trajectory_<r>_from_v0.csv (the same columns), and the standing-start lap
 //   --score lap with --best K --mode mincurv: rank the min-curvature racelines by their lap
 //               time (the lap stage, rl_optimize_best_scored); the lap_time_s column of
 //               <base>_batch_summary.csv then holds every seed's lap
@@ -1193,7 +1196,7 @@ static void compute_mintime_and_save(const string& base, const vector<Vec2>& cen
 // B α-seeds in one launch (beyond the reference): one summary row per instance.
 static void batch_and_save(const string& base, const vector<Vec2>& center, double L, bool closed,
                            const vector<Vec2>& inner_from_mids, const vector<Vec2>& outer_from_mids, int B, int modes,
-                           int repeat, int best, bool score_lap, double traj_dt, int traj_cap) {
+                           int repeat, int best, bool score_lap, double traj_dt, int traj_cap, double start_speed) {
     auto& C = cfg::get();
     SegVec innerE = closed ? edges::ringEdges(inner_from_mids) : edges::polylineEdges(inner_from_mids);
     SegVec outerE = closed ? edges::ringEdges(outer_from_mids) : edges::polylineEdges(outer_from_mids);
@@ -1255,6 +1258,10 @@ static void batch_and_save(const string& base, const vector<Vec2>& center, doubl
     vector<double> tcol[7];
     for (auto& col : tcol) col.resize(RM);
     vector<int32_t> tcount(want_traj ? idx.size() : 0);
+    // --start-speed: the rejoin stage needs the winners' whole rows and the laps T
+    const bool want_rjn = want_traj && start_speed >= 0.0;
+    vector<double> wrow[4], tT(want_rjn ? idx.size() : 0);       // heading, kappa, v, ax
+    for (auto& col : wrow) col.resize(want_rjn ? idx.size() * N : 0);
     auto run_best = [&]() {
         rl_select sel;
         std::memset(&sel, 0, sizeof(sel));
@@ -1271,6 +1278,10 @@ static void batch_and_save(const string& base, const vector<Vec2>& center, doubl
             tj.s = tcol[0].data(); tj.x = tcol[1].data(); tj.y = tcol[2].data(); tj.heading = tcol[3].data();
             tj.kappa = tcol[4].data(); tj.v = tcol[5].data(); tj.ax = tcol[6].data();
             tj.count = tcount.data();
+            if (want_rjn) {
+                ob.heading = wrow[0].data(); ob.kappa = wrow[1].data(); ob.v = wrow[2].data(); ob.ax = wrow[3].data();
+                tj.T = tT.data();
+            }
             gpu::check(rl_optimize_best_trajectory(&pk.prob, &c, 1, seeds.data(), B, &sel,
                                                    score_lap ? RL_SCORE_LAP : RL_SCORE_DEFAULT, idx.data(), sc.data(),
                                                    score_lap ? lap.data() : nullptr, &ob, traj_dt, traj_cap, &tj),
@@ -1317,6 +1328,51 @@ static void batch_and_save(const string& base, const vector<Vec2>& center, doubl
         if (!o) throw std::runtime_error("save trajectory failed");
         o.f << "t,s,x,y,heading_rad,curvature,v_mps,ax_mps2\n";
         o.f.write(text.data(), (std::streamsize)len);
+    }
+    // <base>_trajectory_<r>_from_v0.csv: winner r from sample 0 at --start-speed, along the speed
+    // profile it can reach with the limits of this run's cfg, until that meets the raceline's own
+    if (want_rjn) {
+        const size_t K = idx.size();
+        vector<double> pose(2 * K), v0(K, start_speed), h(K, L / (double)N), rcol[7], tloss(K);
+        vector<int32_t> row(K), hint(K, 0), rcount(K), merge(K);
+        for (size_t r = 0; r < K; ++r) {
+            pose[2 * r] = bx[r * N];
+            pose[2 * r + 1] = by[r * N];
+            row[r] = (int32_t)r;
+        }
+        for (auto& col : rcol) col.resize(K * (size_t)traj_cap);
+        rl_rjn_query q;
+        std::memset(&q, 0, sizeof(q));
+        q.pose_xy = pose.data(); q.row = row.data(); q.seg_hint = hint.data();
+        q.Q = (int32_t)K; q.window = 0; q.M_cap = traj_cap; q.dt = traj_dt;
+        q.v0 = v0.data(); q.cfg = &c; q.K_cap = RL_RJN_MAX_NODES;
+        rl_rjn rj;
+        std::memset(&rj, 0, sizeof(rj));
+        rj.s = rcol[0].data(); rj.x = rcol[1].data(); rj.y = rcol[2].data(); rj.heading = rcol[3].data();
+        rj.kappa = rcol[4].data(); rj.v = rcol[5].data(); rj.ax = rcol[6].data();
+        rj.count = rcount.data(); rj.merge_node = merge.data(); rj.t_loss = tloss.data();
+        gpu::check(rl_rejoin(bx.data(), by.data(), wrow[0].data(), wrow[1].data(), wrow[2].data(), wrow[3].data(), h.data(),
+                             (int32_t)N, (int32_t)K, closed ? 1 : 0, &q, gpu::device, &rj),
+                   "rl_rejoin");
+        std::cerr << std::setprecision(9);
+        for (size_t r = 0; r < K; ++r) {
+            const int64_t rows = rcount[r];
+            vector<double> tab((size_t)rows * 8);
+            for (int64_t m = 0; m < rows; ++m) {
+                tab[(size_t)m * 8] = (double)m * traj_dt;
+                for (int cc = 0; cc < 7; ++cc) tab[(size_t)m * 8 + 1 + cc] = rcol[cc][r * (size_t)traj_cap + (size_t)m];
+            }
+            vector<char> text((size_t)rows * 8 * 22 + 1);
+            int64_t len = 0;
+            gpu::check(rl_format_csv(tab.data(), rows, 8, gpu::device, text.data(), (int64_t)text.size(), &len, nullptr),
+                       "rl_format_csv");
+            io::Csv o(base + "_trajectory_" + std::to_string(r) + "_from_v0.csv");
+            if (!o) throw std::runtime_error("save rejoin trajectory failed");
+            o.f << "t,s,x,y,heading_rad,curvature,v_mps,ax_mps2\n";
+            o.f.write(text.data(), (std::streamsize)len);
+            std::cerr << "[rejoin] winner " << r << " from " << start_speed << " m/s: merge node " << merge[r]
+                      << ", standing-start lap " << tT[r] + tloss[r] << " s (flying " << tT[r] << " s)\n";
+        }
     }
     std::cerr << "[best] " << (mt || score_lap ? "lap_time_s" : "curvature_score") << " of the " << best << " best of B=" << B << ":";
     std::cerr << std::setprecision(9);
@@ -1413,7 +1469,7 @@ int run_pipeline(const string& innerPath, const string& outerPath, const string&
 
 // Steps 7-8 from the reference's step-6 files.
 int run_from_centerline(const string& outPath, double L, double s0, const string& mode, int B, int repeat, int best,
-                        const string& score, double traj_dt, int traj_cap) {
+                        const string& score, double traj_dt, int traj_cap, double start_speed) {
     auto& C = cfg::get();
     const string base = io::dropExt(outPath);
     const bool closed_mode = C.is_closed_track;
@@ -1451,6 +1507,20 @@ int run_from_centerline(const string& outPath, double L, double s0, const string
             return 2;
         }
     }
+    if (!std::isnan(start_speed)) {
+        // (the winners' whole rows come down with a min-time selection; a min-curvature one has
+        // its heading and curvature in the lap stage, which the one-shot call does not download)
+        if (!(traj_dt > 0.0) || mode != "mintime") {
+            std::cerr << "[ERR] --start-speed needs --seeds B --best K --mode mintime --trajectory-dt DT\n";
+            return 2;
+        }
+        if (!std::isfinite(start_speed) || start_speed < 0.0) {
+            std::cerr << "[ERR] --start-speed V: finite and >= 0\n";
+            return 2;
+        }
+    } else {
+        start_speed = -1.0;
+    }
     if (B > 0) {
         const int modes = mode == "mincurv" ? RL_MODE_MINCURV
                                             : mode == "mintime" ? RL_MODE_MINTIME : RL_MODE_MINCURV | RL_MODE_MINTIME;
@@ -1463,7 +1533,7 @@ int run_from_centerline(const string& outPath, double L, double s0, const string
             return 2;
         }
         pipeline::batch_and_save(base, center_for_opt, L, closed_mode, inner, outer, B, modes, repeat, best,
-                                 score == "lap", traj_dt, traj_cap);
+                                 score == "lap", traj_dt, traj_cap, start_speed);
         return 0;
     }
     auto t0 = Clock::now();
@@ -1485,7 +1555,7 @@ int main(int argc, char** argv) {
     string mode = "both", stop_after;
     int B = 0, repeat = 0, best = 0;
     string score;
-    double traj_dt = 0.0;
+    double traj_dt = 0.0, start_speed = NAN;
     int traj_cap = 0;
     try {
         for (int i = 1; i < argc; ++i) {
@@ -1504,6 +1574,7 @@ int main(int argc, char** argv) {
             else if (a == "--best") best = std::stoi(next());
             else if (a == "--score") score = next();
             else if (a == "--trajectory-dt") traj_dt = std::stod(next());
+            else if (a == "--start-speed") start_speed = std::stod(next());
             else if (a == "--trajectory-cap") traj_cap = std::stoi(next());
             else if (a == "--device") gpu::device = std::stoi(next());
             else if (a == "--devices") {
@@ -1523,11 +1594,12 @@ int main(int argc, char** argv) {
                       << "       " << argv[0]
                       << " centerline.csv [--L v] [--s0 v] [--open] [--mode m] [--seeds B] [--repeat R] [--best K]\n"
                       << "         [--score lap]   with --best K --mode mincurv: rank by the lap stage's lap time\n"
-                      << "         [--trajectory-dt DT [--trajectory-cap M]]   with --best K: the winners at ticks of DT s\n";
+                      << "         [--trajectory-dt DT [--trajectory-cap M]]   with --best K: the winners at ticks of DT s\n"
+                      << "         [--start-speed V]   with --mode mintime --trajectory-dt: the winners from sample 0 at V m/s\n";
             return 1;
         }
         if (pos.size() == 3) return run_pipeline(pos[0], pos[1], pos[2], mode, stop_after == "centerline");
-        return run_from_centerline(pos[0], L, s0, mode, B, repeat, best, score, traj_dt, traj_cap);
+        return run_from_centerline(pos[0], L, s0, mode, B, repeat, best, score, traj_dt, traj_cap, start_speed);
     } catch (const std::exception& e) {
         std::cerr << "[ERR] " << e.what() << "\n";
         return 3;

@@ -31,6 +31,7 @@ calls raise :class:`RacelineError` (RL_ENODEV): there is no CPU fallback.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from dataclasses import dataclass
 from typing import Optional, Sequence
@@ -500,6 +501,80 @@ def _hzn_c(P, rw, hint, window, dt, m_cap) -> abi.RlHznQuery:
                           int(m_cap), 0, float(dt))
 
 
+def _hzn_stamps(rows, hs, stamps):
+    """The stamps [B, N + 1] of the rows: trajectory_host's, unless given (a plan's, as fetched)."""
+    B, N = rows[0].shape
+    if stamps is None:
+        with np.errstate(all="ignore"):
+            inc = hs[:, None] / np.where(1e-6 < rows[4], rows[4], 1e-6)
+            return np.cumsum(np.concatenate((np.zeros((B, 1)), inc), axis=1), axis=1)
+    stamps = np.ascontiguousarray(stamps, dtype=np.float64).reshape(-1, N + 1)
+    if stamps.shape[0] != B:
+        raise ValueError(f"horizon: stamps must be [B={B}, N + 1], got {stamps.shape}")
+    return stamps
+
+
+def _hzn_locate(X, Y, t, hb, px, py, g: int, W: int, closed: bool):
+    """The horizon stage's candidates, distance, winner and location of one pose on one row:
+    (seg, u, dist2, e, t0, s0), or None for a NaN winner."""
+    N = X.shape[0]
+    S = N if closed else N - 1
+    if g < 0 or (closed and 2 * W + 1 >= S):
+        cand = np.arange(S)
+    elif closed:
+        cand = (g + np.arange(-W, W + 1)) % S
+    else:
+        cand = np.arange(max(0, g - W), min(S - 1, g + W) + 1)
+    with np.errstate(all="ignore"):
+        i = cand
+        j = (i + 1) % N
+        dx, dy, wx, wy = X[j] - X[i], Y[j] - Y[i], px - X[i], py - Y[i]
+        dd = dx * dx + dy * dy
+        c = wx * dx + wy * dy
+        ratio = c / dd
+        lo = np.where(0.0 < ratio, ratio, 0.0)                  # smax(0.0, c/dd)
+        u = np.where(dd > 0.0, np.where(lo < 1.0, lo, 1.0), 0.0)  # smin(1.0, .)
+        rx, ry = wx - u * dx, wy - u * dy
+        D = rx * rx + ry * ry
+        nan = np.isnan(D)
+        win = np.lexsort((i, np.where(nan, 0.0, D), nan))[0]    # least (isnan(D), D, i)
+        if nan[win]:
+            return None
+        i0, u0, D0 = int(i[win]), u[win], D[win]
+        root = np.sqrt(D0)
+        t0 = t[i0] + u0 * (t[i0 + 1] - t[i0])
+        e = -root if dx[win] * wy[win] - dy[win] * wx[win] < 0.0 else root
+        return i0, u0, D0, e, t0, (np.float64(i0) + u0) * hb
+
+
+def _hzn_wrap(tau, T, closed: bool):
+    """(lap, w): the horizon stage's wrap count and row time of the tick times tau."""
+    if not closed:
+        return np.zeros(tau.shape[0]), tau
+    with np.errstate(all="ignore"):
+        lap = np.floor(tau / T)
+        w = tau - lap * T
+        neg = w < 0.0
+        over = ~neg & (w >= T)
+        return (np.where(neg, lap - 1.0, np.where(over, lap + 1.0, lap)),
+                np.where(neg, w + T, np.where(over, w - T, w)))
+
+
+def _hzn_columns(row6, t, hb, closed: bool, lap, w) -> tuple:
+    """The horizon stage's seven columns (TRAJ_COLS' order) at the row times w in the laps lap."""
+    X, Y, PSI, K, V, A = row6
+    N = X.shape[0]
+    S = N if closed else N - 1
+    with np.errstate(all="ignore"):
+        i = np.clip(np.searchsorted(t[:S + 1], w, side="right") - 1, 0, S - 1)
+        j = (i + 1) % N
+        um = (w - t[i]) / (t[i + 1] - t[i])
+        d = PSI[j] - PSI[i]
+        d = np.where(d > np.pi, d - 2.0 * np.pi, np.where(d < -np.pi, d + 2.0 * np.pi, d))
+        return (((lap * np.float64(S) + i.astype(np.float64)) + um) * hb, X[i] + um * (X[j] - X[i]),
+                Y[i] + um * (Y[j] - Y[i]), PSI[i] + um * d, K[i] + um * (K[j] - K[i]), V[i] + um * (V[j] - V[i]), A[i])
+
+
 def horizon_host(x, y, heading, kappa, v, ax, h, closed: bool, poses, row=None, seg_hint=None, window: int = 0,
                  dt: float = 0.05, m_cap: int = 64, stamps=None) -> Horizon:
     """The specification of the horizon stage (include/rl_abi.h) in NumPy; the kernel
@@ -522,78 +597,32 @@ def horizon_host(x, y, heading, kappa, v, ax, h, closed: bool, poses, row=None, 
         raise ValueError(f"horizon: row outside [0, {B})")
     if np.any(hint < -1) or np.any(hint >= S):
         raise ValueError(f"horizon: seg_hint outside [-1, {S})")
-    with np.errstate(all="ignore"):
-        if stamps is None:
-            inc = hs[:, None] / np.where(1e-6 < rows[4], rows[4], 1e-6)
-            stamps = np.cumsum(np.concatenate((np.zeros((B, 1)), inc), axis=1), axis=1)
-        else:
-            stamps = np.ascontiguousarray(stamps, dtype=np.float64).reshape(-1, N + 1)
-            if stamps.shape[0] != B:
-                raise ValueError(f"horizon: stamps must be [B={B}, N + 1], got {stamps.shape}")
+    stamps = _hzn_stamps(rows, hs, stamps)
     out = Horizon.alloc(Q, m_cap, dt)
     out.seg[:] = -1
     steps = np.arange(m_cap, dtype=np.float64)
-    fS = np.float64(S)
     for k in range(Q):
         if S < 1:
             continue
-        X, Y, PSI, K, V, A = (a[rw[k]] for a in rows)
-        t, hb, px, py, g = stamps[rw[k]], hs[rw[k]], P[k, 0], P[k, 1], int(hint[k])
+        row6 = [a[rw[k]] for a in rows]
+        t, hb = stamps[rw[k]], hs[rw[k]]
         T = t[S]
-        if g < 0 or (closed and 2 * W + 1 >= S):
-            cand = np.arange(S)
-        elif closed:
-            cand = (g + np.arange(-W, W + 1)) % S
-        else:
-            cand = np.arange(max(0, g - W), min(S - 1, g + W) + 1)
+        loc = _hzn_locate(row6[0], row6[1], t, hb, P[k, 0], P[k, 1], int(hint[k]), W, closed)
+        if loc is None:
+            continue
+        out.seg[k], out.u[k], out.dist2[k], out.e[k], out.t0[k], out.s0[k] = loc
         with np.errstate(all="ignore"):
-            i = cand
-            j = (i + 1) % N
-            dx, dy, wx, wy = X[j] - X[i], Y[j] - Y[i], px - X[i], py - Y[i]
-            dd = dx * dx + dy * dy
-            c = wx * dx + wy * dy
-            ratio = c / dd
-            lo = np.where(0.0 < ratio, ratio, 0.0)                  # smax(0.0, c/dd)
-            u = np.where(dd > 0.0, np.where(lo < 1.0, lo, 1.0), 0.0)  # smin(1.0, .)
-            rx, ry = wx - u * dx, wy - u * dy
-            D = rx * rx + ry * ry
-            nan = np.isnan(D)
-            win = np.lexsort((i, np.where(nan, 0.0, D), nan))[0]    # least (isnan(D), D, i)
-            if nan[win]:
-                continue
-            i0, u0, D0 = int(i[win]), u[win], D[win]
-            root = np.sqrt(D0)
-            t0 = t[i0] + u0 * (t[i0 + 1] - t[i0])
-            out.seg[k], out.u[k], out.dist2[k], out.t0[k] = i0, u0, D0, t0
-            out.e[k] = -root if dx[win] * wy[win] - dy[win] * wx[win] < 0.0 else root
-            out.s0[k] = (np.float64(i0) + u0) * hb
-            tau = t0 + steps * dt
+            tau = out.t0[k] + steps * dt
+            lap, w = _hzn_wrap(tau, T, closed)
             if closed:
                 M = m_cap if np.isfinite(T) and T > 0.0 else 0
-                lap = np.floor(tau / T)
-                w = tau - lap * T
-                neg = w < 0.0
-                over = ~neg & (w >= T)
-                w, lap = np.where(neg, w + T, np.where(over, w - T, w)), np.where(neg, lap - 1.0, np.where(over, lap + 1.0, lap))
             else:
                 M = int(np.count_nonzero(tau < T))                  # (monotone in m: the kernel bisects)
-                lap, w = np.zeros(m_cap), tau
             out.count[k] = M
             if M == 0:
                 continue
-            w, lap = w[:M], lap[:M]
-            i = np.clip(np.searchsorted(t[:S + 1], w, side="right") - 1, 0, S - 1)
-            j = (i + 1) % N
-            um = (w - t[i]) / (t[i + 1] - t[i])
-            d = PSI[j] - PSI[i]
-            d = np.where(d > np.pi, d - 2.0 * np.pi, np.where(d < -np.pi, d + 2.0 * np.pi, d))
-            out.s[k, :M] = ((lap * fS + i.astype(np.float64)) + um) * hb
-            out.x[k, :M] = X[i] + um * (X[j] - X[i])
-            out.y[k, :M] = Y[i] + um * (Y[j] - Y[i])
-            out.heading[k, :M] = PSI[i] + um * d
-            out.kappa[k, :M] = K[i] + um * (K[j] - K[i])
-            out.v[k, :M] = V[i] + um * (V[j] - V[i])
-            out.ax[k, :M] = A[i]
+            for n, col in zip(abi.TRAJ_COLS, _hzn_columns(row6, t, hb, closed, lap[:M], w[:M])):
+                getattr(out, n)[k, :M] = col
     return out
 
 
@@ -610,6 +639,263 @@ def horizon(x, y, heading, kappa, v, ax, h, closed: bool, poses, row=None, seg_h
     qc, oc = _hzn_c(P, rw, hint, window, dt, m_cap), out.as_c()
     _check(_lib().rl_horizon(*[_ptr(a, np.float64, "row") for a in rows], _ptr(hs, np.float64, "h"), N, B,
                              1 if closed else 0, C.byref(qc), int(device), C.byref(oc)))
+    return out
+
+
+# ------------------------------------------------- rejoin: a reachable profile from the car's speed
+@dataclass
+class Rejoin(Horizon):
+    """The rejoin stage's answer for Q poses (rl_rjn): Horizon's fields, with the ticks counted
+    from the car (t = m * dt) along the reachable speed profile, and merge_node (the march node
+    at which the profile meets the row's, -1: not within k_cap nodes or the row's end),
+    overspeed (nodes at which the car is faster than the row), t_merge (the time marched),
+    t_loss (the time lost against the row's own schedule, NaN when not merged) [Q]; node_v,
+    node_t [Q, k_cap + 1]: the march's speeds and times, the entries after node_end(q)
+    unspecified."""
+
+    merge_node: np.ndarray = None
+    overspeed: np.ndarray = None
+    t_merge: np.ndarray = None
+    t_loss: np.ndarray = None
+    node_v: np.ndarray = None
+    node_t: np.ndarray = None
+    k_lim: np.ndarray = None      # [Q] nodes the march may take (host side: from seg, N and closed)
+
+    @classmethod
+    def alloc(cls, Q: int, m_cap: int, dt: float, k_cap: int = 1) -> "Rejoin":
+        cols = {n: np.zeros((Q, m_cap)) for n in abi.TRAJ_COLS}
+        per = {n: np.zeros(Q) for n in abi.HZN_LOC + abi.RJN_SCAL}
+        ints = {n: np.zeros(Q, dtype=np.int32) for n in abi.RJN_INTS}
+        nodes = {n: np.zeros((Q, k_cap + 1)) for n in abi.RJN_NODES}
+        return cls(**cols, **per, **ints, **nodes, k_lim=np.zeros(Q, dtype=np.int32), dt=float(dt))
+
+    def as_c(self) -> abi.RlRjn:
+        t = abi.RlRjn()
+        for n in abi.TRAJ_COLS + abi.HZN_LOC + abi.RJN_SCAL + abi.RJN_NODES:
+            setattr(t, n, _ptr(getattr(self, n), np.float64, n))
+        for n in abi.RJN_INTS:
+            setattr(t, n, _ptr(getattr(self, n), np.int32, n))
+        return t
+
+    def set_k_lim(self, N: int, closed: bool) -> None:
+        room = np.full(self.seg.shape, N) if closed else N - 1 - self.seg
+        self.k_lim = np.where(self.seg >= 0, np.minimum(self.node_v.shape[1] - 1, room), 0).astype(np.int32)
+
+    def node_end(self, q: int) -> int:
+        """K_end: the last march node of query q (the merge node, or the last node marched)."""
+        return int(self.merge_node[q]) if self.merge_node[q] >= 0 else int(self.k_lim[q])
+
+    def row(self, q: int) -> dict:
+        """The ticks of query q: t [count[q]] = m * dt, from the car, and the seven columns."""
+        m = int(self.count[q])
+        out = {"t": np.arange(m, dtype=np.float64) * self.dt}
+        for n in abi.TRAJ_COLS:
+            out[n] = getattr(self, n)[q, :m]
+        return out
+
+
+def _rjn_query(poses, v0, cfg, row, seg_hint, window, dt, m_cap, k_cap) -> tuple:
+    P, rw, hint = _hzn_query(poses, row, seg_hint, window, dt, m_cap)
+    Q = P.shape[0]
+    V0 = np.asarray(v0, dtype=np.float64)
+    if V0.ndim == 0:
+        V0 = np.broadcast_to(V0, (Q,))
+    if V0.shape != (Q,):
+        raise ValueError(f"rejoin: v0 must be a number or [Q={Q}] numbers, got shape {V0.shape}")
+    V0 = np.ascontiguousarray(V0)
+    if not np.all(np.isfinite(V0)) or np.any(V0 < 0.0):
+        raise ValueError("rejoin: v0 must be finite and >= 0")
+    if not isinstance(cfg, RlCfg):
+        raise ValueError("rejoin: cfg must be one RlCfg (the car's limits now)")
+    if int(k_cap) != k_cap or not 1 <= int(k_cap) <= abi.RL_RJN_MAX_NODES:
+        raise ValueError(f"rejoin: k_cap must be 1..{abi.RL_RJN_MAX_NODES}, got {k_cap}")
+    return P, rw, hint, V0
+
+
+def _rjn_c(P, rw, hint, V0, cfg, window, dt, m_cap, k_cap) -> abi.RlRjnQuery:
+    return abi.RlRjnQuery(_ptr(P, np.float64, "poses"), None if rw is None else _ptr(rw, np.int32, "row"),
+                          None if hint is None else _ptr(hint, np.int32, "seg_hint"), P.shape[0], int(window),
+                          int(m_cap), 0, float(dt), _ptr(V0, np.float64, "v0"), C.pointer(cfg), int(k_cap), 0)
+
+
+def _smax(a: float, b: float) -> float:
+    return b if a < b else a
+
+
+def _smin(a: float, b: float) -> float:
+    return b if b < a else a
+
+
+def _fdiv(a: float, b: float) -> float:
+    """IEEE a / b (Python raises on a zero divisor)."""
+    with np.errstate(all="ignore"):
+        return float(np.float64(a) / np.float64(b))
+
+
+def _ax_max_at(c: tuple, vi: float, ki: float) -> tuple:
+    """(a_acc, a_brk): the reference's ax_max_at (ref:797-824) with its constant prefixes c."""
+    a_total2, kFd, Fr, mass, Pmax, acc_cap, brk_cap = c
+    alat = vi * vi * abs(ki)
+    a_res = math.sqrt(_smax(0.0, a_total2 - alat * alat))
+    Fd = kFd * vi * vi
+    a_power = (_fdiv(Pmax, mass * vi) - _fdiv(Fd + Fr, mass)) if (Pmax > 0 and vi > 1e-6) else 1e9
+    a_acc = _smax(0.0, _smin(_smin(a_res, acc_cap), a_power))
+    a_brk = _smax(0.0, _smin(a_res, brk_cap) + _fdiv(Fd + Fr, mass))
+    return a_acc, a_brk
+
+
+def _rjn_consts(cfg: RlCfg) -> tuple:
+    a_total = _smax(cfg.a_total_max, cfg.a_lat_max) if cfg.use_total_ge_lat else cfg.a_total_max
+    return (a_total * a_total, 0.5 * cfg.rho_air * cfg.Cd * cfg.A_front_m2, cfg.mass_kg * 9.81 * cfg.c_rr,
+            cfg.mass_kg, cfg.P_max_W, cfg.a_long_acc_cap, cfg.a_long_brake_cap)
+
+
+def _bisect_nodes(tt: np.ndarray, tau: np.ndarray, hi: int) -> np.ndarray:
+    """The kernel's bisection for every tau: a = 0, e = hi; while e - a > 1: mid = a + (e - a) // 2;
+    tt[mid] <= tau ? a = mid : e = mid."""
+    a = np.zeros(tau.shape[0], dtype=np.int64)
+    e = np.full(tau.shape[0], hi, dtype=np.int64)
+    while np.any(e - a > 1):
+        go = e - a > 1
+        mid = a + ((e - a) >> 1)
+        le = tt[mid] <= tau
+        a = np.where(go & le, mid, a)
+        e = np.where(go & ~le, mid, e)
+    return a
+
+
+def rejoin_host(x, y, heading, kappa, v, ax, h, closed: bool, poses, v0, cfg: RlCfg, row=None, seg_hint=None,
+                window: int = 0, dt: float = 0.05, m_cap: int = 64, k_cap: int = 1024, stamps=None) -> Rejoin:
+    """The specification of the rejoin stage (include/rl_abi.h) in NumPy; the kernel
+    equals it bit for bit.  The rows, poses, hints and stamps are horizon_host's, and so is the
+    locate.  v0 (a number or [Q]) is the car's speed and cfg its limits now.  From the located
+    point the reachable speed nearest the row's is marched node by node (the samples ahead, at
+    most k_cap) until it equals the row's; the ticks m * dt, counted from the car, follow the
+    marched profile and then the row's own from the merge on."""
+    rows, hs = _traj_rows(x, y, heading, kappa, v, ax, h)
+    P, rw, hint, V0 = _rjn_query(poses, v0, cfg, row, seg_hint, window, dt, m_cap, k_cap)
+    B, N = rows[0].shape
+    if N < 1:
+        raise ValueError("rejoin: N == 0 (no row)")
+    Q, closed, dt, m_cap, W, k_cap = P.shape[0], bool(closed), float(dt), int(m_cap), int(window), int(k_cap)
+    S = N if closed else N - 1
+    rw = np.zeros(Q, dtype=np.int32) if rw is None else rw
+    hint = np.full(Q, -1, dtype=np.int32) if hint is None else hint
+    if np.any(rw < 0) or np.any(rw >= B):
+        raise ValueError(f"rejoin: row outside [0, {B})")
+    if np.any(hint < -1) or np.any(hint >= S):
+        raise ValueError(f"rejoin: seg_hint outside [-1, {S})")
+    stamps = _hzn_stamps(rows, hs, stamps)
+    consts = _rjn_consts(cfg)
+    out = Rejoin.alloc(Q, m_cap, dt, k_cap)
+    out.seg[:] = -1
+    out.merge_node[:] = -1
+    tau_all = np.arange(m_cap, dtype=np.float64) * dt
+    for q in range(Q):
+        if S < 1:
+            continue
+        row6 = [a[rw[q]] for a in rows]
+        X, Y, PSI, KAP, V, _ = row6
+        t, hb = stamps[rw[q]], float(hs[rw[q]])
+        T = t[S]
+        loc = _hzn_locate(X, Y, t, hb, P[q, 0], P[q, 1], int(hint[q]), W, closed)
+        if loc is None:
+            continue
+        out.seg[q], out.u[q], out.dist2[q], out.e[q], out.t0[q], out.s0[q] = loc
+        i0, u, t0 = int(loc[0]), float(loc[1]), float(loc[4])
+        j0 = (i0 + 1) % N
+        K_lim = min(k_cap, N if closed else N - 1 - i0)
+        out.k_lim[q] = K_lim
+        n = i0 + np.arange(K_lim + 1)                       # the nodes' samples, unwrapped
+        idx = n % N
+        with np.errstate(all="ignore"):
+            kap = KAP[idx].copy()
+            r = V[idx].copy()
+            kap[0] = KAP[i0] + u * (KAP[j0] - KAP[i0])
+            r[0] = V[i0] + u * (V[j0] - V[i0])
+            d0 = (1.0 - u) * hb
+        kl, rl_, w, tt = kap.tolist(), r.tolist(), [float(V0[q])], [0.0]
+        ks, over = -1, 0
+        if w[0] == rl_[0]:
+            ks = 0
+        else:
+            over += w[0] > rl_[0]
+            for k in range(K_lim):
+                d, wk = (d0 if k == 0 else hb), w[k]
+                a_acc, a_brk = _ax_max_at(consts, wk, kl[k])
+                up = math.sqrt(_smax(0.0, wk * wk + (2.0 * a_acc) * d))
+                dn = math.sqrt(_smax(0.0, wk * wk - (2.0 * a_brk) * d))
+                wn = _smin(up, _smax(dn, rl_[k + 1]))
+                w.append(wn)
+                tt.append(tt[k] + _fdiv(2.0 * d, _smax(1e-6, wk + wn)))
+                if wn == rl_[k + 1]:
+                    ks = k + 1
+                    break
+                over += wn > rl_[k + 1]
+        kend = ks if ks >= 0 else K_lim
+        w, tt = np.array(w), np.array(tt)
+        out.node_v[q, :kend + 1], out.node_t[q, :kend + 1] = w, tt
+        tte = tt[kend]
+        nk = i0 + max(ks, 0)
+        c0 = nk // N
+        tref = t0 if ks == 0 else t[nk - c0 * N]
+        out.merge_node[q], out.overspeed[q], out.t_merge[q] = ks, over, tte
+        with np.errstate(all="ignore"):
+            out.t_loss[q] = tte - ((np.float64(c0) * T + tref) - t0) if ks >= 0 else np.nan
+            M1 = int(np.count_nonzero(tau_all < tte))           # (monotone in m: the kernel bisects)
+            wref = tref + (tau_all - tte)
+            if ks < 0:
+                M = M1
+            elif closed:
+                M = m_cap if np.isfinite(T) and T > 0.0 else M1
+            else:
+                M = M1 + int(np.count_nonzero(wref[M1:] < T))
+            out.count[q] = M
+            if M1 > 0:
+                tau = tau_all[:M1]
+                a = _bisect_nodes(tt, tau, kend)
+                b = a + 1
+                um = (tau - tt[a]) / (tt[b] - tt[a])
+                d = np.where(a == 0, d0, hb)
+                # the nodes' values: node 0 the located point, node k >= 1 sample n_k
+                dp0 = PSI[j0] - PSI[i0]
+                dp0 = dp0 - 2.0 * np.pi if dp0 > np.pi else (dp0 + 2.0 * np.pi if dp0 < -np.pi else dp0)
+                nx, ny, npsi = X[idx].copy(), Y[idx].copy(), PSI[idx].copy()
+                ns = n.astype(np.float64) * hb
+                nx[0] = X[i0] + u * (X[j0] - X[i0])
+                ny[0] = Y[i0] + u * (Y[j0] - Y[i0])
+                npsi[0] = PSI[i0] + u * dp0
+                ns[0] = out.s0[q]
+                dp = npsi[b] - npsi[a]
+                dp = np.where(dp > np.pi, dp - 2.0 * np.pi, np.where(dp < -np.pi, dp + 2.0 * np.pi, dp))
+                out.s[q, :M1] = ns[a] + um * (ns[b] - ns[a])
+                out.x[q, :M1] = nx[a] + um * (nx[b] - nx[a])
+                out.y[q, :M1] = ny[a] + um * (ny[b] - ny[a])
+                out.heading[q, :M1] = npsi[a] + um * dp
+                out.kappa[q, :M1] = kap[a] + um * (kap[b] - kap[a])
+                out.v[q, :M1] = w[a] + um * (w[b] - w[a])
+                out.ax[q, :M1] = np.where(d > 0.0, (w[b] * w[b] - w[a] * w[a]) / (2.0 * d), 0.0)
+            if M > M1:
+                lap, wr = _hzn_wrap(wref[M1:M], T, closed)
+                for name, col in zip(abi.TRAJ_COLS, _hzn_columns(row6, t, hb, closed, np.float64(c0) + lap, wr)):
+                    getattr(out, name)[q, M1:M] = col
+    return out
+
+
+def rejoin(x, y, heading, kappa, v, ax, h, closed: bool, poses, v0, cfg: RlCfg, row=None, seg_hint=None,
+           window: int = 0, dt: float = 0.05, m_cap: int = 64, k_cap: int = 1024, device: int = 0) -> Rejoin:
+    """rejoin_host on the GPU (rl_rejoin): the trajectory kernel stamps the B given rows, then the
+    rejoin kernel answers the Q poses; row[q] counts the given rows."""
+    rows, hs = _traj_rows(x, y, heading, kappa, v, ax, h)
+    P, rw, hint, V0 = _rjn_query(poses, v0, cfg, row, seg_hint, window, dt, m_cap, k_cap)
+    B, N = rows[0].shape
+    if N < 1:
+        raise ValueError("rejoin: N == 0 (no row)")
+    out = Rejoin.alloc(P.shape[0], int(m_cap), dt, int(k_cap))
+    qc, oc = _rjn_c(P, rw, hint, V0, cfg, window, dt, m_cap, k_cap), out.as_c()
+    _check(_lib().rl_rejoin(*[_ptr(a, np.float64, "row") for a in rows], _ptr(hs, np.float64, "h"), N, B,
+                            1 if closed else 0, C.byref(qc), int(device), C.byref(oc)))
+    out.set_k_lim(N, bool(closed))
     return out
 
 
@@ -798,6 +1084,35 @@ class Plan:
         out = Horizon.alloc(Q, m_cap, dt)
         t = out.as_c()
         _check(_lib().rl_plan_fetch_horizon(self._h, C.byref(t)))
+        return out
+
+    def rejoin(self, poses, v0, cfg: RlCfg, row=None, seg_hint=None, window: int = 0, dt: float = 0.05,
+               m_cap: int = 64, k_cap: int = 1024, stream_ptr: int = 0) -> None:
+        """Enqueue the rejoin stage after the last trajectory() (rl_plan_rejoin): horizon()'s
+        query with the car's speed v0 (a number or [Q]) and its limits now, cfg (one RlCfg, not
+        necessarily the plan's).  The ticks follow the reachable speed profile from v0 until it
+        meets the row's own, at most k_cap samples ahead.  The trajectory stage and the last
+        horizon() stay as they are."""
+        P, rw, hint, V0 = _rjn_query(poses, v0, cfg, row, seg_hint, window, dt, m_cap, k_cap)
+        self._rjn = None
+        qc = _rjn_c(P, rw, hint, V0, cfg, window, dt, m_cap, k_cap)
+        _check(_lib().rl_plan_rejoin(self._h, C.byref(qc), C.c_void_p(stream_ptr) if stream_ptr else None))
+        self._rjn = (P.shape[0], int(m_cap), float(dt), int(k_cap))
+
+    def fetch_rejoin(self, nodes: bool = True) -> Rejoin:
+        """Download the last rejoin() (rl_plan_fetch_rejoin); nodes=False leaves node_v, node_t on
+        the device."""
+        if getattr(self, "_rjn", None) is None:
+            t = abi.RlRjn()                 # (the library's own answer: no stage on this plan)
+            _check(_lib().rl_plan_fetch_rejoin(self._h, C.byref(t)))
+            raise ValueError("fetch_rejoin: no rejoin() on this plan")
+        Q, m_cap, dt, k_cap = self._rjn
+        out = Rejoin.alloc(Q, m_cap, dt, k_cap)
+        t = out.as_c()
+        if not nodes:
+            t.node_v = t.node_t = None
+        _check(_lib().rl_plan_fetch_rejoin(self._h, C.byref(t)))
+        out.set_k_lim(self.N, bool(self._keep[0].closed))
         return out
 
     def device_outputs(self, which: int) -> abi.RlOut:
