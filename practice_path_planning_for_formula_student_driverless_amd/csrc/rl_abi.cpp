@@ -6,6 +6,61 @@
 
 using namespace rl;
 
+namespace {
+
+// The B host rows in[6] (x, y, heading, kappa, v, ax: [B][N]) and their steps h [B] on the
+// device, with the outputs of a trajectory stage of M_cap ticks over them, all from `mem`:
+// *q is that launch.  fn names the entry point in the messages.
+int rows_on_device(DevArena& mem, const std::string& fn, const double* const (&in)[6], const double* h, int32_t N,
+                   int32_t B, int32_t closed, double dt, int32_t M_cap, rl::TrajParams* q) {
+    const size_t R = (size_t)B, BN = R * (size_t)N;
+    double* d_in[6];
+    for (auto& d : d_in) d = mem.get<double>(BN);
+    double* d_h = mem.get<double>(R);
+    *q = rl::TrajParams{};
+    for (auto& c : q->out) c = mem.get<double>(R * (size_t)M_cap);
+    q->stamps = mem.get<double>(R * ((size_t)N + 1));
+    q->T = mem.get<double>(R);
+    q->count = mem.get<int32_t>(R);
+    if (!mem.ok()) return fail(RL_ENOMEM, fn + ": hipMalloc failed");
+    for (int c = 0; c < 6; ++c)
+        if (BN && hipMemcpy(d_in[c], in[c], BN * 8, hipMemcpyHostToDevice) != hipSuccess) return fail(RL_EHIP, fn + ": upload");
+    if (hipMemcpy(d_h, h, R * 8, hipMemcpyHostToDevice) != hipSuccess) return fail(RL_EHIP, fn + ": upload");
+    q->x = d_in[0]; q->y = d_in[1]; q->heading = d_in[2]; q->kappa = d_in[3]; q->v = d_in[4]; q->ax = d_in[5];
+    q->h = d_h;
+    q->dt = dt;
+    q->N = N; q->B = B; q->R = B; q->closed = closed ? 1 : 0; q->M_cap = M_cap;
+    return RL_OK;
+}
+
+// rl_horizon / rl_rejoin (arguments checked, the device selected; K_cap = 0: the horizon): the
+// trajectory kernel for the stamps of the host rows (one tick per row, not downloaded), then the
+// stage's kernel on them; `row` counts the B given rows
+int query_rows(const std::string& fn, const double* const (&in)[6], const double* h, int32_t N, int32_t B, int32_t closed,
+               const rl_rjn_query& q, const rl_rjn& out) {
+    DevArena mem;
+    rl::TrajParams t;
+    if (int rc = rows_on_device(mem, fn, in, h, N, B, closed, q.dt, 1, &t)) return rc;
+    const QueryLayout L = query_layout(q);
+    char* d_qry = mem.get<char>(L.in_bytes);
+    char* d_res = mem.get<char>(L.out_bytes);
+    if (!mem.ok()) return fail(RL_ENOMEM, fn + ": hipMalloc failed");
+    std::vector<char> block(std::max(L.in_bytes, L.out_bytes));
+    query_pack(q, L, block.data());
+    if (hipMemcpy(d_qry, block.data(), L.in_bytes, hipMemcpyHostToDevice) != hipSuccess) return fail(RL_EHIP, fn + ": upload");
+    if (rl::launch_trajectory(t, nullptr) != hipSuccess) return fail(RL_EHIP, fn + ": trajectory kernel");
+    const rl::RjnParams r = query_params(t, q, L, d_qry, d_res);
+    if ((q.K_cap > 0 ? rl::launch_rejoin(r, nullptr) : rl::launch_horizon(r.hz, nullptr)) != hipSuccess ||
+        hipDeviceSynchronize() != hipSuccess)
+        return fail(RL_EHIP, fn + ": kernel");
+    if (hipMemcpy(block.data(), d_res, out.node_v || out.node_t ? L.out_bytes : L.head_bytes, hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(RL_EHIP, fn + ": download");
+    query_unpack(block.data(), L, out);
+    return RL_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 const char* rl_last_error(void) { return g_err.c_str(); }
@@ -290,28 +345,12 @@ int rl_trajectory(const double* x, const double* y, const double* heading, const
     if (int rc = check_traj(dt, M_cap)) return rc;
     if (N > rl::RL_STREAM_MAX_N) return fail(RL_ETOOBIG, "rl_trajectory: N exceeds 1048576");
     if (int rc = select_device(device)) return rc;
-    const size_t BN = (size_t)B * (size_t)N, BM = (size_t)B * (size_t)M_cap;
     DevArena mem;
-    const double* in[6] = {x, y, heading, kappa, v, ax};
-    double* d_in[6];
-    for (auto& d : d_in) d = mem.get<double>(BN);
-    double* d_h = mem.get<double>((size_t)B);
-    rl::TrajParams q{};
-    for (auto& c : q.out) c = mem.get<double>(BM);
-    q.stamps = mem.get<double>((size_t)B * ((size_t)N + 1));
-    q.T = mem.get<double>((size_t)B);
-    q.count = mem.get<int32_t>((size_t)B);
-    if (!mem.ok()) return fail(RL_ENOMEM, "rl_trajectory: hipMalloc failed");
-    for (int c = 0; c < 6; ++c)
-        if (BN && hipMemcpy(d_in[c], in[c], BN * 8, hipMemcpyHostToDevice) != hipSuccess)
-            return fail(RL_EHIP, "rl_trajectory: upload");
-    if (hipMemcpy(d_h, h, (size_t)B * 8, hipMemcpyHostToDevice) != hipSuccess) return fail(RL_EHIP, "rl_trajectory: upload");
-    q.x = d_in[0]; q.y = d_in[1]; q.heading = d_in[2]; q.kappa = d_in[3]; q.v = d_in[4]; q.ax = d_in[5];
-    q.h = d_h;
-    q.dt = dt;
-    q.N = N; q.B = B; q.R = B; q.closed = closed ? 1 : 0; q.M_cap = M_cap;
+    rl::TrajParams q;
+    if (int rc = rows_on_device(mem, "rl_trajectory", {x, y, heading, kappa, v, ax}, h, N, B, closed, dt, M_cap, &q)) return rc;
     if (rl::launch_trajectory(q, nullptr) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
         return fail(RL_EHIP, "rl_trajectory: kernel");
+    const size_t BM = (size_t)B * (size_t)M_cap;
     double* const dst[rl::TRAJ_COLS] = {out->s, out->x, out->y, out->heading, out->kappa, out->v, out->ax};
     std::vector<CopyJob> jobs;
     for (int c = 0; c < rl::TRAJ_COLS; ++c) add_job(jobs, dst[c], q.out[c], BM * 8);
@@ -324,8 +363,6 @@ int rl_trajectory(const double* x, const double* y, const double* heading, const
     return RL_OK;
 }
 
-// the trajectory kernel for the stamps of host rows (one tick per row, not downloaded), then the
-// horizon kernel on them (rl_horizon.hip): `row` counts the B given rows
 int rl_horizon(const double* x, const double* y, const double* heading, const double* kappa, const double* v,
                const double* ax, const double* h, int32_t N, int32_t B, int32_t closed, const rl_hzn_query* query,
                int32_t device, rl_hzn* out) {
@@ -335,42 +372,9 @@ int rl_horizon(const double* x, const double* y, const double* heading, const do
     if (N > rl::RL_STREAM_MAX_N) return fail(RL_ETOOBIG, "rl_horizon: N exceeds 1048576");
     if (int rc = check_hzn(query, B, N, closed ? 1 : 0)) return rc;
     if (int rc = select_device(device)) return rc;
-    const size_t BN = (size_t)B * (size_t)N, Q = (size_t)query->Q, M = (size_t)query->M_cap;
-    DevArena mem;
-    const double* in[6] = {x, y, heading, kappa, v, ax};
-    double* d_in[6];
-    for (auto& d : d_in) d = mem.get<double>(BN);
-    double* d_h = mem.get<double>((size_t)B);
-    rl::TrajParams q{};
-    for (auto& c : q.out) c = mem.get<double>((size_t)B);
-    q.stamps = mem.get<double>((size_t)B * ((size_t)N + 1));
-    q.T = mem.get<double>((size_t)B);
-    q.count = mem.get<int32_t>((size_t)B);
-    char* d_qry = mem.get<char>(hzn_in_bytes(Q));
-    char* d_res = mem.get<char>(hzn_out_bytes(Q, M));
-    if (!mem.ok()) return fail(RL_ENOMEM, "rl_horizon: hipMalloc failed");
-    std::vector<char> block(std::max(hzn_in_bytes(Q), hzn_out_bytes(Q, M)));
-    hzn_pack(query, block.data());
-    for (int c = 0; c < 6; ++c)
-        if (hipMemcpy(d_in[c], in[c], BN * 8, hipMemcpyHostToDevice) != hipSuccess) return fail(RL_EHIP, "rl_horizon: upload");
-    if (hipMemcpy(d_h, h, (size_t)B * 8, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d_qry, block.data(), hzn_in_bytes(Q), hipMemcpyHostToDevice) != hipSuccess)
-        return fail(RL_EHIP, "rl_horizon: upload");
-    q.x = d_in[0]; q.y = d_in[1]; q.heading = d_in[2]; q.kappa = d_in[3]; q.v = d_in[4]; q.ax = d_in[5];
-    q.h = d_h;
-    q.dt = query->dt;
-    q.N = N; q.B = B; q.R = B; q.closed = closed ? 1 : 0; q.M_cap = 1;
-    if (rl::launch_trajectory(q, nullptr) != hipSuccess) return fail(RL_EHIP, "rl_horizon: trajectory kernel");
-    const rl::HznParams hp = hzn_params(q, query, d_qry, d_res);
-    if (rl::launch_horizon(hp, nullptr) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
-        return fail(RL_EHIP, "rl_horizon: kernel");
-    if (hipMemcpy(block.data(), d_res, hzn_out_bytes(Q, M), hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(RL_EHIP, "rl_horizon: download");
-    hzn_unpack(block.data(), Q, M, out);
-    return RL_OK;
+    return query_rows("rl_horizon", {x, y, heading, kappa, v, ax}, h, N, B, closed, as_rjn(*query), as_rjn(*out));
 }
 
-// rl_horizon's route with the rejoin kernel (rl_rejoin.hip) in the horizon kernel's place
 int rl_rejoin(const double* x, const double* y, const double* heading, const double* kappa, const double* v,
               const double* ax, const double* h, int32_t N, int32_t B, int32_t closed, const rl_rjn_query* query,
               int32_t device, rl_rjn* out) {
@@ -380,40 +384,7 @@ int rl_rejoin(const double* x, const double* y, const double* heading, const dou
     if (N > rl::RL_STREAM_MAX_N) return fail(RL_ETOOBIG, "rl_rejoin: N exceeds 1048576");
     if (int rc = check_rjn(query, B, N, closed ? 1 : 0)) return rc;
     if (int rc = select_device(device)) return rc;
-    const size_t BN = (size_t)B * (size_t)N, Q = (size_t)query->Q, M = (size_t)query->M_cap, K = (size_t)query->K_cap;
-    DevArena mem;
-    const double* in[6] = {x, y, heading, kappa, v, ax};
-    double* d_in[6];
-    for (auto& d : d_in) d = mem.get<double>(BN);
-    double* d_h = mem.get<double>((size_t)B);
-    rl::TrajParams q{};
-    for (auto& c : q.out) c = mem.get<double>((size_t)B);
-    q.stamps = mem.get<double>((size_t)B * ((size_t)N + 1));
-    q.T = mem.get<double>((size_t)B);
-    q.count = mem.get<int32_t>((size_t)B);
-    char* d_qry = mem.get<char>(rjn_in_bytes(Q));
-    char* d_res = mem.get<char>(rjn_out_bytes(Q, M, K));
-    if (!mem.ok()) return fail(RL_ENOMEM, "rl_rejoin: hipMalloc failed");
-    std::vector<char> block(std::max(rjn_in_bytes(Q), rjn_out_bytes(Q, M, K)));
-    rjn_pack(query, block.data());
-    for (int c = 0; c < 6; ++c)
-        if (hipMemcpy(d_in[c], in[c], BN * 8, hipMemcpyHostToDevice) != hipSuccess) return fail(RL_EHIP, "rl_rejoin: upload");
-    if (hipMemcpy(d_h, h, (size_t)B * 8, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d_qry, block.data(), rjn_in_bytes(Q), hipMemcpyHostToDevice) != hipSuccess)
-        return fail(RL_EHIP, "rl_rejoin: upload");
-    q.x = d_in[0]; q.y = d_in[1]; q.heading = d_in[2]; q.kappa = d_in[3]; q.v = d_in[4]; q.ax = d_in[5];
-    q.h = d_h;
-    q.dt = query->dt;
-    q.N = N; q.B = B; q.R = B; q.closed = closed ? 1 : 0; q.M_cap = 1;
-    if (rl::launch_trajectory(q, nullptr) != hipSuccess) return fail(RL_EHIP, "rl_rejoin: trajectory kernel");
-    const rl::RjnParams rp = rjn_params(q, query, d_qry, d_res);
-    if (rl::launch_rejoin(rp, nullptr) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
-        return fail(RL_EHIP, "rl_rejoin: kernel");
-    const bool nodes = out->node_v || out->node_t;
-    if (hipMemcpy(block.data(), d_res, nodes ? rjn_out_bytes(Q, M, K) : rjn_head_bytes(Q, M), hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(RL_EHIP, "rl_rejoin: download");
-    rjn_unpack(block.data(), Q, M, K, out);
-    return RL_OK;
+    return query_rows("rl_rejoin", {x, y, heading, kappa, v, ax}, h, N, B, closed, *query, *out);
 }
 
 // rank host scores with rl_rank_kernel (rl_select.hip)

@@ -21,6 +21,7 @@
 #include "rl_trajectory.h"
 #include "rl_horizon.h"
 #include "rl_rejoin.h"
+#include "rl_query.h"
 
 namespace rl {
 
@@ -374,6 +375,55 @@ inline int queue_downloads(const std::vector<CopyJob>& jobs, hipStream_t st) {
     return RL_OK;
 }
 
+// ------------------------------------------------------------------ pose-query stages
+// The plan's side of one pose-query stage (horizon, rejoin).  The queries go up and the results
+// come down as one packed block each (in, out; rl_query.h has their layout), through one pinned
+// host block (pin) of the larger capacity; all three grow with Q, M_cap and K_cap.  ev[0] is
+// recorded after the upload, which reads pin, ev[1] after the kernel.  Q = 0: no stage since
+// the last run or trajectory stage; M, K (0 for the horizon) are that stage's M_cap and K_cap.
+struct QueryStage {
+    char *in = nullptr, *out = nullptr, *pin = nullptr;
+    size_t in_cap = 0, out_cap = 0;
+    DevArena mem;                     // in, out: they count toward the plan's dev_bytes()
+    int Q = 0, M = 0, K = 0;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+
+    void release_blocks() {
+        mem.release();
+        if (pin) hipHostFree(pin);
+        in = out = pin = nullptr;
+        in_cap = out_cap = 0;
+    }
+    void release() {
+        release_blocks();
+        for (auto& e : ev) {
+            if (e) hipEventDestroy(e);
+            e = nullptr;
+        }
+    }
+    // blocks of at least in_bytes and out_bytes; they only grow.  last_stream: the plan's, which
+    // may still use the old ones.  `what` names the stage in the message.
+    int reserve(hipStream_t last_stream, size_t in_bytes, size_t out_bytes, const char* what) {
+        if (in && in_bytes <= in_cap && out_bytes <= out_cap) return RL_OK;
+        if (last_stream) HIPCHK(hipStreamSynchronize(last_stream));
+        const size_t ic = std::max(in_bytes, in_cap), oc = std::max(out_bytes, out_cap);
+        release_blocks();
+        char* d_in = mem.get<char>(ic);
+        char* d_out = mem.get<char>(oc);
+        void* host = nullptr;
+        if (!mem.ok() || hipHostMalloc(&host, std::max(ic, oc), hipHostMallocDefault) != hipSuccess) {
+            mem.release();
+            return fail(RL_ENOMEM, std::string("allocation of the ") + what + " buffers failed");
+        }
+        in = d_in;
+        out = d_out;
+        pin = (char*)host;
+        in_cap = ic;
+        out_cap = oc;
+        return RL_OK;
+    }
+};
+
 }  // namespace rl
 
 // ------------------------------------------------------------------ the plan
@@ -448,33 +498,16 @@ struct rl_plan {
     rl::DevArena traj_mem;
     int traj_cap_R = 0, traj_cap_M = 0, traj_R = 0, traj_M = 0;
     hipEvent_t ev_traj[2] = {nullptr, nullptr};
-    // horizon stage (rl_plan_horizon): it reads the last trajectory stage through traj_q, that
-    // stage's launch parameters, which stay valid while traj_R != 0 and the rows they point at
-    // are those the stamps were made from: traj_sel_epoch / traj_lap_epoch are sel_epoch /
-    // lap_epoch (counted up by every selection / lap stage) at that launch.  The queries go up
-    // and the results come down as one packed block each (hzn_in, hzn_out), through one pinned
-    // host block (hzn_pin); all three grow with Q and M_cap.  hzn_Q = 0: no stage since the
-    // last run or trajectory stage.
+    // pose-query stages (rl_plan_horizon, rl_plan_rejoin; rl::QueryStage): they read the last
+    // trajectory stage through traj_q, that stage's launch parameters, which stay valid while
+    // traj_R != 0 and the rows they point at are those the stamps were made from:
+    // traj_sel_epoch / traj_lap_epoch are sel_epoch / lap_epoch (counted up by every selection /
+    // lap stage) at that launch.  Each stage has blocks of its own, so the last horizon stage
+    // stays fetchable after a rejoin stage and the other way round.
     rl::TrajParams traj_q{};
     int traj_mode = 0;
     uint32_t sel_epoch = 0, lap_epoch = 0, traj_sel_epoch = 0, traj_lap_epoch = 0;
-    char* hzn_in = nullptr;
-    char* hzn_out = nullptr;
-    char* hzn_pin = nullptr;
-    size_t hzn_in_cap = 0, hzn_out_cap = 0, hzn_pin_cap = 0;
-    rl::DevArena hzn_mem;
-    int hzn_Q = 0, hzn_M = 0;
-    hipEvent_t ev_hzn[2] = {nullptr, nullptr};            // after the upload, after the kernel
-    // rejoin stage (rl_plan_rejoin): the horizon stage's scheme with blocks of its own (rjn_in,
-    // rjn_out, rjn_pin), so that the last horizon stage stays fetchable; they grow with Q, M_cap
-    // and K_cap.  rjn_Q = 0: no stage since the last run or trajectory stage.
-    char* rjn_in = nullptr;
-    char* rjn_out = nullptr;
-    char* rjn_pin = nullptr;
-    size_t rjn_in_cap = 0, rjn_out_cap = 0;
-    rl::DevArena rjn_mem;
-    int rjn_Q = 0, rjn_M = 0, rjn_K = 0;
-    hipEvent_t ev_rjn[2] = {nullptr, nullptr};            // after the upload, after the kernel
+    rl::QueryStage hzn, rjn;
 
     template <class T>
     int alloc(T** p, size_t n) {
@@ -483,7 +516,7 @@ struct rl_plan {
     }
     int nomem() const { return rl::fail(RL_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(mem.err)); }
     // device memory held (plan cache budget)
-    size_t dev_bytes() const { return mem.bytes + sel_mem.bytes + lap_mem.bytes + traj_mem.bytes + hzn_mem.bytes + rjn_mem.bytes; }
+    size_t dev_bytes() const { return mem.bytes + sel_mem.bytes + lap_mem.bytes + traj_mem.bytes + hzn.mem.bytes + rjn.mem.bytes; }
     // the stream of the last run or stage
     hipStream_t run_stream() const { return last_stream ? last_stream : own_stream; }
     // the batch size the kernel shape is chosen for
@@ -521,32 +554,11 @@ void traj_jobs(const rl_plan* p, const rl_traj* t, std::vector<CopyJob>& jobs);
 // argument checks shared by the horizon entry points (no device call): the queries against a
 // trajectory stage of R rows of N samples
 int check_hzn(const rl_hzn_query* q, int32_t R, int32_t N, int32_t closed);
-// the packed blocks of a horizon stage of Q queries and M ticks: the queries are poses [Q][2],
-// rows [Q], hints [Q]; the results the columns [Q][M] in rl_hzn's order, then u, t0, s0, e,
-// dist2 [Q], then seg, count [Q]
-inline size_t hzn_in_bytes(size_t Q) { return Q * 24; }
-inline size_t hzn_out_bytes(size_t Q, size_t M) { return ((size_t)TRAJ_COLS * Q * M + (size_t)HZN_LOC * Q) * 8 + 2 * Q * 4; }
-// fill the queries' block (host) from q
-void hzn_pack(const rl_hzn_query* q, char* block);
-// the launch parameters of q on the blocks `in` and `out` (device)
-HznParams hzn_params(const TrajParams& src, const rl_hzn_query* q, char* in, char* out);
-// copy a results' block (host) into the non-NULL fields of o
-void hzn_unpack(const char* block, size_t Q, size_t M, const rl_hzn* o);
 // argument checks shared by the rejoin entry points (no device call): check_hzn's, then v0, cfg
 // and K_cap
 int check_rjn(const rl_rjn_query* q, int32_t R, int32_t N, int32_t closed);
-// the packed blocks of a rejoin stage of Q queries, M ticks and K = K_cap nodes: the queries are
-// poses [Q][2], v0 [Q], rows [Q], hints [Q]; the results the columns [Q][M] in rl_rjn's order,
-// then u, t0, s0, e, dist2, t_merge, t_loss [Q], then seg, count, merge_node, overspeed [Q] (the
-// head, always downloaded), then node_v, node_t [Q][K + 1]
-inline size_t rjn_in_bytes(size_t Q) { return Q * 32; }
-inline size_t rjn_head_bytes(size_t Q, size_t M) {
-    return ((size_t)TRAJ_COLS * Q * M + (size_t)(HZN_LOC + RJN_SCAL) * Q) * 8 + 4 * Q * 4;
-}
-inline size_t rjn_out_bytes(size_t Q, size_t M, size_t K) { return rjn_head_bytes(Q, M) + 2 * Q * (K + 1) * 8; }
-void rjn_pack(const rl_rjn_query* q, char* block);
-RjnParams rjn_params(const TrajParams& src, const rl_rjn_query* q, char* in, char* out);
-// copy a results' block (host) into the non-NULL fields of o
-void rjn_unpack(const char* block, size_t Q, size_t M, size_t K, const rl_rjn* o);
+// the launch parameters of q on the blocks `in` and `out` (device) laid out as L, reading the
+// trajectory stage src: rl_query.h's pointers, and for a rejoin query ax_max_at's constants
+RjnParams query_params(const TrajParams& src, const rl_rjn_query& q, const QueryLayout& L, char* in, char* out);
 
 }  // namespace rl

@@ -193,14 +193,8 @@ int rl_plan_destroy(rl_plan* plan) {
     plan->traj_mem.release();
     for (auto& e : plan->ev_traj)
         if (e) hipEventDestroy(e);
-    plan->hzn_mem.release();
-    if (plan->hzn_pin) hipHostFree(plan->hzn_pin);
-    for (auto& e : plan->ev_hzn)
-        if (e) hipEventDestroy(e);
-    plan->rjn_mem.release();
-    if (plan->rjn_pin) hipHostFree(plan->rjn_pin);
-    for (auto& e : plan->ev_rjn)
-        if (e) hipEventDestroy(e);
+    plan->hzn.release();
+    plan->rjn.release();
     for (auto& e : plan->ev)
         if (e) hipEventDestroy(e);
     for (auto& e : plan->ev_end)
@@ -299,8 +293,7 @@ int rl_plan_run(rl_plan* p, void* hip_stream) {
     p->sel_mode = 0;                                   // an earlier selection is of an earlier run
     p->lap_valid = false;                              // and so is an earlier lap stage
     p->traj_R = 0;                                     // and an earlier trajectory stage
-    p->hzn_Q = 0;                                      // and the horizon stage that read it
-    p->rjn_Q = 0;                                      // and the rejoin stage
+    p->hzn.Q = p->rjn.Q = 0;                           // and the pose-query stages that read it
     return RL_OK;
 }
 
@@ -424,8 +417,7 @@ int rl_plan_run_group(rl_plan* const* plans, int32_t n, void* hip_stream) {
         plans[i]->sel_mode = 0;
         plans[i]->lap_valid = false;
         plans[i]->traj_R = 0;
-        plans[i]->hzn_Q = 0;
-        plans[i]->rjn_Q = 0;
+        plans[i]->hzn.Q = plans[i]->rjn.Q = 0;
     }
     return RL_OK;
 }
@@ -437,6 +429,7 @@ int rl_plan_kernel_ms(rl_plan* p, int32_t idx, float* ms) {
     // idx 0: whole run; 1: min-curv kernel; 2: min-time kernel; 3: the selection stage
     hipEvent_t a, b;
     const bool mc = p->modes & RL_MODE_MINCURV, mt = p->modes & RL_MODE_MINTIME;
+    const rl::QueryStage& stage = idx == 9 ? p->rjn : p->hzn;   // 8: the horizon stage; 9: the rejoin stage
     if (idx == 0) { a = p->ev[0]; b = p->ev[3]; }
     else if (idx == 3 && p->sel_mode) {
         a = p->ev_sel[0];
@@ -454,14 +447,9 @@ int rl_plan_kernel_ms(rl_plan* p, int32_t idx, float* ms) {
         b = p->ev_traj[1];
         HIPCHK(hipEventSynchronize(b));
     }
-    else if (idx == 8 && p->hzn_Q && p->traj_R) {
-        a = p->ev_hzn[0];
-        b = p->ev_hzn[1];
-        HIPCHK(hipEventSynchronize(b));
-    }
-    else if (idx == 9 && p->rjn_Q && p->traj_R) {
-        a = p->ev_rjn[0];
-        b = p->ev_rjn[1];
+    else if ((idx == 8 || idx == 9) && stage.Q && p->traj_R) {
+        a = stage.ev[0];
+        b = stage.ev[1];
         HIPCHK(hipEventSynchronize(b));
     }
     else if (idx == 1 && mc) { a = p->ev[1]; b = p->ev_end[0]; }

@@ -1,0 +1,120 @@
+// rl_query.h — the packed blocks of the pose-query stages (horizon; rejoin, §3m):
+// where every array lies, and the host code that fills the queries' block, points a launch at
+// both blocks and copies a results' block out.  The horizon stage is the rejoin stage with the
+// optional parts empty, so both go through the rejoin forms (as_rjn) with K = K_cap = 0 for
+// the horizon.  No HIP call: a host compiler builds it without a device (tests/
+// test_query_layout_cpu.py).  Not part of the public ABI.
+#pragma once
+#include <cstddef>
+#include <cstring>
+
+#include "rl_abi.h"
+#include "rl_rejoin.h"
+
+namespace rl {
+
+constexpr int QRY_PER = HZN_LOC + RJN_SCAL;   // u, t0, s0, e, dist2, t_merge, t_loss
+constexpr int QRY_INTS = 4;                   // seg, count, merge_node, overspeed
+constexpr int QRY_NODES = 2;                  // node_v, node_t
+
+// Byte offsets of the arrays of a stage of Q queries, M ticks and K nodes.  The queries' block:
+// pose [Q][2], v0 [Q] (rejoin), row [Q], hint [Q].  The results' block: the columns [Q][M] in
+// rl_hzn's order, the n_per doubles [Q], the n_ints ints [Q] (the head, always downloaded), the
+// n_nodes node arrays [Q][K + 1].
+struct QueryLayout {
+    size_t Q, M, K;
+    size_t pose, v0, row, hint, in_bytes;
+    int n_per, n_ints, n_nodes;
+    size_t col[TRAJ_COLS], per[QRY_PER], ints[QRY_INTS], nodes[QRY_NODES], head_bytes, out_bytes;
+};
+
+inline QueryLayout query_layout(size_t Q, size_t M, size_t K) {
+    QueryLayout L{};
+    const bool rjn = K > 0;
+    L.Q = Q; L.M = M; L.K = K;
+    L.n_per = HZN_LOC + (rjn ? RJN_SCAL : 0);
+    L.n_ints = rjn ? QRY_INTS : 2;
+    L.n_nodes = rjn ? QRY_NODES : 0;
+    size_t at = 0;                             // the cursor
+    auto take = [&at](size_t bytes) { const size_t o = at; at += bytes; return o; };
+    L.pose = take(Q * 16);
+    L.v0 = take(rjn ? Q * 8 : 0);
+    L.row = take(Q * 4);
+    L.hint = take(Q * 4);
+    L.in_bytes = at;
+    at = 0;
+    for (auto& o : L.col) o = take(Q * M * 8);
+    for (int c = 0; c < L.n_per; ++c) L.per[c] = take(Q * 8);
+    for (int c = 0; c < L.n_ints; ++c) L.ints[c] = take(Q * 4);
+    L.head_bytes = at;
+    for (int c = 0; c < L.n_nodes; ++c) L.nodes[c] = take(Q * (K + 1) * 8);
+    L.out_bytes = at;
+    return L;
+}
+
+// a horizon query and its results in the rejoin forms: no v0, no cfg, K_cap = 0, the extra
+// fields NULL
+inline rl_rjn_query as_rjn(const rl_hzn_query& q) {
+    return {q.pose_xy, q.row, q.seg_hint, q.Q, q.window, q.M_cap, 0, q.dt, nullptr, nullptr, 0, 0};
+}
+inline rl_rjn as_rjn(const rl_hzn& o) {
+    return {o.s, o.x, o.y, o.heading, o.kappa, o.v, o.ax, o.u, o.t0, o.s0, o.e, o.dist2, o.seg, o.count,
+            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+}
+inline QueryLayout query_layout(const rl_rjn_query& q) { return query_layout((size_t)q.Q, (size_t)q.M_cap, (size_t)q.K_cap); }
+
+// fill the queries' block (host) from q: a NULL row is 0, a NULL seg_hint -1
+inline void query_pack(const rl_rjn_query& q, const QueryLayout& L, char* block) {
+    std::memcpy(block + L.pose, q.pose_xy, L.Q * 16);
+    if (L.K) std::memcpy(block + L.v0, q.v0, L.Q * 8);
+    int32_t* row = (int32_t*)(block + L.row);
+    int32_t* hint = (int32_t*)(block + L.hint);
+    for (size_t k = 0; k < L.Q; ++k) {
+        row[k] = q.row ? q.row[k] : 0;
+        hint[k] = q.seg_hint ? q.seg_hint[k] : -1;
+    }
+}
+
+// the pointers and sizes of a launch of q on the blocks `in` and `out` (hz alone is the horizon
+// kernel's); hz.src and cfg are the caller's
+inline RjnParams query_pointers(const rl_rjn_query& q, const QueryLayout& L, char* in, char* out) {
+    RjnParams r{};
+    HznParams& h = r.hz;
+    h.pose = (const double*)(in + L.pose);
+    h.row = (const int32_t*)(in + L.row);
+    h.hint = (const int32_t*)(in + L.hint);
+    for (int c = 0; c < TRAJ_COLS; ++c) h.out[c] = (double*)(out + L.col[c]);
+    for (int c = 0; c < HZN_LOC; ++c) h.loc[c] = (double*)(out + L.per[c]);
+    h.seg = (int32_t*)(out + L.ints[0]);
+    h.count = (int32_t*)(out + L.ints[1]);
+    h.dt = q.dt;
+    h.Q = q.Q; h.window = q.window; h.M_cap = q.M_cap;
+    if (!L.K) return r;
+    r.v0 = (const double*)(in + L.v0);
+    for (int c = 0; c < RJN_SCAL; ++c) r.scal[c] = (double*)(out + L.per[HZN_LOC + c]);
+    r.merge_node = (int32_t*)(out + L.ints[2]);
+    r.overspeed = (int32_t*)(out + L.ints[3]);
+    r.node_v = (double*)(out + L.nodes[0]);
+    r.node_t = (double*)(out + L.nodes[1]);
+    r.K_cap = q.K_cap;
+    return r;
+}
+
+// copy a results' block (host) into the non-NULL fields of o; with node_v and node_t NULL only
+// the head is read
+inline void query_unpack(const char* block, const QueryLayout& L, const rl_rjn& o) {
+    double* const col[TRAJ_COLS] = {o.s, o.x, o.y, o.heading, o.kappa, o.v, o.ax};
+    double* const per[QRY_PER] = {o.u, o.t0, o.s0, o.e, o.dist2, o.t_merge, o.t_loss};
+    int32_t* const ints[QRY_INTS] = {o.seg, o.count, o.merge_node, o.overspeed};
+    double* const nodes[QRY_NODES] = {o.node_v, o.node_t};
+    for (int c = 0; c < TRAJ_COLS; ++c)
+        if (col[c]) std::memcpy(col[c], block + L.col[c], L.Q * L.M * 8);
+    for (int c = 0; c < L.n_per; ++c)
+        if (per[c]) std::memcpy(per[c], block + L.per[c], L.Q * 8);
+    for (int c = 0; c < L.n_ints; ++c)
+        if (ints[c]) std::memcpy(ints[c], block + L.ints[c], L.Q * 4);
+    for (int c = 0; c < L.n_nodes; ++c)
+        if (nodes[c]) std::memcpy(nodes[c], block + L.nodes[c], L.Q * (L.K + 1) * 8);
+}
+
+}  // namespace rl

@@ -4,7 +4,7 @@
 // stage (rl_trajectory.hip): time stamps and the state at every control tick.
 // Horizon stage (rl_horizon.hip): poses located on that stage's rows, and the next
 // ticks from there.  Rejoin stage (rl_rejoin.hip): the same from the car's speed, along a
-// reachable profile.
+// reachable profile.  These two pose-query stages share one enqueue and one fetch routine.
 #include "rl_host.h"
 
 using namespace rl;
@@ -75,50 +75,6 @@ int rl::check_hzn(const rl_hzn_query* q, int32_t R, int32_t N, int32_t closed) {
     return RL_OK;
 }
 
-void rl::hzn_pack(const rl_hzn_query* q, char* block) {
-    const size_t Q = (size_t)q->Q;
-    std::memcpy(block, q->pose_xy, Q * 16);
-    int32_t* row = (int32_t*)(block + Q * 16);
-    int32_t* hint = row + Q;
-    for (size_t k = 0; k < Q; ++k) {
-        row[k] = q->row ? q->row[k] : 0;
-        hint[k] = q->seg_hint ? q->seg_hint[k] : -1;
-    }
-}
-
-HznParams rl::hzn_params(const TrajParams& src, const rl_hzn_query* q, char* in, char* out) {
-    const size_t Q = (size_t)q->Q, M = (size_t)q->M_cap;
-    HznParams h{};
-    h.src = src;
-    h.pose = (const double*)in;
-    h.row = (const int32_t*)(in + Q * 16);
-    h.hint = h.row + Q;
-    double* d = (double*)out;
-    for (auto& c : h.out) { c = d; d += Q * M; }
-    for (auto& c : h.loc) { c = d; d += Q; }
-    h.seg = (int32_t*)d;
-    h.count = h.seg + Q;
-    h.dt = q->dt;
-    h.Q = q->Q; h.window = q->window; h.M_cap = q->M_cap;
-    return h;
-}
-
-void rl::hzn_unpack(const char* block, size_t Q, size_t M, const rl_hzn* o) {
-    double* const col[TRAJ_COLS] = {o->s, o->x, o->y, o->heading, o->kappa, o->v, o->ax};
-    double* const loc[HZN_LOC] = {o->u, o->t0, o->s0, o->e, o->dist2};
-    const char* src = block;
-    for (double* c : col) {
-        if (c) std::memcpy(c, src, Q * M * 8);
-        src += Q * M * 8;
-    }
-    for (double* c : loc) {
-        if (c) std::memcpy(c, src, Q * 8);
-        src += Q * 8;
-    }
-    if (o->seg) std::memcpy(o->seg, src, Q * 4);
-    if (o->count) std::memcpy(o->count, src + Q * 4, Q * 4);
-}
-
 int rl::check_rjn(const rl_rjn_query* q, int32_t R, int32_t N, int32_t closed) {
     if (!q) return fail(RL_EINVAL, "rejoin: the query is NULL");
     const rl_hzn_query hq{q->pose_xy, q->row, q->seg_hint, q->Q, q->window, q->M_cap, 0, q->dt};
@@ -130,42 +86,12 @@ int rl::check_rjn(const rl_rjn_query* q, int32_t R, int32_t N, int32_t closed) {
     return RL_OK;
 }
 
-void rl::rjn_pack(const rl_rjn_query* q, char* block) {
-    const size_t Q = (size_t)q->Q;
-    std::memcpy(block, q->pose_xy, Q * 16);
-    std::memcpy(block + Q * 16, q->v0, Q * 8);
-    int32_t* row = (int32_t*)(block + Q * 24);
-    int32_t* hint = row + Q;
-    for (size_t k = 0; k < Q; ++k) {
-        row[k] = q->row ? q->row[k] : 0;
-        hint[k] = q->seg_hint ? q->seg_hint[k] : -1;
-    }
-}
-
-RjnParams rl::rjn_params(const TrajParams& src, const rl_rjn_query* q, char* in, char* out) {
-    const size_t Q = (size_t)q->Q, M = (size_t)q->M_cap, K = (size_t)q->K_cap;
-    RjnParams r{};
-    HznParams& h = r.hz;
-    h.src = src;
-    h.pose = (const double*)in;
-    r.v0 = h.pose + 2 * Q;
-    h.row = (const int32_t*)(in + Q * 24);
-    h.hint = h.row + Q;
-    double* d = (double*)out;
-    for (auto& c : h.out) { c = d; d += Q * M; }
-    for (auto& c : h.loc) { c = d; d += Q; }
-    for (auto& c : r.scal) { c = d; d += Q; }
-    h.seg = (int32_t*)d;
-    h.count = h.seg + Q;
-    r.merge_node = h.count + Q;
-    r.overspeed = r.merge_node + Q;
-    r.node_v = (double*)(r.overspeed + Q);
-    r.node_t = r.node_v + Q * (K + 1);
-    h.dt = q->dt;
-    h.Q = q->Q; h.window = q->window; h.M_cap = q->M_cap;
-    r.K_cap = q->K_cap;
+RjnParams rl::query_params(const TrajParams& src, const rl_rjn_query& q, const QueryLayout& L, char* in, char* out) {
+    RjnParams r = query_pointers(q, L, in, out);
+    r.hz.src = src;
+    if (!q.cfg) return r;                              // a horizon query
     // ax_max_at's constant prefixes, as the optimisers' VConst evaluates them
-    const rl_cfg& C = *q->cfg;
+    const rl_cfg& C = *q.cfg;
     const double a_total = C.use_total_ge_lat ? smax_h(C.a_total_max, C.a_lat_max) : C.a_total_max;
     r.cfg.a_total2 = a_total * a_total;
     r.cfg.kFd = 0.5 * C.rho_air * C.Cd * C.A_front_m2;
@@ -175,85 +101,7 @@ RjnParams rl::rjn_params(const TrajParams& src, const rl_rjn_query* q, char* in,
     return r;
 }
 
-void rl::rjn_unpack(const char* block, size_t Q, size_t M, size_t K, const rl_rjn* o) {
-    double* const col[TRAJ_COLS] = {o->s, o->x, o->y, o->heading, o->kappa, o->v, o->ax};
-    double* const per[HZN_LOC + RJN_SCAL] = {o->u, o->t0, o->s0, o->e, o->dist2, o->t_merge, o->t_loss};
-    int32_t* const ints[4] = {o->seg, o->count, o->merge_node, o->overspeed};
-    double* const nodes[2] = {o->node_v, o->node_t};
-    const char* src = block;
-    for (double* c : col) {
-        if (c) std::memcpy(c, src, Q * M * 8);
-        src += Q * M * 8;
-    }
-    for (double* c : per) {
-        if (c) std::memcpy(c, src, Q * 8);
-        src += Q * 8;
-    }
-    for (int32_t* c : ints) {
-        if (c) std::memcpy(c, src, Q * 4);
-        src += Q * 4;
-    }
-    for (double* c : nodes) {
-        if (c) std::memcpy(c, src, Q * (K + 1) * 8);
-        src += Q * (K + 1) * 8;
-    }
-}
-
 namespace {
-
-// plan-owned horizon blocks for Q queries of M ticks; the device blocks count toward dev_bytes()
-int hzn_alloc(rl_plan* p, size_t Q, size_t M) {
-    const size_t in = hzn_in_bytes(Q), out = hzn_out_bytes(Q, M);
-    if (p->hzn_in && in <= p->hzn_in_cap && out <= p->hzn_out_cap) return RL_OK;
-    if (p->last_stream) HIPCHK(hipStreamSynchronize(p->last_stream));   // it may still use the old ones
-    DevArena& a = p->hzn_mem;
-    a.release();
-    if (p->hzn_pin) hipHostFree(p->hzn_pin);
-    p->hzn_in = p->hzn_out = p->hzn_pin = nullptr;
-    const size_t in_cap = std::max(in, p->hzn_in_cap), out_cap = std::max(out, p->hzn_out_cap);
-    p->hzn_in_cap = p->hzn_out_cap = p->hzn_pin_cap = 0;
-    char* d_in = a.get<char>(in_cap);
-    char* d_out = a.get<char>(out_cap);
-    void* pin = nullptr;
-    if (!a.ok() || hipHostMalloc(&pin, std::max(in_cap, out_cap), hipHostMallocDefault) != hipSuccess) {
-        a.release();
-        return fail(RL_ENOMEM, "allocation of the horizon buffers failed");
-    }
-    p->hzn_in = d_in;
-    p->hzn_out = d_out;
-    p->hzn_pin = (char*)pin;
-    p->hzn_in_cap = in_cap;
-    p->hzn_out_cap = out_cap;
-    p->hzn_pin_cap = std::max(in_cap, out_cap);
-    return RL_OK;
-}
-
-// plan-owned rejoin blocks for Q queries of M ticks and K nodes; the device blocks count toward
-// dev_bytes()
-int rjn_alloc(rl_plan* p, size_t Q, size_t M, size_t K) {
-    const size_t in = rjn_in_bytes(Q), out = rjn_out_bytes(Q, M, K);
-    if (p->rjn_in && in <= p->rjn_in_cap && out <= p->rjn_out_cap) return RL_OK;
-    if (p->last_stream) HIPCHK(hipStreamSynchronize(p->last_stream));   // it may still use the old ones
-    DevArena& a = p->rjn_mem;
-    a.release();
-    if (p->rjn_pin) hipHostFree(p->rjn_pin);
-    p->rjn_in = p->rjn_out = p->rjn_pin = nullptr;
-    const size_t in_cap = std::max(in, p->rjn_in_cap), out_cap = std::max(out, p->rjn_out_cap);
-    p->rjn_in_cap = p->rjn_out_cap = 0;
-    char* d_in = a.get<char>(in_cap);
-    char* d_out = a.get<char>(out_cap);
-    void* pin = nullptr;
-    if (!a.ok() || hipHostMalloc(&pin, std::max(in_cap, out_cap), hipHostMallocDefault) != hipSuccess) {
-        a.release();
-        return fail(RL_ENOMEM, "allocation of the rejoin buffers failed");
-    }
-    p->rjn_in = d_in;
-    p->rjn_out = d_out;
-    p->rjn_pin = (char*)pin;
-    p->rjn_in_cap = in_cap;
-    p->rjn_out_cap = out_cap;
-    return RL_OK;
-}
 
 // plan-owned trajectory buffers for R rows of M ticks; they count toward dev_bytes()
 int traj_alloc(rl_plan* p, int R, int M) {
@@ -386,6 +234,57 @@ int select_impl(rl_plan* p, const rl_select* sel, int gs, bool by_lap, void* hip
     return RL_OK;
 }
 
+// rl_plan_horizon / rl_plan_rejoin (arguments checked; K_cap = 0: the horizon): one launch of
+// the stage's kernel on the last trajectory stage.  The queries go up in one block, through
+// s's pinned block, ahead of the kernel on the same stream.
+int query_enqueue(rl_plan* p, QueryStage& s, const rl_rjn_query& q, void* hip_stream) {
+    const bool rjn = q.K_cap > 0;
+    const char* what = rjn ? "rejoin" : "horizon";
+    const std::string fn = std::string("rl_plan_") + what;
+    if (p->traj_q.index && p->traj_sel_epoch != p->sel_epoch)
+        return fail(RL_EINVAL, fn + ": a selection has replaced the winners the trajectory stage read");
+    if (p->traj_mode == RL_MODE_MINCURV && p->traj_lap_epoch != p->lap_epoch)
+        return fail(RL_EINVAL, fn + ": a lap stage has rewritten the rows the trajectory stage read");
+    HIPCHK(hipSetDevice(p->device));
+    hipStream_t run_st = p->run_stream();
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : run_st;
+    // An earlier upload may still read the pinned block, also one whose stage a run, a
+    // trajectory stage or a failed launch has invalidated since (an event that was never
+    // recorded is complete).
+    if (s.ev[0]) HIPCHK(hipEventSynchronize(s.ev[0]));
+    s.Q = 0;
+    const QueryLayout L = query_layout(q);
+    if (int rc = s.reserve(p->last_stream, L.in_bytes, L.out_bytes, what)) return rc;
+    for (auto& e : s.ev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    if (st != run_st) HIPCHK(hipStreamWaitEvent(st, p->ev_traj[1], 0));
+    p->last_stream = st;
+    query_pack(q, L, s.pin);
+    HIPCHK(hipMemcpyAsync(s.in, s.pin, L.in_bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(hipEventRecord(s.ev[0], st));
+    const RjnParams r = query_params(p->traj_q, q, L, s.in, s.out);
+    const hipError_t e = rjn ? rl::launch_rejoin(r, st) : rl::launch_horizon(r.hz, st);
+    if (e != hipSuccess) return fail(RL_EHIP, std::string(what) + " launch: " + hipGetErrorString(e));
+    HIPCHK(hipEventRecord(s.ev[1], st));
+    s.Q = q.Q;
+    s.M = q.M_cap;
+    s.K = q.K_cap;
+    return RL_OK;
+}
+
+// rl_plan_fetch_horizon / rl_plan_fetch_rejoin (a valid stage in s): the results' block comes
+// down through the pinned block, without the node arrays if o asks for neither
+int query_fetch(rl_plan* p, QueryStage& s, const rl_rjn& o) {
+    HIPCHK(hipSetDevice(p->device));
+    hipStream_t st = p->run_stream();
+    HIPCHK(hipStreamWaitEvent(st, s.ev[1], 0));         // (a later stage may have moved to another stream)
+    const QueryLayout L = query_layout((size_t)s.Q, (size_t)s.M, (size_t)s.K);
+    HIPCHK(hipMemcpyAsync(s.pin, s.out, o.node_v || o.node_t ? L.out_bytes : L.head_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    query_unpack(s.pin, L, o);
+    return RL_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -505,8 +404,7 @@ int rl_plan_trajectory(rl_plan* p, int32_t mode, int32_t rows, double dt, int32_
         return fail(RL_EINVAL, "rl_plan_trajectory: no selection of this mode since the plan's last run");
     const bool mc = mode == RL_MODE_MINCURV;
     p->traj_R = 0;
-    p->hzn_Q = 0;                                      // a horizon stage read the stage before this one
-    p->rjn_Q = 0;                                      // and so did a rejoin stage
+    p->hzn.Q = p->rjn.Q = 0;                           // they read the stage before this one
     if (mc && !p->lap_valid)
         if (int rc = rl_plan_lap(p, hip_stream)) return rc;
     HIPCHK(hipSetDevice(p->device));
@@ -563,107 +461,37 @@ int rl_plan_fetch_trajectory(rl_plan* p, rl_traj* out) {
     return RL_OK;
 }
 
-// One launch of rl_horizon_kernel on the last trajectory stage: the queries go up in one
-// block, through the plan's pinned block, ahead of the kernel on the same stream.
 int rl_plan_horizon(rl_plan* p, const rl_hzn_query* query, void* hip_stream) {
     if (!p) return fail(RL_EINVAL, "plan is NULL");
     if (!query) return fail(RL_EINVAL, "horizon: the query or its pose_xy is NULL");
     if (!p->traj_R) return fail(RL_EINVAL, "rl_plan_horizon: no trajectory stage since the plan's last run");
     if (int rc = check_hzn(query, p->traj_R, p->N, p->closed)) return rc;
-    if (p->traj_q.index && p->traj_sel_epoch != p->sel_epoch)
-        return fail(RL_EINVAL, "rl_plan_horizon: a selection has replaced the winners the trajectory stage read");
-    if (p->traj_mode == RL_MODE_MINCURV && p->traj_lap_epoch != p->lap_epoch)
-        return fail(RL_EINVAL, "rl_plan_horizon: a lap stage has rewritten the rows the trajectory stage read");
-    HIPCHK(hipSetDevice(p->device));
-    hipStream_t run_st = p->run_stream();
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : run_st;
-    // the last stage's upload may still read the pinned block
-    if (p->hzn_Q) HIPCHK(hipEventSynchronize(p->ev_hzn[0]));
-    p->hzn_Q = 0;
-    const size_t Q = (size_t)query->Q, M = (size_t)query->M_cap;
-    if (int rc = hzn_alloc(p, Q, M)) return rc;
-    for (auto& e : p->ev_hzn)
-        if (!e) HIPCHK(hipEventCreate(&e));
-    if (st != run_st) HIPCHK(hipStreamWaitEvent(st, p->ev_traj[1], 0));
-    p->last_stream = st;
-    hzn_pack(query, p->hzn_pin);
-    HIPCHK(hipMemcpyAsync(p->hzn_in, p->hzn_pin, hzn_in_bytes(Q), hipMemcpyHostToDevice, st));
-    HIPCHK(hipEventRecord(p->ev_hzn[0], st));
-    const rl::HznParams h = hzn_params(p->traj_q, query, p->hzn_in, p->hzn_out);
-    const hipError_t e = rl::launch_horizon(h, st);
-    if (e != hipSuccess) return fail(RL_EHIP, std::string("horizon launch: ") + hipGetErrorString(e));
-    HIPCHK(hipEventRecord(p->ev_hzn[1], st));
-    p->hzn_Q = query->Q;
-    p->hzn_M = query->M_cap;
-    return RL_OK;
+    return query_enqueue(p, p->hzn, as_rjn(*query), hip_stream);
 }
 
 int rl_plan_fetch_horizon(rl_plan* p, rl_hzn* out) {
     if (!p) return fail(RL_EINVAL, "plan is NULL");
     if (!out) return fail(RL_EINVAL, "rl_plan_fetch_horizon: out is NULL");
-    if (!p->hzn_Q || !p->traj_R)
+    if (!p->hzn.Q || !p->traj_R)
         return fail(RL_EINVAL, "rl_plan_fetch_horizon: no horizon stage since the plan's last run or trajectory stage");
-    HIPCHK(hipSetDevice(p->device));
-    hipStream_t st = p->run_stream();
-    HIPCHK(hipStreamWaitEvent(st, p->ev_hzn[1], 0));    // (a later stage may have moved to another stream)
-    const size_t Q = (size_t)p->hzn_Q, M = (size_t)p->hzn_M;
-    HIPCHK(hipMemcpyAsync(p->hzn_pin, p->hzn_out, hzn_out_bytes(Q, M), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    hzn_unpack(p->hzn_pin, Q, M, out);
-    return RL_OK;
+    return query_fetch(p, p->hzn, as_rjn(*out));
 }
 
-// rl_plan_horizon with the rejoin kernel and blocks of its own: the last horizon stage stays
-// as it is.
+// blocks of its own: the last horizon stage stays as it is
 int rl_plan_rejoin(rl_plan* p, const rl_rjn_query* query, void* hip_stream) {
     if (!p) return fail(RL_EINVAL, "plan is NULL");
     if (!query) return fail(RL_EINVAL, "rejoin: the query is NULL");
     if (!p->traj_R) return fail(RL_EINVAL, "rl_plan_rejoin: no trajectory stage since the plan's last run");
     if (int rc = check_rjn(query, p->traj_R, p->N, p->closed)) return rc;
-    if (p->traj_q.index && p->traj_sel_epoch != p->sel_epoch)
-        return fail(RL_EINVAL, "rl_plan_rejoin: a selection has replaced the winners the trajectory stage read");
-    if (p->traj_mode == RL_MODE_MINCURV && p->traj_lap_epoch != p->lap_epoch)
-        return fail(RL_EINVAL, "rl_plan_rejoin: a lap stage has rewritten the rows the trajectory stage read");
-    HIPCHK(hipSetDevice(p->device));
-    hipStream_t run_st = p->run_stream();
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : run_st;
-    // the last stage's upload may still read the pinned block
-    if (p->rjn_Q) HIPCHK(hipEventSynchronize(p->ev_rjn[0]));
-    p->rjn_Q = 0;
-    const size_t Q = (size_t)query->Q, M = (size_t)query->M_cap, K = (size_t)query->K_cap;
-    if (int rc = rjn_alloc(p, Q, M, K)) return rc;
-    for (auto& e : p->ev_rjn)
-        if (!e) HIPCHK(hipEventCreate(&e));
-    if (st != run_st) HIPCHK(hipStreamWaitEvent(st, p->ev_traj[1], 0));
-    p->last_stream = st;
-    rjn_pack(query, p->rjn_pin);
-    HIPCHK(hipMemcpyAsync(p->rjn_in, p->rjn_pin, rjn_in_bytes(Q), hipMemcpyHostToDevice, st));
-    HIPCHK(hipEventRecord(p->ev_rjn[0], st));
-    const rl::RjnParams r = rjn_params(p->traj_q, query, p->rjn_in, p->rjn_out);
-    const hipError_t e = rl::launch_rejoin(r, st);
-    if (e != hipSuccess) return fail(RL_EHIP, std::string("rejoin launch: ") + hipGetErrorString(e));
-    HIPCHK(hipEventRecord(p->ev_rjn[1], st));
-    p->rjn_Q = query->Q;
-    p->rjn_M = query->M_cap;
-    p->rjn_K = query->K_cap;
-    return RL_OK;
+    return query_enqueue(p, p->rjn, *query, hip_stream);
 }
 
 int rl_plan_fetch_rejoin(rl_plan* p, rl_rjn* out) {
     if (!p) return fail(RL_EINVAL, "plan is NULL");
     if (!out) return fail(RL_EINVAL, "rl_plan_fetch_rejoin: out is NULL");
-    if (!p->rjn_Q || !p->traj_R)
+    if (!p->rjn.Q || !p->traj_R)
         return fail(RL_EINVAL, "rl_plan_fetch_rejoin: no rejoin stage since the plan's last run or trajectory stage");
-    HIPCHK(hipSetDevice(p->device));
-    hipStream_t st = p->run_stream();
-    HIPCHK(hipStreamWaitEvent(st, p->ev_rjn[1], 0));    // (a later stage may have moved to another stream)
-    const size_t Q = (size_t)p->rjn_Q, M = (size_t)p->rjn_M, K = (size_t)p->rjn_K;
-    const bool nodes = out->node_v || out->node_t;
-    HIPCHK(hipMemcpyAsync(p->rjn_pin, p->rjn_out, nodes ? rjn_out_bytes(Q, M, K) : rjn_head_bytes(Q, M),
-                          hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    rjn_unpack(p->rjn_pin, Q, M, K, out);
-    return RL_OK;
+    return query_fetch(p, p->rjn, *out);
 }
 
 }  // extern "C"

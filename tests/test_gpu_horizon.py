@@ -361,6 +361,48 @@ def test_horizon_life_cycle():
     pl.close()
 
 
+def test_a_stage_after_an_unfetched_stage_and_a_new_trajectory_stage():
+    """The order of waits of the pose-query stages' shared host path (the life-cycle test's plan):
+    a stage whose upload nobody waited for, invalidated by a trajectory stage, then a smaller
+    stage through the same pinned block; and a rejoin stage followed at once by a horizon stage,
+    each in blocks of its own."""
+    from test_gpu_rejoin import assert_rjn_equal
+
+    _lib()
+    case = O.load_case("track_training_map")
+    prob, cfg = O.case_problem(case), O.case_cfg(case)
+    N = prob.N
+    pl = raceline.Plan(prob, cfg, seeds=np.arange(4, dtype=np.uint64), B=4, modes=MC | MT)
+    pl.run()
+    full = pl.fetch()[1]
+    rows = (full.x, full.y, full.heading, full.kappa, full.v, full.ax)
+    pl.trajectory("mintime", 0.05, 256)
+    stamps = pl.fetch_trajectory().stamps
+    P1, row1, _ = plan_poses(full.x, full.y, 21, 5)
+    P2, row2, _ = plan_poses(full.x, full.y, 22, 1)
+    kw1 = dict(row=row1, dt=0.05, m_cap=32)
+    kw2 = dict(row=row2, dt=0.05, m_cap=16)
+    v1 = np.linspace(0.0, 8.0, 5)
+    hzn2 = raceline.horizon_host(*rows, prob.L / N, prob.closed, P2, stamps=stamps, **kw2)
+    rjn1 = raceline.rejoin_host(*rows, prob.L / N, prob.closed, P1, v1, cfg, stamps=stamps, k_cap=64, **kw1)
+    rjn2 = raceline.rejoin_host(*rows, prob.L / N, prob.closed, P2, 2.0, cfg, stamps=stamps, k_cap=64, **kw2)
+    pl.horizon(P1, **kw1)                                          # not fetched
+    pl.trajectory("mintime", 0.05, 256)                            # (the same rows: the same stamps)
+    _einval(pl.fetch_horizon)
+    pl.horizon(P2, **kw2)
+    assert_hzn_equal(pl.fetch_horizon(), hzn2, "horizon after an unfetched horizon")
+    pl.rejoin(P1, v1, cfg, k_cap=64, **kw1)                        # not fetched
+    pl.trajectory("mintime", 0.05, 256)
+    _einval(pl.fetch_rejoin)
+    pl.rejoin(P2, 2.0, cfg, k_cap=64, **kw2)
+    assert_rjn_equal(pl.fetch_rejoin(), rjn2, "rejoin after an unfetched rejoin")
+    pl.rejoin(P1, v1, cfg, k_cap=64, **kw1)
+    pl.horizon(P2, **kw2)                                          # at once
+    assert_rjn_equal(pl.fetch_rejoin(), rjn1, "rejoin, then a horizon at once")
+    assert_hzn_equal(pl.fetch_horizon(), hzn2, "a horizon at once after a rejoin")
+    pl.close()
+
+
 def test_horizon_reads_bound_device_outputs():
     _lib()
     case = O.load_case("track_training_map")
