@@ -24,7 +24,10 @@
 //   * outer-level state (P, n, α_total) lives in the instance's slice of the
 //     result arrays in HBM and is touched once per outer iteration; P and n cross
 //     to the corridor scan's mapping through the LDS coefficient area, and α_last
-//     is stored by the last update only;
+//     is stored by the last update only.  The closed min-curvature kernels of 8 samples
+//     per lane on several waves (C2's) keep n and α_total on chip instead, in the halves
+//     of the coefficient area their PGD loop does not read, and store α_total once, with
+//     α_last (rl_optimize_body.inc ONCHIP);
 //   * the serial v(s) recurrence runs as an exact chunked relaxation: every
 //     thread recomputes its chunk from the pass-start values with the value its
 //     neighbour published, until no published value changes; the fixed point

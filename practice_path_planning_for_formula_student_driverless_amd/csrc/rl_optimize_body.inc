@@ -211,12 +211,33 @@
     // lin-geom fills it: slot k*T+t of coef[0] holds (x, y) of sample t*K+k and the same slot
     // of coef[1] its normal; the scan replaces (x, y) of a sample with its bounds.  The global
     // stores of x, y and the normals stay (outputs, and what lin-geom, the final pass and
-    // the next update read much later), but nothing waits for them.  Not for VSPLIT, whose
+    // the next update read much later; ONCHIP below keeps the normals in LDS for those two
+    // readers and stores none), but nothing waits for them.  Not for VSPLIT, whose
     // curvature needs the path's halo of 2 (normals_kappa).
     constexpr bool LDSX = !VSPLIT;
+    // which of the linearisation's coefficients live in registers during the PGD loop (the
+    // account is with the state they are kept in, below)
+    constexpr bool ALLR = K <= 2;
+    constexpr bool A12R = ALLR || (!MT && (CLOSED || K < 8)) || (MT && CLOSED && T >= 256);   // (A1, A2) in registers instead of LDS
+    constexpr bool N0R = ALLR || (A12R && !MT);                                                // and N0
+    constexpr bool WR = ALLR;                                                                  // and W
+    // ONCHIP (the closed min-curvature kernels of 8 samples per lane on several waves: C2's
+    // (8, 256), (8, 128), (8, 512)): with A1, A2 and N0 in registers the PGD loop reads only
+    // the W half of coef[1], so the normals and alpha_total stay in the owner's own slots
+    // instead of going through global memory.  An outer iteration's life of the slots
+    // [k][tid] (no other thread touches them outside the corridor phase):
+    //   update          reads n from coef[0] and alpha_total from coef[1].x (kept in registers
+    //                   across the corridor phase), then writes P into coef[0]
+    //   normals         n into coef[1] (the scan's mapping reads P and n of any sample)
+    //   scan, collect   bounds into coef[0], read back by their owners; two barriers
+    //   lin-geom        reads n from coef[1], writes n into coef[0] and (alpha_total, W) into
+    //                   coef[1]
+    //   PGD loop        reads coef[1].y (W) only
+    // alpha_total reaches global memory once, with alpha_last, in the last update.
+    constexpr bool ONCHIP = !MT && CLOSED && K == 8 && A12R && N0R && !WR && LDSX && !GHOST && NW > 1;
     // normals_from_points_generic ref:581-593 of the own samples xs, ys (k < cnt valid): the
-    // two neighbour samples from the owners' slots (after a barrier), the normals -> NX/NY and
-    // coef[1]
+    // two neighbour samples from the owners' slots (after a barrier), the normals -> coef[1]
+    // and, unless they stay on chip (ONCHIP), NX/NY
     auto normals = [&](const double (&xs)[K], const double (&ys)[K]) RL_AI {
         if (!active) return;
         const double2* pxy = &sm.u.coef[0][0][0];
@@ -241,7 +262,9 @@
             double n = sqrt(vx * vx + vy * vy);              // geom::normalize ref:132
             double ox = 0, oy = 0;
             if (!(n < 1e-15)) { ox = vx / n; oy = vy / n; }
-            if (k < cnt) { NX[i] = ox; NY[i] = oy; }
+            if constexpr (!ONCHIP) {         // (ONCHIP: lin-geom and the update read the slots below)
+                if (k < cnt) { NX[i] = ox; NY[i] = oy; }
+            }
             pn[k * T + tid] = make_double2(ox, oy);
         }
     };
@@ -767,10 +790,7 @@
     // (profiles/r05/ab_c3_a12mt.log)
     // The latency shapes (K <= 2 samples per lane, registers to spare) hold all four
     // coefficients in registers: no LDS read on the evaluation's dependency chain
-    constexpr bool ALLR = K <= 2;
-    constexpr bool A12R = ALLR || (!MT && (CLOSED || K < 8)) || (MT && CLOSED && T >= 256);   // (A1, A2) in registers instead of LDS
-    constexpr bool N0R = ALLR || (A12R && !MT);                                                // and N0
-    constexpr bool WR = ALLR;                                                                  // and W
+    // (ALLR, A12R, N0R, WR: defined with LDSX above)
     double A1r[K], A2r[K], N0r[K], Wr[K];
 
     // One evaluation (eval_cost_grad_frozen ref:654-675 / _timeweighted ref:866-895)
@@ -994,6 +1014,7 @@
         double xs[K], ys[K];                             // P of the own samples (LDSX; 0 beyond cnt)
 #pragma unroll
         for (int k = 0; k < K; ++k) { xs[k] = 0.0; ys[k] = 0.0; }
+        double atot[ONCHIP ? K : 1] = {};                // alpha_accum from the update to lin-geom (ONCHIP)
         if (LDSX && outer == 0 && active) {              // P = center (stored above)
             const int bu = opaque(base);
 #pragma unroll
@@ -1012,13 +1033,28 @@
                 if (k < cnt) {
                     const int i = bu + k;
                     if (last_upd) ALAST[i] = al[k];
-                    xs[k] = X[i] + NX[i] * al[k];
-                    ys[k] = Y[i] + NY[i] * al[k];
-                    X[i] = xs[k];
-                    Y[i] = ys[k];
-                    double at = 0.0;
-                    if (!first_upd) at = ATOT[i];
-                    ATOT[i] = at + al[k];
+                    if constexpr (ONCHIP) {
+                        // n and alpha_accum from the own slots (lin-geom left them there; the
+                        // PGD loop writes neither).  The sum crosses the corridor phase, which
+                        // takes both areas, in atot; only the last one is an output
+                        const double2 nk = sm.u.coef[0][k][tid];
+                        xs[k] = X[i] + nk.x * al[k];
+                        ys[k] = Y[i] + nk.y * al[k];
+                        X[i] = xs[k];
+                        Y[i] = ys[k];
+                        double at = 0.0;
+                        if (!first_upd) at = sm.u.coef[1][k][tid].x;
+                        atot[k] = at + al[k];
+                        if (last_upd) ATOT[i] = atot[k];
+                    } else {
+                        xs[k] = X[i] + NX[i] * al[k];
+                        ys[k] = Y[i] + NY[i] * al[k];
+                        X[i] = xs[k];
+                        Y[i] = ys[k];
+                        double at = 0.0;
+                        if (!first_upd) at = ATOT[i];
+                        ATOT[i] = at + al[k];
+                    }
                 }
             }
         }
@@ -1217,8 +1253,18 @@
             for (int k = 0; k < K; ++k) {
                 double xp, yp, xpp, ypp;
                 deriv(px, py, k, xp, yp, xpp, ypp);
-                const int i = own(k);
-                double nxk = NX[i], nyk = NY[i];
+                double nxk, nyk;
+                if constexpr (ONCHIP) {
+                    // the own slot `normals` wrote (a padding sample's, or an inactive lane's
+                    // unwritten one, feeds only values the selects below drop); from here to
+                    // the next update the normal waits in coef[0] and alpha_accum beside W
+                    const double2 nk = sm.u.coef[1][k][tid];
+                    nxk = nk.x; nyk = nk.y;
+                    sm.u.coef[0][k][tid] = nk;
+                } else {
+                    const int i = own(k);
+                    nxk = NX[i]; nyk = NY[i];
+                }
                 double a1 = nxk * ypp - nyk * xpp;
                 double a2 = xp * nyk - yp * nxk;
                 double n0 = xp * ypp - yp * xpp;
@@ -1229,6 +1275,7 @@
                 if (N0R) N0r[k] = v ? n0 : 0.0;
                 else sm.u.coef[0][k][tid] = make_double2(v ? a1 : 0.0, v ? a2 : 0.0);
                 if (WR) Wr[k] = v ? w : 0.0;
+                else if constexpr (ONCHIP) sm.u.coef[1][k][tid] = make_double2(atot[k], v ? w : 0.0);   // (N0 is in N0r)
                 else sm.u.coef[1][k][tid] = make_double2(v ? n0 : 0.0, v ? w : 0.0);
             }
         }

@@ -1,18 +1,21 @@
 #!/usr/bin/env python3
 """Compare the gfx950 device code of two source trees, translation unit by translation unit.
 
-  scripts/isa_diff.py TREE_A TREE_B [-DRL_STAMPS=1 ...]
+  scripts/isa_diff.py [--kernels] TREE_A TREE_B [-DRL_STAMPS=1 ...]
 
 Every .hip file of build.KERNEL_SRCS is compiled in both trees to device assembly with
 build.HIPCC, build.HIP_FLAGS and that source's build.TU_FLAGS (plus the extra flags given),
 and the two listings are compared as whole files.  A source that only one tree has (a new
 kernel in a translation unit of its own) is reported and not compared.  Exit status 0: every
-source both trees have is byte-identical.
+source both trees have is byte-identical.  --kernels: for a source that differs, the same
+verdict per kernel (its instructions from its label to its end, and its kernel descriptor:
+registers, LDS, scratch), for a change that is gated to some instantiations of a template.
 Needs no GPU.  A refactor that must not change the kernels is checked with this.
 """
 from __future__ import annotations
 
 import os
+import re
 import subprocess
 import sys
 import tempfile
@@ -42,7 +45,34 @@ def listing(tree: str, src: str, extra=()):
             return f.read()
 
 
+def kernels(asm: bytes) -> dict:
+    """symbol -> its code (label to .Lfunc_end) and its .amdhsa_kernel block (registers, LDS,
+    scratch) of every global function of a listing."""
+    out, sym, desc = {}, None, None
+    for line in asm.decode(errors="replace").splitlines():
+        m = re.match(r"^(_Z\w+):", line)
+        if m and sym is None:
+            sym = m.group(1)
+            out[sym] = []
+        elif sym is not None:
+            if re.match(r"^\.Lfunc_end\d+:", line):
+                sym = None
+            else:
+                out[sym].append(line)
+        m = re.match(r"^\s*\.amdhsa_kernel\s+(\S+)", line)
+        if m:
+            desc = m.group(1)
+        elif desc is not None:
+            if ".end_amdhsa_kernel" in line:
+                desc = None
+            else:
+                out.setdefault(desc, []).append(line)
+    return out
+
+
 def main(argv) -> int:
+    by_kernel = "--kernels" in argv
+    argv = [a for a in argv if a != "--kernels"]
     trees, extra = [a for a in argv if not a.startswith("-")], [a for a in argv if a.startswith("-")]
     if len(trees) != 2:
         sys.exit(__doc__)
@@ -53,6 +83,10 @@ def main(argv) -> int:
     differ = [s for s in SRCS if s not in only and asm[(trees[0], s)] != asm[(trees[1], s)]]
     for s in SRCS:
         print(("one tree   " if s in only else "DIFFER     " if s in differ else "identical  ") + s)
+        if by_kernel and s in differ:
+            a, b = kernels(asm[(trees[0], s)]), kernels(asm[(trees[1], s)])
+            for k in sorted(set(a) | set(b)):
+                print("    " + ("one tree   " if (k in a) != (k in b) else "DIFFER     " if a[k] != b[k] else "identical  ") + k)
     return 1 if differ else 0
 
 
