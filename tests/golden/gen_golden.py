@@ -16,6 +16,10 @@ Cases:
   sweep_*               competition_map1 default N, (mu, P_max_W, lambda_smooth) grid corners,
                         time_weight_use_inv_v / use_total_ge_lat variants; both modes
   oval_n10000           synthetic oval, samples=10000 (C5); both modes
+  cfg_<edge>            training_map, closed or open, one cfg edge each (CFG_EDGES: time_gamma_power
+                        1.5 and 0, P_max_W = 0, a binding v_cap, a zero acceleration cap, the inv-v
+                        weight at its clamp, max_vpass_iters = 0, max_inner_iters = 1); both modes.
+                        `gen_golden.py --cfg-edges` regenerates only these
   geom_<case>           step 6 (compute_geom_and_save, main.cpp:1295-1335): splines, rings and the
                         full-precision rows, plus the reference's own <base>_with_geom.csv text
                         (7 tracks, training_map open, competition_map1 samples=2000);
@@ -291,38 +295,7 @@ def cli_fixtures(ref, manifest):
         print("cli", name, rc, err, len(files), "files")
 
 
-def main():
-    if "--cli" in sys.argv:
-        ref = Ref()
-        with open(os.path.join(HERE, "manifest.json")) as f:
-            manifest = json.load(f)
-        cli_fixtures(ref, manifest)
-        with open(os.path.join(HERE, "manifest.json"), "w") as f:
-            json.dump(manifest, f, indent=1, sort_keys=True)
-        shutil.rmtree(ref.tmp, ignore_errors=True)
-        return
-    if "--debug" in sys.argv:
-        ref = Ref()
-        with open(os.path.join(HERE, "manifest.json")) as f:
-            manifest = json.load(f)
-        debug_fixtures(ref, manifest)
-        with open(os.path.join(HERE, "manifest.json"), "w") as f:
-            json.dump(manifest, f, indent=1, sort_keys=True)
-        shutil.rmtree(ref.tmp, ignore_errors=True)
-        return
-    if "--geom" in sys.argv:
-        ref = Ref()
-        with open(os.path.join(HERE, "manifest.json")) as f:
-            manifest = json.load(f)
-        geom_fixtures(ref, manifest)
-        with open(os.path.join(HERE, "manifest.json"), "w") as f:
-            json.dump(manifest, f, indent=1, sort_keys=True)
-        shutil.rmtree(ref.tmp, ignore_errors=True)
-        return
-    ref = Ref()
-    manifest = {"generator": "tests/golden/gen_golden.py", "reference": "src/main.cpp sha256 e7820e5852246581...",
-                "cases": {}, "known_answers": {}}
-
+def make_case(ref, manifest):
     def case(name, inner, outer, closed=True, samples=None, tweak=None, modes=(True, True)):
         ref.reset()
         ref.lib.ref_set_closed(1 if closed else 0)
@@ -353,6 +326,75 @@ def main():
         manifest["cases"][name] = meta
         print(f"{name:28s} N={meta['N']:6d} L={inp['L']:.6f} lap={meta.get('lap', float('nan')):.6f}", flush=True)
         return inp
+
+    return case
+
+
+# cfg edges the oracle is otherwise certified for only at default-like values (tests/cfg_cases.py
+# holds the same overrides): name -> (closed, overrides); training_map, dynamic N
+CFG_EDGES = {
+    "cfg_gamma1.5": (True, dict(time_gamma_power=1.5)),
+    "cfg_gamma0": (False, dict(time_gamma_power=0.0)),
+    "cfg_power_off": (True, dict(P_max_W=0.0)),
+    "cfg_vcap_binds": (False, dict(v_cap_mps=9.0)),
+    "cfg_acc_cap0": (True, dict(a_long_acc_cap=0.0)),
+    "cfg_invv_big": (False, dict(time_weight_use_inv_v=1, inv_v_gain=4.0, P_max_W=25000.0)),
+    "cfg_vpass0": (True, dict(max_vpass_iters=0)),
+    "cfg_inner1": (False, dict(max_inner_iters=1)),
+}
+
+
+def cfg_edge_fixtures(case):
+    """`gen_golden.py --cfg-edges` regenerates only these."""
+    for name, (closed, over) in CFG_EDGES.items():
+        def tw(c, over=over):
+            for k, v in over.items():
+                setattr(c, k, v)
+        case(name, f"{REF_CSV}/training_map_inner.csv", f"{REF_CSV}/training_map_outer.csv", closed=closed, tweak=tw)
+
+
+def main():
+    if "--cli" in sys.argv:
+        ref = Ref()
+        with open(os.path.join(HERE, "manifest.json")) as f:
+            manifest = json.load(f)
+        cli_fixtures(ref, manifest)
+        with open(os.path.join(HERE, "manifest.json"), "w") as f:
+            json.dump(manifest, f, indent=1, sort_keys=True)
+        shutil.rmtree(ref.tmp, ignore_errors=True)
+        return
+    if "--cfg-edges" in sys.argv:
+        ref = Ref()
+        with open(os.path.join(HERE, "manifest.json")) as f:
+            manifest = json.load(f)
+        cfg_edge_fixtures(make_case(ref, manifest))
+        with open(os.path.join(HERE, "manifest.json"), "w") as f:
+            json.dump(manifest, f, indent=1, sort_keys=True)
+        shutil.rmtree(ref.tmp, ignore_errors=True)
+        return
+    if "--debug" in sys.argv:
+        ref = Ref()
+        with open(os.path.join(HERE, "manifest.json")) as f:
+            manifest = json.load(f)
+        debug_fixtures(ref, manifest)
+        with open(os.path.join(HERE, "manifest.json"), "w") as f:
+            json.dump(manifest, f, indent=1, sort_keys=True)
+        shutil.rmtree(ref.tmp, ignore_errors=True)
+        return
+    if "--geom" in sys.argv:
+        ref = Ref()
+        with open(os.path.join(HERE, "manifest.json")) as f:
+            manifest = json.load(f)
+        geom_fixtures(ref, manifest)
+        with open(os.path.join(HERE, "manifest.json"), "w") as f:
+            json.dump(manifest, f, indent=1, sort_keys=True)
+        shutil.rmtree(ref.tmp, ignore_errors=True)
+        return
+    ref = Ref()
+    manifest = {"generator": "tests/golden/gen_golden.py", "reference": "src/main.cpp sha256 e7820e5852246581...",
+                "cases": {}, "known_answers": {}}
+
+    case = make_case(ref, manifest)
 
     track_inputs = {}
     for tr in TRACKS:
@@ -388,6 +430,7 @@ def main():
 
     oval_in, oval_out = write_oval(ref.tmp)
     case("oval_n10000", oval_in, oval_out, samples=10000)
+    cfg_edge_fixtures(case)
 
     # known answer: shuffled rings give bit-identical hot-path inputs
     shuf = {}

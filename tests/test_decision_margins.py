@@ -17,7 +17,8 @@ import pytest
 
 import oracle_lib as O
 
-CASES = ["cmap1_n2000", "oval_n10000", "sweep_hi", "sweep_invv", "sweep_lo", "sweep_mid", "sweep_nototal",
+CASES = ["cfg_acc_cap0", "cfg_gamma0", "cfg_gamma1.5", "cfg_inner1", "cfg_invv_big", "cfg_power_off", "cfg_vcap_binds",
+         "cfg_vpass0", "cmap1_n2000", "oval_n10000", "sweep_hi", "sweep_invv", "sweep_lo", "sweep_mid", "sweep_nototal",
          "track_competition_map1", "track_competition_map2", "track_competition_map3",
          "track_competition_map_testday1", "track_competition_map_testday2", "track_competition_map_testday3",
          "track_training_map", "training_open"]
