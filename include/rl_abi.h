@@ -245,7 +245,8 @@ int rl_plan_bind_device_outputs(rl_plan* plan, int32_t which, const rl_out* dev_
  * selection stage of the last rl_plan_select (score, rank and gather kernels), 4 = the lap
  * stage of the last rl_plan_lap (5 = its preparation kernel, 6 = its evaluation kernel), 7 =
  * the trajectory stage of the last rl_plan_trajectory, 8 = the horizon stage of the last
- * rl_plan_horizon, 9 = the rejoin stage of the last rl_plan_rejoin. */
+ * rl_plan_horizon, 9 = the rejoin stage of the last rl_plan_rejoin, 10 = the stop stage of the
+ * last rl_plan_stop. */
 int rl_plan_kernel_ms(rl_plan* plan, int32_t idx, float* ms);
 /* The batch size the plan's kernel shape is chosen for (rl_kernel_shape's B); 0 = the plan's
  * own B (the default).  Shapes differ in the tree order of the J / decrease / lap sums, so
@@ -563,6 +564,86 @@ int rl_rejoin(const double* x, const double* y, const double* heading, const dou
               const double* v, const double* ax, const double* h, int32_t N, int32_t B,
               int32_t closed, const rl_rjn_query* query, int32_t device, rl_rjn* out);
 
+/* ------------------------------------------------- stop stage: brake to a target speed at a sample
+ * The horizon and rejoin stages serve profiles that are periodic or open-ended.  This stage
+ * answers "be at speed v_target when you reach sample J": the stop after the finish line, the
+ * stop before the end of the visible track, the slow zone.  It is the rejoin stage's query with
+ * a target.  A brake envelope is swept backward from the target with the car's cfg, the car's
+ * speed is marched forward under it, and the ticks follow the march up to the target.  Inside
+ * the envelope the envelope caps the speed, so a car that starts inside it meets the target.
+ * In fp64 without contraction; smax, smin, the row and ax_max_at are the rejoin stage's:
+ *   locate, nodes   the rejoin stage's: seg = i, u, e, dist2, t0, s0; kappa_k, r_k, d_k,
+ *           n_k = i + k for k = 0..K_lim, K_lim = min(K_cap, closed ? N : N-1-i).  A NaN winner,
+ *           or S = 0: seg = -1, stop_node = -1, count = 0, nothing else is specified.
+ *   target  J = stop_sample[q].  Closed rows: K_s = ((J - i - 1) mod N + N) mod N + 1, in
+ *           [1, N], the first time sample J comes up ahead of the located segment (J == i:
+ *           K_s = N, J == i + 1: K_s = 1).  Open rows: K_s = J - i.  K_s < 1 or K_s > K_lim:
+ *           out of range, stop_node = -1, count = 0, the location (seg, u, t0, s0, e, dist2) is
+ *           still written and nothing else is specified; the caller falls back on the rejoin
+ *           or the horizon stage.
+ *   envelope   serial, backward: b_{K_s} = v_target.  For k = K_s-1 .. 0:
+ *           (., a_brk) = ax_max_at(cfg, b_{k+1}, kappa_{k+1});
+ *           b_k = sqrt(smax(0.0, b_{k+1}*b_{k+1} + (2.0*a_brk)*d_k))
+ *           (the reference's backward sweep with the car's cfg).  reachable = (v0 <= b_0).
+ *   march   serial, forward, always to K_s (no early exit, no special case for v0 == r_0):
+ *           w_0 = v0, tt_0 = 0.0.  For k = 0 .. K_s-1:
+ *           (a_acc, a_brk) = ax_max_at(cfg, w_k, kappa_k);
+ *           up = sqrt(smax(0.0, w_k*w_k + (2.0*a_acc)*d_k));
+ *           dn = sqrt(smax(0.0, w_k*w_k - (2.0*a_brk)*d_k));
+ *           w_{k+1} = smin(up, (w_k <= b_k) ? smin(b_{k+1}, smax(dn, r_{k+1}))
+ *                                           : smax(dn, smin(b_{k+1}, r_{k+1})));
+ *           tt_{k+1} = tt_k + (2.0*d_k)/smax(1e-6, w_k + w_{k+1}).
+ *           A car inside the envelope stays inside it (w_{k+1} <= b_{k+1}), so reachable implies
+ *           v_end <= v_target; a car outside brakes as hard as the cfg allows.  A NaN r never
+ *           enters w.
+ *   per query   stop_node = K_s; reachable (0 or 1); with g_k = smin(b_k, r_k):
+ *           overspeed = #{k in [0, K_s] : w_k > g_k}, v_excess = the largest w_k - g_k over the
+ *           same k, or 0.0 (serial: e = 0.0, then e = smax(e, w_k - g_k) in index order);
+ *           t_stop = tt_{K_s}; v_end = w_{K_s}; s_stop = (double)n_{K_s}*h; brake_node = the
+ *           first k in [0, K_s] with b_k < r_k, where the stop starts to bind (none, a target
+ *           that is not below the row's speed: K_s).
+ *   ticks   tau_m = (double)m*dt, counted from the car.  count = #{m < M_cap : tau_m < tt_{K_s}};
+ *           every tick lies on the march: the rejoin stage's node bisection over tt[0..K_s] and
+ *           its march-tick columns s, x, y, heading, kappa, v, ax apply unchanged.  Ticks at or
+ *           after t_stop are not produced: the caller holds the target state.
+ * raceline.stop_host states the same in NumPy; the kernel equals it bit for bit.  These are
+ * additions to ABI 6.1 that leave RL_ABI_MINOR as it is: RL_FEATURE_STOP announces them. */
+typedef struct rl_stp_query {
+    rl_rjn_query   rj;           /* the rejoin stage's query, with the same meaning and checks */
+    const int32_t* stop_sample;  /* [Q] row sample J in [0, N) */
+    const double*  v_target;     /* [Q] the speed to have at J, finite and >= 0; NULL: all 0.0 */
+} rl_stp_query;
+
+typedef struct rl_stp {          /* caller-allocated; NULL fields skipped; it begins as rl_rjn does */
+    double *s, *x, *y, *heading, *kappa, *v, *ax;   /* [Q][M_cap]; ticks m >= count[q] are unspecified */
+    double *u, *t0, *s0, *e, *dist2;                /* [Q] */
+    int32_t *seg, *count;                           /* [Q] */
+    int32_t *stop_node, *overspeed;                 /* [Q] */
+    double *t_stop, *v_end;                         /* [Q] */
+    double *node_v, *node_t;                        /* [Q][K_cap+1] w_k, tt_k; entries past K_s are unspecified;
+                                                       downloaded only when asked for */
+    int32_t *reachable, *brake_node;                /* [Q] */
+    double *s_stop, *v_excess;                      /* [Q] */
+    double *node_b;                                 /* [Q][K_cap+1] b_k, as node_v */
+} rl_stp;
+
+/* Enqueue the stage after the plan's last trajectory stage: rl_plan_horizon's stream, validity
+ * and invalidation rules.  It leaves the results, the trajectory stage and the last horizon and
+ * rejoin stages untouched; its buffers are plan-owned (they count toward the plan cache's
+ * budget) and grow with Q, M_cap and K_cap.  The query's arrays and cfg are read before the
+ * call returns.  rl_plan_kernel_ms index 10 is the stage.  RL_EINVAL before any device work
+ * for: every error of rl_plan_rejoin, a NULL stop_sample, a stop_sample[q] outside [0, N), a
+ * v_target[q] that is not finite or is < 0. */
+int rl_plan_stop(rl_plan* plan, const rl_stp_query* query, void* hip_stream);
+/* Download the last stop stage (synchronises its stream) into the non-NULL fields of out.
+ * RL_EINVAL before a stage, or after a run or trajectory stage that followed it. */
+int rl_plan_fetch_stop(rl_plan* plan, rl_stp* out);
+/* The same on B given rows [B][N] with steps h [B] (host in, host out): the trajectory kernel
+ * for the stamps, then the stop kernel.  Errors as rl_rejoin's, and the query errors above. */
+int rl_stop(const double* x, const double* y, const double* heading, const double* kappa,
+            const double* v, const double* ax, const double* h, int32_t N, int32_t B,
+            int32_t closed, const rl_stp_query* query, int32_t device, rl_stp* out);
+
 /* B lap evaluations of given paths: heading/curvature
  * (heading_curv_from_points_generic, ref:595-620) and velocity_profile_forward_backward
  * (ref:782-862) with h = L[b]/N on path b — the min-time driver's final step
@@ -641,6 +722,7 @@ int         rl_abi_minor(void);
 #define RL_FEATURE_TRAJECTORY 1   /* bit 0: the trajectory stage */
 #define RL_FEATURE_HORIZON 2      /* bit 1: the horizon stage */
 #define RL_FEATURE_REJOIN 4       /* bit 2: the rejoin stage */
+#define RL_FEATURE_STOP 8         /* bit 3: the stop stage */
 int         rl_abi_features(void);
 /* samples per lane of the THROUGHPUT shape for N (4: N <= 256, 5: N <= 320, 8: N <= 4096;
  * 1 = the streaming kernel), or RL_ETOOBIG.  Batches small enough for a latency shape launch fewer samples per lane:

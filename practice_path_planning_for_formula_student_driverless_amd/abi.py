@@ -178,6 +178,30 @@ class RlRjn(C.Structure):
                 [(n, C.POINTER(C.c_double)) for n in RJN_SCAL + RJN_NODES])
 
 
+RL_FEATURE_STOP = 8        # rl_abi_features() bit 3: the stop stage
+STP_SCAL = ("t_stop", "v_end", "s_stop", "v_excess")
+STP_INTS = ("seg", "count", "stop_node", "overspeed", "reachable", "brake_node")
+STP_NODES = ("node_v", "node_t", "node_b")
+
+
+class RlStpQuery(C.Structure):
+    """``rl_stp_query`` — one ``rl_rjn_query`` plus the target samples stop_sample [Q] and the
+    speeds to have there v_target [Q] (NULL: all 0.0)."""
+
+    _fields_ = [("rj", RlRjnQuery), ("stop_sample", C.POINTER(C.c_int32)), ("v_target", C.POINTER(C.c_double))]
+
+
+class RlStp(C.Structure):
+    """``rl_stp`` — ``rl_rjn``'s layout with stop_node, overspeed, t_stop, v_end in the place of
+    its four, then reachable, brake_node, s_stop, v_excess [Q] and the optional node_b
+    [Q][K_cap + 1]; NULL fields are skipped."""
+
+    _fields_ = (RlHzn._fields_ + [(n, C.POINTER(C.c_int32)) for n in STP_INTS[2:4]] +
+                [(n, C.POINTER(C.c_double)) for n in STP_SCAL[:2] + STP_NODES[:2]] +
+                [(n, C.POINTER(C.c_int32)) for n in STP_INTS[4:]] +
+                [(n, C.POINTER(C.c_double)) for n in STP_SCAL[2:] + STP_NODES[2:]])
+
+
 OUT_F64 = ("x", "y", "heading", "kappa", "alpha_total", "alpha_last")
 OUT_F64_MT = OUT_F64 + ("v", "ax")
 
@@ -544,6 +568,14 @@ DECLS_RJN = [
     ("rl_rejoin", C.c_int, [_F64] * 7 + [C.c_int32, C.c_int32, C.c_int32, _RJNQ, C.c_int32, _RJN]),
 ]
 
+# the stop stage: bound only in a library whose rl_abi_features() has RL_FEATURE_STOP
+_STP, _STPQ = _P(RlStp), _P(RlStpQuery)
+DECLS_STP = [
+    ("rl_plan_stop", C.c_int, [C.c_void_p, _STPQ, C.c_void_p]),
+    ("rl_plan_fetch_stop", C.c_int, [C.c_void_p, _STP]),
+    ("rl_stop", C.c_int, [_F64] * 7 + [C.c_int32, C.c_int32, C.c_int32, _STPQ, C.c_int32, _STP]),
+]
+
 
 def declare_optimize(fn) -> None:
     """rl_optimize's signature (the oracle's oracle_optimize shares it)."""
@@ -556,8 +588,8 @@ _LIB = None
 def load_library(path: str = LIB_PATH) -> C.CDLL:
     """Load librl.so (the HIP path).  Raises if it is missing: there is no fallback; a library
     that lacks a function of DECLS or DECLS_EXT raises AttributeError naming it, and so does
-    one that announces RL_FEATURE_HORIZON / RL_FEATURE_REJOIN and lacks a function of DECLS_HZN /
-    DECLS_RJN."""
+    one that announces RL_FEATURE_HORIZON / RL_FEATURE_REJOIN / RL_FEATURE_STOP and lacks a
+    function of DECLS_HZN / DECLS_RJN / DECLS_STP."""
     global _LIB
     if _LIB is not None and path == LIB_PATH:
         return _LIB
@@ -579,6 +611,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         bind(DECLS_HZN)
     if ext and lib.rl_abi_features() & RL_FEATURE_REJOIN:
         bind(DECLS_RJN)
+    if ext and lib.rl_abi_features() & RL_FEATURE_STOP:
+        bind(DECLS_STP)
     if path == LIB_PATH:
         _LIB = lib
     return lib

@@ -33,14 +33,15 @@ int rows_on_device(DevArena& mem, const std::string& fn, const double* const (&i
     return RL_OK;
 }
 
-// rl_horizon / rl_rejoin (arguments checked, the device selected; K_cap = 0: the horizon): the
+// rl_horizon / rl_rejoin / rl_stop (arguments checked, the device selected; K_cap = 0: the
+// horizon; a stop_sample: the stop stage): the
 // trajectory kernel for the stamps of the host rows (one tick per row, not downloaded), then the
 // stage's kernel on them; `row` counts the B given rows
 int query_rows(const std::string& fn, const double* const (&in)[6], const double* h, int32_t N, int32_t B, int32_t closed,
-               const rl_rjn_query& q, const rl_rjn& out) {
+               const rl_stp_query& q, const rl_stp& out) {
     DevArena mem;
     rl::TrajParams t;
-    if (int rc = rows_on_device(mem, fn, in, h, N, B, closed, q.dt, 1, &t)) return rc;
+    if (int rc = rows_on_device(mem, fn, in, h, N, B, closed, q.rj.dt, 1, &t)) return rc;
     const QueryLayout L = query_layout(q);
     char* d_qry = mem.get<char>(L.in_bytes);
     char* d_res = mem.get<char>(L.out_bytes);
@@ -49,11 +50,9 @@ int query_rows(const std::string& fn, const double* const (&in)[6], const double
     query_pack(q, L, block.data());
     if (hipMemcpy(d_qry, block.data(), L.in_bytes, hipMemcpyHostToDevice) != hipSuccess) return fail(RL_EHIP, fn + ": upload");
     if (rl::launch_trajectory(t, nullptr) != hipSuccess) return fail(RL_EHIP, fn + ": trajectory kernel");
-    const rl::RjnParams r = query_params(t, q, L, d_qry, d_res);
-    if ((q.K_cap > 0 ? rl::launch_rejoin(r, nullptr) : rl::launch_horizon(r.hz, nullptr)) != hipSuccess ||
-        hipDeviceSynchronize() != hipSuccess)
+    if (query_launch(query_params(t, q, L, d_qry, d_res), nullptr) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
         return fail(RL_EHIP, fn + ": kernel");
-    if (hipMemcpy(block.data(), d_res, out.node_v || out.node_t ? L.out_bytes : L.head_bytes, hipMemcpyDeviceToHost) != hipSuccess)
+    if (hipMemcpy(block.data(), d_res, query_wants_nodes(out) ? L.out_bytes : L.head_bytes, hipMemcpyDeviceToHost) != hipSuccess)
         return fail(RL_EHIP, fn + ": download");
     query_unpack(block.data(), L, out);
     return RL_OK;
@@ -66,7 +65,7 @@ extern "C" {
 const char* rl_last_error(void) { return g_err.c_str(); }
 int rl_abi_version(void) { return RL_ABI_VERSION; }
 int rl_abi_minor(void) { return RL_ABI_MINOR; }
-int rl_abi_features(void) { return RL_FEATURE_TRAJECTORY | RL_FEATURE_HORIZON | RL_FEATURE_REJOIN; }
+int rl_abi_features(void) { return RL_FEATURE_TRAJECTORY | RL_FEATURE_HORIZON | RL_FEATURE_REJOIN | RL_FEATURE_STOP; }
 
 int rl_device_count(void) {
     int n = 0;
@@ -372,7 +371,7 @@ int rl_horizon(const double* x, const double* y, const double* heading, const do
     if (N > rl::RL_STREAM_MAX_N) return fail(RL_ETOOBIG, "rl_horizon: N exceeds 1048576");
     if (int rc = check_hzn(query, B, N, closed ? 1 : 0)) return rc;
     if (int rc = select_device(device)) return rc;
-    return query_rows("rl_horizon", {x, y, heading, kappa, v, ax}, h, N, B, closed, as_rjn(*query), as_rjn(*out));
+    return query_rows("rl_horizon", {x, y, heading, kappa, v, ax}, h, N, B, closed, as_stp(as_rjn(*query)), as_stp(as_rjn(*out)));
 }
 
 int rl_rejoin(const double* x, const double* y, const double* heading, const double* kappa, const double* v,
@@ -384,7 +383,19 @@ int rl_rejoin(const double* x, const double* y, const double* heading, const dou
     if (N > rl::RL_STREAM_MAX_N) return fail(RL_ETOOBIG, "rl_rejoin: N exceeds 1048576");
     if (int rc = check_rjn(query, B, N, closed ? 1 : 0)) return rc;
     if (int rc = select_device(device)) return rc;
-    return query_rows("rl_rejoin", {x, y, heading, kappa, v, ax}, h, N, B, closed, *query, *out);
+    return query_rows("rl_rejoin", {x, y, heading, kappa, v, ax}, h, N, B, closed, as_stp(*query), as_stp(*out));
+}
+
+int rl_stop(const double* x, const double* y, const double* heading, const double* kappa, const double* v,
+            const double* ax, const double* h, int32_t N, int32_t B, int32_t closed, const rl_stp_query* query,
+            int32_t device, rl_stp* out) {
+    if (!x || !y || !heading || !kappa || !v || !ax || !h || !query || !out)
+        return fail(RL_EINVAL, "rl_stop: an input row, h, the query or out is NULL");
+    if (B < 1 || N < 0) return fail(RL_EINVAL, "rl_stop: B < 1 or N < 0");
+    if (N > rl::RL_STREAM_MAX_N) return fail(RL_ETOOBIG, "rl_stop: N exceeds 1048576");
+    if (int rc = check_stp(query, B, N, closed ? 1 : 0)) return rc;
+    if (int rc = select_device(device)) return rc;
+    return query_rows("rl_stop", {x, y, heading, kappa, v, ax}, h, N, B, closed, *query, *out);
 }
 
 // rank host scores with rl_rank_kernel (rl_select.hip)

@@ -376,16 +376,18 @@ inline int queue_downloads(const std::vector<CopyJob>& jobs, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------ pose-query stages
-// The plan's side of one pose-query stage (horizon, rejoin).  The queries go up and the results
+// The plan's side of one pose-query stage (horizon, rejoin, stop).  The queries go up and the results
 // come down as one packed block each (in, out; rl_query.h has their layout), through one pinned
 // host block (pin) of the larger capacity; all three grow with Q, M_cap and K_cap.  ev[0] is
 // recorded after the upload, which reads pin, ev[1] after the kernel.  Q = 0: no stage since
-// the last run or trajectory stage; M, K (0 for the horizon) are that stage's M_cap and K_cap.
+// the last run or trajectory stage; M, K (0 for the horizon) are that stage's M_cap and K_cap,
+// stop whether its blocks have the stop stage's arrays.
 struct QueryStage {
     char *in = nullptr, *out = nullptr, *pin = nullptr;
     size_t in_cap = 0, out_cap = 0;
     DevArena mem;                     // in, out: they count toward the plan's dev_bytes()
     int Q = 0, M = 0, K = 0;
+    bool stop = false;
     hipEvent_t ev[2] = {nullptr, nullptr};
 
     void release_blocks() {
@@ -498,16 +500,18 @@ struct rl_plan {
     rl::DevArena traj_mem;
     int traj_cap_R = 0, traj_cap_M = 0, traj_R = 0, traj_M = 0;
     hipEvent_t ev_traj[2] = {nullptr, nullptr};
-    // pose-query stages (rl_plan_horizon, rl_plan_rejoin; rl::QueryStage): they read the last
+    // pose-query stages (rl_plan_horizon, rl_plan_rejoin, rl_plan_stop; rl::QueryStage): they read the last
     // trajectory stage through traj_q, that stage's launch parameters, which stay valid while
     // traj_R != 0 and the rows they point at are those the stamps were made from:
     // traj_sel_epoch / traj_lap_epoch are sel_epoch / lap_epoch (counted up by every selection /
     // lap stage) at that launch.  Each stage has blocks of its own, so the last horizon stage
-    // stays fetchable after a rejoin stage and the other way round.
+    // stays fetchable after a rejoin or stop stage and the other way round.
     rl::TrajParams traj_q{};
     int traj_mode = 0;
     uint32_t sel_epoch = 0, lap_epoch = 0, traj_sel_epoch = 0, traj_lap_epoch = 0;
-    rl::QueryStage hzn, rjn;
+    rl::QueryStage hzn, rjn, stp;
+    // a run or a trajectory stage invalidates the pose-query stages that read the one before
+    void drop_queries() { hzn.Q = rjn.Q = stp.Q = 0; }
 
     template <class T>
     int alloc(T** p, size_t n) {
@@ -516,7 +520,7 @@ struct rl_plan {
     }
     int nomem() const { return rl::fail(RL_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(mem.err)); }
     // device memory held (plan cache budget)
-    size_t dev_bytes() const { return mem.bytes + sel_mem.bytes + lap_mem.bytes + traj_mem.bytes + hzn.mem.bytes + rjn.mem.bytes; }
+    size_t dev_bytes() const { return mem.bytes + sel_mem.bytes + lap_mem.bytes + traj_mem.bytes + hzn.mem.bytes + rjn.mem.bytes + stp.mem.bytes; }
     // the stream of the last run or stage
     hipStream_t run_stream() const { return last_stream ? last_stream : own_stream; }
     // the batch size the kernel shape is chosen for
@@ -557,8 +561,14 @@ int check_hzn(const rl_hzn_query* q, int32_t R, int32_t N, int32_t closed);
 // argument checks shared by the rejoin entry points (no device call): check_hzn's, then v0, cfg
 // and K_cap
 int check_rjn(const rl_rjn_query* q, int32_t R, int32_t N, int32_t closed);
+// argument checks shared by the stop entry points (no device call): check_rjn's, then
+// stop_sample and v_target
+int check_stp(const rl_stp_query* q, int32_t R, int32_t N, int32_t closed);
 // the launch parameters of q on the blocks `in` and `out` (device) laid out as L, reading the
-// trajectory stage src: rl_query.h's pointers, and for a rejoin query ax_max_at's constants
-RjnParams query_params(const TrajParams& src, const rl_rjn_query& q, const QueryLayout& L, char* in, char* out);
+// trajectory stage src: rl_query.h's pointers, and for a rejoin or stop query ax_max_at's
+// constants
+StpParams query_params(const TrajParams& src, const rl_stp_query& q, const QueryLayout& L, char* in, char* out);
+// the stage's kernel for those parameters: a stop_sample: stop; K_cap > 0: rejoin; else horizon
+hipError_t query_launch(const StpParams& s, hipStream_t st);
 
 }  // namespace rl

@@ -195,6 +195,7 @@ int rl_plan_destroy(rl_plan* plan) {
         if (e) hipEventDestroy(e);
     plan->hzn.release();
     plan->rjn.release();
+    plan->stp.release();
     for (auto& e : plan->ev)
         if (e) hipEventDestroy(e);
     for (auto& e : plan->ev_end)
@@ -293,7 +294,7 @@ int rl_plan_run(rl_plan* p, void* hip_stream) {
     p->sel_mode = 0;                                   // an earlier selection is of an earlier run
     p->lap_valid = false;                              // and so is an earlier lap stage
     p->traj_R = 0;                                     // and an earlier trajectory stage
-    p->hzn.Q = p->rjn.Q = 0;                           // and the pose-query stages that read it
+    p->drop_queries();                                 // and the pose-query stages that read it
     return RL_OK;
 }
 
@@ -417,7 +418,7 @@ int rl_plan_run_group(rl_plan* const* plans, int32_t n, void* hip_stream) {
         plans[i]->sel_mode = 0;
         plans[i]->lap_valid = false;
         plans[i]->traj_R = 0;
-        plans[i]->hzn.Q = plans[i]->rjn.Q = 0;
+        plans[i]->drop_queries();
     }
     return RL_OK;
 }
@@ -429,7 +430,8 @@ int rl_plan_kernel_ms(rl_plan* p, int32_t idx, float* ms) {
     // idx 0: whole run; 1: min-curv kernel; 2: min-time kernel; 3: the selection stage
     hipEvent_t a, b;
     const bool mc = p->modes & RL_MODE_MINCURV, mt = p->modes & RL_MODE_MINTIME;
-    const rl::QueryStage& stage = idx == 9 ? p->rjn : p->hzn;   // 8: the horizon stage; 9: the rejoin stage
+    // 8: the horizon stage; 9: the rejoin stage; 10: the stop stage
+    const rl::QueryStage& stage = idx == 10 ? p->stp : idx == 9 ? p->rjn : p->hzn;
     if (idx == 0) { a = p->ev[0]; b = p->ev[3]; }
     else if (idx == 3 && p->sel_mode) {
         a = p->ev_sel[0];
@@ -447,7 +449,7 @@ int rl_plan_kernel_ms(rl_plan* p, int32_t idx, float* ms) {
         b = p->ev_traj[1];
         HIPCHK(hipEventSynchronize(b));
     }
-    else if ((idx == 8 || idx == 9) && stage.Q && p->traj_R) {
+    else if (idx >= 8 && idx <= 10 && stage.Q && p->traj_R) {
         a = stage.ev[0];
         b = stage.ev[1];
         HIPCHK(hipEventSynchronize(b));

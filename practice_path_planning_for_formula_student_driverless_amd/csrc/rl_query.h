@@ -1,15 +1,19 @@
-// rl_query.h — the packed blocks of the pose-query stages (horizon; rejoin, §3m):
-// where every array lies, and the host code that fills the queries' block, points a launch at
-// both blocks and copies a results' block out.  The horizon stage is the rejoin stage with the
-// optional parts empty, so both go through the rejoin forms (as_rjn) with K = K_cap = 0 for
-// the horizon.  No HIP call: a host compiler builds it without a device (tests/
-// test_query_layout_cpu.py).  Not part of the public ABI.
+// rl_query.h — the packed blocks of the pose-query stages (horizon; rejoin, §3m;
+// stop, §3n): where every array lies, and the host code that fills the queries' block, points a
+// launch at both blocks and copies a results' block out.  The horizon stage is the rejoin stage
+// with the optional parts empty, so both go through the rejoin forms (as_rjn) with K = K_cap =
+// 0 for the horizon.  The stop stage is the rejoin stage with a target and more results: its
+// forms (as_stp) hold the rejoin forms, and a layout with `stop` set has the extra arrays, each
+// kind behind the rejoin stage's of that kind; without it no offset or byte count moves.  No HIP
+// call: a host compiler builds it without a device (tests/test_query_layout_cpu.py,
+// tests/test_stop_layout_cpu.py).  Not part of the public ABI.
 #pragma once
 #include <cstddef>
 #include <cstring>
 
 #include "rl_abi.h"
 #include "rl_rejoin.h"
+#include "rl_stop.h"
 
 namespace rl {
 
@@ -20,18 +24,25 @@ constexpr int QRY_NODES = 2;                  // node_v, node_t
 // Byte offsets of the arrays of a stage of Q queries, M ticks and K nodes.  The queries' block:
 // pose [Q][2], v0 [Q] (rejoin), row [Q], hint [Q].  The results' block: the columns [Q][M] in
 // rl_hzn's order, the n_per doubles [Q], the n_ints ints [Q] (the head, always downloaded), the
-// n_nodes node arrays [Q][K + 1].
+// n_nodes node arrays [Q][K + 1].  A stop stage's blocks have as well: v_target [Q] and
+// stop_sample [Q] behind hint; s_stop and v_excess [Q] behind the n_per doubles, reachable and
+// brake_node [Q] behind the n_ints ints (all four in the head), node_b [Q][K + 1] behind the
+// node arrays.  Its stop_node, t_stop and v_end lie where the rejoin stage's merge_node,
+// t_merge and t_loss do.
 struct QueryLayout {
     size_t Q, M, K;
     size_t pose, v0, row, hint, in_bytes;
     int n_per, n_ints, n_nodes;
     size_t col[TRAJ_COLS], per[QRY_PER], ints[QRY_INTS], nodes[QRY_NODES], head_bytes, out_bytes;
+    bool stop;
+    size_t v_target, stop_sample, sper[STP_SCAL], sints[STP_INTS], node_b;
 };
 
-inline QueryLayout query_layout(size_t Q, size_t M, size_t K) {
+inline QueryLayout query_layout(size_t Q, size_t M, size_t K, bool stop = false) {
     QueryLayout L{};
     const bool rjn = K > 0;
     L.Q = Q; L.M = M; L.K = K;
+    L.stop = stop;
     L.n_per = HZN_LOC + (rjn ? RJN_SCAL : 0);
     L.n_ints = rjn ? QRY_INTS : 2;
     L.n_nodes = rjn ? QRY_NODES : 0;
@@ -41,13 +52,18 @@ inline QueryLayout query_layout(size_t Q, size_t M, size_t K) {
     L.v0 = take(rjn ? Q * 8 : 0);
     L.row = take(Q * 4);
     L.hint = take(Q * 4);
+    L.v_target = take(stop ? Q * 8 : 0);
+    L.stop_sample = take(stop ? Q * 4 : 0);
     L.in_bytes = at;
     at = 0;
     for (auto& o : L.col) o = take(Q * M * 8);
     for (int c = 0; c < L.n_per; ++c) L.per[c] = take(Q * 8);
+    for (auto& o : L.sper) o = take(stop ? Q * 8 : 0);
     for (int c = 0; c < L.n_ints; ++c) L.ints[c] = take(Q * 4);
+    for (auto& o : L.sints) o = take(stop ? Q * 4 : 0);
     L.head_bytes = at;
     for (int c = 0; c < L.n_nodes; ++c) L.nodes[c] = take(Q * (K + 1) * 8);
+    L.node_b = take(stop ? Q * (K + 1) * 8 : 0);
     L.out_bytes = at;
     return L;
 }
@@ -63,6 +79,23 @@ inline rl_rjn as_rjn(const rl_hzn& o) {
 }
 inline QueryLayout query_layout(const rl_rjn_query& q) { return query_layout((size_t)q.Q, (size_t)q.M_cap, (size_t)q.K_cap); }
 
+// a horizon or rejoin query and its results in the stop forms: no target, the extra fields
+// NULL; and the rejoin part of a stop stage's results (rl_stp begins with rl_rjn's fields)
+inline rl_stp_query as_stp(const rl_rjn_query& q) { return {q, nullptr, nullptr}; }
+inline rl_rjn as_rjn(const rl_stp& o) {
+    return {o.s, o.x, o.y, o.heading, o.kappa, o.v, o.ax, o.u, o.t0, o.s0, o.e, o.dist2, o.seg, o.count,
+            o.stop_node, o.overspeed, o.t_stop, o.v_end, o.node_v, o.node_t};
+}
+inline rl_stp as_stp(const rl_rjn& o) {
+    return {o.s, o.x, o.y, o.heading, o.kappa, o.v, o.ax, o.u, o.t0, o.s0, o.e, o.dist2, o.seg, o.count,
+            o.merge_node, o.overspeed, o.t_merge, o.t_loss, o.node_v, o.node_t,
+            nullptr, nullptr, nullptr, nullptr, nullptr};
+}
+// a query with a stop_sample is a stop stage's
+inline QueryLayout query_layout(const rl_stp_query& q) {
+    return query_layout((size_t)q.rj.Q, (size_t)q.rj.M_cap, (size_t)q.rj.K_cap, q.stop_sample != nullptr);
+}
+
 // fill the queries' block (host) from q: a NULL row is 0, a NULL seg_hint -1
 inline void query_pack(const rl_rjn_query& q, const QueryLayout& L, char* block) {
     std::memcpy(block + L.pose, q.pose_xy, L.Q * 16);
@@ -73,6 +106,15 @@ inline void query_pack(const rl_rjn_query& q, const QueryLayout& L, char* block)
         row[k] = q.row ? q.row[k] : 0;
         hint[k] = q.seg_hint ? q.seg_hint[k] : -1;
     }
+}
+
+// the same, and for a stop stage the targets: a NULL v_target is all 0.0
+inline void query_pack(const rl_stp_query& q, const QueryLayout& L, char* block) {
+    query_pack(q.rj, L, block);
+    if (!L.stop) return;
+    if (q.v_target) std::memcpy(block + L.v_target, q.v_target, L.Q * 8);
+    else std::memset(block + L.v_target, 0, L.Q * 8);
+    std::memcpy(block + L.stop_sample, q.stop_sample, L.Q * 4);
 }
 
 // the pointers and sizes of a launch of q on the blocks `in` and `out` (hz alone is the horizon
@@ -100,6 +142,20 @@ inline RjnParams query_pointers(const rl_rjn_query& q, const QueryLayout& L, cha
     return r;
 }
 
+// the same, and for a stop stage the pointers of its extra arrays (rj alone is the rejoin kernel's)
+inline StpParams query_pointers(const rl_stp_query& q, const QueryLayout& L, char* in, char* out) {
+    StpParams s{};
+    s.rj = query_pointers(q.rj, L, in, out);
+    if (!L.stop) return s;
+    s.v_target = (const double*)(in + L.v_target);
+    s.stop_sample = (const int32_t*)(in + L.stop_sample);
+    for (int c = 0; c < STP_SCAL; ++c) s.scal[c] = (double*)(out + L.sper[c]);
+    s.reachable = (int32_t*)(out + L.sints[0]);
+    s.brake_node = (int32_t*)(out + L.sints[1]);
+    s.node_b = (double*)(out + L.node_b);
+    return s;
+}
+
 // copy a results' block (host) into the non-NULL fields of o; with node_v and node_t NULL only
 // the head is read
 inline void query_unpack(const char* block, const QueryLayout& L, const rl_rjn& o) {
@@ -116,5 +172,21 @@ inline void query_unpack(const char* block, const QueryLayout& L, const rl_rjn& 
     for (int c = 0; c < L.n_nodes; ++c)
         if (nodes[c]) std::memcpy(nodes[c], block + L.nodes[c], L.Q * (L.K + 1) * 8);
 }
+
+// the same, and for a stop stage its extra arrays; with node_v, node_t and node_b NULL only the
+// head is read
+inline void query_unpack(const char* block, const QueryLayout& L, const rl_stp& o) {
+    query_unpack(block, L, as_rjn(o));
+    if (!L.stop) return;
+    double* const sper[STP_SCAL] = {o.s_stop, o.v_excess};
+    int32_t* const sints[STP_INTS] = {o.reachable, o.brake_node};
+    for (int c = 0; c < STP_SCAL; ++c)
+        if (sper[c]) std::memcpy(sper[c], block + L.sper[c], L.Q * 8);
+    for (int c = 0; c < STP_INTS; ++c)
+        if (sints[c]) std::memcpy(sints[c], block + L.sints[c], L.Q * 4);
+    if (o.node_b) std::memcpy(o.node_b, block + L.node_b, L.Q * (L.K + 1) * 8);
+}
+// whether a fetch into o needs the node arrays, which lie behind the head
+inline bool query_wants_nodes(const rl_stp& o) { return o.node_v || o.node_t || o.node_b; }
 
 }  // namespace rl

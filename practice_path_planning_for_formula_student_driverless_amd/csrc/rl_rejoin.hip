@@ -28,27 +28,6 @@
 
 namespace rl {
 
-// ax_max_at (ref:797-824) with the constant prefixes of RjnCfg, in the reference's operation
-// order and its select forms of std::max / std::min
-struct AxMax {
-    double acc, brk;
-};
-__device__ __forceinline__ AxMax ax_max_at(const RjnCfg& c, double vi, double ki) {
-    const double alat = vi * vi * fabs(ki);
-    const double a_res = sqrt(smax(0.0, c.a_total2 - alat * alat));
-    const double Fd = c.kFd * vi * vi;
-    const double a_power = (c.Pmax > 0 && vi > 1e-6) ? (c.Pmax / (c.mass * vi) - (Fd + c.Fr) / c.mass) : 1e9;
-    AxMax r;
-    r.acc = smax(0.0, smin(smin(a_res, c.acc_cap), a_power));
-    r.brk = smax(0.0, smin(a_res, c.brk_cap) + (Fd + c.Fr) / c.mass);
-    return r;
-}
-
-// position, heading, curvature and arc length of a march node
-struct Node {
-    double x, y, psi, kap, s;
-};
-
 // One workgroup per query, in the horizon kernel's steps with a march in the middle.  The locate
 // is hzn_locate; its barrier also publishes the stamps of a row of N <= TRAJ_LDS_N samples.
 // All lanes then stage kappa_k and r_k of the nodes k <= K_lim into LDS; lane 0 marches over
@@ -109,21 +88,8 @@ __global__ __launch_bounds__(HZN_THREADS) void rl_rejoin_kernel(RjnParams rp) {
     const double d0 = (1.0 - f.u) * h;
     const int room = q.closed ? N : N - 1 - i0;   // >= 1: i0 < S
     const int K_lim = rp.K_cap < room ? rp.K_cap : room;
-    auto sample = [&](int kk) {                    // row index of node kk >= 1 (i0 + kk < 2N)
-        const int n = i0 + kk;
-        return n >= N ? n - N : n;
-    };
-    for (int kk = tid; kk <= K_lim; kk += HZN_THREADS) {
-        if (kk == 0) {
-            const double ki = row.kap[i0], vi = row.v[i0];
-            s_kap[0] = ki + f.u * (row.kap[j0] - ki);
-            s_r[0] = vi + f.u * (row.v[j0] - vi);
-        } else {
-            const int n = sample(kk);
-            s_kap[kk] = row.kap[n];
-            s_r[kk] = row.v[n];
-        }
-    }
+    const March mr{row, s_kap, f.u, h, d0, i0, j0, N};
+    march_stage(mr, tid, K_lim, s_kap, s_r);
     __syncthreads();
     if (tid == 0) {
         double w = rp.v0[k], tt = 0.0;
@@ -204,52 +170,12 @@ __global__ __launch_bounds__(HZN_THREADS) void rl_rejoin_kernel(RjnParams rp) {
         rp.node_v[nrow + kk] = s_w[kk];
         rp.node_t[nrow + kk] = s_tt[kk];
     }
-    auto node = [&](int kk) {
-        Node n;
-        if (kk == 0) {
-            const double xi = row.x[i0], yi = row.y[i0], pi = row.psi[i0];
-            double d = row.psi[j0] - pi;
-            if (d > M_PI) d -= 2.0 * M_PI;
-            else if (d < -M_PI) d += 2.0 * M_PI;
-            n.x = xi + f.u * (row.x[j0] - xi);
-            n.y = yi + f.u * (row.y[j0] - yi);
-            n.psi = pi + f.u * d;
-            n.s = ((double)i0 + f.u) * h;
-        } else {
-            const int j = sample(kk);
-            n.x = row.x[j];
-            n.y = row.y[j];
-            n.psi = row.psi[j];
-            n.s = (double)(i0 + kk) * h;
-        }
-        n.kap = s_kap[kk];
-        return n;
-    };
     const size_t orow = (size_t)k * (size_t)p.M_cap;
     for (int m = tid; m < M; m += HZN_THREADS) {
         const double tau = (double)m * p.dt;
         const size_t o = orow + m;
         if (m < m1) {
-            int a = 0, e = kend;                   // tt_a <= tau < tt_e
-            while (e - a > 1) {
-                const int mid = a + ((e - a) >> 1);
-                if (s_tt[mid] <= tau) a = mid;
-                else e = mid;
-            }
-            const double ta = s_tt[a], tb = s_tt[a + 1], wa = s_w[a], wb = s_w[a + 1];
-            const double u = (tau - ta) / (tb - ta);
-            const double d = a == 0 ? d0 : h;
-            const Node A = node(a), B = node(a + 1);
-            double dp = B.psi - A.psi;
-            if (dp > M_PI) dp -= 2.0 * M_PI;
-            else if (dp < -M_PI) dp += 2.0 * M_PI;
-            p.out[0][o] = A.s + u * (B.s - A.s);
-            p.out[1][o] = A.x + u * (B.x - A.x);
-            p.out[2][o] = A.y + u * (B.y - A.y);
-            p.out[3][o] = A.psi + u * dp;
-            p.out[4][o] = A.kap + u * (B.kap - A.kap);
-            p.out[5][o] = wa + u * (wb - wa);
-            p.out[6][o] = d > 0.0 ? (wb * wb - wa * wa) / (2.0 * d) : 0.0;
+            march_columns(p, mr, s_w, s_tt, kend, tau, o);
         } else {
             const HznLap l = hzn_wrap(q.closed, T, tref + (tau - tte));
             hzn_columns(p, row, stamp, N, S, h, (double)c0 + l.c, l.w, o);

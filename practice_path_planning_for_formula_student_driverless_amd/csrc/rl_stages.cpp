@@ -4,7 +4,8 @@
 // stage (rl_trajectory.hip): time stamps and the state at every control tick.
 // Horizon stage (rl_horizon.hip): poses located on that stage's rows, and the next
 // ticks from there.  Rejoin stage (rl_rejoin.hip): the same from the car's speed, along a
-// reachable profile.  These two pose-query stages share one enqueue and one fetch routine.
+// reachable profile.  Stop stage (rl_stop.hip): the same under a brake envelope, up
+// to a target sample.  These three pose-query stages share one enqueue and one fetch routine.
 #include "rl_host.h"
 
 using namespace rl;
@@ -86,19 +87,37 @@ int rl::check_rjn(const rl_rjn_query* q, int32_t R, int32_t N, int32_t closed) {
     return RL_OK;
 }
 
-RjnParams rl::query_params(const TrajParams& src, const rl_rjn_query& q, const QueryLayout& L, char* in, char* out) {
-    RjnParams r = query_pointers(q, L, in, out);
+int rl::check_stp(const rl_stp_query* q, int32_t R, int32_t N, int32_t closed) {
+    if (!q) return fail(RL_EINVAL, "stop: the query is NULL");
+    if (int rc = check_rjn(&q->rj, R, N, closed)) return rc;
+    if (!q->stop_sample) return fail(RL_EINVAL, "stop: stop_sample is NULL");
+    for (int32_t k = 0; k < q->rj.Q; ++k) {
+        if (q->stop_sample[k] < 0 || q->stop_sample[k] >= N) return fail(RL_EINVAL, "stop: a stop_sample outside [0, N)");
+        if (q->v_target && (!std::isfinite(q->v_target[k]) || q->v_target[k] < 0.0))
+            return fail(RL_EINVAL, "stop: a v_target that is not finite or is < 0");
+    }
+    return RL_OK;
+}
+
+StpParams rl::query_params(const TrajParams& src, const rl_stp_query& q, const QueryLayout& L, char* in, char* out) {
+    StpParams s = query_pointers(q, L, in, out);
+    RjnParams& r = s.rj;
     r.hz.src = src;
-    if (!q.cfg) return r;                              // a horizon query
+    if (!q.rj.cfg) return s;                           // a horizon query
     // ax_max_at's constant prefixes, as the optimisers' VConst evaluates them
-    const rl_cfg& C = *q.cfg;
+    const rl_cfg& C = *q.rj.cfg;
     const double a_total = C.use_total_ge_lat ? smax_h(C.a_total_max, C.a_lat_max) : C.a_total_max;
     r.cfg.a_total2 = a_total * a_total;
     r.cfg.kFd = 0.5 * C.rho_air * C.Cd * C.A_front_m2;
     r.cfg.Fr = C.mass_kg * 9.81 * C.c_rr;
     r.cfg.mass = C.mass_kg; r.cfg.Pmax = C.P_max_W;
     r.cfg.acc_cap = C.a_long_acc_cap; r.cfg.brk_cap = C.a_long_brake_cap;
-    return r;
+    return s;
+}
+
+hipError_t rl::query_launch(const StpParams& s, hipStream_t st) {
+    if (s.stop_sample) return rl::launch_stop(s, st);
+    return s.rj.K_cap > 0 ? rl::launch_rejoin(s.rj, st) : rl::launch_horizon(s.rj.hz, st);
 }
 
 namespace {
@@ -234,12 +253,12 @@ int select_impl(rl_plan* p, const rl_select* sel, int gs, bool by_lap, void* hip
     return RL_OK;
 }
 
-// rl_plan_horizon / rl_plan_rejoin (arguments checked; K_cap = 0: the horizon): one launch of
-// the stage's kernel on the last trajectory stage.  The queries go up in one block, through
-// s's pinned block, ahead of the kernel on the same stream.
-int query_enqueue(rl_plan* p, QueryStage& s, const rl_rjn_query& q, void* hip_stream) {
-    const bool rjn = q.K_cap > 0;
-    const char* what = rjn ? "rejoin" : "horizon";
+// rl_plan_horizon / rl_plan_rejoin / rl_plan_stop (arguments checked; K_cap = 0: the horizon;
+// a stop_sample: the stop stage): one launch of the stage's kernel on the last trajectory stage.
+// The queries go up in one block, through s's pinned block, ahead of the kernel on the same
+// stream.
+int query_enqueue(rl_plan* p, QueryStage& s, const rl_stp_query& q, void* hip_stream) {
+    const char* what = q.stop_sample ? "stop" : q.rj.K_cap > 0 ? "rejoin" : "horizon";
     const std::string fn = std::string("rl_plan_") + what;
     if (p->traj_q.index && p->traj_sel_epoch != p->sel_epoch)
         return fail(RL_EINVAL, fn + ": a selection has replaced the winners the trajectory stage read");
@@ -262,24 +281,24 @@ int query_enqueue(rl_plan* p, QueryStage& s, const rl_rjn_query& q, void* hip_st
     query_pack(q, L, s.pin);
     HIPCHK(hipMemcpyAsync(s.in, s.pin, L.in_bytes, hipMemcpyHostToDevice, st));
     HIPCHK(hipEventRecord(s.ev[0], st));
-    const RjnParams r = query_params(p->traj_q, q, L, s.in, s.out);
-    const hipError_t e = rjn ? rl::launch_rejoin(r, st) : rl::launch_horizon(r.hz, st);
+    const hipError_t e = query_launch(query_params(p->traj_q, q, L, s.in, s.out), st);
     if (e != hipSuccess) return fail(RL_EHIP, std::string(what) + " launch: " + hipGetErrorString(e));
     HIPCHK(hipEventRecord(s.ev[1], st));
-    s.Q = q.Q;
-    s.M = q.M_cap;
-    s.K = q.K_cap;
+    s.Q = q.rj.Q;
+    s.M = q.rj.M_cap;
+    s.K = q.rj.K_cap;
+    s.stop = L.stop;
     return RL_OK;
 }
 
-// rl_plan_fetch_horizon / rl_plan_fetch_rejoin (a valid stage in s): the results' block comes
-// down through the pinned block, without the node arrays if o asks for neither
-int query_fetch(rl_plan* p, QueryStage& s, const rl_rjn& o) {
+// rl_plan_fetch_horizon / rl_plan_fetch_rejoin / rl_plan_fetch_stop (a valid stage in s): the
+// results' block comes down through the pinned block, without the node arrays if o asks for none
+int query_fetch(rl_plan* p, QueryStage& s, const rl_stp& o) {
     HIPCHK(hipSetDevice(p->device));
     hipStream_t st = p->run_stream();
     HIPCHK(hipStreamWaitEvent(st, s.ev[1], 0));         // (a later stage may have moved to another stream)
-    const QueryLayout L = query_layout((size_t)s.Q, (size_t)s.M, (size_t)s.K);
-    HIPCHK(hipMemcpyAsync(s.pin, s.out, o.node_v || o.node_t ? L.out_bytes : L.head_bytes, hipMemcpyDeviceToHost, st));
+    const QueryLayout L = query_layout((size_t)s.Q, (size_t)s.M, (size_t)s.K, s.stop);
+    HIPCHK(hipMemcpyAsync(s.pin, s.out, query_wants_nodes(o) ? L.out_bytes : L.head_bytes, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     query_unpack(s.pin, L, o);
     return RL_OK;
@@ -404,7 +423,7 @@ int rl_plan_trajectory(rl_plan* p, int32_t mode, int32_t rows, double dt, int32_
         return fail(RL_EINVAL, "rl_plan_trajectory: no selection of this mode since the plan's last run");
     const bool mc = mode == RL_MODE_MINCURV;
     p->traj_R = 0;
-    p->hzn.Q = p->rjn.Q = 0;                           // they read the stage before this one
+    p->drop_queries();                                 // they read the stage before this one
     if (mc && !p->lap_valid)
         if (int rc = rl_plan_lap(p, hip_stream)) return rc;
     HIPCHK(hipSetDevice(p->device));
@@ -466,7 +485,7 @@ int rl_plan_horizon(rl_plan* p, const rl_hzn_query* query, void* hip_stream) {
     if (!query) return fail(RL_EINVAL, "horizon: the query or its pose_xy is NULL");
     if (!p->traj_R) return fail(RL_EINVAL, "rl_plan_horizon: no trajectory stage since the plan's last run");
     if (int rc = check_hzn(query, p->traj_R, p->N, p->closed)) return rc;
-    return query_enqueue(p, p->hzn, as_rjn(*query), hip_stream);
+    return query_enqueue(p, p->hzn, as_stp(as_rjn(*query)), hip_stream);
 }
 
 int rl_plan_fetch_horizon(rl_plan* p, rl_hzn* out) {
@@ -474,7 +493,7 @@ int rl_plan_fetch_horizon(rl_plan* p, rl_hzn* out) {
     if (!out) return fail(RL_EINVAL, "rl_plan_fetch_horizon: out is NULL");
     if (!p->hzn.Q || !p->traj_R)
         return fail(RL_EINVAL, "rl_plan_fetch_horizon: no horizon stage since the plan's last run or trajectory stage");
-    return query_fetch(p, p->hzn, as_rjn(*out));
+    return query_fetch(p, p->hzn, as_stp(as_rjn(*out)));
 }
 
 // blocks of its own: the last horizon stage stays as it is
@@ -483,7 +502,7 @@ int rl_plan_rejoin(rl_plan* p, const rl_rjn_query* query, void* hip_stream) {
     if (!query) return fail(RL_EINVAL, "rejoin: the query is NULL");
     if (!p->traj_R) return fail(RL_EINVAL, "rl_plan_rejoin: no trajectory stage since the plan's last run");
     if (int rc = check_rjn(query, p->traj_R, p->N, p->closed)) return rc;
-    return query_enqueue(p, p->rjn, *query, hip_stream);
+    return query_enqueue(p, p->rjn, as_stp(*query), hip_stream);
 }
 
 int rl_plan_fetch_rejoin(rl_plan* p, rl_rjn* out) {
@@ -491,7 +510,24 @@ int rl_plan_fetch_rejoin(rl_plan* p, rl_rjn* out) {
     if (!out) return fail(RL_EINVAL, "rl_plan_fetch_rejoin: out is NULL");
     if (!p->rjn.Q || !p->traj_R)
         return fail(RL_EINVAL, "rl_plan_fetch_rejoin: no rejoin stage since the plan's last run or trajectory stage");
-    return query_fetch(p, p->rjn, *out);
+    return query_fetch(p, p->rjn, as_stp(*out));
+}
+
+// blocks of its own: the last horizon and rejoin stages stay as they are
+int rl_plan_stop(rl_plan* p, const rl_stp_query* query, void* hip_stream) {
+    if (!p) return fail(RL_EINVAL, "plan is NULL");
+    if (!query) return fail(RL_EINVAL, "stop: the query is NULL");
+    if (!p->traj_R) return fail(RL_EINVAL, "rl_plan_stop: no trajectory stage since the plan's last run");
+    if (int rc = check_stp(query, p->traj_R, p->N, p->closed)) return rc;
+    return query_enqueue(p, p->stp, *query, hip_stream);
+}
+
+int rl_plan_fetch_stop(rl_plan* p, rl_stp* out) {
+    if (!p) return fail(RL_EINVAL, "plan is NULL");
+    if (!out) return fail(RL_EINVAL, "rl_plan_fetch_stop: out is NULL");
+    if (!p->stp.Q || !p->traj_R)
+        return fail(RL_EINVAL, "rl_plan_fetch_stop: no stop stage since the plan's last run or trajectory stage");
+    return query_fetch(p, p->stp, *out);
 }
 
 }  // extern "C"

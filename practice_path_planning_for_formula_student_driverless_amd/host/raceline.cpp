@@ -47,6 +47,10 @@
 //   --start-speed V  with --best K --mode mintime --trajectory-dt DT: also the winners' ticks from
 //               sample 0 at speed V along the reachable speed profile (rl_rejoin), in
 //               <base>_trajectory_<r>_from_v0.csv (the same columns), and the standing-start lap
+//   --stop-sample J [--stop-speed V] [--stop-from K]  with --best K --mode mintime --trajectory-dt DT:
+//               also the winners' ticks from the sample K nodes before J (512; clipped to the row
+//               and to RL_RJN_MAX_NODES), at the raceline's own speed there, braking to V m/s (0)
+//               at sample J (rl_stop), in <base>_trajectory_<r>_stop.csv (the same columns)
 //   --score lap with --best K --mode mincurv: rank the min-curvature racelines by their lap
 //               time (the lap stage, rl_optimize_best_scored); the lap_time_s column of
 //               <base>_batch_summary.csv then holds every seed's lap
@@ -1196,7 +1200,8 @@ static void compute_mintime_and_save(const string& base, const vector<Vec2>& cen
 // B α-seeds in one launch (beyond the reference): one summary row per instance.
 static void batch_and_save(const string& base, const vector<Vec2>& center, double L, bool closed,
                            const vector<Vec2>& inner_from_mids, const vector<Vec2>& outer_from_mids, int B, int modes,
-                           int repeat, int best, bool score_lap, double traj_dt, int traj_cap, double start_speed) {
+                           int repeat, int best, bool score_lap, double traj_dt, int traj_cap, double start_speed,
+                           int stop_sample, double stop_speed, int stop_from) {
     auto& C = cfg::get();
     SegVec innerE = closed ? edges::ringEdges(inner_from_mids) : edges::polylineEdges(inner_from_mids);
     SegVec outerE = closed ? edges::ringEdges(outer_from_mids) : edges::polylineEdges(outer_from_mids);
@@ -1260,8 +1265,11 @@ static void batch_and_save(const string& base, const vector<Vec2>& center, doubl
     vector<int32_t> tcount(want_traj ? idx.size() : 0);
     // --start-speed: the rejoin stage needs the winners' whole rows and the laps T
     const bool want_rjn = want_traj && start_speed >= 0.0;
-    vector<double> wrow[4], tT(want_rjn ? idx.size() : 0);       // heading, kappa, v, ax
-    for (auto& col : wrow) col.resize(want_rjn ? idx.size() * N : 0);
+    // --stop-sample: the stop stage needs the winners' whole rows as well
+    const bool want_stp = want_traj && stop_sample >= 0;
+    const bool want_rows = want_rjn || want_stp;
+    vector<double> wrow[4], tT(want_rows ? idx.size() : 0);      // heading, kappa, v, ax
+    for (auto& col : wrow) col.resize(want_rows ? idx.size() * N : 0);
     auto run_best = [&]() {
         rl_select sel;
         std::memset(&sel, 0, sizeof(sel));
@@ -1278,7 +1286,7 @@ static void batch_and_save(const string& base, const vector<Vec2>& center, doubl
             tj.s = tcol[0].data(); tj.x = tcol[1].data(); tj.y = tcol[2].data(); tj.heading = tcol[3].data();
             tj.kappa = tcol[4].data(); tj.v = tcol[5].data(); tj.ax = tcol[6].data();
             tj.count = tcount.data();
-            if (want_rjn) {
+            if (want_rows) {
                 ob.heading = wrow[0].data(); ob.kappa = wrow[1].data(); ob.v = wrow[2].data(); ob.ax = wrow[3].data();
                 tj.T = tT.data();
             }
@@ -1372,6 +1380,61 @@ static void batch_and_save(const string& base, const vector<Vec2>& center, doubl
             o.f.write(text.data(), (std::streamsize)len);
             std::cerr << "[rejoin] winner " << r << " from " << start_speed << " m/s: merge node " << merge[r]
                       << ", standing-start lap " << tT[r] + tloss[r] << " s (flying " << tT[r] << " s)\n";
+        }
+    }
+    // <base>_trajectory_<r>_stop.csv: winner r from the sample --stop-from nodes before
+    // --stop-sample, at the raceline's own speed there, braking to --stop-speed at that sample
+    // with the limits of this run's cfg
+    if (want_stp) {
+        const size_t K = idx.size();
+        // the nodes between the pose and the target: what the row and the stage allow
+        int from = std::min(stop_from, (int)RL_RJN_MAX_NODES);
+        from = std::min(from, closed ? (int)N : stop_sample);
+        const int at = ((stop_sample - from) % (int)N + (int)N) % (int)N;   // (open rows: stop_sample - from >= 0)
+        vector<double> pose(2 * K), v0(K), vt(K, stop_speed), h(K, L / (double)N), rcol[7], tstop(K), vend(K);
+        vector<int32_t> row(K), hint(K, at), target(K, stop_sample), rcount(K), node(K), brake(K);
+        for (size_t r = 0; r < K; ++r) {
+            pose[2 * r] = bx[r * N + at];
+            pose[2 * r + 1] = by[r * N + at];
+            v0[r] = wrow[2][r * N + at];
+            row[r] = (int32_t)r;
+        }
+        for (auto& col : rcol) col.resize(K * (size_t)traj_cap);
+        rl_stp_query q;
+        std::memset(&q, 0, sizeof(q));
+        q.rj.pose_xy = pose.data(); q.rj.row = row.data(); q.rj.seg_hint = hint.data();
+        q.rj.Q = (int32_t)K; q.rj.window = 0; q.rj.M_cap = traj_cap; q.rj.dt = traj_dt;
+        q.rj.v0 = v0.data(); q.rj.cfg = &c; q.rj.K_cap = RL_RJN_MAX_NODES;
+        q.stop_sample = target.data(); q.v_target = vt.data();
+        rl_stp sp;
+        std::memset(&sp, 0, sizeof(sp));
+        sp.s = rcol[0].data(); sp.x = rcol[1].data(); sp.y = rcol[2].data(); sp.heading = rcol[3].data();
+        sp.kappa = rcol[4].data(); sp.v = rcol[5].data(); sp.ax = rcol[6].data();
+        sp.count = rcount.data(); sp.stop_node = node.data(); sp.brake_node = brake.data();
+        sp.t_stop = tstop.data(); sp.v_end = vend.data();
+        gpu::check(rl_stop(bx.data(), by.data(), wrow[0].data(), wrow[1].data(), wrow[2].data(), wrow[3].data(), h.data(),
+                           (int32_t)N, (int32_t)K, closed ? 1 : 0, &q, gpu::device, &sp),
+                   "rl_stop");
+        std::cerr << std::setprecision(9);
+        for (size_t r = 0; r < K; ++r) {
+            if (node[r] < 0) throw std::runtime_error("stop: the target is not among the nodes ahead of the pose");
+            const int64_t rows = rcount[r];
+            vector<double> tab((size_t)rows * 8);
+            for (int64_t m = 0; m < rows; ++m) {
+                tab[(size_t)m * 8] = (double)m * traj_dt;
+                for (int cc = 0; cc < 7; ++cc) tab[(size_t)m * 8 + 1 + cc] = rcol[cc][r * (size_t)traj_cap + (size_t)m];
+            }
+            vector<char> text((size_t)rows * 8 * 22 + 1);
+            int64_t len = 0;
+            gpu::check(rl_format_csv(tab.data(), rows, 8, gpu::device, text.data(), (int64_t)text.size(), &len, nullptr),
+                       "rl_format_csv");
+            io::Csv o(base + "_trajectory_" + std::to_string(r) + "_stop.csv");
+            if (!o) throw std::runtime_error("save stop trajectory failed");
+            o.f << "t,s,x,y,heading_rad,curvature,v_mps,ax_mps2\n";
+            o.f.write(text.data(), (std::streamsize)len);
+            std::cerr << "[stop] winner " << r << " from sample " << at << " to " << stop_speed << " m/s at sample " << stop_sample
+                      << ": stop: t_stop " << tstop[r] << " s, brake_node " << brake[r] << " of " << node[r] << ", v_end "
+                      << vend[r] << " m/s\n";
         }
     }
     std::cerr << "[best] " << (mt || score_lap ? "lap_time_s" : "curvature_score") << " of the " << best << " best of B=" << B << ":";
@@ -1469,7 +1532,8 @@ int run_pipeline(const string& innerPath, const string& outerPath, const string&
 
 // Steps 7-8 from the reference's step-6 files.
 int run_from_centerline(const string& outPath, double L, double s0, const string& mode, int B, int repeat, int best,
-                        const string& score, double traj_dt, int traj_cap, double start_speed) {
+                        const string& score, double traj_dt, int traj_cap, double start_speed, int stop_sample,
+                        double stop_speed, int stop_from) {
     auto& C = cfg::get();
     const string base = io::dropExt(outPath);
     const bool closed_mode = C.is_closed_track;
@@ -1521,6 +1585,29 @@ int run_from_centerline(const string& outPath, double L, double s0, const string
     } else {
         start_speed = -1.0;
     }
+    if (stop_sample != -1 || !std::isnan(stop_speed) || stop_from != 0) {
+        // (the winners' whole rows: as for --start-speed)
+        if (stop_sample == -1 || !(traj_dt > 0.0) || mode != "mintime") {
+            std::cerr << "[ERR] --stop-sample J [--stop-speed V] [--stop-from K] needs --seeds B --best K --mode mintime "
+                         "--trajectory-dt DT\n";
+            return 2;
+        }
+        const int N = (int)center_for_opt.size();
+        if (stop_sample < (closed_mode ? 0 : 1) || stop_sample >= N) {
+            std::cerr << "[ERR] --stop-sample J: a sample of the raceline, " << (closed_mode ? 0 : 1) << ".." << N - 1 << "\n";
+            return 2;
+        }
+        if (std::isnan(stop_speed)) stop_speed = 0.0;
+        if (!std::isfinite(stop_speed) || stop_speed < 0.0) {
+            std::cerr << "[ERR] --stop-speed V: finite and >= 0\n";
+            return 2;
+        }
+        if (stop_from == 0) stop_from = 512;
+        if (stop_from < 1) {
+            std::cerr << "[ERR] --stop-from K: >= 1\n";
+            return 2;
+        }
+    }
     if (B > 0) {
         const int modes = mode == "mincurv" ? RL_MODE_MINCURV
                                             : mode == "mintime" ? RL_MODE_MINTIME : RL_MODE_MINCURV | RL_MODE_MINTIME;
@@ -1533,7 +1620,7 @@ int run_from_centerline(const string& outPath, double L, double s0, const string
             return 2;
         }
         pipeline::batch_and_save(base, center_for_opt, L, closed_mode, inner, outer, B, modes, repeat, best,
-                                 score == "lap", traj_dt, traj_cap, start_speed);
+                                 score == "lap", traj_dt, traj_cap, start_speed, stop_sample, stop_speed, stop_from);
         return 0;
     }
     auto t0 = Clock::now();
@@ -1555,8 +1642,8 @@ int main(int argc, char** argv) {
     string mode = "both", stop_after;
     int B = 0, repeat = 0, best = 0;
     string score;
-    double traj_dt = 0.0, start_speed = NAN;
-    int traj_cap = 0;
+    double traj_dt = 0.0, start_speed = NAN, stop_speed = NAN;
+    int traj_cap = 0, stop_sample = -1, stop_from = 0;
     try {
         for (int i = 1; i < argc; ++i) {
             const string a = argv[i];
@@ -1576,6 +1663,15 @@ int main(int argc, char** argv) {
             else if (a == "--trajectory-dt") traj_dt = std::stod(next());
             else if (a == "--start-speed") start_speed = std::stod(next());
             else if (a == "--trajectory-cap") traj_cap = std::stoi(next());
+            else if (a == "--stop-sample") {
+                stop_sample = std::stoi(next());
+                if (stop_sample == -1) stop_sample = -2;           // (-1 stands for "not given")
+            }
+            else if (a == "--stop-speed") stop_speed = std::stod(next());
+            else if (a == "--stop-from") {
+                stop_from = std::stoi(next());
+                if (stop_from == 0) stop_from = -1;                // (0 stands for "not given")
+            }
             else if (a == "--device") gpu::device = std::stoi(next());
             else if (a == "--devices") {
                 std::stringstream ss(next());
@@ -1595,11 +1691,14 @@ int main(int argc, char** argv) {
                       << " centerline.csv [--L v] [--s0 v] [--open] [--mode m] [--seeds B] [--repeat R] [--best K]\n"
                       << "         [--score lap]   with --best K --mode mincurv: rank by the lap stage's lap time\n"
                       << "         [--trajectory-dt DT [--trajectory-cap M]]   with --best K: the winners at ticks of DT s\n"
-                      << "         [--start-speed V]   with --mode mintime --trajectory-dt: the winners from sample 0 at V m/s\n";
+                      << "         [--start-speed V]   with --mode mintime --trajectory-dt: the winners from sample 0 at V m/s\n"
+                      << "         [--stop-sample J [--stop-speed V] [--stop-from K]]   with --mode mintime --trajectory-dt: the winners\n"
+                      << "             from K (512) samples before J, braking to V (0) m/s at sample J\n";
             return 1;
         }
         if (pos.size() == 3) return run_pipeline(pos[0], pos[1], pos[2], mode, stop_after == "centerline");
-        return run_from_centerline(pos[0], L, s0, mode, B, repeat, best, score, traj_dt, traj_cap, start_speed);
+        return run_from_centerline(pos[0], L, s0, mode, B, repeat, best, score, traj_dt, traj_cap, start_speed, stop_sample,
+                                   stop_speed, stop_from);
     } catch (const std::exception& e) {
         std::cerr << "[ERR] " << e.what() << "\n";
         return 3;

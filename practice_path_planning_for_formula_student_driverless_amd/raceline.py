@@ -899,6 +899,227 @@ def rejoin(x, y, heading, kappa, v, ax, h, closed: bool, poses, v0, cfg: RlCfg, 
     return out
 
 
+# ------------------------------------------------- stop: brake to a target speed at a sample
+@dataclass
+class Stop(Horizon):
+    """The stop stage's answer for Q poses (rl_stp): Horizon's fields, with the ticks counted from
+    the car (t = m * dt) along the march up to the target, and stop_node (the march node of the
+    target sample, -1: the target is not among the nodes ahead), reachable (1: the car is inside
+    the brake envelope and meets the target), overspeed (nodes at which the car is faster than
+    the lower of the envelope and the row), brake_node (the first node at which the envelope is
+    below the row's speed), t_stop, v_end (the time and the speed at the target), s_stop (its arc
+    length), v_excess (the largest excess over the lower of the envelope and the row) [Q];
+    node_v, node_t, node_b [Q, k_cap + 1]: the march's speeds and times and the envelope, the
+    entries after node_end(q) unspecified.  Where stop_node is -1 only seg, count and the
+    location are specified."""
+
+    stop_node: np.ndarray = None
+    overspeed: np.ndarray = None
+    reachable: np.ndarray = None
+    brake_node: np.ndarray = None
+    t_stop: np.ndarray = None
+    v_end: np.ndarray = None
+    s_stop: np.ndarray = None
+    v_excess: np.ndarray = None
+    node_v: np.ndarray = None
+    node_t: np.ndarray = None
+    node_b: np.ndarray = None
+
+    @classmethod
+    def alloc(cls, Q: int, m_cap: int, dt: float, k_cap: int = 1) -> "Stop":
+        cols = {n: np.zeros((Q, m_cap)) for n in abi.TRAJ_COLS}
+        per = {n: np.zeros(Q) for n in abi.HZN_LOC + abi.STP_SCAL}
+        ints = {n: np.zeros(Q, dtype=np.int32) for n in abi.STP_INTS}
+        nodes = {n: np.zeros((Q, k_cap + 1)) for n in abi.STP_NODES}
+        return cls(**cols, **per, **ints, **nodes, dt=float(dt))
+
+    def as_c(self) -> abi.RlStp:
+        t = abi.RlStp()
+        for n in abi.TRAJ_COLS + abi.HZN_LOC + abi.STP_SCAL + abi.STP_NODES:
+            setattr(t, n, _ptr(getattr(self, n), np.float64, n))
+        for n in abi.STP_INTS:
+            setattr(t, n, _ptr(getattr(self, n), np.int32, n))
+        return t
+
+    def node_end(self, q: int) -> int:
+        """K_s: the target's march node of query q (-1: out of range)."""
+        return int(self.stop_node[q])
+
+    def row(self, q: int) -> dict:
+        """The ticks of query q: t [count[q]] = m * dt, from the car, and the seven columns."""
+        m = int(self.count[q])
+        out = {"t": np.arange(m, dtype=np.float64) * self.dt}
+        for n in abi.TRAJ_COLS:
+            out[n] = getattr(self, n)[q, :m]
+        return out
+
+
+def _stp_query(poses, v0, cfg, stop_sample, v_target, row, seg_hint, window, dt, m_cap, k_cap) -> tuple:
+    P, rw, hint, V0 = _rjn_query(poses, v0, cfg, row, seg_hint, window, dt, m_cap, k_cap)
+    Q = P.shape[0]
+    if stop_sample is None:
+        raise ValueError("stop: stop_sample is None")
+    J = np.asarray(stop_sample)
+    if J.ndim == 0:
+        J = np.broadcast_to(J, (Q,))
+    if J.shape != (Q,) or not np.issubdtype(J.dtype, np.integer):
+        raise ValueError(f"stop: stop_sample must be an integer or [Q={Q}] integers, got {J.dtype} {J.shape}")
+    J = np.ascontiguousarray(J, dtype=np.int32)
+    VT = np.asarray(0.0 if v_target is None else v_target, dtype=np.float64)
+    if VT.ndim == 0:
+        VT = np.broadcast_to(VT, (Q,))
+    if VT.shape != (Q,):
+        raise ValueError(f"stop: v_target must be a number or [Q={Q}] numbers, got shape {VT.shape}")
+    VT = np.ascontiguousarray(VT)
+    if not np.all(np.isfinite(VT)) or np.any(VT < 0.0):
+        raise ValueError("stop: v_target must be finite and >= 0")
+    return P, rw, hint, V0, J, VT
+
+
+def _stp_c(P, rw, hint, V0, cfg, J, VT, window, dt, m_cap, k_cap) -> abi.RlStpQuery:
+    """VT None: a NULL v_target, all 0.0."""
+    return abi.RlStpQuery(_rjn_c(P, rw, hint, V0, cfg, window, dt, m_cap, k_cap), _ptr(J, np.int32, "stop_sample"),
+                          None if VT is None else _ptr(VT, np.float64, "v_target"))
+
+
+def stop_host(x, y, heading, kappa, v, ax, h, closed: bool, poses, v0, cfg: RlCfg, stop_sample, v_target=None,
+              row=None, seg_hint=None, window: int = 0, dt: float = 0.05, m_cap: int = 64, k_cap: int = 1024,
+              stamps=None) -> Stop:
+    """The specification of the stop stage (include/rl_abi.h) in NumPy; the kernel
+    equals it bit for bit.  The rows, poses, hints, stamps, v0 and cfg are rejoin_host's, and so
+    are the locate and the nodes.  stop_sample (an integer or [Q]) is the row sample at which the
+    car must do v_target (a number or [Q]; None: 0.0): its node K_s is the first time that
+    sample comes up ahead of the located segment.  A brake envelope b is swept backward from
+    b[K_s] = v_target with cfg, v0 is marched forward to K_s under it (inside the envelope the
+    envelope caps the speed, outside it the car brakes as hard as cfg allows), and the ticks
+    m * dt before t_stop follow the march."""
+    rows, hs = _traj_rows(x, y, heading, kappa, v, ax, h)
+    P, rw, hint, V0, J, VT = _stp_query(poses, v0, cfg, stop_sample, v_target, row, seg_hint, window, dt, m_cap, k_cap)
+    B, N = rows[0].shape
+    if N < 1:
+        raise ValueError("stop: N == 0 (no row)")
+    Q, closed, dt, m_cap, W, k_cap = P.shape[0], bool(closed), float(dt), int(m_cap), int(window), int(k_cap)
+    S = N if closed else N - 1
+    rw = np.zeros(Q, dtype=np.int32) if rw is None else rw
+    hint = np.full(Q, -1, dtype=np.int32) if hint is None else hint
+    if np.any(rw < 0) or np.any(rw >= B):
+        raise ValueError(f"stop: row outside [0, {B})")
+    if np.any(hint < -1) or np.any(hint >= S):
+        raise ValueError(f"stop: seg_hint outside [-1, {S})")
+    if np.any(J < 0) or np.any(J >= N):
+        raise ValueError(f"stop: stop_sample outside [0, {N})")
+    stamps = _hzn_stamps(rows, hs, stamps)
+    consts = _rjn_consts(cfg)
+    out = Stop.alloc(Q, m_cap, dt, k_cap)
+    out.seg[:] = -1
+    out.stop_node[:] = -1
+    tau_all = np.arange(m_cap, dtype=np.float64) * dt
+    for q in range(Q):
+        if S < 1:
+            continue
+        row6 = [a[rw[q]] for a in rows]
+        X, Y, PSI, KAP, V, _ = row6
+        t, hb = stamps[rw[q]], float(hs[rw[q]])
+        loc = _hzn_locate(X, Y, t, hb, P[q, 0], P[q, 1], int(hint[q]), W, closed)
+        if loc is None:
+            continue
+        out.seg[q], out.u[q], out.dist2[q], out.e[q], out.t0[q], out.s0[q] = loc
+        i0, u = int(loc[0]), float(loc[1])
+        j0 = (i0 + 1) % N
+        K_lim = min(k_cap, N if closed else N - 1 - i0)
+        Ks = (int(J[q]) - i0 - 1) % N + 1 if closed else int(J[q]) - i0
+        if Ks < 1 or Ks > K_lim:
+            continue
+        n = i0 + np.arange(Ks + 1)                          # the nodes' samples, unwrapped
+        idx = n % N
+        with np.errstate(all="ignore"):
+            kap = KAP[idx].copy()
+            r = V[idx].copy()
+            kap[0] = KAP[i0] + u * (KAP[j0] - KAP[i0])
+            r[0] = V[i0] + u * (V[j0] - V[i0])
+            d0 = (1.0 - u) * hb
+        kl, rl_ = kap.tolist(), r.tolist()
+        b = [0.0] * (Ks + 1)                                # the envelope, backward from the target
+        b[Ks] = float(VT[q])
+        for k in range(Ks - 1, -1, -1):
+            d, bn = (d0 if k == 0 else hb), b[k + 1]
+            a_brk = _ax_max_at(consts, bn, kl[k + 1])[1]
+            b[k] = math.sqrt(_smax(0.0, bn * bn + (2.0 * a_brk) * d))
+        w, tt = [float(V0[q])], [0.0]                       # the march, forward to the target
+        over, ve, brake = 0, 0.0, -1
+        for k in range(Ks + 1):
+            wk = w[k]
+            g = _smin(b[k], rl_[k])
+            over += wk > g
+            ve = _smax(ve, wk - g)
+            if brake < 0 and b[k] < rl_[k]:
+                brake = k
+            if k == Ks:
+                break
+            d = d0 if k == 0 else hb
+            a_acc, a_brk = _ax_max_at(consts, wk, kl[k])
+            up = math.sqrt(_smax(0.0, wk * wk + (2.0 * a_acc) * d))
+            dn = math.sqrt(_smax(0.0, wk * wk - (2.0 * a_brk) * d))
+            if wk <= b[k]:
+                wn = _smin(up, _smin(b[k + 1], _smax(dn, rl_[k + 1])))
+            else:
+                wn = _smin(up, _smax(dn, _smin(b[k + 1], rl_[k + 1])))
+            w.append(wn)
+            tt.append(tt[k] + _fdiv(2.0 * d, _smax(1e-6, wk + wn)))
+        reach = float(V0[q]) <= b[0]
+        w, tt, b = np.array(w), np.array(tt), np.array(b)
+        out.node_v[q, :Ks + 1], out.node_t[q, :Ks + 1], out.node_b[q, :Ks + 1] = w, tt, b
+        tte = tt[Ks]
+        out.stop_node[q], out.overspeed[q], out.reachable[q] = Ks, over, 1 if reach else 0
+        out.brake_node[q] = Ks if brake < 0 else brake
+        out.t_stop[q], out.v_end[q], out.v_excess[q] = tte, w[Ks], ve
+        with np.errstate(all="ignore"):
+            out.s_stop[q] = np.float64(i0 + Ks) * hb
+            M1 = int(np.count_nonzero(tau_all < tte))           # (monotone in m: the kernel bisects)
+            out.count[q] = M1
+            if M1 > 0:
+                tau = tau_all[:M1]
+                a = _bisect_nodes(tt, tau, Ks)
+                e = a + 1
+                um = (tau - tt[a]) / (tt[e] - tt[a])
+                d = np.where(a == 0, d0, hb)
+                # the nodes' values: node 0 the located point, node k >= 1 sample n_k
+                dp0 = PSI[j0] - PSI[i0]
+                dp0 = dp0 - 2.0 * np.pi if dp0 > np.pi else (dp0 + 2.0 * np.pi if dp0 < -np.pi else dp0)
+                nx, ny, npsi = X[idx].copy(), Y[idx].copy(), PSI[idx].copy()
+                ns = n.astype(np.float64) * hb
+                nx[0] = X[i0] + u * (X[j0] - X[i0])
+                ny[0] = Y[i0] + u * (Y[j0] - Y[i0])
+                npsi[0] = PSI[i0] + u * dp0
+                ns[0] = out.s0[q]
+                dp = npsi[e] - npsi[a]
+                dp = np.where(dp > np.pi, dp - 2.0 * np.pi, np.where(dp < -np.pi, dp + 2.0 * np.pi, dp))
+                out.s[q, :M1] = ns[a] + um * (ns[e] - ns[a])
+                out.x[q, :M1] = nx[a] + um * (nx[e] - nx[a])
+                out.y[q, :M1] = ny[a] + um * (ny[e] - ny[a])
+                out.heading[q, :M1] = npsi[a] + um * dp
+                out.kappa[q, :M1] = kap[a] + um * (kap[e] - kap[a])
+                out.v[q, :M1] = w[a] + um * (w[e] - w[a])
+                out.ax[q, :M1] = np.where(d > 0.0, (w[e] * w[e] - w[a] * w[a]) / (2.0 * d), 0.0)
+    return out
+
+
+def stop(x, y, heading, kappa, v, ax, h, closed: bool, poses, v0, cfg: RlCfg, stop_sample, v_target=None, row=None,
+         seg_hint=None, window: int = 0, dt: float = 0.05, m_cap: int = 64, k_cap: int = 1024, device: int = 0) -> Stop:
+    """stop_host on the GPU (rl_stop): the trajectory kernel stamps the B given rows, then the
+    stop kernel answers the Q poses; row[q] counts the given rows."""
+    rows, hs = _traj_rows(x, y, heading, kappa, v, ax, h)
+    P, rw, hint, V0, J, VT = _stp_query(poses, v0, cfg, stop_sample, v_target, row, seg_hint, window, dt, m_cap, k_cap)
+    B, N = rows[0].shape
+    if N < 1:
+        raise ValueError("stop: N == 0 (no row)")
+    out = Stop.alloc(P.shape[0], int(m_cap), dt, int(k_cap))
+    qc, oc = _stp_c(P, rw, hint, V0, cfg, J, None if v_target is None else VT, window, dt, m_cap, k_cap), out.as_c()
+    _check(_lib().rl_stop(*[_ptr(a, np.float64, "row") for a in rows], _ptr(hs, np.float64, "h"), N, B,
+                          1 if closed else 0, C.byref(qc), int(device), C.byref(oc)))
+    return out
+
+
 def path_lengths(x, y, closed: bool, device: int = 0) -> np.ndarray:
     """L [B]: the debug dump's path_length (ref:1443-1448) of B paths given as rows x [B, N],
     y [B, N], summed on the GPU in the reference's order (rl_path_lengths): L[b] equals
@@ -1113,6 +1334,34 @@ class Plan:
             t.node_v = t.node_t = None
         _check(_lib().rl_plan_fetch_rejoin(self._h, C.byref(t)))
         out.set_k_lim(self.N, bool(self._keep[0].closed))
+        return out
+
+    def stop(self, poses, v0, cfg: RlCfg, stop_sample, v_target=None, row=None, seg_hint=None, window: int = 0,
+             dt: float = 0.05, m_cap: int = 64, k_cap: int = 1024, stream_ptr: int = 0) -> None:
+        """Enqueue the stop stage after the last trajectory() (rl_plan_stop): rejoin()'s query
+        with a target, "do v_target (None: 0.0) at row sample stop_sample".  The ticks follow
+        the march from v0 under the brake envelope of cfg up to the target, at most k_cap
+        samples ahead.  The trajectory stage and the last horizon() and rejoin() stay as they
+        are."""
+        P, rw, hint, V0, J, VT = _stp_query(poses, v0, cfg, stop_sample, v_target, row, seg_hint, window, dt, m_cap, k_cap)
+        self._stp = None
+        qc = _stp_c(P, rw, hint, V0, cfg, J, None if v_target is None else VT, window, dt, m_cap, k_cap)
+        _check(_lib().rl_plan_stop(self._h, C.byref(qc), C.c_void_p(stream_ptr) if stream_ptr else None))
+        self._stp = (P.shape[0], int(m_cap), float(dt), int(k_cap))
+
+    def fetch_stop(self, nodes: bool = True) -> Stop:
+        """Download the last stop() (rl_plan_fetch_stop); nodes=False leaves node_v, node_t, node_b
+        on the device."""
+        if getattr(self, "_stp", None) is None:
+            t = abi.RlStp()                 # (the library's own answer: no stage on this plan)
+            _check(_lib().rl_plan_fetch_stop(self._h, C.byref(t)))
+            raise ValueError("fetch_stop: no stop() on this plan")
+        Q, m_cap, dt, k_cap = self._stp
+        out = Stop.alloc(Q, m_cap, dt, k_cap)
+        t = out.as_c()
+        if not nodes:
+            t.node_v = t.node_t = t.node_b = None
+        _check(_lib().rl_plan_fetch_stop(self._h, C.byref(t)))
         return out
 
     def device_outputs(self, which: int) -> abi.RlOut:
