@@ -246,7 +246,8 @@ int rl_plan_bind_device_outputs(rl_plan* plan, int32_t which, const rl_out* dev_
  * stage of the last rl_plan_lap (5 = its preparation kernel, 6 = its evaluation kernel), 7 =
  * the trajectory stage of the last rl_plan_trajectory, 8 = the horizon stage of the last
  * rl_plan_horizon, 9 = the rejoin stage of the last rl_plan_rejoin, 10 = the stop stage of the
- * last rl_plan_stop. */
+ * last rl_plan_stop, 11 = the bounds stage of the last rl_plan_bounds, 12 = the bounds at the
+ * horizon stage's ticks of the last rl_plan_horizon_bounds. */
 int rl_plan_kernel_ms(rl_plan* plan, int32_t idx, float* ms);
 /* The batch size the plan's kernel shape is chosen for (rl_kernel_shape's B); 0 = the plan's
  * own B (the default).  Shapes differ in the tree order of the J / decrease / lap sums, so
@@ -644,6 +645,77 @@ int rl_stop(const double* x, const double* y, const double* heading, const doubl
             const double* v, const double* ax, const double* h, int32_t N, int32_t B,
             int32_t closed, const rl_stp_query* query, int32_t device, rl_stp* out);
 
+/* ------------------------------------------------- bounds stage: the free track width along the rows
+ * Every tick of the stages above carries s, x, y, heading, kappa, v, ax, and the location carries
+ * the lateral offset e.  This stage says how much room there is on either side: an MPC's track
+ * constraint at every tick, a tracker's margin for e.  It casts the optimisers' corridor
+ * (rl_corridor's device code, the plan's resident rings) about the rows of the last trajectory
+ * stage as they lie on the device.  In fp64 without contraction, per row r (the trajectory
+ * stage's row r: instance index[r] of a stage over the selected rows) and sample i, with the
+ * row's own points P_i = (x_i, y_i):
+ *   normal  normals_from_points_generic (ref:581-593): N == 1: t = (1, 0).  Closed rows:
+ *           t = (P_{(i+1) mod N} - P_{(i-1) mod N})*0.5.  Open rows: t = P_1 - P_0 at i = 0,
+ *           t = P_{N-1} - P_{N-2} at i = N-1, t = (P_{i+1} - P_{i-1})*0.5 between.
+ *           sqrt(tx*tx + ty*ty) < 1e-15: t = (1, 0).  v = (-ty, tx), l = sqrt(vx*vx + vy*vy),
+ *           (nx, ny) = l < 1e-15 ? (0, 0) : (vx/l, vy/l): +n is left of travel, the sign of the
+ *           horizon stage's e.
+ *   bounds  guard = veh_width*0.5 + margin; dpos / dneg the safe_ray distances (ref:694-699)
+ *           along +n / -n to the nearer ring; hi = max(0, dpos - guard), lo = -max(0, dneg - guard)
+ *           (ref:692-711): bit for bit rl_corridor's lo, hi for a problem whose center_xy is the
+ *           row, whose veh_width is veh_width and whose cfg.safety_margin_m is margin, zero signs
+ *           and empty rings included.
+ * At the horizon stage's ticks (rl_plan_horizon_bounds), per query q with seg >= 0 and tick
+ * m < count[q]: tau_m = t0 + (double)m*dt, the horizon stage's wrap (c, w) and its bisection on w
+ * give the tick's segment i, j = (i + 1) mod N, and with smax(a, b) = a < b ? b : a and
+ * smin(a, b) = b < a ? b : a
+ *           lo_m = smax(lo_i, lo_j), hi_m = smin(hi_i, hi_j),
+ * the conservative pair of the segment's two samples: never looser than either, no rounding.
+ * lo0, hi0 are the same pair of the located segment seg: with e, the room now is hi0 - e on the
+ * left and e - lo0 on the right.  A query with seg = -1 writes nothing that is specified.  The
+ * ticks of the rejoin and stop stages lie on march nodes, node k is sample n_k: rl_bnd's rows
+ * serve them as they are.  raceline.normals_host and raceline.horizon_bounds_host state the
+ * two new pieces in NumPy.  These are additions to ABI 6.1 that leave RL_ABI_MINOR as it is:
+ * RL_FEATURE_BOUNDS announces them. */
+typedef struct rl_bnd_query {
+    double veh_width;            /* finite */
+    double margin;               /* finite */
+} rl_bnd_query;
+
+typedef struct rl_bnd {          /* caller-allocated; NULL fields skipped */
+    double *lo, *hi, *nx, *ny;   /* [R][N] */
+} rl_bnd;
+
+typedef struct rl_hzn_bnd {      /* caller-allocated; NULL fields skipped */
+    double *lo, *hi;             /* [Q][M_cap]; ticks m >= count[q] are unspecified */
+    double *lo0, *hi0;           /* [Q] */
+} rl_hzn_bnd;
+
+/* Enqueue the stage after the plan's last trajectory stage: rl_plan_horizon's stream, validity
+ * and invalidation rules.  Bounds row r is trajectory row r for every later query.  It leaves
+ * the results, the trajectory stage and the horizon, rejoin and stop stages untouched; its
+ * buffers are plan-owned (they count toward the plan cache's budget) and grow with R.
+ * rl_plan_kernel_ms index 11 is the stage.  RL_EINVAL before any device work for: a NULL plan or
+ * query, a veh_width or margin that is not finite, no valid trajectory stage. */
+int rl_plan_bounds(rl_plan* plan, const rl_bnd_query* query, void* hip_stream);
+/* Download the last bounds stage (synchronises its stream) into the non-NULL fields of out.
+ * RL_EINVAL before a stage, or after a run or trajectory stage that followed it. */
+int rl_plan_fetch_bounds(rl_plan* plan, rl_bnd* out);
+/* Enqueue the bounds at the ticks of the last horizon stage; it reads that stage's row, seg, t0
+ * and count and the bounds stage's rows on the device and uploads nothing.  RL_EINVAL unless a
+ * valid horizon stage and a valid bounds stage follow the same trajectory stage.  A later
+ * horizon or bounds stage needs another call.  rl_plan_kernel_ms index 12 is the stage. */
+int rl_plan_horizon_bounds(rl_plan* plan, void* hip_stream);
+/* Download the last rl_plan_horizon_bounds (synchronises its stream) into the non-NULL fields of
+ * out, Q and M_cap the horizon stage's.  RL_EINVAL before one, or after a run, a trajectory,
+ * horizon or bounds stage that followed it. */
+int rl_plan_fetch_horizon_bounds(rl_plan* plan, rl_hzn_bnd* out);
+/* The same bounds for B given rows x, y [B][N] (host in, host out).  The rings, N and closed
+ * are prob's; prob->center_xy, L and veh_width are not read.  The rings are uploaded once for
+ * all rows.  RL_EINVAL before any device work for: a NULL prob, x, y or out, B < 1, N < 0, bad
+ * segments, a veh_width or margin that is not finite; RL_ETOOBIG for N > 1048576. */
+int rl_bounds(const rl_problem* prob, const double* x, const double* y, int32_t B, double veh_width,
+              double margin, int32_t device, rl_bnd* out);
+
 /* B lap evaluations of given paths: heading/curvature
  * (heading_curv_from_points_generic, ref:595-620) and velocity_profile_forward_backward
  * (ref:782-862) with h = L[b]/N on path b — the min-time driver's final step
@@ -723,6 +795,7 @@ int         rl_abi_minor(void);
 #define RL_FEATURE_HORIZON 2      /* bit 1: the horizon stage */
 #define RL_FEATURE_REJOIN 4       /* bit 2: the rejoin stage */
 #define RL_FEATURE_STOP 8         /* bit 3: the stop stage */
+#define RL_FEATURE_BOUNDS 16      /* bit 4: the bounds stage */
 int         rl_abi_features(void);
 /* samples per lane of the THROUGHPUT shape for N (4: N <= 256, 5: N <= 320, 8: N <= 4096;
  * 1 = the streaming kernel), or RL_ETOOBIG.  Batches small enough for a latency shape launch fewer samples per lane:

@@ -202,6 +202,29 @@ class RlStp(C.Structure):
                 [(n, C.POINTER(C.c_double)) for n in STP_SCAL[2:] + STP_NODES[2:]])
 
 
+RL_FEATURE_BOUNDS = 16     # rl_abi_features() bit 4: the bounds stage
+BND_ROWS = ("lo", "hi", "nx", "ny")
+HZN_BND = ("lo", "hi", "lo0", "hi0")
+
+
+class RlBndQuery(C.Structure):
+    """``rl_bnd_query`` — the vehicle width and the safety margin of the guard, both finite."""
+
+    _fields_ = [("veh_width", C.c_double), ("margin", C.c_double)]
+
+
+class RlBnd(C.Structure):
+    """``rl_bnd`` — caller-allocated lo, hi, nx, ny [R][N]; NULL fields are skipped."""
+
+    _fields_ = [(n, C.POINTER(C.c_double)) for n in BND_ROWS]
+
+
+class RlHznBnd(C.Structure):
+    """``rl_hzn_bnd`` — caller-allocated lo, hi [Q][M_cap] and lo0, hi0 [Q]; NULL fields are skipped."""
+
+    _fields_ = [(n, C.POINTER(C.c_double)) for n in HZN_BND]
+
+
 OUT_F64 = ("x", "y", "heading", "kappa", "alpha_total", "alpha_last")
 OUT_F64_MT = OUT_F64 + ("v", "ax")
 
@@ -576,6 +599,16 @@ DECLS_STP = [
     ("rl_stop", C.c_int, [_F64] * 7 + [C.c_int32, C.c_int32, C.c_int32, _STPQ, C.c_int32, _STP]),
 ]
 
+# the bounds stage: bound only in a library whose rl_abi_features() has RL_FEATURE_BOUNDS
+_BND, _BNDQ, _HZNBND = _P(RlBnd), _P(RlBndQuery), _P(RlHznBnd)
+DECLS_BND = [
+    ("rl_plan_bounds", C.c_int, [C.c_void_p, _BNDQ, C.c_void_p]),
+    ("rl_plan_fetch_bounds", C.c_int, [C.c_void_p, _BND]),
+    ("rl_plan_horizon_bounds", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("rl_plan_fetch_horizon_bounds", C.c_int, [C.c_void_p, _HZNBND]),
+    ("rl_bounds", C.c_int, [_P(RlProblem), _F64, _F64, C.c_int32, C.c_double, C.c_double, C.c_int32, _BND]),
+]
+
 
 def declare_optimize(fn) -> None:
     """rl_optimize's signature (the oracle's oracle_optimize shares it)."""
@@ -588,8 +621,8 @@ _LIB = None
 def load_library(path: str = LIB_PATH) -> C.CDLL:
     """Load librl.so (the HIP path).  Raises if it is missing: there is no fallback; a library
     that lacks a function of DECLS or DECLS_EXT raises AttributeError naming it, and so does
-    one that announces RL_FEATURE_HORIZON / RL_FEATURE_REJOIN / RL_FEATURE_STOP and lacks a
-    function of DECLS_HZN / DECLS_RJN / DECLS_STP."""
+    one that announces RL_FEATURE_HORIZON / RL_FEATURE_REJOIN / RL_FEATURE_STOP /
+    RL_FEATURE_BOUNDS and lacks a function of DECLS_HZN / DECLS_RJN / DECLS_STP / DECLS_BND."""
     global _LIB
     if _LIB is not None and path == LIB_PATH:
         return _LIB
@@ -613,6 +646,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         bind(DECLS_RJN)
     if ext and lib.rl_abi_features() & RL_FEATURE_STOP:
         bind(DECLS_STP)
+    if ext and lib.rl_abi_features() & RL_FEATURE_BOUNDS:
+        bind(DECLS_BND)
     if path == LIB_PATH:
         _LIB = lib
     return lib

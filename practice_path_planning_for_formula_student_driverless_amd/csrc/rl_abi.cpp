@@ -65,7 +65,9 @@ extern "C" {
 const char* rl_last_error(void) { return g_err.c_str(); }
 int rl_abi_version(void) { return RL_ABI_VERSION; }
 int rl_abi_minor(void) { return RL_ABI_MINOR; }
-int rl_abi_features(void) { return RL_FEATURE_TRAJECTORY | RL_FEATURE_HORIZON | RL_FEATURE_REJOIN | RL_FEATURE_STOP; }
+int rl_abi_features(void) {
+    return RL_FEATURE_TRAJECTORY | RL_FEATURE_HORIZON | RL_FEATURE_REJOIN | RL_FEATURE_STOP | RL_FEATURE_BOUNDS;
+}
 
 int rl_device_count(void) {
     int n = 0;
@@ -192,6 +194,43 @@ int rl_corridor(const rl_problem* prob, const rl_cfg* cfg, int32_t device, doubl
     if (hipMemcpy(lo, d_out, (size_t)N * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
         hipMemcpy(hi, d_out + N, (size_t)N * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
         return fail(RL_EHIP, "rl_corridor: download");
+    return RL_OK;
+}
+
+// the bounds stage's kernel (rl_bounds.hip) on B host rows: the rings go up once for all of them
+int rl_bounds(const rl_problem* prob, const double* x, const double* y, int32_t B, double veh_width, double margin,
+              int32_t device, rl_bnd* out) {
+    if (!prob || !x || !y || !out) return fail(RL_EINVAL, "rl_bounds: prob, x, y or out is NULL");
+    if (B < 1 || prob->N < 0) return fail(RL_EINVAL, "rl_bounds: B < 1 or N < 0");
+    if (prob->Ei < 0 || prob->Eo < 0 || (prob->Ei > 0 && !prob->inner_seg) || (prob->Eo > 0 && !prob->outer_seg))
+        return fail(RL_EINVAL, "rl_bounds: bad segments");
+    if (!std::isfinite(veh_width) || !std::isfinite(margin)) return fail(RL_EINVAL, "rl_bounds: veh_width or margin is not finite");
+    if (prob->N > rl::RL_STREAM_MAX_N) return fail(RL_ETOOBIG, "rl_bounds: N exceeds 1048576");
+    if (int rc = select_device(device)) return rc;
+    const int N = prob->N;
+    if (N == 0) return RL_OK;
+    const size_t BN = (size_t)B * (size_t)N;
+    const RingHost rh[2] = {make_ring(prob->inner_seg, prob->Ei), make_ring(prob->outer_seg, prob->Eo)};
+    DevArena mem;
+    DevRing ring;
+    double* d_xy = mem.get<double>(2 * BN);
+    double* d_out = mem.get<double>(4 * BN);
+    if (!ring.alloc(mem, rh)) return fail(RL_ENOMEM, "rl_bounds: hipMalloc failed");
+    rl::BndParams b{};
+    b.x = d_xy; b.y = d_xy + BN;
+    ring.fill(b.ring, rh[0].E, rh[1].E);
+    b.guard = veh_width * 0.5 + margin;                          // ref:706
+    b.lo = d_out; b.hi = d_out + BN; b.nx = d_out + 2 * BN; b.ny = d_out + 3 * BN;
+    b.N = N; b.B = B; b.R = B; b.closed = prob->closed ? 1 : 0;
+    if (hipMemcpy(d_xy, x, BN * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_xy + BN, y, BN * sizeof(double), hipMemcpyHostToDevice) != hipSuccess || !ring.upload(rh, nullptr))
+        return fail(RL_EHIP, "rl_bounds: upload");
+    if (rl::launch_bounds(b, nullptr) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+        return fail(RL_EHIP, "rl_bounds: kernel");
+    double* const dst[4] = {out->lo, out->hi, out->nx, out->ny};
+    for (int c = 0; c < 4; ++c)
+        if (dst[c] && hipMemcpy(dst[c], d_out + (size_t)c * BN, BN * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(RL_EHIP, "rl_bounds: download");
     return RL_OK;
 }
 

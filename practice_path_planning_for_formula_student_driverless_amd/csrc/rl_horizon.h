@@ -155,21 +155,28 @@ __device__ __forceinline__ HznLap hzn_wrap(int closed, double T, double tau) {
     return {c, w};
 }
 
-// the source rows of one instance, and a tick's seven columns at row time w in lap c, written to
-// element o of p.out: §3k's bisection on w over stamp(0 .. S), then §3l's columns
-struct HznRow {
-    const double *x, *y, *psi, *kap, *v, *ax;
-};
+// the segment of row time w: §3k's bisection on w over stamp(0 .. S) (the bounds stage's tick
+// kernel, rl_bounds.hip, takes its segments from here too)
 template <class Stamp>
-__device__ __forceinline__ void hzn_columns(const HznParams& p, const HznRow& r, const Stamp& stamp, int N, int S,
-                                            double h, double c, double w, size_t o) {
+__device__ __forceinline__ int hzn_segment(const Stamp& stamp, int S, double w) {
     int a = 0, e = S;                          // t_a <= w < t_e on a sorted row; clipped otherwise
     while (e - a > 1) {
         const int mid = a + ((e - a) >> 1);
         if (stamp(mid) <= w) a = mid;
         else e = mid;
     }
-    const int i = a, jn = i + 1 < N ? i + 1 : 0;
+    return a;
+}
+
+// the source rows of one instance, and a tick's seven columns at row time w in lap c, written to
+// element o of p.out: hzn_segment's segment, then §3l's columns
+struct HznRow {
+    const double *x, *y, *psi, *kap, *v, *ax;
+};
+template <class Stamp>
+__device__ __forceinline__ void hzn_columns(const HznParams& p, const HznRow& r, const Stamp& stamp, int N, int S,
+                                            double h, double c, double w, size_t o) {
+    const int i = hzn_segment(stamp, S, w), jn = i + 1 < N ? i + 1 : 0;
     const double ta = stamp(i), tb = stamp(i + 1);
     const double u = (w - ta) / (tb - ta);
     const double xi = r.x[i], yi = r.y[i], vi = r.v[i], ki = r.kap[i], pi = r.psi[i];

@@ -22,6 +22,7 @@
 #include "rl_horizon.h"
 #include "rl_rejoin.h"
 #include "rl_query.h"
+#include "rl_bounds.h"
 
 namespace rl {
 
@@ -388,6 +389,7 @@ struct QueryStage {
     DevArena mem;                     // in, out: they count toward the plan's dev_bytes()
     int Q = 0, M = 0, K = 0;
     bool stop = false;
+    double dt = 0;                    // that stage's tick step (the bounds stage's tick kernel reads it)
     hipEvent_t ev[2] = {nullptr, nullptr};
 
     void release_blocks() {
@@ -510,8 +512,24 @@ struct rl_plan {
     int traj_mode = 0;
     uint32_t sel_epoch = 0, lap_epoch = 0, traj_sel_epoch = 0, traj_lap_epoch = 0;
     rl::QueryStage hzn, rjn, stp;
-    // a run or a trajectory stage invalidates the pose-query stages that read the one before
-    void drop_queries() { hzn.Q = rjn.Q = stp.Q = 0; }
+    // bounds stage (rl_plan_bounds, rl::BndParams): lo, hi, nx, ny [bnd_R][N] of the last
+    // trajectory stage's rows, row for row, in buffers sized for bnd_cap_R rows; bnd_R = 0: no
+    // stage since the last run or trajectory stage.  Its tick kernel (rl_plan_horizon_bounds)
+    // reads them and the last horizon stage's results: lo, hi [hb_Q][hb_M] and lo0, hi0 [hb_Q] in
+    // buffers of hb_cap_QM and hb_cap_Q doubles; hb_Q = 0: none since the last horizon or bounds
+    // stage.
+    double* bnd[4] = {};              // lo, hi, nx, ny (rl_bnd's order)
+    rl::DevArena bnd_mem;
+    int bnd_cap_R = 0, bnd_R = 0;
+    hipEvent_t ev_bnd[2] = {nullptr, nullptr};
+    double* hb[4] = {};               // lo, hi, lo0, hi0 (rl_hzn_bnd's order)
+    rl::DevArena hb_mem;
+    size_t hb_cap_QM = 0, hb_cap_Q = 0;
+    int hb_Q = 0, hb_M = 0;
+    hipEvent_t ev_hb[2] = {nullptr, nullptr};
+    // a run or a trajectory stage invalidates the pose-query stages that read the one before,
+    // and the bounds of its rows
+    void drop_queries() { hzn.Q = rjn.Q = stp.Q = bnd_R = hb_Q = 0; }
 
     template <class T>
     int alloc(T** p, size_t n) {
@@ -520,7 +538,10 @@ struct rl_plan {
     }
     int nomem() const { return rl::fail(RL_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(mem.err)); }
     // device memory held (plan cache budget)
-    size_t dev_bytes() const { return mem.bytes + sel_mem.bytes + lap_mem.bytes + traj_mem.bytes + hzn.mem.bytes + rjn.mem.bytes + stp.mem.bytes; }
+    size_t dev_bytes() const {
+        return mem.bytes + sel_mem.bytes + lap_mem.bytes + traj_mem.bytes + hzn.mem.bytes + rjn.mem.bytes + stp.mem.bytes +
+               bnd_mem.bytes + hb_mem.bytes;
+    }
     // the stream of the last run or stage
     hipStream_t run_stream() const { return last_stream ? last_stream : own_stream; }
     // the batch size the kernel shape is chosen for

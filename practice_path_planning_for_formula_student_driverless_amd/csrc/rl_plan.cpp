@@ -196,6 +196,12 @@ int rl_plan_destroy(rl_plan* plan) {
     plan->hzn.release();
     plan->rjn.release();
     plan->stp.release();
+    plan->bnd_mem.release();
+    plan->hb_mem.release();
+    for (auto& e : plan->ev_bnd)
+        if (e) hipEventDestroy(e);
+    for (auto& e : plan->ev_hb)
+        if (e) hipEventDestroy(e);
     for (auto& e : plan->ev)
         if (e) hipEventDestroy(e);
     for (auto& e : plan->ev_end)
@@ -452,6 +458,16 @@ int rl_plan_kernel_ms(rl_plan* p, int32_t idx, float* ms) {
     else if (idx >= 8 && idx <= 10 && stage.Q && p->traj_R) {
         a = stage.ev[0];
         b = stage.ev[1];
+        HIPCHK(hipEventSynchronize(b));
+    }
+    else if (idx == 11 && p->bnd_R && p->traj_R) {      // 11: the bounds stage
+        a = p->ev_bnd[0];
+        b = p->ev_bnd[1];
+        HIPCHK(hipEventSynchronize(b));
+    }
+    else if (idx == 12 && p->hb_Q && p->traj_R) {       // 12: the bounds at the horizon stage's ticks
+        a = p->ev_hb[0];
+        b = p->ev_hb[1];
         HIPCHK(hipEventSynchronize(b));
     }
     else if (idx == 1 && mc) { a = p->ev[1]; b = p->ev_end[0]; }

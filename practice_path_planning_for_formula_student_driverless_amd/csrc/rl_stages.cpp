@@ -6,6 +6,8 @@
 // ticks from there.  Rejoin stage (rl_rejoin.hip): the same from the car's speed, along a
 // reachable profile.  Stop stage (rl_stop.hip): the same under a brake envelope, up
 // to a target sample.  These three pose-query stages share one enqueue and one fetch routine.
+// Bounds stage (rl_bounds.hip): the free track width about the trajectory stage's
+// rows, and at the horizon stage's ticks.
 #include "rl_host.h"
 
 using namespace rl;
@@ -272,6 +274,7 @@ int query_enqueue(rl_plan* p, QueryStage& s, const rl_stp_query& q, void* hip_st
     // recorded is complete).
     if (s.ev[0]) HIPCHK(hipEventSynchronize(s.ev[0]));
     s.Q = 0;
+    if (&s == &p->hzn) p->hb_Q = 0;                    // the tick bounds of the horizon stage before
     const QueryLayout L = query_layout(q);
     if (int rc = s.reserve(p->last_stream, L.in_bytes, L.out_bytes, what)) return rc;
     for (auto& e : s.ev)
@@ -288,6 +291,43 @@ int query_enqueue(rl_plan* p, QueryStage& s, const rl_stp_query& q, void* hip_st
     s.M = q.rj.M_cap;
     s.K = q.rj.K_cap;
     s.stop = L.stop;
+    s.dt = q.rj.dt;
+    return RL_OK;
+}
+
+// plan-owned bounds buffers for R rows; they count toward dev_bytes()
+int bounds_alloc(rl_plan* p, int R) {
+    if (p->bnd[0] && R <= p->bnd_cap_R) return RL_OK;
+    if (p->last_stream) HIPCHK(hipStreamSynchronize(p->last_stream));   // it may still use the old ones
+    DevArena& a = p->bnd_mem;
+    a.release();
+    p->bnd_cap_R = 0;
+    for (auto& b : p->bnd) b = a.get<double>((size_t)R * (size_t)p->N);
+    if (!a.ok()) {
+        a.release();
+        for (auto& b : p->bnd) b = nullptr;
+        return fail(RL_ENOMEM, "hipMalloc (bounds buffers) failed");
+    }
+    p->bnd_cap_R = R;
+    return RL_OK;
+}
+
+// plan-owned buffers of the bounds at Q queries' M ticks each; they count toward dev_bytes()
+int horizon_bounds_alloc(rl_plan* p, size_t Q, size_t M) {
+    if (p->hb[0] && Q * M <= p->hb_cap_QM && Q <= p->hb_cap_Q) return RL_OK;
+    if (p->last_stream) HIPCHK(hipStreamSynchronize(p->last_stream));
+    DevArena& a = p->hb_mem;
+    a.release();
+    const size_t QM = std::max(Q * M, p->hb_cap_QM), Qc = std::max(Q, p->hb_cap_Q);
+    p->hb_cap_QM = p->hb_cap_Q = 0;
+    for (int c = 0; c < 4; ++c) p->hb[c] = a.get<double>(c < 2 ? QM : Qc);
+    if (!a.ok()) {
+        a.release();
+        for (auto& b : p->hb) b = nullptr;
+        return fail(RL_ENOMEM, "hipMalloc (horizon bounds buffers) failed");
+    }
+    p->hb_cap_QM = QM;
+    p->hb_cap_Q = Qc;
     return RL_OK;
 }
 
@@ -528,6 +568,108 @@ int rl_plan_fetch_stop(rl_plan* p, rl_stp* out) {
     if (!p->stp.Q || !p->traj_R)
         return fail(RL_EINVAL, "rl_plan_fetch_stop: no stop stage since the plan's last run or trajectory stage");
     return query_fetch(p, p->stp, *out);
+}
+
+// One launch of rl_bounds_kernel over the rows the last trajectory stage read: its x, y and
+// index, the plan's resident rings.  Buffers of its own: every other stage stays as it is.
+int rl_plan_bounds(rl_plan* p, const rl_bnd_query* query, void* hip_stream) {
+    if (!p) return fail(RL_EINVAL, "plan is NULL");
+    if (!query) return fail(RL_EINVAL, "bounds: the query is NULL");
+    if (!std::isfinite(query->veh_width) || !std::isfinite(query->margin))
+        return fail(RL_EINVAL, "bounds: veh_width or margin is not finite");
+    if (!p->traj_R) return fail(RL_EINVAL, "rl_plan_bounds: no trajectory stage since the plan's last run");
+    if (p->traj_q.index && p->traj_sel_epoch != p->sel_epoch)
+        return fail(RL_EINVAL, "rl_plan_bounds: a selection has replaced the winners the trajectory stage read");
+    if (p->traj_mode == RL_MODE_MINCURV && p->traj_lap_epoch != p->lap_epoch)
+        return fail(RL_EINVAL, "rl_plan_bounds: a lap stage has rewritten the rows the trajectory stage read");
+    HIPCHK(hipSetDevice(p->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : p->run_stream();
+    p->bnd_R = p->hb_Q = 0;                            // (the tick bounds read the stage before this one)
+    if (int rc = bounds_alloc(p, p->traj_R)) return rc;
+    for (auto& e : p->ev_bnd)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    HIPCHK(hipStreamWaitEvent(st, p->ev_traj[1], 0));
+    p->last_stream = st;
+    HIPCHK(hipEventRecord(p->ev_bnd[0], st));
+    const TrajParams& t = p->traj_q;
+    rl::BndParams b{};
+    b.x = t.x; b.y = t.y;
+    b.index = t.index;
+    p->ring.fill(b.ring, p->Ei, p->Eo);
+    b.guard = query->veh_width * 0.5 + query->margin;  // ref:706, as rl_corridor forms it
+    b.lo = p->bnd[0]; b.hi = p->bnd[1]; b.nx = p->bnd[2]; b.ny = p->bnd[3];
+    b.N = t.N; b.B = t.B; b.R = t.R; b.closed = t.closed;
+    const hipError_t e = rl::launch_bounds(b, st);
+    if (e != hipSuccess) return fail(RL_EHIP, std::string("bounds launch: ") + hipGetErrorString(e));
+    HIPCHK(hipEventRecord(p->ev_bnd[1], st));
+    p->bnd_R = t.R;
+    return RL_OK;
+}
+
+int rl_plan_fetch_bounds(rl_plan* p, rl_bnd* out) {
+    if (!p) return fail(RL_EINVAL, "plan is NULL");
+    if (!out) return fail(RL_EINVAL, "rl_plan_fetch_bounds: out is NULL");
+    if (!p->bnd_R || !p->traj_R)
+        return fail(RL_EINVAL, "rl_plan_fetch_bounds: no bounds stage since the plan's last run or trajectory stage");
+    HIPCHK(hipSetDevice(p->device));
+    hipStream_t st = p->run_stream();
+    HIPCHK(hipStreamWaitEvent(st, p->ev_bnd[1], 0));    // (a later stage may have moved to another stream)
+    double* const dst[4] = {out->lo, out->hi, out->nx, out->ny};
+    std::vector<CopyJob> jobs;
+    for (int c = 0; c < 4; ++c) add_job(jobs, dst[c], p->bnd[c], (size_t)p->bnd_R * (size_t)p->N * 8);
+    if (int rc = queue_downloads(jobs, st)) return rc;
+    HIPCHK(hipStreamSynchronize(st));
+    return RL_OK;
+}
+
+// One launch of rl_horizon_bounds_kernel on what the last horizon stage left in its results'
+// block and the bounds stage's rows: no upload.
+int rl_plan_horizon_bounds(rl_plan* p, void* hip_stream) {
+    if (!p) return fail(RL_EINVAL, "plan is NULL");
+    if (!p->traj_R || !p->hzn.Q || !p->bnd_R)
+        return fail(RL_EINVAL, "rl_plan_horizon_bounds: no horizon stage and bounds stage since the plan's last trajectory stage");
+    HIPCHK(hipSetDevice(p->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : p->run_stream();
+    const QueryStage& s = p->hzn;
+    p->hb_Q = 0;
+    if (int rc = horizon_bounds_alloc(p, (size_t)s.Q, (size_t)s.M)) return rc;
+    for (auto& e : p->ev_hb)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    HIPCHK(hipStreamWaitEvent(st, s.ev[1], 0));
+    HIPCHK(hipStreamWaitEvent(st, p->ev_bnd[1], 0));
+    p->last_stream = st;
+    HIPCHK(hipEventRecord(p->ev_hb[0], st));
+    // the horizon stage's launch again, as query_enqueue made it
+    rl_rjn_query q{};
+    q.Q = s.Q; q.M_cap = s.M; q.dt = s.dt;
+    rl::HznBndParams h{};
+    h.hz = query_pointers(q, query_layout((size_t)s.Q, (size_t)s.M, 0), s.in, s.out).hz;
+    h.hz.src = p->traj_q;
+    h.lo = p->bnd[0]; h.hi = p->bnd[1];
+    h.tlo = p->hb[0]; h.thi = p->hb[1]; h.lo0 = p->hb[2]; h.hi0 = p->hb[3];
+    const hipError_t e = rl::launch_horizon_bounds(h, st);
+    if (e != hipSuccess) return fail(RL_EHIP, std::string("horizon bounds launch: ") + hipGetErrorString(e));
+    HIPCHK(hipEventRecord(p->ev_hb[1], st));
+    p->hb_Q = s.Q;
+    p->hb_M = s.M;
+    return RL_OK;
+}
+
+int rl_plan_fetch_horizon_bounds(rl_plan* p, rl_hzn_bnd* out) {
+    if (!p) return fail(RL_EINVAL, "plan is NULL");
+    if (!out) return fail(RL_EINVAL, "rl_plan_fetch_horizon_bounds: out is NULL");
+    if (!p->hb_Q || !p->traj_R)
+        return fail(RL_EINVAL, "rl_plan_fetch_horizon_bounds: no rl_plan_horizon_bounds since the plan's last run or stage it reads");
+    HIPCHK(hipSetDevice(p->device));
+    hipStream_t st = p->run_stream();
+    HIPCHK(hipStreamWaitEvent(st, p->ev_hb[1], 0));
+    const size_t Q = (size_t)p->hb_Q, M = (size_t)p->hb_M;
+    double* const dst[4] = {out->lo, out->hi, out->lo0, out->hi0};
+    std::vector<CopyJob> jobs;
+    for (int c = 0; c < 4; ++c) add_job(jobs, dst[c], p->hb[c], (c < 2 ? Q * M : Q) * 8);
+    if (int rc = queue_downloads(jobs, st)) return rc;
+    HIPCHK(hipStreamSynchronize(st));
+    return RL_OK;
 }
 
 }  // extern "C"

@@ -51,6 +51,9 @@
 //               also the winners' ticks from the sample K nodes before J (512; clipped to the row
 //               and to RL_RJN_MAX_NODES), at the raceline's own speed there, braking to V m/s (0)
 //               at sample J (rl_stop), in <base>_trajectory_<r>_stop.csv (the same columns)
+//   --bounds    with --best K --trajectory-dt DT: also the free track width about every sample of
+//               the winners (rl_bounds, guard = cfg veh_width_m / 2 + safety_margin_m), in
+//               <base>_bounds_<r>.csv: i,x,y,nx,ny,lo,hi
 //   --score lap with --best K --mode mincurv: rank the min-curvature racelines by their lap
 //               time (the lap stage, rl_optimize_best_scored); the lap_time_s column of
 //               <base>_batch_summary.csv then holds every seed's lap
@@ -1201,7 +1204,7 @@ static void compute_mintime_and_save(const string& base, const vector<Vec2>& cen
 static void batch_and_save(const string& base, const vector<Vec2>& center, double L, bool closed,
                            const vector<Vec2>& inner_from_mids, const vector<Vec2>& outer_from_mids, int B, int modes,
                            int repeat, int best, bool score_lap, double traj_dt, int traj_cap, double start_speed,
-                           int stop_sample, double stop_speed, int stop_from) {
+                           int stop_sample, double stop_speed, int stop_from, bool want_bounds) {
     auto& C = cfg::get();
     SegVec innerE = closed ? edges::ringEdges(inner_from_mids) : edges::polylineEdges(inner_from_mids);
     SegVec outerE = closed ? edges::ringEdges(outer_from_mids) : edges::polylineEdges(outer_from_mids);
@@ -1437,6 +1440,28 @@ static void batch_and_save(const string& base, const vector<Vec2>& center, doubl
                       << vend[r] << " m/s\n";
         }
     }
+    // <base>_bounds_<r>.csv: the room on either side of every sample of winner r along its unit
+    // normal (+n left of travel), with this run's vehicle width and safety margin
+    if (want_traj && want_bounds) {
+        const size_t K = idx.size();
+        vector<double> col[4];                                   // lo, hi, nx, ny
+        for (auto& a : col) a.resize(K * N);
+        rl_bnd bd;
+        std::memset(&bd, 0, sizeof(bd));
+        bd.lo = col[0].data(); bd.hi = col[1].data(); bd.nx = col[2].data(); bd.ny = col[3].data();
+        gpu::check(rl_bounds(&pk.prob, bx.data(), by.data(), (int32_t)K, C.veh_width_m, C.safety_margin_m, gpu::device, &bd),
+                   "rl_bounds");
+        for (size_t r = 0; r < K; ++r) {
+            io::Csv o(base + "_bounds_" + std::to_string(r) + ".csv");
+            if (!o) throw std::runtime_error("save bounds failed");
+            o.f << "i,x,y,nx,ny,lo,hi\n";
+            for (size_t i = 0; i < N; ++i) {
+                const size_t at = r * N + i;
+                o.f << i << "," << bx[at] << "," << by[at] << "," << col[2][at] << "," << col[3][at] << "," << col[0][at] << ","
+                    << col[1][at] << "\n";
+            }
+        }
+    }
     std::cerr << "[best] " << (mt || score_lap ? "lap_time_s" : "curvature_score") << " of the " << best << " best of B=" << B << ":";
     std::cerr << std::setprecision(9);
     for (int r = 0; r < best; ++r) std::cerr << " seed " << seeds[idx[r]] << " = " << sc[r];
@@ -1533,7 +1558,7 @@ int run_pipeline(const string& innerPath, const string& outerPath, const string&
 // Steps 7-8 from the reference's step-6 files.
 int run_from_centerline(const string& outPath, double L, double s0, const string& mode, int B, int repeat, int best,
                         const string& score, double traj_dt, int traj_cap, double start_speed, int stop_sample,
-                        double stop_speed, int stop_from) {
+                        double stop_speed, int stop_from, bool want_bounds) {
     auto& C = cfg::get();
     const string base = io::dropExt(outPath);
     const bool closed_mode = C.is_closed_track;
@@ -1608,6 +1633,10 @@ int run_from_centerline(const string& outPath, double L, double s0, const string
             return 2;
         }
     }
+    if (want_bounds && (!(traj_dt > 0.0) || best <= 0)) {
+        std::cerr << "[ERR] --bounds needs --seeds B --best K --trajectory-dt DT\n";
+        return 2;
+    }
     if (B > 0) {
         const int modes = mode == "mincurv" ? RL_MODE_MINCURV
                                             : mode == "mintime" ? RL_MODE_MINTIME : RL_MODE_MINCURV | RL_MODE_MINTIME;
@@ -1620,7 +1649,8 @@ int run_from_centerline(const string& outPath, double L, double s0, const string
             return 2;
         }
         pipeline::batch_and_save(base, center_for_opt, L, closed_mode, inner, outer, B, modes, repeat, best,
-                                 score == "lap", traj_dt, traj_cap, start_speed, stop_sample, stop_speed, stop_from);
+                                 score == "lap", traj_dt, traj_cap, start_speed, stop_sample, stop_speed, stop_from,
+                                 want_bounds);
         return 0;
     }
     auto t0 = Clock::now();
@@ -1644,6 +1674,7 @@ int main(int argc, char** argv) {
     string score;
     double traj_dt = 0.0, start_speed = NAN, stop_speed = NAN;
     int traj_cap = 0, stop_sample = -1, stop_from = 0;
+    bool want_bounds = false;
     try {
         for (int i = 1; i < argc; ++i) {
             const string a = argv[i];
@@ -1672,6 +1703,7 @@ int main(int argc, char** argv) {
                 stop_from = std::stoi(next());
                 if (stop_from == 0) stop_from = -1;                // (0 stands for "not given")
             }
+            else if (a == "--bounds") want_bounds = true;
             else if (a == "--device") gpu::device = std::stoi(next());
             else if (a == "--devices") {
                 std::stringstream ss(next());
@@ -1693,12 +1725,13 @@ int main(int argc, char** argv) {
                       << "         [--trajectory-dt DT [--trajectory-cap M]]   with --best K: the winners at ticks of DT s\n"
                       << "         [--start-speed V]   with --mode mintime --trajectory-dt: the winners from sample 0 at V m/s\n"
                       << "         [--stop-sample J [--stop-speed V] [--stop-from K]]   with --mode mintime --trajectory-dt: the winners\n"
-                      << "             from K (512) samples before J, braking to V (0) m/s at sample J\n";
+                      << "             from K (512) samples before J, braking to V (0) m/s at sample J\n"
+                      << "         [--bounds]   with --best K --trajectory-dt: the free track width along the winners\n";
             return 1;
         }
         if (pos.size() == 3) return run_pipeline(pos[0], pos[1], pos[2], mode, stop_after == "centerline");
         return run_from_centerline(pos[0], L, s0, mode, B, repeat, best, score, traj_dt, traj_cap, start_speed, stop_sample,
-                                   stop_speed, stop_from);
+                                   stop_speed, stop_from, want_bounds);
     } catch (const std::exception& e) {
         std::cerr << "[ERR] " << e.what() << "\n";
         return 3;

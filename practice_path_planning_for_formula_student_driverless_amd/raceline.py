@@ -24,6 +24,9 @@ specification in NumPy.
 :func:`horizon` / :meth:`Plan.horizon` locate poses on those trajectories' rows and resample
 the next ticks from there, across the start line on a closed track; :func:`horizon_host` is
 their specification in NumPy.
+:func:`bounds` / :meth:`Plan.bounds` cast the free track width about every sample of those rows,
+and :meth:`Plan.horizon_bounds` takes it to the horizon's ticks; :func:`normals_host` and
+:func:`horizon_bounds_host` state the two new pieces in NumPy.
 
 Every compute call goes through ``librl.so`` (HIP, gfx950).  With no GPU the
 calls raise :class:`RacelineError` (RL_ENODEV): there is no CPU fallback.
@@ -560,13 +563,18 @@ def _hzn_wrap(tau, T, closed: bool):
                 np.where(neg, w + T, np.where(over, w - T, w)))
 
 
+def _hzn_segment(t, S: int, w):
+    """The segments of the row times w: the trajectory stage's bisection over the stamps t[0..S]."""
+    return np.clip(np.searchsorted(t[:S + 1], w, side="right") - 1, 0, S - 1)
+
+
 def _hzn_columns(row6, t, hb, closed: bool, lap, w) -> tuple:
     """The horizon stage's seven columns (TRAJ_COLS' order) at the row times w in the laps lap."""
     X, Y, PSI, K, V, A = row6
     N = X.shape[0]
     S = N if closed else N - 1
     with np.errstate(all="ignore"):
-        i = np.clip(np.searchsorted(t[:S + 1], w, side="right") - 1, 0, S - 1)
+        i = _hzn_segment(t, S, w)
         j = (i + 1) % N
         um = (w - t[i]) / (t[i + 1] - t[i])
         d = PSI[j] - PSI[i]
@@ -1120,6 +1128,136 @@ def stop(x, y, heading, kappa, v, ax, h, closed: bool, poses, v0, cfg: RlCfg, st
     return out
 
 
+# ------------------------------------------------- bounds: the free track width along the rows
+@dataclass
+class Bounds:
+    """The bounds stage's rows (rl_bnd), [R, N] each: the lateral room lo <= 0 <= hi about every
+    sample along its unit normal (nx, ny), +n left of travel (the sign of Horizon.e)."""
+
+    lo: np.ndarray
+    hi: np.ndarray
+    nx: np.ndarray
+    ny: np.ndarray
+
+    @classmethod
+    def alloc(cls, R: int, N: int) -> "Bounds":
+        return cls(*[np.zeros((R, N)) for _ in abi.BND_ROWS])
+
+    def as_c(self) -> abi.RlBnd:
+        return abi.RlBnd(*[_ptr(getattr(self, n), np.float64, n) for n in abi.BND_ROWS])
+
+
+@dataclass
+class HorizonBounds:
+    """The bounds at the horizon stage's ticks (rl_hzn_bnd): lo, hi [Q, M_cap], of which the first
+    Horizon.count[q] of query q are specified, and lo0, hi0 [Q] at the located segment: with
+    Horizon.e the room now is hi0 - e on the left and e - lo0 on the right.  A query with
+    seg = -1 has nothing specified."""
+
+    lo: np.ndarray
+    hi: np.ndarray
+    lo0: np.ndarray
+    hi0: np.ndarray
+
+    @classmethod
+    def alloc(cls, Q: int, m_cap: int) -> "HorizonBounds":
+        return cls(np.zeros((Q, m_cap)), np.zeros((Q, m_cap)), np.zeros(Q), np.zeros(Q))
+
+    def as_c(self) -> abi.RlHznBnd:
+        return abi.RlHznBnd(*[_ptr(getattr(self, n), np.float64, n) for n in abi.HZN_BND])
+
+
+def _bnd_rows(x, y) -> tuple:
+    """x, y as contiguous float64 [B, N] (one row [N] is B = 1)."""
+    X = np.ascontiguousarray(x, dtype=np.float64)
+    Y = np.ascontiguousarray(y, dtype=np.float64)
+    if X.ndim == 1:
+        X, Y = X[None], Y[None] if Y.ndim == 1 else Y
+    if X.ndim != 2 or X.shape != Y.shape or X.shape[0] < 1:
+        raise ValueError(f"bounds: x and y must be [B, N] with B >= 1, got {X.shape} and {Y.shape}")
+    return X, Y
+
+
+def _bnd_guard(veh_width, margin) -> tuple:
+    try:
+        w, m = float(veh_width), float(margin)
+    except (TypeError, ValueError):
+        raise ValueError(f"bounds: veh_width and margin must be numbers, got {veh_width!r}, {margin!r}") from None
+    if not (math.isfinite(w) and math.isfinite(m)):
+        raise ValueError(f"bounds: veh_width and margin must be finite, got {w}, {m}")
+    return w, m
+
+
+def normals_host(x, y, closed: bool) -> tuple:
+    """The bounds stage's unit normals (nx, ny) [B, N] of the rows x, y [B, N] (or one row [N])
+    in NumPy: normals_from_points_generic (ref:581-593) per row, +n left of travel; the kernel
+    equals it bit for bit."""
+    X, Y = _bnd_rows(x, y)
+    n = np.stack([normals_from_points(np.stack([X[b], Y[b]], axis=1), bool(closed)) for b in range(X.shape[0])])
+    n = n.reshape(X.shape[0], X.shape[1], 2)
+    return np.ascontiguousarray(n[..., 0]), np.ascontiguousarray(n[..., 1])
+
+
+def horizon_bounds_host(lo, hi, stamps, T, row, seg, t0, count, dt: float, m_cap: int, closed: bool) -> HorizonBounds:
+    """The bounds at the horizon stage's ticks (include/rl_abi.h) in NumPy; the kernel
+    equals it bit for bit.  lo, hi [R, N] are the bounds stage's rows, stamps [R, N + 1] and T [R]
+    the trajectory stage's, row, seg, t0, count [Q] the horizon stage's (row None: all 0).  Tick
+    m < count[q] at t0 + m * dt lies on segment i after the horizon stage's wrap and bisection,
+    and gets lo = smax(lo_i, lo_j), hi = smin(hi_i, hi_j), j = (i + 1) mod N; lo0, hi0 are that
+    pair of seg.  Queries with seg = -1 and the ticks from count[q] on stay NaN."""
+    lo = np.ascontiguousarray(lo, dtype=np.float64)
+    hi = np.ascontiguousarray(hi, dtype=np.float64)
+    if lo.ndim == 1:
+        lo, hi = lo[None], hi[None]
+    R, N = lo.shape
+    stamps = np.ascontiguousarray(stamps, dtype=np.float64).reshape(R, N + 1)
+    T = np.ascontiguousarray(T, dtype=np.float64).reshape(R)
+    seg = np.asarray(seg).reshape(-1)
+    Q = seg.shape[0]
+    row = np.zeros(Q, dtype=np.int64) if row is None else np.broadcast_to(np.asarray(row), (Q,))
+    t0 = np.ascontiguousarray(t0, dtype=np.float64).reshape(Q)
+    count = np.asarray(count).reshape(Q)
+    _check_ticks(dt, m_cap)
+    closed, dt, m_cap = bool(closed), float(dt), int(m_cap)
+    S = N if closed else N - 1
+    out = HorizonBounds.alloc(Q, m_cap)
+    for a in (out.lo, out.hi, out.lo0, out.hi0):
+        a[:] = np.nan
+
+    def pair(r, i):
+        j = (i + 1) % N
+        a, b, c, d = lo[r, i], lo[r, j], hi[r, i], hi[r, j]
+        return np.where(a < b, b, a), np.where(d < c, d, c)        # smax(lo_i, lo_j), smin(hi_i, hi_j)
+
+    for q in range(Q):
+        r, i0 = int(row[q]), int(seg[q])
+        if i0 < 0 or i0 >= S or r < 0 or r >= R:
+            continue
+        out.lo0[q], out.hi0[q] = pair(r, i0)
+        M = min(int(count[q]), m_cap)
+        if M <= 0:
+            continue
+        with np.errstate(all="ignore"):
+            tau = t0[q] + np.arange(M, dtype=np.float64) * dt
+            _, w = _hzn_wrap(tau, T[r], closed)
+            out.lo[q, :M], out.hi[q, :M] = pair(r, _hzn_segment(stamps[r], S, w))
+    return out
+
+
+def bounds(prob: Problem, x, y, veh_width: float, margin: float, device: int = 0) -> Bounds:
+    """The bounds stage for B given rows x, y [B, N] (or one row [N]) on the GPU (rl_bounds): the
+    rings, N and closed are prob's (its centre is not read) and go up once for all rows."""
+    X, Y = _bnd_rows(x, y)
+    w, m = _bnd_guard(veh_width, margin)
+    B, N = X.shape
+    if N != prob.N:
+        raise ValueError(f"bounds: the rows have {N} samples, the problem {prob.N}")
+    out = Bounds.alloc(B, N)
+    p, oc = prob.as_c(), out.as_c()
+    _check(_lib().rl_bounds(C.byref(p), abi.dptr(X), abi.dptr(Y), B, w, m, int(device), C.byref(oc)))
+    return out
+
+
 def path_lengths(x, y, closed: bool, device: int = 0) -> np.ndarray:
     """L [B]: the debug dump's path_length (ref:1443-1448) of B paths given as rows x [B, N],
     y [B, N], summed on the GPU in the reference's order (rl_path_lengths): L[b] equals
@@ -1362,6 +1500,47 @@ class Plan:
         if not nodes:
             t.node_v = t.node_t = t.node_b = None
         _check(_lib().rl_plan_fetch_stop(self._h, C.byref(t)))
+        return out
+
+    def bounds(self, veh_width: Optional[float] = None, margin: Optional[float] = None, stream_ptr: int = 0) -> None:
+        """Enqueue the bounds stage after the last trajectory() (rl_plan_bounds): the free track
+        width lo, hi along the unit normal of every sample of that stage's rows, row for row, with
+        guard = veh_width / 2 + margin (None: the problem's veh_width, the safety_margin_m of the
+        plan's first cfg).  Every other stage stays as it is."""
+        w, m = _bnd_guard(self._keep[0].veh_width if veh_width is None else veh_width,
+                          self._keep[1][0].safety_margin_m if margin is None else margin)
+        self._bnd = self._hbnd = None
+        q = abi.RlBndQuery(w, m)
+        _check(_lib().rl_plan_bounds(self._h, C.byref(q), C.c_void_p(stream_ptr) if stream_ptr else None))
+        self._bnd = getattr(self, "_traj", None)
+
+    def fetch_bounds(self) -> Bounds:
+        """Download the last bounds() (rl_plan_fetch_bounds): Bounds(lo, hi, nx, ny), [R, N] each."""
+        if getattr(self, "_bnd", None) is None:
+            t = abi.RlBnd()                 # (the library's own answer: no stage on this plan)
+            _check(_lib().rl_plan_fetch_bounds(self._h, C.byref(t)))
+            raise ValueError("fetch_bounds: no bounds() on this plan")
+        out = Bounds.alloc(self._bnd[0], self.N)
+        t = out.as_c()
+        _check(_lib().rl_plan_fetch_bounds(self._h, C.byref(t)))
+        return out
+
+    def horizon_bounds(self, stream_ptr: int = 0) -> None:
+        """Enqueue the bounds at the ticks of the last horizon() (rl_plan_horizon_bounds), from
+        the last bounds() of the same trajectory(); nothing is uploaded."""
+        self._hbnd = None
+        _check(_lib().rl_plan_horizon_bounds(self._h, C.c_void_p(stream_ptr) if stream_ptr else None))
+        self._hbnd = getattr(self, "_hzn", None)
+
+    def fetch_horizon_bounds(self) -> HorizonBounds:
+        """Download the last horizon_bounds() (rl_plan_fetch_horizon_bounds)."""
+        if getattr(self, "_hbnd", None) is None:
+            t = abi.RlHznBnd()              # (the library's own answer: no stage on this plan)
+            _check(_lib().rl_plan_fetch_horizon_bounds(self._h, C.byref(t)))
+            raise ValueError("fetch_horizon_bounds: no horizon_bounds() on this plan")
+        out = HorizonBounds.alloc(self._hbnd[0], self._hbnd[1])
+        t = out.as_c()
+        _check(_lib().rl_plan_fetch_horizon_bounds(self._h, C.byref(t)))
         return out
 
     def device_outputs(self, which: int) -> abi.RlOut:
