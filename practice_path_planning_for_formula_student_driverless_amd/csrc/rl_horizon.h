@@ -1,9 +1,10 @@
 // rl_horizon.h — launch interface of the horizon stage's kernel (rl_horizon.hip):
 // query poses are located on rows of a trajectory stage and the next ticks from there are
 // resampled, across the start line on closed rows (rl_stages.cpp rl_plan_horizon, rl_abi.cpp
-// rl_horizon).  Below it, the device functions of that kernel which the rejoin stage's kernel
-// (rl_rejoin.hip) shares: the parallel locate and a tick's wrap and columns.  Not
-// part of the public ABI.
+// rl_horizon).  Below it, the device functions of that kernel which the rejoin and stop stages'
+// kernels (rl_rejoin.hip; rl_stop.hip, §3n) share: the query's row, the empty answer,
+// the parallel locate, the located point and its stores, the tick count's bisection and a tick's
+// wrap and columns.  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -190,6 +191,66 @@ __device__ __forceinline__ void hzn_columns(const HznParams& p, const HznRow& r,
     p.out[4][o] = ki + u * (r.kap[jn] - ki);
     p.out[5][o] = vi + u * (r.v[jn] - vi);
     p.out[6][o] = r.ax[i];
+}
+
+// The row of query k: the instance of row r of the trajectory stage, -1 for an r outside the
+// stage (the caller also refuses an instance outside the batch and a row without a segment); its
+// source rows, its stamps in global memory and its step
+__device__ __forceinline__ int hzn_instance(const TrajParams& q, int r) {
+    int b = -1;
+    if (r >= 0 && r < q.R) b = q.index ? q.index[r] : r;
+    return b;
+}
+__device__ __forceinline__ HznRow hzn_row(const TrajParams& q, int b) {
+    const size_t off = (size_t)b * (size_t)q.N;
+    return {q.x + off, q.y + off, q.heading + off, q.kappa + off, q.v + off, q.ax + off};
+}
+__device__ __forceinline__ const double* hzn_stamps(const TrajParams& q, int r) {
+    return q.stamps + (size_t)r * ((size_t)q.N + 1);
+}
+__device__ __forceinline__ double hzn_step(const TrajParams& q, int b) {
+    return q.h ? q.h[b] : (q.Ls ? q.Ls[b] : q.L) / (double)q.N;
+}
+
+// the answer of a query without a row or without a winner, by the calling lane
+__device__ __forceinline__ void hzn_empty(const HznParams& p, int k) {
+    p.seg[k] = -1;
+    p.count[k] = 0;
+}
+
+// the located point: the pose's foot on the winning segment i0, and its time on the row
+__device__ __forceinline__ Foot hzn_foot(const double* x, const double* y, int N, int i0, double px, double py) {
+    const int j0 = i0 + 1 < N ? i0 + 1 : 0;
+    return foot(x[i0], y[i0], x[j0], y[j0], px, py);
+}
+template <class Stamp>
+__device__ __forceinline__ double hzn_t0(const Stamp& stamp, int i0, double u) {
+    const double ta = stamp(i0);
+    return ta + u * (stamp(i0 + 1) - ta);
+}
+// seg, count and the five location fields of query k, by the calling lane (§3l "location")
+__device__ __forceinline__ void hzn_store_loc(const HznParams& p, int k, const Foot& f, int i0, double h, double t0,
+                                              int cnt) {
+    const double root = sqrt(f.D);
+    p.seg[k] = i0;
+    p.count[k] = cnt;
+    p.loc[0][k] = f.u;
+    p.loc[1][k] = t0;
+    p.loc[2][k] = ((double)i0 + f.u) * h;
+    p.loc[3][k] = (f.dx * f.wy - f.dy * f.wx) < 0.0 ? -root : root;
+    p.loc[4][k] = f.D;
+}
+
+// the first m in [a, M_cap] with !before(m), for a `before` that is monotone in m: a tick count
+template <class Before>
+__device__ __forceinline__ int tick_end(int a, int M_cap, const Before& before) {
+    int e = M_cap;
+    while (a < e) {
+        const int mid = a + ((e - a) >> 1);
+        if (before(mid)) a = mid + 1;
+        else e = mid;
+    }
+    return a;
 }
 
 }  // namespace rl

@@ -44,63 +44,35 @@ __global__ __launch_bounds__(HZN_THREADS) void rl_horizon_kernel(HznParams p) {
     const TrajParams& q = p.src;
     const int k = blockIdx.x, tid = threadIdx.x, N = q.N;
     const int S = q.closed ? N : N - 1;
-    const int r = p.row ? p.row[k] : 0;
-    int b = -1;
-    if (r >= 0 && r < q.R) b = q.index ? q.index[r] : r;
+    const int r = p.row ? p.row[k] : 0, b = hzn_instance(q, r);
     if (b < 0 || b >= q.B || S < 1) {             // no row, or a row without a segment
-        if (tid == 0) {
-            p.seg[k] = -1;
-            p.count[k] = 0;
-        }
+        if (tid == 0) hzn_empty(p, k);
         return;
     }
+    // x and y for the locate; the other four rows are formed where the ticks need them
     const size_t off = (size_t)b * (size_t)N;
-    const double* x = q.x + off;
-    const double* y = q.y + off;
-    const double* tg = q.stamps + (size_t)r * ((size_t)N + 1);
+    const double *x = q.x + off, *y = q.y + off, *tg = hzn_stamps(q, r);
     const bool lds = N <= TRAJ_LDS_N;
     if (lds)
         for (int i = tid; i <= N; i += HZN_THREADS) s_t[i] = tg[i];
     const double px = p.pose[2 * (size_t)k], py = p.pose[2 * (size_t)k + 1];
 
     const HznWin win = hzn_locate(p, k, tid, x, y, px, py, s_key, s_idx);
-    const uint64_t bk = win.key;
-    const uint32_t bi = win.idx;
-    if (bk >= HZN_KEY_NAN || bi >= (uint32_t)S) {  // a NaN winner, or no candidate at all
-        if (tid == 0) {
-            p.seg[k] = -1;
-            p.count[k] = 0;
-        }
+    if (win.key >= HZN_KEY_NAN || win.idx >= (uint32_t)S) {  // a NaN winner, or no candidate at all
+        if (tid == 0) hzn_empty(p, k);
         return;
     }
     auto stamp = [&](int i) { return lds ? s_t[i] : tg[i]; };
-    const double h = q.h ? q.h[b] : (q.Ls ? q.Ls[b] : q.L) / (double)N;
+    const double h = hzn_step(q, b);
     const double T = q.T[r];
-    if (tid == 0) {
-        const int i = (int)bi, j = i + 1 < N ? i + 1 : 0;
-        const Foot f = foot(x[i], y[i], x[j], y[j], px, py);
-        const double ta = stamp(i);
-        const double t0 = ta + f.u * (stamp(i + 1) - ta);
-        const double root = sqrt(f.D);
+    if (tid == 0) {                                // only lane 0 needs the located point: the ticks start from s_t0
+        const int i = (int)win.idx;
+        const Foot f = hzn_foot(x, y, N, i, px, py);
+        const double t0 = hzn_t0(stamp, i, f.u);
         int cnt;
-        if (q.closed) {
-            cnt = (__builtin_isfinite(T) && T > 0.0) ? p.M_cap : 0;
-        } else {
-            int a = 0, e = p.M_cap;                // the first m with !(tau_m < T)
-            while (a < e) {
-                const int mid = a + ((e - a) >> 1);
-                if (t0 + (double)mid * p.dt < T) a = mid + 1;
-                else e = mid;
-            }
-            cnt = a;
-        }
-        p.seg[k] = i;
-        p.count[k] = cnt;
-        p.loc[0][k] = f.u;
-        p.loc[1][k] = t0;
-        p.loc[2][k] = ((double)i + f.u) * h;
-        p.loc[3][k] = (f.dx * f.wy - f.dy * f.wx) < 0.0 ? -root : root;
-        p.loc[4][k] = f.D;
+        if (!q.closed) cnt = tick_end(0, p.M_cap, [&](int m) { return t0 + (double)m * p.dt < T; });
+        else cnt = (__builtin_isfinite(T) && T > 0.0) ? p.M_cap : 0;
+        hzn_store_loc(p, k, f, i, h, t0, cnt);
         s_t0 = t0;
         s_count = cnt;
     }

@@ -2,8 +2,9 @@
 // horizon stage's query with the car's speed and limits: a reachable speed profile is marched
 // from the located point until it meets the row's own, and the ticks follow it (rl_stages.cpp
 // rl_plan_rejoin, rl_abi.cpp rl_rejoin).  Below it, the device functions of that kernel which
-// the stop stage's kernel (rl_stop.hip) shares: ax_max_at, the march nodes and a
-// march tick's columns.  Not part of the public ABI.
+// the stop stage's kernel (rl_stop.hip) shares: the empty answer, ax_max_at and the
+// march's step, the march nodes and their set-up, and a march tick's columns.  Not part of the
+// public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -56,6 +57,25 @@ __device__ __forceinline__ AxMax ax_max_at(const RjnCfg& c, double vi, double ki
     return r;
 }
 
+// one step of the march from the speed w at a node of curvature kappa over the distance d: the
+// fastest and the slowest speed at the next node; and that node's time, reached at wn
+struct Reach {
+    double up, dn;
+};
+__device__ __forceinline__ Reach march_step(const RjnCfg& c, double w, double kappa, double d) {
+    const AxMax a = ax_max_at(c, w, kappa);
+    return {sqrt(smax(0.0, w * w + (2.0 * a.acc) * d)), sqrt(smax(0.0, w * w - (2.0 * a.brk) * d))};
+}
+__device__ __forceinline__ double march_time(double tt, double d, double w, double wn) {
+    return tt + (2.0 * d) / smax(1e-6, w + wn);
+}
+
+// the answer of a query without a row or without a winner, by the calling lane
+__device__ __forceinline__ void march_empty(const RjnParams& rp, int k) {
+    hzn_empty(rp.hz, k);
+    rp.merge_node[k] = -1;
+}
+
 // position, heading, curvature and arc length of a march node
 struct Node {
     double x, y, psi, kap, s;
@@ -70,6 +90,10 @@ struct March {
     double u, h, d0;
     int i0, j0, N;
 };
+// the march from the foot f on segment i0 (kap: where march_stage will put the curvatures)
+__device__ __forceinline__ March march_from(const HznRow& row, const double* kap, const Foot& f, int i0, int N, double h) {
+    return {row, kap, f.u, h, (1.0 - f.u) * h, i0, i0 + 1 < N ? i0 + 1 : 0, N};
+}
 __device__ __forceinline__ int march_sample(const March& m, int kk) {   // row index of node kk >= 1 (i0 + kk < 2N)
     const int n = m.i0 + kk;
     return n >= m.N ? n - m.N : n;

@@ -49,20 +49,13 @@ __global__ __launch_bounds__(HZN_THREADS) void rl_rejoin_kernel(RjnParams rp) {
     const TrajParams& q = p.src;
     const int k = blockIdx.x, tid = threadIdx.x, N = q.N;
     const int S = q.closed ? N : N - 1;
-    const int r = p.row ? p.row[k] : 0;
-    int b = -1;
-    if (r >= 0 && r < q.R) b = q.index ? q.index[r] : r;
+    const int r = p.row ? p.row[k] : 0, b = hzn_instance(q, r);
     if (b < 0 || b >= q.B || S < 1) {             // no row, or a row without a segment
-        if (tid == 0) {
-            p.seg[k] = -1;
-            p.count[k] = 0;
-            rp.merge_node[k] = -1;
-        }
+        if (tid == 0) march_empty(rp, k);
         return;
     }
-    const size_t off = (size_t)b * (size_t)N;
-    const HznRow row{q.x + off, q.y + off, q.heading + off, q.kappa + off, q.v + off, q.ax + off};
-    const double* tg = q.stamps + (size_t)r * ((size_t)N + 1);
+    const HznRow row = hzn_row(q, b);
+    const double* tg = hzn_stamps(q, r);
     const bool lds = N <= TRAJ_LDS_N;
     if (lds)
         for (int i = tid; i <= N; i += HZN_THREADS) s_t[i] = tg[i];
@@ -70,25 +63,20 @@ __global__ __launch_bounds__(HZN_THREADS) void rl_rejoin_kernel(RjnParams rp) {
 
     const HznWin win = hzn_locate(p, k, tid, row.x, row.y, px, py, s_key, s_idx);
     if (win.key >= HZN_KEY_NAN || win.idx >= (uint32_t)S) {  // a NaN winner, or no candidate at all
-        if (tid == 0) {
-            p.seg[k] = -1;
-            p.count[k] = 0;
-            rp.merge_node[k] = -1;
-        }
+        if (tid == 0) march_empty(rp, k);
         return;
     }
     auto stamp = [&](int i) { return lds ? s_t[i] : tg[i]; };
-    const double h = q.h ? q.h[b] : (q.Ls ? q.Ls[b] : q.L) / (double)N;
+    const double h = hzn_step(q, b);
     const double T = q.T[r];
-    // the located point, by every lane: node 0 needs it in the tick phase
-    const int i0 = (int)win.idx, j0 = i0 + 1 < N ? i0 + 1 : 0;
-    const Foot f = foot(row.x[i0], row.y[i0], row.x[j0], row.y[j0], px, py);
-    const double ta0 = stamp(i0);
-    const double t0 = ta0 + f.u * (stamp(i0 + 1) - ta0);
-    const double d0 = (1.0 - f.u) * h;
+    // the located point, by every lane (the horizon kernel: lane 0 only): node 0 needs it in the tick phase
+    const int i0 = (int)win.idx;
+    const Foot f = hzn_foot(row.x, row.y, N, i0, px, py);
+    const double t0 = hzn_t0(stamp, i0, f.u);
     const int room = q.closed ? N : N - 1 - i0;   // >= 1: i0 < S
     const int K_lim = rp.K_cap < room ? rp.K_cap : room;
-    const March mr{row, s_kap, f.u, h, d0, i0, j0, N};
+    const March mr = march_from(row, s_kap, f, i0, N, h);
+    const double d0 = mr.d0;
     march_stage(mr, tid, K_lim, s_kap, s_r);
     __syncthreads();
     if (tid == 0) {
@@ -102,12 +90,10 @@ __global__ __launch_bounds__(HZN_THREADS) void rl_rejoin_kernel(RjnParams rp) {
             over += w > s_r[0];
             for (int kk = 0; kk < K_lim; ++kk) {
                 const double d = kk == 0 ? d0 : h;
-                const AxMax a = ax_max_at(rp.cfg, w, s_kap[kk]);
-                const double up = sqrt(smax(0.0, w * w + (2.0 * a.acc) * d));
-                const double dn = sqrt(smax(0.0, w * w - (2.0 * a.brk) * d));
+                const Reach s = march_step(rp.cfg, w, s_kap[kk], d);
                 const double rn = s_r[kk + 1];
-                const double wn = smin(up, smax(dn, rn));
-                tt = tt + (2.0 * d) / smax(1e-6, w + wn);
+                const double wn = smin(s.up, smax(s.dn, rn));
+                tt = march_time(tt, d, w, wn);
                 s_w[kk + 1] = wn;
                 s_tt[kk + 1] = tt;
                 w = wn;
@@ -122,35 +108,15 @@ __global__ __launch_bounds__(HZN_THREADS) void rl_rejoin_kernel(RjnParams rp) {
         const double tte = s_tt[kend];
         const int nk = i0 + (ks >= 0 ? ks : 0), c0 = nk >= N ? 1 : 0;
         const double tref = ks == 0 ? t0 : stamp(nk - c0 * N);
-        int a = 0, e = p.M_cap;                    // the first m with !(tau_m < tt_{K_end})
-        while (a < e) {
-            const int mid = a + ((e - a) >> 1);
-            if ((double)mid * p.dt < tte) a = mid + 1;
-            else e = mid;
-        }
-        const int m1 = a;
+        // M1: the first m with !(tau_m < tt_{K_end}); on a merged open row, the count: the first
+        // m >= M1 whose row time is not < T
+        const int m1 = tick_end(0, p.M_cap, [&](int m) { return (double)m * p.dt < tte; });
         int cnt = m1;
         if (ks >= 0) {
-            if (q.closed) {
-                if (__builtin_isfinite(T) && T > 0.0) cnt = p.M_cap;
-            } else {
-                e = p.M_cap;                       // the first m >= M1 whose row time is not < T
-                while (a < e) {
-                    const int mid = a + ((e - a) >> 1);
-                    if (tref + ((double)mid * p.dt - tte) < T) a = mid + 1;
-                    else e = mid;
-                }
-                cnt = a;
-            }
+            if (!q.closed) cnt = tick_end(m1, p.M_cap, [&](int m) { return tref + ((double)m * p.dt - tte) < T; });
+            else if (__builtin_isfinite(T) && T > 0.0) cnt = p.M_cap;
         }
-        const double root = sqrt(f.D);
-        p.seg[k] = i0;
-        p.count[k] = cnt;
-        p.loc[0][k] = f.u;
-        p.loc[1][k] = t0;
-        p.loc[2][k] = ((double)i0 + f.u) * h;
-        p.loc[3][k] = (f.dx * f.wy - f.dy * f.wx) < 0.0 ? -root : root;
-        p.loc[4][k] = f.D;
+        hzn_store_loc(p, k, f, i0, h, t0, cnt);
         rp.merge_node[k] = ks;
         rp.overspeed[k] = over;
         rp.scal[0][k] = tte;

@@ -49,36 +49,25 @@ __global__ __launch_bounds__(HZN_THREADS) void rl_stop_kernel(StpParams sp) {
     const TrajParams& q = p.src;
     const int k = blockIdx.x, tid = threadIdx.x, N = q.N;
     const int S = q.closed ? N : N - 1;
-    const int r = p.row ? p.row[k] : 0;
-    int b = -1;
-    if (r >= 0 && r < q.R) b = q.index ? q.index[r] : r;
+    const int r = p.row ? p.row[k] : 0, b = hzn_instance(q, r);
     if (b < 0 || b >= q.B || S < 1) {             // no row, or a row without a segment
-        if (tid == 0) {
-            p.seg[k] = -1;
-            p.count[k] = 0;
-            rp.merge_node[k] = -1;
-        }
+        if (tid == 0) march_empty(rp, k);
         return;
     }
-    const size_t off = (size_t)b * (size_t)N;
-    const HznRow row{q.x + off, q.y + off, q.heading + off, q.kappa + off, q.v + off, q.ax + off};
-    const double* tg = q.stamps + (size_t)r * ((size_t)N + 1);
+    const HznRow row = hzn_row(q, b);
+    // no stamps in LDS (the horizon and rejoin kernels stage them): only t0 reads two, from here
+    const double* tg = hzn_stamps(q, r);
     const double px = p.pose[2 * (size_t)k], py = p.pose[2 * (size_t)k + 1];
 
     const HznWin win = hzn_locate(p, k, tid, row.x, row.y, px, py, s_key, s_idx);
     if (win.key >= HZN_KEY_NAN || win.idx >= (uint32_t)S) {  // a NaN winner, or no candidate at all
-        if (tid == 0) {
-            p.seg[k] = -1;
-            p.count[k] = 0;
-            rp.merge_node[k] = -1;
-        }
+        if (tid == 0) march_empty(rp, k);
         return;
     }
-    const double h = q.h ? q.h[b] : (q.Ls ? q.Ls[b] : q.L) / (double)N;
+    const double h = hzn_step(q, b);
     // the located point, by every lane: node 0 needs it in the tick phase
-    const int i0 = (int)win.idx, j0 = i0 + 1 < N ? i0 + 1 : 0;
-    const Foot f = foot(row.x[i0], row.y[i0], row.x[j0], row.y[j0], px, py);
-    const double d0 = (1.0 - f.u) * h;
+    const int i0 = (int)win.idx;
+    const Foot f = hzn_foot(row.x, row.y, N, i0, px, py);
     const int room = q.closed ? N : N - 1 - i0;   // >= 1: i0 < S
     const int K_lim = rp.K_cap < room ? rp.K_cap : room;
     // the target node: the first time sample J comes up ahead of the located segment (the entry
@@ -88,6 +77,10 @@ __global__ __launch_bounds__(HZN_THREADS) void rl_stop_kernel(StpParams sp) {
     int Ks = -1;
     if (J >= 0 && J < N) Ks = q.closed ? ((J - i0 - 1) % N + N) % N + 1 : J - i0;
     const bool in_range = Ks >= 1 && Ks <= K_lim;  // K_lim <= RJN_MAX_NODES: the nodes fit the LDS arrays
+    // the location first: a target out of range still answers where the car is.  These are
+    // hzn_store_loc's stores and hzn_t0's formula written out: a store helper without the count
+    // (the count stored by the callers), one for the sign of e alone, and hzn_t0 here were each
+    // compiled, and each changed the register allocation of this kernel or of the other two
     if (tid == 0) {
         const double ta0 = tg[i0];
         const double root = sqrt(f.D);
@@ -103,7 +96,8 @@ __global__ __launch_bounds__(HZN_THREADS) void rl_stop_kernel(StpParams sp) {
         }
     }
     if (!in_range) return;                         // (the same for every lane)
-    const March mr{row, s_kap, f.u, h, d0, i0, j0, N};
+    const March mr = march_from(row, s_kap, f, i0, N, h);
+    const double d0 = mr.d0;
     march_stage(mr, tid, Ks, s_kap, s_r);
     __syncthreads();
     if (tid == 0) {
@@ -128,17 +122,17 @@ __global__ __launch_bounds__(HZN_THREADS) void rl_stop_kernel(StpParams sp) {
             if (bn < 0 && bk < rk) bn = kk;
             if (kk == Ks) break;
             const double d = kk == 0 ? d0 : h;
-            const AxMax a = ax_max_at(rp.cfg, w, s_kap[kk]);
-            const double up = sqrt(smax(0.0, w * w + (2.0 * a.acc) * d));
-            const double dn = sqrt(smax(0.0, w * w - (2.0 * a.brk) * d));
+            const Reach s = march_step(rp.cfg, w, s_kap[kk], d);
             const double bn1 = s_b[kk + 1], rn = s_r[kk + 1];
-            const double wn = smin(up, w <= bk ? smin(bn1, smax(dn, rn)) : smax(dn, smin(bn1, rn)));
-            tt = tt + (2.0 * d) / smax(1e-6, w + wn);
+            const double wn = smin(s.up, w <= bk ? smin(bn1, smax(s.dn, rn)) : smax(s.dn, smin(bn1, rn)));
+            tt = march_time(tt, d, w, wn);
             s_w[kk + 1] = wn;
             s_tt[kk + 1] = tt;
             w = wn;
         }
-        int a = 0, m = p.M_cap;                    // the first m with !(tau_m < tt_{K_s})
+        // the first m with !(tau_m < tt_{K_s}): tick_end's loop, written out here because through
+        // the helper the compiler orders this kernel's two selects the other way round
+        int a = 0, m = p.M_cap;
         while (a < m) {
             const int mid = a + ((m - a) >> 1);
             if ((double)mid * p.dt < tt) a = mid + 1;

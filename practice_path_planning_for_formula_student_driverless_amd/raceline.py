@@ -517,6 +517,44 @@ def _hzn_stamps(rows, hs, stamps):
     return stamps
 
 
+def _open_query(what: str, rows7, query) -> tuple:
+    """What the pose-query stages' specifications and one-shot entries open with: the rows and
+    steps (_traj_rows), the query as query() builds it, and B and N >= 1."""
+    rows, hs = _traj_rows(*rows7)
+    qy = query()
+    B, N = rows[0].shape
+    if N < 1:
+        raise ValueError(f"{what}: N == 0 (no row)")
+    return rows, hs, qy, B, N
+
+
+def _query_rows(what: str, rows7, closed: bool, query, stamps, check=None) -> tuple:
+    """The prologue of horizon_host, rejoin_host and stop_host: _open_query, row and seg_hint
+    with their defaults and in range, the stage's own check(N, query) if any, and the stamps.
+    Returns rows, hs, stamps [B, N + 1], N, S and the query with row and seg_hint filled in."""
+    rows, hs, qy, B, N = _open_query(what, rows7, query)
+    P, rw, hint = qy[:3]
+    Q, S = P.shape[0], N if closed else N - 1
+    rw = np.zeros(Q, dtype=np.int32) if rw is None else rw
+    hint = np.full(Q, -1, dtype=np.int32) if hint is None else hint
+    if np.any(rw < 0) or np.any(rw >= B):
+        raise ValueError(f"{what}: row outside [0, {B})")
+    if np.any(hint < -1) or np.any(hint >= S):
+        raise ValueError(f"{what}: seg_hint outside [-1, {S})")
+    if check is not None:
+        check(N, qy)
+    return rows, hs, _hzn_stamps(rows, hs, stamps), N, S, (P, rw, hint) + tuple(qy[3:])
+
+
+def _one_shot(symbol: str, rows, hs, N: int, B: int, closed: bool, qc, out, device: int):
+    """The one-shot C entry `symbol` (rl_horizon, rl_rejoin, rl_stop) on the B given rows with
+    the query struct qc, into out."""
+    oc = out.as_c()
+    _check(getattr(_lib(), symbol)(*[_ptr(a, np.float64, "row") for a in rows], _ptr(hs, np.float64, "h"), N, B,
+                                   1 if closed else 0, C.byref(qc), int(device), C.byref(oc)))
+    return out
+
+
 def _hzn_locate(X, Y, t, hb, px, py, g: int, W: int, closed: bool):
     """The horizon stage's candidates, distance, winner and location of one pose on one row:
     (seg, u, dist2, e, t0, s0), or None for a NaN winner."""
@@ -592,20 +630,11 @@ def horizon_host(x, y, heading, kappa, v, ax, h, closed: bool, poses, row=None, 
     segments within `window` of seg_hint[q], around the start line on a closed row; the winner
     is the least (isnan(D), D, i).  Then up to m_cap ticks at t0 + m * dt: open rows stop
     before T, closed rows wrap modulo T and count the laps in s."""
-    rows, hs = _traj_rows(x, y, heading, kappa, v, ax, h)
-    P, rw, hint = _hzn_query(poses, row, seg_hint, window, dt, m_cap)
-    B, N = rows[0].shape
-    if N < 1:
-        raise ValueError("horizon: N == 0 (no row)")
-    Q, closed, dt, m_cap, W = P.shape[0], bool(closed), float(dt), int(m_cap), int(window)
-    S = N if closed else N - 1
-    rw = np.zeros(Q, dtype=np.int32) if rw is None else rw
-    hint = np.full(Q, -1, dtype=np.int32) if hint is None else hint
-    if np.any(rw < 0) or np.any(rw >= B):
-        raise ValueError(f"horizon: row outside [0, {B})")
-    if np.any(hint < -1) or np.any(hint >= S):
-        raise ValueError(f"horizon: seg_hint outside [-1, {S})")
-    stamps = _hzn_stamps(rows, hs, stamps)
+    closed = bool(closed)
+    rows, hs, stamps, N, S, (P, rw, hint) = _query_rows(
+        "horizon", (x, y, heading, kappa, v, ax, h), closed, lambda: _hzn_query(poses, row, seg_hint, window, dt, m_cap),
+        stamps)
+    Q, dt, m_cap, W = P.shape[0], float(dt), int(m_cap), int(window)
     out = Horizon.alloc(Q, m_cap, dt)
     out.seg[:] = -1
     steps = np.arange(m_cap, dtype=np.float64)
@@ -638,21 +667,27 @@ def horizon(x, y, heading, kappa, v, ax, h, closed: bool, poses, row=None, seg_h
             dt: float = 0.05, m_cap: int = 64, device: int = 0) -> Horizon:
     """horizon_host on the GPU (rl_horizon): the trajectory kernel stamps the B given rows, then
     the horizon kernel answers the Q poses; row[q] counts the given rows."""
-    rows, hs = _traj_rows(x, y, heading, kappa, v, ax, h)
-    P, rw, hint = _hzn_query(poses, row, seg_hint, window, dt, m_cap)
-    B, N = rows[0].shape
-    if N < 1:
-        raise ValueError("horizon: N == 0 (no row)")
-    out = Horizon.alloc(P.shape[0], int(m_cap), dt)
-    qc, oc = _hzn_c(P, rw, hint, window, dt, m_cap), out.as_c()
-    _check(_lib().rl_horizon(*[_ptr(a, np.float64, "row") for a in rows], _ptr(hs, np.float64, "h"), N, B,
-                             1 if closed else 0, C.byref(qc), int(device), C.byref(oc)))
-    return out
+    rows, hs, (P, rw, hint), B, N = _open_query("horizon", (x, y, heading, kappa, v, ax, h),
+                                                lambda: _hzn_query(poses, row, seg_hint, window, dt, m_cap))
+    return _one_shot("rl_horizon", rows, hs, N, B, closed, _hzn_c(P, rw, hint, window, dt, m_cap),
+                     Horizon.alloc(P.shape[0], int(m_cap), dt), device)
 
 
 # ------------------------------------------------- rejoin: a reachable profile from the car's speed
+class _FromTheCar(Horizon):
+    """Horizon whose ticks are counted from the car (the rejoin and stop stages' answers)."""
+
+    def row(self, q: int) -> dict:
+        """The ticks of query q: t [count[q]] = m * dt, from the car, and the seven columns."""
+        m = int(self.count[q])
+        out = {"t": np.arange(m, dtype=np.float64) * self.dt}
+        for n in abi.TRAJ_COLS:
+            out[n] = getattr(self, n)[q, :m]
+        return out
+
+
 @dataclass
-class Rejoin(Horizon):
+class Rejoin(_FromTheCar):
     """The rejoin stage's answer for Q poses (rl_rjn): Horizon's fields, with the ticks counted
     from the car (t = m * dt) along the reachable speed profile, and merge_node (the march node
     at which the profile meets the row's, -1: not within k_cap nodes or the row's end),
@@ -693,14 +728,6 @@ class Rejoin(Horizon):
         """K_end: the last march node of query q (the merge node, or the last node marched)."""
         return int(self.merge_node[q]) if self.merge_node[q] >= 0 else int(self.k_lim[q])
 
-    def row(self, q: int) -> dict:
-        """The ticks of query q: t [count[q]] = m * dt, from the car, and the seven columns."""
-        m = int(self.count[q])
-        out = {"t": np.arange(m, dtype=np.float64) * self.dt}
-        for n in abi.TRAJ_COLS:
-            out[n] = getattr(self, n)[q, :m]
-        return out
-
 
 def _rjn_query(poses, v0, cfg, row, seg_hint, window, dt, m_cap, k_cap) -> tuple:
     P, rw, hint = _hzn_query(poses, row, seg_hint, window, dt, m_cap)
@@ -721,9 +748,9 @@ def _rjn_query(poses, v0, cfg, row, seg_hint, window, dt, m_cap, k_cap) -> tuple
 
 
 def _rjn_c(P, rw, hint, V0, cfg, window, dt, m_cap, k_cap) -> abi.RlRjnQuery:
-    return abi.RlRjnQuery(_ptr(P, np.float64, "poses"), None if rw is None else _ptr(rw, np.int32, "row"),
-                          None if hint is None else _ptr(hint, np.int32, "seg_hint"), P.shape[0], int(window),
-                          int(m_cap), 0, float(dt), _ptr(V0, np.float64, "v0"), C.pointer(cfg), int(k_cap), 0)
+    hq = _hzn_c(P, rw, hint, window, dt, m_cap)
+    return abi.RlRjnQuery(*[getattr(hq, n) for n, _ in abi.RlHznQuery._fields_], _ptr(V0, np.float64, "v0"), C.pointer(cfg),
+                          int(k_cap), 0)
 
 
 def _smax(a: float, b: float) -> float:
@@ -772,6 +799,61 @@ def _bisect_nodes(tt: np.ndarray, tau: np.ndarray, hi: int) -> np.ndarray:
     return a
 
 
+def _march_nodes(row6, i0: int, u: float, hb: float, K: int) -> tuple:
+    """The march nodes 0 .. K of a point located on segment i0 at u: (n, idx, kap, r, d0), the
+    nodes' samples unwrapped and as row indices, their curvatures and the row's speeds there
+    (node 0: interpolated with u) and node 0's distance to node 1."""
+    KAP, V = row6[3], row6[4]
+    N = KAP.shape[0]
+    j0 = (i0 + 1) % N
+    n = i0 + np.arange(K + 1)
+    idx = n % N
+    with np.errstate(all="ignore"):
+        kap = KAP[idx].copy()
+        r = V[idx].copy()
+        kap[0] = KAP[i0] + u * (KAP[j0] - KAP[i0])
+        r[0] = V[i0] + u * (V[j0] - V[i0])
+        d0 = (1.0 - u) * hb
+    return n, idx, kap, r, d0
+
+
+def _march_step(consts: tuple, wk: float, kap_k: float, d: float) -> tuple:
+    """(up, dn): the fastest and the slowest speed at the next node, from wk over the distance d
+    (the device's march_step)."""
+    a_acc, a_brk = _ax_max_at(consts, wk, kap_k)
+    return math.sqrt(_smax(0.0, wk * wk + (2.0 * a_acc) * d)), math.sqrt(_smax(0.0, wk * wk - (2.0 * a_brk) * d))
+
+
+def _march_ticks(out, q: int, M1: int, tau, tt, w, kend: int, row6, nodes, i0: int, u: float, hb: float) -> None:
+    """The seven columns of the ticks tau[:M1] of query q on the march w, tt over the nodes
+    0 .. kend, nodes = _march_nodes' (the device's march_columns)."""
+    X, Y, PSI = row6[:3]
+    n, idx, kap, _, d0 = nodes
+    j0 = (i0 + 1) % X.shape[0]
+    a = _bisect_nodes(tt, tau, kend)
+    b = a + 1
+    um = (tau - tt[a]) / (tt[b] - tt[a])
+    d = np.where(a == 0, d0, hb)
+    # the nodes' values: node 0 the located point, node k >= 1 sample n_k
+    dp0 = PSI[j0] - PSI[i0]
+    dp0 = dp0 - 2.0 * np.pi if dp0 > np.pi else (dp0 + 2.0 * np.pi if dp0 < -np.pi else dp0)
+    nx, ny, npsi = X[idx].copy(), Y[idx].copy(), PSI[idx].copy()
+    ns = n.astype(np.float64) * hb
+    nx[0] = X[i0] + u * (X[j0] - X[i0])
+    ny[0] = Y[i0] + u * (Y[j0] - Y[i0])
+    npsi[0] = PSI[i0] + u * dp0
+    ns[0] = out.s0[q]
+    dp = npsi[b] - npsi[a]
+    dp = np.where(dp > np.pi, dp - 2.0 * np.pi, np.where(dp < -np.pi, dp + 2.0 * np.pi, dp))
+    out.s[q, :M1] = ns[a] + um * (ns[b] - ns[a])
+    out.x[q, :M1] = nx[a] + um * (nx[b] - nx[a])
+    out.y[q, :M1] = ny[a] + um * (ny[b] - ny[a])
+    out.heading[q, :M1] = npsi[a] + um * dp
+    out.kappa[q, :M1] = kap[a] + um * (kap[b] - kap[a])
+    out.v[q, :M1] = w[a] + um * (w[b] - w[a])
+    out.ax[q, :M1] = np.where(d > 0.0, (w[b] * w[b] - w[a] * w[a]) / (2.0 * d), 0.0)
+
+
 def rejoin_host(x, y, heading, kappa, v, ax, h, closed: bool, poses, v0, cfg: RlCfg, row=None, seg_hint=None,
                 window: int = 0, dt: float = 0.05, m_cap: int = 64, k_cap: int = 1024, stamps=None) -> Rejoin:
     """The specification of the rejoin stage (include/rl_abi.h) in NumPy; the kernel
@@ -780,20 +862,11 @@ def rejoin_host(x, y, heading, kappa, v, ax, h, closed: bool, poses, v0, cfg: Rl
     point the reachable speed nearest the row's is marched node by node (the samples ahead, at
     most k_cap) until it equals the row's; the ticks m * dt, counted from the car, follow the
     marched profile and then the row's own from the merge on."""
-    rows, hs = _traj_rows(x, y, heading, kappa, v, ax, h)
-    P, rw, hint, V0 = _rjn_query(poses, v0, cfg, row, seg_hint, window, dt, m_cap, k_cap)
-    B, N = rows[0].shape
-    if N < 1:
-        raise ValueError("rejoin: N == 0 (no row)")
-    Q, closed, dt, m_cap, W, k_cap = P.shape[0], bool(closed), float(dt), int(m_cap), int(window), int(k_cap)
-    S = N if closed else N - 1
-    rw = np.zeros(Q, dtype=np.int32) if rw is None else rw
-    hint = np.full(Q, -1, dtype=np.int32) if hint is None else hint
-    if np.any(rw < 0) or np.any(rw >= B):
-        raise ValueError(f"rejoin: row outside [0, {B})")
-    if np.any(hint < -1) or np.any(hint >= S):
-        raise ValueError(f"rejoin: seg_hint outside [-1, {S})")
-    stamps = _hzn_stamps(rows, hs, stamps)
+    closed = bool(closed)
+    rows, hs, stamps, N, S, (P, rw, hint, V0) = _query_rows(
+        "rejoin", (x, y, heading, kappa, v, ax, h), closed,
+        lambda: _rjn_query(poses, v0, cfg, row, seg_hint, window, dt, m_cap, k_cap), stamps)
+    Q, dt, m_cap, W, k_cap = P.shape[0], float(dt), int(m_cap), int(window), int(k_cap)
     consts = _rjn_consts(cfg)
     out = Rejoin.alloc(Q, m_cap, dt, k_cap)
     out.seg[:] = -1
@@ -803,25 +876,16 @@ def rejoin_host(x, y, heading, kappa, v, ax, h, closed: bool, poses, v0, cfg: Rl
         if S < 1:
             continue
         row6 = [a[rw[q]] for a in rows]
-        X, Y, PSI, KAP, V, _ = row6
         t, hb = stamps[rw[q]], float(hs[rw[q]])
         T = t[S]
-        loc = _hzn_locate(X, Y, t, hb, P[q, 0], P[q, 1], int(hint[q]), W, closed)
+        loc = _hzn_locate(row6[0], row6[1], t, hb, P[q, 0], P[q, 1], int(hint[q]), W, closed)
         if loc is None:
             continue
         out.seg[q], out.u[q], out.dist2[q], out.e[q], out.t0[q], out.s0[q] = loc
         i0, u, t0 = int(loc[0]), float(loc[1]), float(loc[4])
-        j0 = (i0 + 1) % N
         K_lim = min(k_cap, N if closed else N - 1 - i0)
         out.k_lim[q] = K_lim
-        n = i0 + np.arange(K_lim + 1)                       # the nodes' samples, unwrapped
-        idx = n % N
-        with np.errstate(all="ignore"):
-            kap = KAP[idx].copy()
-            r = V[idx].copy()
-            kap[0] = KAP[i0] + u * (KAP[j0] - KAP[i0])
-            r[0] = V[i0] + u * (V[j0] - V[i0])
-            d0 = (1.0 - u) * hb
+        nodes = _, _, kap, r, d0 = _march_nodes(row6, i0, u, hb, K_lim)
         kl, rl_, w, tt = kap.tolist(), r.tolist(), [float(V0[q])], [0.0]
         ks, over = -1, 0
         if w[0] == rl_[0]:
@@ -830,9 +894,7 @@ def rejoin_host(x, y, heading, kappa, v, ax, h, closed: bool, poses, v0, cfg: Rl
             over += w[0] > rl_[0]
             for k in range(K_lim):
                 d, wk = (d0 if k == 0 else hb), w[k]
-                a_acc, a_brk = _ax_max_at(consts, wk, kl[k])
-                up = math.sqrt(_smax(0.0, wk * wk + (2.0 * a_acc) * d))
-                dn = math.sqrt(_smax(0.0, wk * wk - (2.0 * a_brk) * d))
+                up, dn = _march_step(consts, wk, kl[k], d)
                 wn = _smin(up, _smax(dn, rl_[k + 1]))
                 w.append(wn)
                 tt.append(tt[k] + _fdiv(2.0 * d, _smax(1e-6, wk + wn)))
@@ -860,29 +922,7 @@ def rejoin_host(x, y, heading, kappa, v, ax, h, closed: bool, poses, v0, cfg: Rl
                 M = M1 + int(np.count_nonzero(wref[M1:] < T))
             out.count[q] = M
             if M1 > 0:
-                tau = tau_all[:M1]
-                a = _bisect_nodes(tt, tau, kend)
-                b = a + 1
-                um = (tau - tt[a]) / (tt[b] - tt[a])
-                d = np.where(a == 0, d0, hb)
-                # the nodes' values: node 0 the located point, node k >= 1 sample n_k
-                dp0 = PSI[j0] - PSI[i0]
-                dp0 = dp0 - 2.0 * np.pi if dp0 > np.pi else (dp0 + 2.0 * np.pi if dp0 < -np.pi else dp0)
-                nx, ny, npsi = X[idx].copy(), Y[idx].copy(), PSI[idx].copy()
-                ns = n.astype(np.float64) * hb
-                nx[0] = X[i0] + u * (X[j0] - X[i0])
-                ny[0] = Y[i0] + u * (Y[j0] - Y[i0])
-                npsi[0] = PSI[i0] + u * dp0
-                ns[0] = out.s0[q]
-                dp = npsi[b] - npsi[a]
-                dp = np.where(dp > np.pi, dp - 2.0 * np.pi, np.where(dp < -np.pi, dp + 2.0 * np.pi, dp))
-                out.s[q, :M1] = ns[a] + um * (ns[b] - ns[a])
-                out.x[q, :M1] = nx[a] + um * (nx[b] - nx[a])
-                out.y[q, :M1] = ny[a] + um * (ny[b] - ny[a])
-                out.heading[q, :M1] = npsi[a] + um * dp
-                out.kappa[q, :M1] = kap[a] + um * (kap[b] - kap[a])
-                out.v[q, :M1] = w[a] + um * (w[b] - w[a])
-                out.ax[q, :M1] = np.where(d > 0.0, (w[b] * w[b] - w[a] * w[a]) / (2.0 * d), 0.0)
+                _march_ticks(out, q, M1, tau_all[:M1], tt, w, kend, row6, nodes, i0, u, hb)
             if M > M1:
                 lap, wr = _hzn_wrap(wref[M1:M], T, closed)
                 for name, col in zip(abi.TRAJ_COLS, _hzn_columns(row6, t, hb, closed, np.float64(c0) + lap, wr)):
@@ -894,22 +934,17 @@ def rejoin(x, y, heading, kappa, v, ax, h, closed: bool, poses, v0, cfg: RlCfg, 
            window: int = 0, dt: float = 0.05, m_cap: int = 64, k_cap: int = 1024, device: int = 0) -> Rejoin:
     """rejoin_host on the GPU (rl_rejoin): the trajectory kernel stamps the B given rows, then the
     rejoin kernel answers the Q poses; row[q] counts the given rows."""
-    rows, hs = _traj_rows(x, y, heading, kappa, v, ax, h)
-    P, rw, hint, V0 = _rjn_query(poses, v0, cfg, row, seg_hint, window, dt, m_cap, k_cap)
-    B, N = rows[0].shape
-    if N < 1:
-        raise ValueError("rejoin: N == 0 (no row)")
-    out = Rejoin.alloc(P.shape[0], int(m_cap), dt, int(k_cap))
-    qc, oc = _rjn_c(P, rw, hint, V0, cfg, window, dt, m_cap, k_cap), out.as_c()
-    _check(_lib().rl_rejoin(*[_ptr(a, np.float64, "row") for a in rows], _ptr(hs, np.float64, "h"), N, B,
-                            1 if closed else 0, C.byref(qc), int(device), C.byref(oc)))
+    rows, hs, (P, rw, hint, V0), B, N = _open_query(
+        "rejoin", (x, y, heading, kappa, v, ax, h), lambda: _rjn_query(poses, v0, cfg, row, seg_hint, window, dt, m_cap, k_cap))
+    out = _one_shot("rl_rejoin", rows, hs, N, B, closed, _rjn_c(P, rw, hint, V0, cfg, window, dt, m_cap, k_cap),
+                    Rejoin.alloc(P.shape[0], int(m_cap), dt, int(k_cap)), device)
     out.set_k_lim(N, bool(closed))
     return out
 
 
 # ------------------------------------------------- stop: brake to a target speed at a sample
 @dataclass
-class Stop(Horizon):
+class Stop(_FromTheCar):
     """The stop stage's answer for Q poses (rl_stp): Horizon's fields, with the ticks counted from
     the car (t = m * dt) along the march up to the target, and stop_node (the march node of the
     target sample, -1: the target is not among the nodes ahead), reachable (1: the car is inside
@@ -953,14 +988,6 @@ class Stop(Horizon):
         """K_s: the target's march node of query q (-1: out of range)."""
         return int(self.stop_node[q])
 
-    def row(self, q: int) -> dict:
-        """The ticks of query q: t [count[q]] = m * dt, from the car, and the seven columns."""
-        m = int(self.count[q])
-        out = {"t": np.arange(m, dtype=np.float64) * self.dt}
-        for n in abi.TRAJ_COLS:
-            out[n] = getattr(self, n)[q, :m]
-        return out
-
 
 def _stp_query(poses, v0, cfg, stop_sample, v_target, row, seg_hint, window, dt, m_cap, k_cap) -> tuple:
     P, rw, hint, V0 = _rjn_query(poses, v0, cfg, row, seg_hint, window, dt, m_cap, k_cap)
@@ -1001,22 +1028,16 @@ def stop_host(x, y, heading, kappa, v, ax, h, closed: bool, poses, v0, cfg: RlCf
     b[K_s] = v_target with cfg, v0 is marched forward to K_s under it (inside the envelope the
     envelope caps the speed, outside it the car brakes as hard as cfg allows), and the ticks
     m * dt before t_stop follow the march."""
-    rows, hs = _traj_rows(x, y, heading, kappa, v, ax, h)
-    P, rw, hint, V0, J, VT = _stp_query(poses, v0, cfg, stop_sample, v_target, row, seg_hint, window, dt, m_cap, k_cap)
-    B, N = rows[0].shape
-    if N < 1:
-        raise ValueError("stop: N == 0 (no row)")
-    Q, closed, dt, m_cap, W, k_cap = P.shape[0], bool(closed), float(dt), int(m_cap), int(window), int(k_cap)
-    S = N if closed else N - 1
-    rw = np.zeros(Q, dtype=np.int32) if rw is None else rw
-    hint = np.full(Q, -1, dtype=np.int32) if hint is None else hint
-    if np.any(rw < 0) or np.any(rw >= B):
-        raise ValueError(f"stop: row outside [0, {B})")
-    if np.any(hint < -1) or np.any(hint >= S):
-        raise ValueError(f"stop: seg_hint outside [-1, {S})")
-    if np.any(J < 0) or np.any(J >= N):
-        raise ValueError(f"stop: stop_sample outside [0, {N})")
-    stamps = _hzn_stamps(rows, hs, stamps)
+    def in_row(N, qy):
+        _P, _rw, _hint, _V0, J, _VT = qy
+        if np.any(J < 0) or np.any(J >= N):
+            raise ValueError(f"stop: stop_sample outside [0, {N})")
+
+    closed = bool(closed)
+    rows, hs, stamps, N, S, (P, rw, hint, V0, J, VT) = _query_rows(
+        "stop", (x, y, heading, kappa, v, ax, h), closed,
+        lambda: _stp_query(poses, v0, cfg, stop_sample, v_target, row, seg_hint, window, dt, m_cap, k_cap), stamps, in_row)
+    Q, dt, m_cap, W, k_cap = P.shape[0], float(dt), int(m_cap), int(window), int(k_cap)
     consts = _rjn_consts(cfg)
     out = Stop.alloc(Q, m_cap, dt, k_cap)
     out.seg[:] = -1
@@ -1026,26 +1047,17 @@ def stop_host(x, y, heading, kappa, v, ax, h, closed: bool, poses, v0, cfg: RlCf
         if S < 1:
             continue
         row6 = [a[rw[q]] for a in rows]
-        X, Y, PSI, KAP, V, _ = row6
         t, hb = stamps[rw[q]], float(hs[rw[q]])
-        loc = _hzn_locate(X, Y, t, hb, P[q, 0], P[q, 1], int(hint[q]), W, closed)
+        loc = _hzn_locate(row6[0], row6[1], t, hb, P[q, 0], P[q, 1], int(hint[q]), W, closed)
         if loc is None:
             continue
         out.seg[q], out.u[q], out.dist2[q], out.e[q], out.t0[q], out.s0[q] = loc
         i0, u = int(loc[0]), float(loc[1])
-        j0 = (i0 + 1) % N
         K_lim = min(k_cap, N if closed else N - 1 - i0)
         Ks = (int(J[q]) - i0 - 1) % N + 1 if closed else int(J[q]) - i0
         if Ks < 1 or Ks > K_lim:
             continue
-        n = i0 + np.arange(Ks + 1)                          # the nodes' samples, unwrapped
-        idx = n % N
-        with np.errstate(all="ignore"):
-            kap = KAP[idx].copy()
-            r = V[idx].copy()
-            kap[0] = KAP[i0] + u * (KAP[j0] - KAP[i0])
-            r[0] = V[i0] + u * (V[j0] - V[i0])
-            d0 = (1.0 - u) * hb
+        nodes = _, _, kap, r, d0 = _march_nodes(row6, i0, u, hb, Ks)
         kl, rl_ = kap.tolist(), r.tolist()
         b = [0.0] * (Ks + 1)                                # the envelope, backward from the target
         b[Ks] = float(VT[q])
@@ -1065,9 +1077,7 @@ def stop_host(x, y, heading, kappa, v, ax, h, closed: bool, poses, v0, cfg: RlCf
             if k == Ks:
                 break
             d = d0 if k == 0 else hb
-            a_acc, a_brk = _ax_max_at(consts, wk, kl[k])
-            up = math.sqrt(_smax(0.0, wk * wk + (2.0 * a_acc) * d))
-            dn = math.sqrt(_smax(0.0, wk * wk - (2.0 * a_brk) * d))
+            up, dn = _march_step(consts, wk, kl[k], d)
             if wk <= b[k]:
                 wn = _smin(up, _smin(b[k + 1], _smax(dn, rl_[k + 1])))
             else:
@@ -1086,29 +1096,7 @@ def stop_host(x, y, heading, kappa, v, ax, h, closed: bool, poses, v0, cfg: RlCf
             M1 = int(np.count_nonzero(tau_all < tte))           # (monotone in m: the kernel bisects)
             out.count[q] = M1
             if M1 > 0:
-                tau = tau_all[:M1]
-                a = _bisect_nodes(tt, tau, Ks)
-                e = a + 1
-                um = (tau - tt[a]) / (tt[e] - tt[a])
-                d = np.where(a == 0, d0, hb)
-                # the nodes' values: node 0 the located point, node k >= 1 sample n_k
-                dp0 = PSI[j0] - PSI[i0]
-                dp0 = dp0 - 2.0 * np.pi if dp0 > np.pi else (dp0 + 2.0 * np.pi if dp0 < -np.pi else dp0)
-                nx, ny, npsi = X[idx].copy(), Y[idx].copy(), PSI[idx].copy()
-                ns = n.astype(np.float64) * hb
-                nx[0] = X[i0] + u * (X[j0] - X[i0])
-                ny[0] = Y[i0] + u * (Y[j0] - Y[i0])
-                npsi[0] = PSI[i0] + u * dp0
-                ns[0] = out.s0[q]
-                dp = npsi[e] - npsi[a]
-                dp = np.where(dp > np.pi, dp - 2.0 * np.pi, np.where(dp < -np.pi, dp + 2.0 * np.pi, dp))
-                out.s[q, :M1] = ns[a] + um * (ns[e] - ns[a])
-                out.x[q, :M1] = nx[a] + um * (nx[e] - nx[a])
-                out.y[q, :M1] = ny[a] + um * (ny[e] - ny[a])
-                out.heading[q, :M1] = npsi[a] + um * dp
-                out.kappa[q, :M1] = kap[a] + um * (kap[e] - kap[a])
-                out.v[q, :M1] = w[a] + um * (w[e] - w[a])
-                out.ax[q, :M1] = np.where(d > 0.0, (w[e] * w[e] - w[a] * w[a]) / (2.0 * d), 0.0)
+                _march_ticks(out, q, M1, tau_all[:M1], tt, w, Ks, row6, nodes, i0, u, hb)
     return out
 
 
@@ -1116,16 +1104,11 @@ def stop(x, y, heading, kappa, v, ax, h, closed: bool, poses, v0, cfg: RlCfg, st
          seg_hint=None, window: int = 0, dt: float = 0.05, m_cap: int = 64, k_cap: int = 1024, device: int = 0) -> Stop:
     """stop_host on the GPU (rl_stop): the trajectory kernel stamps the B given rows, then the
     stop kernel answers the Q poses; row[q] counts the given rows."""
-    rows, hs = _traj_rows(x, y, heading, kappa, v, ax, h)
-    P, rw, hint, V0, J, VT = _stp_query(poses, v0, cfg, stop_sample, v_target, row, seg_hint, window, dt, m_cap, k_cap)
-    B, N = rows[0].shape
-    if N < 1:
-        raise ValueError("stop: N == 0 (no row)")
-    out = Stop.alloc(P.shape[0], int(m_cap), dt, int(k_cap))
-    qc, oc = _stp_c(P, rw, hint, V0, cfg, J, None if v_target is None else VT, window, dt, m_cap, k_cap), out.as_c()
-    _check(_lib().rl_stop(*[_ptr(a, np.float64, "row") for a in rows], _ptr(hs, np.float64, "h"), N, B,
-                          1 if closed else 0, C.byref(qc), int(device), C.byref(oc)))
-    return out
+    rows, hs, (P, rw, hint, V0, J, VT), B, N = _open_query(
+        "stop", (x, y, heading, kappa, v, ax, h),
+        lambda: _stp_query(poses, v0, cfg, stop_sample, v_target, row, seg_hint, window, dt, m_cap, k_cap))
+    qc = _stp_c(P, rw, hint, V0, cfg, J, None if v_target is None else VT, window, dt, m_cap, k_cap)
+    return _one_shot("rl_stop", rows, hs, N, B, closed, qc, Stop.alloc(P.shape[0], int(m_cap), dt, int(k_cap)), device)
 
 
 # ------------------------------------------------- bounds: the free track width along the rows

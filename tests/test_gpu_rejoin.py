@@ -10,7 +10,10 @@ import pytest
 import torch  # noqa: F401  (before librl.so is loaded: torch then initialises its own HIP runtime first)
 
 import oracle_lib as O
+import query_cases as QC
 from practice_path_planning_for_formula_student_driverless_amd import abi, raceline
+from query_cases import B, CASES, DT, K, M_CAP, Q, ROW, bits, source_rows, synthetic_poses, synthetic_rows
+from query_cases import einval as _einval
 
 pytestmark = pytest.mark.gpu
 
@@ -19,15 +22,7 @@ COLS, LOC = abi.TRAJ_COLS, abi.HZN_LOC
 
 
 def _lib():
-    lib = abi.load_library()
-    if lib.rl_device_count() < 1:
-        pytest.fail("GPU test collected but no HIP device is visible")
-    assert lib.rl_abi_features() & abi.RL_FEATURE_REJOIN
-    return lib
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+    return QC.lib(abi.RL_FEATURE_REJOIN)
 
 
 def assert_rjn_equal(got, want, label):
@@ -39,11 +34,8 @@ def assert_rjn_equal(got, want, label):
     for f in LOC + abi.RJN_SCAL:
         np.testing.assert_array_equal(bits(getattr(got, f))[found], bits(getattr(want, f))[found], err_msg=f"{label}: {f}")
     np.testing.assert_array_equal(got.k_lim, want.k_lim, err_msg=f"{label}: k_lim")
+    QC.assert_ticks_equal(got, want, label)
     for q in range(len(want.count)):
-        m = int(want.count[q])
-        for f in COLS:
-            np.testing.assert_array_equal(bits(getattr(got, f)[q, :m]), bits(getattr(want, f)[q, :m]),
-                                          err_msg=f"{label}: query {q} {f}")
         if found[q]:
             e = want.node_end(q) + 1
             for f in abi.RJN_NODES:
@@ -58,11 +50,7 @@ def assert_cols_equal(got, want, label):
     found = want.seg >= 0
     for f in LOC:
         np.testing.assert_array_equal(bits(getattr(got, f))[found], bits(getattr(want, f))[found], err_msg=f"{label}: {f}")
-    for q in range(len(want.count)):
-        m = int(want.count[q])
-        for f in COLS:
-            np.testing.assert_array_equal(bits(getattr(got, f)[q, :m]), bits(getattr(want, f)[q, :m]),
-                                          err_msg=f"{label}: query {q} {f}")
+    QC.assert_ticks_equal(got, want, label)
 
 
 # ------------------------------------------------------------------ 1. synthetic rows
@@ -70,38 +58,7 @@ def assert_cols_equal(got, want, label):
 # samples than RL_RJN_MAX_NODES (a march that K_cap ends), 4097: the first N whose stamps are
 # read from the global row
 SYN_N = [1, 2, 3, 63, 64, 65, 257, 1025, 4097]
-B, Q = 3, 7
-ROW = np.array([0, 1, 2, 0, 1, 2, 1], dtype=np.int32)
 CFG = abi.default_cfg()
-
-
-def synthetic_rows(N, seed, smooth=False):
-    """B wobbly rings around the origin, each with its own speeds and step.  smooth: speeds that
-    vary slowly along the row, so that a march takes many nodes to meet them."""
-    rng = np.random.default_rng(seed)
-    ang = 2.0 * np.pi * (np.arange(N) + rng.uniform(-0.3, 0.3, size=(B, N))) / max(N, 1)
-    rad = 40.0 * (1.0 + 0.2 * rng.uniform(-1, 1, size=(B, N)))
-    x, y = rad * np.cos(ang), rad * np.sin(ang)
-    psi = rng.uniform(-np.pi, np.pi, size=(B, N))                  # neighbours straddle +-pi often
-    kap = rng.normal(size=(B, N)) * (0.01 if smooth else 0.1)
-    if smooth:
-        v = 18.0 + 6.0 * np.sin(3.0 * ang + rng.uniform(0, 6, size=(B, 1)))
-    else:
-        v = rng.uniform(0.5, 30.0, size=(B, N))
-    ax = rng.normal(size=(B, N)) * 5.0
-    h = rng.uniform(0.05, 0.5, size=B)
-    return (x, y, psi, kap, v, ax), h
-
-
-def synthetic_poses(rows, N, S, rng):
-    """Q poses on rows ROW: jittered off the row, exactly on a sample, and one far outside."""
-    at = rng.integers(0, N, size=Q)
-    at[0], at[1] = 0, N - 1                                        # both ends of the row
-    P = np.stack([rows[0][ROW, at], rows[1][ROW, at]], axis=1)
-    P[[0, 2, 4, 6]] += rng.normal(size=(4, 2)) * 2.0
-    P[5] = [300.0, -200.0]
-    hint = np.clip(at, 0, max(S - 1, 0)).astype(np.int32)
-    return np.ascontiguousarray(P), hint
 
 
 def own_speed(rows, h, closed, P, row, **kw):
@@ -207,12 +164,6 @@ def test_hand_worked_standing_start_on_the_device():
 
 
 # ------------------------------------------------------------------ 2. the plan path
-CASES = {"training_map": ("track_training_map", 16, 16),
-         "training_open": ("training_open", 16, 16),
-         "oval_n10000": ("oval_n10000", 4, 4)}                    # the streaming kernel; stamps from global
-DT, M_CAP, K = 0.05, 1024, 3
-
-
 def plan_poses(x, y, seed, nq):
     rng = np.random.default_rng(seed)
     R, N = x.shape
@@ -229,23 +180,14 @@ def plan_run(name):
     horizon stage, then rejoin stages (the rows' own speeds, standing starts at sample 0 with the
     plan's cfg and with half its acceleration cap), with the trajectory and the horizon stage
     fetched before and after them."""
-    case_name, nb, gs = CASES[name]
-    case = O.load_case(case_name)
-    prob, cfg = O.case_problem(case), O.case_cfg(case)
+    cfg = O.case_cfg(O.load_case(CASES[name][0]))
     weak = abi.RlCfg.from_buffer_copy(cfg)
     weak.a_long_acc_cap = 0.5 * cfg.a_long_acc_cap
-    pl = raceline.Plan(prob, cfg, seeds=np.arange(nb, dtype=np.uint64), B=nb, modes=MC | MT)
-    pl.run()
-    before = pl.fetch()
     res = {}
-    for mode in ("mintime", "mincurv"):
-        pl.select(mode, k=K, group_size=gs, score="lap")
-        sel = pl.fetch_selected()
-        stage, path_len = pl.fetch_lap() if mode == "mincurv" else (None, None)
+    for t in QC.plan_to_trajectory(name):
+        pl, prob, _, before, mode, sel, stage, path_len, traj = t
         idx = sel.index.ravel()
         v = (stage.v if mode == "mincurv" else before[1].v)[idx]
-        pl.trajectory(mode, DT, M_CAP, rows="selected")
-        traj = pl.fetch_trajectory()
         P, row = plan_poses(sel.out.x, sel.out.y, 21, 6)
         pl.horizon(P, row=row, dt=DT, m_cap=64)
         hz = pl.fetch_horizon()
@@ -264,20 +206,9 @@ def plan_run(name):
         res[mode] = dict(sel=sel, stage=stage, path_len=path_len, traj=traj, traj_after=pl.fetch_trajectory(), hz=hz,
                          hz_after=pl.fetch_horizon(), P=P, row=row, own=own, r_own=r_own, start=start, kw=kw,
                          r_start=r_start, r_weak=r_weak, ms=ms)
-    after = pl.fetch()
-    pl.close()
-    return dict(prob=prob, cfg=cfg, weak=weak, before=before, after=after, **res)
-
-
-def source_rows(r, mode):
-    """The winners' rows a plan's trajectory stage read, as downloaded, and their steps."""
-    prob, m = r["prob"], r[mode]
-    idx = m["sel"].index.ravel()
-    if mode == "mintime":
-        o = r["before"][1]
-        return [a[idx] for a in (o.x, o.y, o.heading, o.kappa, o.v, o.ax)], prob.L / prob.N
-    o, s = r["before"][0], m["stage"]
-    return [a[idx] for a in (o.x, o.y, s.heading, s.kappa, s.v, s.ax)], m["path_len"][idx] / prob.N
+    after = t.pl.fetch()                                           # (t: the last mode's; one plan, one problem)
+    t.pl.close()
+    return dict(prob=t.prob, cfg=cfg, weak=weak, before=t.before, after=after, **res)
 
 
 @pytest.mark.parametrize("mode", ["mintime", "mincurv"])
@@ -339,12 +270,6 @@ def test_rejoin_stage_leaves_the_other_stages_and_the_results_as_they_were(name)
 
 
 # ----------------------------------------------------------------------- 3. life cycle
-def _einval(fn, *args, **kw):
-    with pytest.raises(raceline.RacelineError) as ei:
-        fn(*args, **kw)
-    assert ei.value.code == abi.RL_EINVAL
-
-
 def test_rejoin_life_cycle():
     _lib()
     case = O.load_case("track_training_map")
