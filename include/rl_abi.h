@@ -247,7 +247,8 @@ int rl_plan_bind_device_outputs(rl_plan* plan, int32_t which, const rl_out* dev_
  * the trajectory stage of the last rl_plan_trajectory, 8 = the horizon stage of the last
  * rl_plan_horizon, 9 = the rejoin stage of the last rl_plan_rejoin, 10 = the stop stage of the
  * last rl_plan_stop, 11 = the bounds stage of the last rl_plan_bounds, 12 = the bounds at the
- * horizon stage's ticks of the last rl_plan_horizon_bounds. */
+ * horizon stage's ticks of the last rl_plan_horizon_bounds, 13 = the retime stage of the last
+ * rl_plan_retime. */
 int rl_plan_kernel_ms(rl_plan* plan, int32_t idx, float* ms);
 /* The batch size the plan's kernel shape is chosen for (rl_kernel_shape's B); 0 = the plan's
  * own B (the default).  Shapes differ in the tree order of the J / decrease / lap sums, so
@@ -645,6 +646,84 @@ int rl_stop(const double* x, const double* y, const double* heading, const doubl
             const double* v, const double* ax, const double* h, int32_t N, int32_t B,
             int32_t closed, const rl_stp_query* query, int32_t device, rl_stp* out);
 
+/* ------------------------------------------------- retime stage: the look-ahead speed profile under the car's limits now
+ * The rejoin and stop stages follow the row's own speed r, which was computed under the planning
+ * cfg; the car's limits now enter their marches only along the path (ax_max_at).  With less grip
+ * than the plan had, every corner of r is too fast, and neither stage brakes for a corner ahead.
+ * This stage runs the reference's velocity_profile_forward_backward itself over the nodes ahead
+ * of the car, with the query's cfg and from the car's speed: the path stays, the speeds are
+ * recomputed.  It is what a controller calls when its friction estimate changes.  The query is
+ * the rejoin stage's.  In fp64 without contraction; smax, smin, the row, ax_max_at, the march's
+ * step and time are the rejoin stage's:
+ *   locate, nodes   the rejoin stage's: seg = i, u, e, dist2, t0, s0; kappa_k, r_k, d_k,
+ *           n_k = i + k for k = 0..K, K = K_lim = min(K_cap, closed ? N : N-1-i).  A NaN winner,
+ *           S = 0, or K_lim < 1 (an open row's last sample): seg as located or -1,
+ *           end_node = -1, count = 0, nothing else is specified.
+ *   ceiling   per node, independent of the others:
+ *           c_k = smin(smin(v_cap_mps, sqrt(a_lat_max / smax(fabs(kappa_k), kappa_eps))), r_k)
+ *           with the query's cfg: the reference's initial profile, in its order, capped by the
+ *           row's speed.  A NaN r_k does not cap (smin(x, NaN) = x).  r caps on purpose: the
+ *           stage never drives the path faster than it was planned for.
+ *   envelope   serial, backward: b_K = c_K.  For k = K-1 .. 0:
+ *           (., a_brk) = ax_max_at(cfg, b_{k+1}, kappa_{k+1});
+ *           b_k = smin(c_k, sqrt(smax(0.0, b_{k+1}*b_{k+1} + (2.0*a_brk)*d_k)))
+ *           (the reference's backward step).  feasible = (v0 <= b_0).
+ *   march   serial, forward, always to K: w_0 = v0, tt_0 = 0.0.  For k = 0 .. K-1:
+ *           (up, dn) = the rejoin march's step from w_k at kappa_k over d_k;
+ *           w_{k+1} = smin(up, (w_k <= b_k) ? b_{k+1} : smax(dn, b_{k+1}));
+ *           tt_{k+1} = tt_k + (2.0*d_k)/smax(1e-6, w_k + w_{k+1}).
+ *           Inside the envelope the envelope caps the speed, as in the stop stage; outside it
+ *           the car brakes as hard as the cfg allows.  From v0 = b_0 on a row whose nodes are its
+ *           samples, w is the reference's converged profile bit for bit (one backward and one
+ *           forward sweep reach its fixed point).
+ *   per query   end_node = K; feasible (0 or 1); overspeed = #{k in [0, K] : w_k > b_k};
+ *           v_excess = the largest w_k - b_k over the same k, or 0.0 (serial: e = 0.0, then
+ *           e = smax(e, w_k - b_k) in index order); bind_node = the first k in [0, K] with
+ *           b_k < r_k, where today's limits first fall below the plan (none: -1);
+ *           t_end = tt_K; with c0 = floor(n_K / N) and j = n_K - c0*N,
+ *           t_loss = tt_K - (((double)c0*T + t[j]) - t0), the time lost against the plan over
+ *           the window.
+ *   ticks   tau_m = (double)m*dt, counted from the car.  count = #{m < M_cap : tau_m < tt_K};
+ *           every tick lies on the march: the rejoin stage's node bisection over tt[0..K] and
+ *           its march-tick columns apply unchanged.  The stage never hands over to the row's
+ *           own ticks.
+ * Known limit: the envelope starts from c_K, so a corner beyond node K is not foreseen.  Callers
+ * use the first part of the window and query again.
+ * raceline.retime_host states the same in NumPy; the kernel equals it bit for bit.  These are
+ * additions to ABI 6.1 that leave RL_ABI_MINOR as it is: RL_FEATURE_RETIME announces them. */
+typedef struct rl_rtm_query {
+    rl_rjn_query   rj;           /* the rejoin stage's query, with the same meaning and checks */
+} rl_rtm_query;
+
+typedef struct rl_rtm {          /* caller-allocated; NULL fields skipped; it begins as rl_rjn does */
+    double *s, *x, *y, *heading, *kappa, *v, *ax;   /* [Q][M_cap]; ticks m >= count[q] are unspecified */
+    double *u, *t0, *s0, *e, *dist2;                /* [Q] */
+    int32_t *seg, *count;                           /* [Q] */
+    int32_t *end_node, *overspeed;                  /* [Q] */
+    double *t_end, *t_loss;                         /* [Q] */
+    double *node_v, *node_t;                        /* [Q][K_cap+1] w_k, tt_k; entries past K are unspecified;
+                                                       downloaded only when asked for */
+    int32_t *feasible, *bind_node;                  /* [Q] */
+    double *v_excess;                               /* [Q] */
+    double *node_b, *node_c;                        /* [Q][K_cap+1] b_k, c_k, as node_v */
+} rl_rtm;
+
+/* Enqueue the stage after the plan's last trajectory stage: rl_plan_horizon's stream, validity
+ * and invalidation rules.  It leaves the results, the trajectory stage and the last horizon,
+ * rejoin and stop stages untouched; its buffers are plan-owned (they count toward the plan
+ * cache's budget) and grow with Q, M_cap and K_cap.  The query's arrays and cfg are read before
+ * the call returns.  rl_plan_kernel_ms index 13 is the stage.  RL_EINVAL before any device work
+ * for: every error of rl_plan_rejoin. */
+int rl_plan_retime(rl_plan* plan, const rl_rtm_query* query, void* hip_stream);
+/* Download the last retime stage (synchronises its stream) into the non-NULL fields of out.
+ * RL_EINVAL before a stage, or after a run or trajectory stage that followed it. */
+int rl_plan_fetch_retime(rl_plan* plan, rl_rtm* out);
+/* The same on B given rows [B][N] with steps h [B] (host in, host out): the trajectory kernel
+ * for the stamps, then the retime kernel.  Errors as rl_rejoin's. */
+int rl_retime(const double* x, const double* y, const double* heading, const double* kappa,
+              const double* v, const double* ax, const double* h, int32_t N, int32_t B,
+              int32_t closed, const rl_rtm_query* query, int32_t device, rl_rtm* out);
+
 /* ------------------------------------------------- bounds stage: the free track width along the rows
  * Every tick of the stages above carries s, x, y, heading, kappa, v, ax, and the location carries
  * the lateral offset e.  This stage says how much room there is on either side: an MPC's track
@@ -796,6 +875,7 @@ int         rl_abi_minor(void);
 #define RL_FEATURE_REJOIN 4       /* bit 2: the rejoin stage */
 #define RL_FEATURE_STOP 8         /* bit 3: the stop stage */
 #define RL_FEATURE_BOUNDS 16      /* bit 4: the bounds stage */
+#define RL_FEATURE_RETIME 32      /* bit 5: the retime stage */
 int         rl_abi_features(void);
 /* samples per lane of the THROUGHPUT shape for N (4: N <= 256, 5: N <= 320, 8: N <= 4096;
  * 1 = the streaming kernel), or RL_ETOOBIG.  Batches small enough for a latency shape launch fewer samples per lane:

@@ -202,6 +202,29 @@ class RlStp(C.Structure):
                 [(n, C.POINTER(C.c_double)) for n in STP_SCAL[2:] + STP_NODES[2:]])
 
 
+RL_FEATURE_RETIME = 32     # rl_abi_features() bit 5: the retime stage
+RTM_SCAL = ("t_end", "t_loss", "v_excess")
+RTM_INTS = ("seg", "count", "end_node", "overspeed", "feasible", "bind_node")
+RTM_NODES = ("node_v", "node_t", "node_b", "node_c")
+
+
+class RlRtmQuery(C.Structure):
+    """``rl_rtm_query`` — one ``rl_rjn_query``: the pose, the car's speed and its limits now."""
+
+    _fields_ = [("rj", RlRjnQuery)]
+
+
+class RlRtm(C.Structure):
+    """``rl_rtm`` — ``rl_rjn``'s layout with end_node, overspeed, t_end, t_loss in the place of its
+    four, then feasible, bind_node, v_excess [Q] and the optional node_b, node_c [Q][K_cap + 1];
+    NULL fields are skipped."""
+
+    _fields_ = (RlHzn._fields_ + [(n, C.POINTER(C.c_int32)) for n in RTM_INTS[2:4]] +
+                [(n, C.POINTER(C.c_double)) for n in RTM_SCAL[:2] + RTM_NODES[:2]] +
+                [(n, C.POINTER(C.c_int32)) for n in RTM_INTS[4:]] +
+                [(n, C.POINTER(C.c_double)) for n in RTM_SCAL[2:] + RTM_NODES[2:]])
+
+
 RL_FEATURE_BOUNDS = 16     # rl_abi_features() bit 4: the bounds stage
 BND_ROWS = ("lo", "hi", "nx", "ny")
 HZN_BND = ("lo", "hi", "lo0", "hi0")
@@ -609,6 +632,14 @@ DECLS_BND = [
     ("rl_bounds", C.c_int, [_P(RlProblem), _F64, _F64, C.c_int32, C.c_double, C.c_double, C.c_int32, _BND]),
 ]
 
+# the retime stage: bound only in a library whose rl_abi_features() has RL_FEATURE_RETIME
+_RTM, _RTMQ = _P(RlRtm), _P(RlRtmQuery)
+DECLS_RTM = [
+    ("rl_plan_retime", C.c_int, [C.c_void_p, _RTMQ, C.c_void_p]),
+    ("rl_plan_fetch_retime", C.c_int, [C.c_void_p, _RTM]),
+    ("rl_retime", C.c_int, [_F64] * 7 + [C.c_int32, C.c_int32, C.c_int32, _RTMQ, C.c_int32, _RTM]),
+]
+
 
 def declare_optimize(fn) -> None:
     """rl_optimize's signature (the oracle's oracle_optimize shares it)."""
@@ -622,7 +653,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     """Load librl.so (the HIP path).  Raises if it is missing: there is no fallback; a library
     that lacks a function of DECLS or DECLS_EXT raises AttributeError naming it, and so does
     one that announces RL_FEATURE_HORIZON / RL_FEATURE_REJOIN / RL_FEATURE_STOP /
-    RL_FEATURE_BOUNDS and lacks a function of DECLS_HZN / DECLS_RJN / DECLS_STP / DECLS_BND."""
+    RL_FEATURE_BOUNDS / RL_FEATURE_RETIME and lacks a function of DECLS_HZN / DECLS_RJN / DECLS_STP /
+    DECLS_BND / DECLS_RTM."""
     global _LIB
     if _LIB is not None and path == LIB_PATH:
         return _LIB
@@ -648,6 +680,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         bind(DECLS_STP)
     if ext and lib.rl_abi_features() & RL_FEATURE_BOUNDS:
         bind(DECLS_BND)
+    if ext and lib.rl_abi_features() & RL_FEATURE_RETIME:
+        bind(DECLS_RTM)
     if path == LIB_PATH:
         _LIB = lib
     return lib

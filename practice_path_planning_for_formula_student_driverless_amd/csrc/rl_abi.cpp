@@ -2,6 +2,8 @@
 // plan, the cfg defaults, and the one-shot entry points that upload, run one kernel and
 // download.  Plans are in rl_plan.cpp, their stages in rl_stages.cpp, rl_optimize and the
 // plan cache in rl_cache.cpp.  The compute path is the gfx950 kernels; there is no CPU fallback.
+#include <type_traits>
+
 #include "rl_host.h"
 
 using namespace rl;
@@ -33,16 +35,18 @@ int rows_on_device(DevArena& mem, const std::string& fn, const double* const (&i
     return RL_OK;
 }
 
-// rl_horizon / rl_rejoin / rl_stop (arguments checked, the device selected; K_cap = 0: the
-// horizon; a stop_sample: the stop stage): the
+// rl_horizon / rl_rejoin / rl_stop / rl_retime (arguments checked, the device selected; K_cap = 0:
+// the horizon; a stop_sample: the stop stage; Out = rl_rtm: the retime stage of a rejoin query): the
 // trajectory kernel for the stamps of the host rows (one tick per row, not downloaded), then the
 // stage's kernel on them; `row` counts the B given rows
+template <class Out>
 int query_rows(const std::string& fn, const double* const (&in)[6], const double* h, int32_t N, int32_t B, int32_t closed,
-               const rl_stp_query& q, const rl_stp& out) {
+               const rl_stp_query& q, const Out& out) {
+    constexpr bool retime = std::is_same<Out, rl_rtm>::value;
     DevArena mem;
     rl::TrajParams t;
     if (int rc = rows_on_device(mem, fn, in, h, N, B, closed, q.rj.dt, 1, &t)) return rc;
-    const QueryLayout L = query_layout(q);
+    const QueryLayout L = query_layout(q, retime);
     char* d_qry = mem.get<char>(L.in_bytes);
     char* d_res = mem.get<char>(L.out_bytes);
     if (!mem.ok()) return fail(RL_ENOMEM, fn + ": hipMalloc failed");
@@ -50,7 +54,9 @@ int query_rows(const std::string& fn, const double* const (&in)[6], const double
     query_pack(q, L, block.data());
     if (hipMemcpy(d_qry, block.data(), L.in_bytes, hipMemcpyHostToDevice) != hipSuccess) return fail(RL_EHIP, fn + ": upload");
     if (rl::launch_trajectory(t, nullptr) != hipSuccess) return fail(RL_EHIP, fn + ": trajectory kernel");
-    if (query_launch(query_params(t, q, L, d_qry, d_res), nullptr) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+    const StpParams sp = query_params(t, q, L, d_qry, d_res);
+    const hipError_t e = retime ? retime_launch(sp, *q.rj.cfg, L, d_res, nullptr) : query_launch(sp, nullptr);
+    if (e != hipSuccess || hipDeviceSynchronize() != hipSuccess)
         return fail(RL_EHIP, fn + ": kernel");
     if (hipMemcpy(block.data(), d_res, query_wants_nodes(out) ? L.out_bytes : L.head_bytes, hipMemcpyDeviceToHost) != hipSuccess)
         return fail(RL_EHIP, fn + ": download");
@@ -66,7 +72,8 @@ const char* rl_last_error(void) { return g_err.c_str(); }
 int rl_abi_version(void) { return RL_ABI_VERSION; }
 int rl_abi_minor(void) { return RL_ABI_MINOR; }
 int rl_abi_features(void) {
-    return RL_FEATURE_TRAJECTORY | RL_FEATURE_HORIZON | RL_FEATURE_REJOIN | RL_FEATURE_STOP | RL_FEATURE_BOUNDS;
+    return RL_FEATURE_TRAJECTORY | RL_FEATURE_HORIZON | RL_FEATURE_REJOIN | RL_FEATURE_STOP | RL_FEATURE_BOUNDS |
+           RL_FEATURE_RETIME;
 }
 
 int rl_device_count(void) {
@@ -435,6 +442,18 @@ int rl_stop(const double* x, const double* y, const double* heading, const doubl
     if (int rc = check_stp(query, B, N, closed ? 1 : 0)) return rc;
     if (int rc = select_device(device)) return rc;
     return query_rows("rl_stop", {x, y, heading, kappa, v, ax}, h, N, B, closed, *query, *out);
+}
+
+int rl_retime(const double* x, const double* y, const double* heading, const double* kappa, const double* v,
+              const double* ax, const double* h, int32_t N, int32_t B, int32_t closed, const rl_rtm_query* query,
+              int32_t device, rl_rtm* out) {
+    if (!x || !y || !heading || !kappa || !v || !ax || !h || !query || !out)
+        return fail(RL_EINVAL, "rl_retime: an input row, h, the query or out is NULL");
+    if (B < 1 || N < 0) return fail(RL_EINVAL, "rl_retime: B < 1 or N < 0");
+    if (N > rl::RL_STREAM_MAX_N) return fail(RL_ETOOBIG, "rl_retime: N exceeds 1048576");
+    if (int rc = check_rjn(&query->rj, B, N, closed ? 1 : 0)) return rc;
+    if (int rc = select_device(device)) return rc;
+    return query_rows("rl_retime", {x, y, heading, kappa, v, ax}, h, N, B, closed, as_stp(query->rj), *out);
 }
 
 // rank host scores with rl_rank_kernel (rl_select.hip)

@@ -4,9 +4,12 @@
 // with the optional parts empty, so both go through the rejoin forms (as_rjn) with K = K_cap =
 // 0 for the horizon.  The stop stage is the rejoin stage with a target and more results: its
 // forms (as_stp) hold the rejoin forms, and a layout with `stop` set has the extra arrays, each
-// kind behind the rejoin stage's of that kind; without it no offset or byte count moves.  No HIP
-// call: a host compiler builds it without a device (tests/test_query_layout_cpu.py,
-// tests/test_stop_layout_cpu.py).  Not part of the public ABI.
+// kind behind the rejoin stage's of that kind; without it no offset or byte count moves.  The
+// retime stage (§3p) is the rejoin stage with more results: its query is the rejoin stage's, and
+// a layout with `retime` set has its extra arrays in the same places; without it no offset or
+// byte count moves.  No HIP call: a host compiler builds it without a device
+// (tests/test_query_layout_cpu.py, tests/test_stop_layout_cpu.py, tests/test_retime_cpu.py).
+// Not part of the public ABI.
 #pragma once
 #include <cstddef>
 #include <cstring>
@@ -14,6 +17,7 @@
 #include "rl_abi.h"
 #include "rl_rejoin.h"
 #include "rl_stop.h"
+#include "rl_retime.h"
 
 namespace rl {
 
@@ -28,7 +32,10 @@ constexpr int QRY_NODES = 2;                  // node_v, node_t
 // stop_sample [Q] behind hint; s_stop and v_excess [Q] behind the n_per doubles, reachable and
 // brake_node [Q] behind the n_ints ints (all four in the head), node_b [Q][K + 1] behind the
 // node arrays.  Its stop_node, t_stop and v_end lie where the rejoin stage's merge_node,
-// t_merge and t_loss do.
+// t_merge and t_loss do.  A retime stage's results' block has as well: v_excess [Q] behind the
+// n_per doubles, feasible and bind_node [Q] behind the n_ints ints (all three in the head),
+// node_b and node_c [Q][K + 1] behind the node arrays.  Its end_node and t_end lie where the
+// rejoin stage's merge_node and t_merge do.
 struct QueryLayout {
     size_t Q, M, K;
     size_t pose, v0, row, hint, in_bytes;
@@ -36,13 +43,16 @@ struct QueryLayout {
     size_t col[TRAJ_COLS], per[QRY_PER], ints[QRY_INTS], nodes[QRY_NODES], head_bytes, out_bytes;
     bool stop;
     size_t v_target, stop_sample, sper[STP_SCAL], sints[STP_INTS], node_b;
+    bool retime;
+    size_t rper[RTM_SCAL], rints[RTM_INTS], rnodes[RTM_NODES];
 };
 
-inline QueryLayout query_layout(size_t Q, size_t M, size_t K, bool stop = false) {
+inline QueryLayout query_layout(size_t Q, size_t M, size_t K, bool stop = false, bool retime = false) {
     QueryLayout L{};
     const bool rjn = K > 0;
     L.Q = Q; L.M = M; L.K = K;
     L.stop = stop;
+    L.retime = retime;
     L.n_per = HZN_LOC + (rjn ? RJN_SCAL : 0);
     L.n_ints = rjn ? QRY_INTS : 2;
     L.n_nodes = rjn ? QRY_NODES : 0;
@@ -59,11 +69,14 @@ inline QueryLayout query_layout(size_t Q, size_t M, size_t K, bool stop = false)
     for (auto& o : L.col) o = take(Q * M * 8);
     for (int c = 0; c < L.n_per; ++c) L.per[c] = take(Q * 8);
     for (auto& o : L.sper) o = take(stop ? Q * 8 : 0);
+    for (auto& o : L.rper) o = take(retime ? Q * 8 : 0);
     for (int c = 0; c < L.n_ints; ++c) L.ints[c] = take(Q * 4);
     for (auto& o : L.sints) o = take(stop ? Q * 4 : 0);
+    for (auto& o : L.rints) o = take(retime ? Q * 4 : 0);
     L.head_bytes = at;
     for (int c = 0; c < L.n_nodes; ++c) L.nodes[c] = take(Q * (K + 1) * 8);
     L.node_b = take(stop ? Q * (K + 1) * 8 : 0);
+    for (auto& o : L.rnodes) o = take(retime ? Q * (K + 1) * 8 : 0);
     L.out_bytes = at;
     return L;
 }
@@ -91,9 +104,14 @@ inline rl_stp as_stp(const rl_rjn& o) {
             o.merge_node, o.overspeed, o.t_merge, o.t_loss, o.node_v, o.node_t,
             nullptr, nullptr, nullptr, nullptr, nullptr};
 }
-// a query with a stop_sample is a stop stage's
-inline QueryLayout query_layout(const rl_stp_query& q) {
-    return query_layout((size_t)q.rj.Q, (size_t)q.rj.M_cap, (size_t)q.rj.K_cap, q.stop_sample != nullptr);
+// a query with a stop_sample is a stop stage's; retime: the rejoin query of a retime stage
+inline QueryLayout query_layout(const rl_stp_query& q, bool retime = false) {
+    return query_layout((size_t)q.rj.Q, (size_t)q.rj.M_cap, (size_t)q.rj.K_cap, q.stop_sample != nullptr, retime);
+}
+// the rejoin part of a retime stage's results (rl_rtm begins with rl_rjn's fields)
+inline rl_rjn as_rjn(const rl_rtm& o) {
+    return {o.s, o.x, o.y, o.heading, o.kappa, o.v, o.ax, o.u, o.t0, o.s0, o.e, o.dist2, o.seg, o.count,
+            o.end_node, o.overspeed, o.t_end, o.t_loss, o.node_v, o.node_t};
 }
 
 // fill the queries' block (host) from q: a NULL row is 0, a NULL seg_hint -1
@@ -156,6 +174,20 @@ inline StpParams query_pointers(const rl_stp_query& q, const QueryLayout& L, cha
     return s;
 }
 
+// a retime stage's launch on the rejoin pointers r of its query: the pointers of its extra arrays
+// in `out`, and the ceiling's cfg fields
+inline RtmParams retime_pointers(const RjnParams& r, const rl_cfg& cfg, const QueryLayout& L, char* out) {
+    RtmParams t{};
+    t.rj = r;
+    t.v_cap = cfg.v_cap_mps; t.a_lat_max = cfg.a_lat_max; t.kappa_eps = cfg.kappa_eps;
+    t.v_excess = (double*)(out + L.rper[0]);
+    t.feasible = (int32_t*)(out + L.rints[0]);
+    t.bind_node = (int32_t*)(out + L.rints[1]);
+    t.node_b = (double*)(out + L.rnodes[0]);
+    t.node_c = (double*)(out + L.rnodes[1]);
+    return t;
+}
+
 // copy a results' block (host) into the non-NULL fields of o; with node_v and node_t NULL only
 // the head is read
 inline void query_unpack(const char* block, const QueryLayout& L, const rl_rjn& o) {
@@ -188,5 +220,18 @@ inline void query_unpack(const char* block, const QueryLayout& L, const rl_stp& 
 }
 // whether a fetch into o needs the node arrays, which lie behind the head
 inline bool query_wants_nodes(const rl_stp& o) { return o.node_v || o.node_t || o.node_b; }
+
+// the same for a retime stage (L.retime set)
+inline void query_unpack(const char* block, const QueryLayout& L, const rl_rtm& o) {
+    query_unpack(block, L, as_rjn(o));
+    int32_t* const rints[RTM_INTS] = {o.feasible, o.bind_node};
+    double* const rnodes[RTM_NODES] = {o.node_b, o.node_c};
+    if (o.v_excess) std::memcpy(o.v_excess, block + L.rper[0], L.Q * 8);
+    for (int c = 0; c < RTM_INTS; ++c)
+        if (rints[c]) std::memcpy(rints[c], block + L.rints[c], L.Q * 4);
+    for (int c = 0; c < RTM_NODES; ++c)
+        if (rnodes[c]) std::memcpy(rnodes[c], block + L.rnodes[c], L.Q * (L.K + 1) * 8);
+}
+inline bool query_wants_nodes(const rl_rtm& o) { return o.node_v || o.node_t || o.node_b || o.node_c; }
 
 }  // namespace rl

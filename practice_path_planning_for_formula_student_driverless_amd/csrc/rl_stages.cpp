@@ -5,7 +5,9 @@
 // Horizon stage (rl_horizon.hip): poses located on that stage's rows, and the next
 // ticks from there.  Rejoin stage (rl_rejoin.hip): the same from the car's speed, along a
 // reachable profile.  Stop stage (rl_stop.hip): the same under a brake envelope, up
-// to a target sample.  These three pose-query stages share one enqueue and one fetch routine.
+// to a target sample.  Retime stage (rl_retime.hip): the reference's speed pass
+// over the nodes ahead, under the car's cfg.  These four pose-query stages share one enqueue and
+// one fetch routine.
 // Bounds stage (rl_bounds.hip): the free track width about the trajectory stage's
 // rows, and at the horizon stage's ticks.
 #include "rl_host.h"
@@ -120,6 +122,10 @@ StpParams rl::query_params(const TrajParams& src, const rl_stp_query& q, const Q
 hipError_t rl::query_launch(const StpParams& s, hipStream_t st) {
     if (s.stop_sample) return rl::launch_stop(s, st);
     return s.rj.K_cap > 0 ? rl::launch_rejoin(s.rj, st) : rl::launch_horizon(s.rj.hz, st);
+}
+
+hipError_t rl::retime_launch(const StpParams& s, const rl_cfg& cfg, const QueryLayout& L, char* out, hipStream_t st) {
+    return rl::launch_retime(retime_pointers(s.rj, cfg, L, out), st);
 }
 
 namespace {
@@ -255,12 +261,13 @@ int select_impl(rl_plan* p, const rl_select* sel, int gs, bool by_lap, void* hip
     return RL_OK;
 }
 
-// rl_plan_horizon / rl_plan_rejoin / rl_plan_stop (arguments checked; K_cap = 0: the horizon;
-// a stop_sample: the stop stage): one launch of the stage's kernel on the last trajectory stage.
+// rl_plan_horizon / rl_plan_rejoin / rl_plan_stop / rl_plan_retime (arguments checked; K_cap = 0:
+// the horizon; a stop_sample: the stop stage; retime: the retime stage of a rejoin query): one
+// launch of the stage's kernel on the last trajectory stage.
 // The queries go up in one block, through s's pinned block, ahead of the kernel on the same
 // stream.
-int query_enqueue(rl_plan* p, QueryStage& s, const rl_stp_query& q, void* hip_stream) {
-    const char* what = q.stop_sample ? "stop" : q.rj.K_cap > 0 ? "rejoin" : "horizon";
+int query_enqueue(rl_plan* p, QueryStage& s, const rl_stp_query& q, void* hip_stream, bool retime = false) {
+    const char* what = retime ? "retime" : q.stop_sample ? "stop" : q.rj.K_cap > 0 ? "rejoin" : "horizon";
     const std::string fn = std::string("rl_plan_") + what;
     if (p->traj_q.index && p->traj_sel_epoch != p->sel_epoch)
         return fail(RL_EINVAL, fn + ": a selection has replaced the winners the trajectory stage read");
@@ -275,7 +282,7 @@ int query_enqueue(rl_plan* p, QueryStage& s, const rl_stp_query& q, void* hip_st
     if (s.ev[0]) HIPCHK(hipEventSynchronize(s.ev[0]));
     s.Q = 0;
     if (&s == &p->hzn) p->hb_Q = 0;                    // the tick bounds of the horizon stage before
-    const QueryLayout L = query_layout(q);
+    const QueryLayout L = query_layout(q, retime);
     if (int rc = s.reserve(p->last_stream, L.in_bytes, L.out_bytes, what)) return rc;
     for (auto& e : s.ev)
         if (!e) HIPCHK(hipEventCreate(&e));
@@ -284,13 +291,15 @@ int query_enqueue(rl_plan* p, QueryStage& s, const rl_stp_query& q, void* hip_st
     query_pack(q, L, s.pin);
     HIPCHK(hipMemcpyAsync(s.in, s.pin, L.in_bytes, hipMemcpyHostToDevice, st));
     HIPCHK(hipEventRecord(s.ev[0], st));
-    const hipError_t e = query_launch(query_params(p->traj_q, q, L, s.in, s.out), st);
+    const StpParams sp = query_params(p->traj_q, q, L, s.in, s.out);
+    const hipError_t e = retime ? retime_launch(sp, *q.rj.cfg, L, s.out, st) : query_launch(sp, st);
     if (e != hipSuccess) return fail(RL_EHIP, std::string(what) + " launch: " + hipGetErrorString(e));
     HIPCHK(hipEventRecord(s.ev[1], st));
     s.Q = q.rj.Q;
     s.M = q.rj.M_cap;
     s.K = q.rj.K_cap;
     s.stop = L.stop;
+    s.retime = L.retime;
     s.dt = q.rj.dt;
     return RL_OK;
 }
@@ -331,13 +340,15 @@ int horizon_bounds_alloc(rl_plan* p, size_t Q, size_t M) {
     return RL_OK;
 }
 
-// rl_plan_fetch_horizon / rl_plan_fetch_rejoin / rl_plan_fetch_stop (a valid stage in s): the
-// results' block comes down through the pinned block, without the node arrays if o asks for none
-int query_fetch(rl_plan* p, QueryStage& s, const rl_stp& o) {
+// rl_plan_fetch_horizon / rl_plan_fetch_rejoin / rl_plan_fetch_stop / rl_plan_fetch_retime (a valid
+// stage in s; Out: rl_stp, or rl_rtm for the retime stage): the results' block comes down through
+// the pinned block, without the node arrays if o asks for none
+template <class Out>
+int query_fetch(rl_plan* p, QueryStage& s, const Out& o) {
     HIPCHK(hipSetDevice(p->device));
     hipStream_t st = p->run_stream();
     HIPCHK(hipStreamWaitEvent(st, s.ev[1], 0));         // (a later stage may have moved to another stream)
-    const QueryLayout L = query_layout((size_t)s.Q, (size_t)s.M, (size_t)s.K, s.stop);
+    const QueryLayout L = query_layout((size_t)s.Q, (size_t)s.M, (size_t)s.K, s.stop, s.retime);
     HIPCHK(hipMemcpyAsync(s.pin, s.out, query_wants_nodes(o) ? L.out_bytes : L.head_bytes, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     query_unpack(s.pin, L, o);
@@ -568,6 +579,23 @@ int rl_plan_fetch_stop(rl_plan* p, rl_stp* out) {
     if (!p->stp.Q || !p->traj_R)
         return fail(RL_EINVAL, "rl_plan_fetch_stop: no stop stage since the plan's last run or trajectory stage");
     return query_fetch(p, p->stp, *out);
+}
+
+// blocks of its own: the last horizon, rejoin and stop stages stay as they are
+int rl_plan_retime(rl_plan* p, const rl_rtm_query* query, void* hip_stream) {
+    if (!p) return fail(RL_EINVAL, "plan is NULL");
+    if (!query) return fail(RL_EINVAL, "retime: the query is NULL");
+    if (!p->traj_R) return fail(RL_EINVAL, "rl_plan_retime: no trajectory stage since the plan's last run");
+    if (int rc = check_rjn(&query->rj, p->traj_R, p->N, p->closed)) return rc;
+    return query_enqueue(p, p->rtm, as_stp(query->rj), hip_stream, true);
+}
+
+int rl_plan_fetch_retime(rl_plan* p, rl_rtm* out) {
+    if (!p) return fail(RL_EINVAL, "plan is NULL");
+    if (!out) return fail(RL_EINVAL, "rl_plan_fetch_retime: out is NULL");
+    if (!p->rtm.Q || !p->traj_R)
+        return fail(RL_EINVAL, "rl_plan_fetch_retime: no retime stage since the plan's last run or trajectory stage");
+    return query_fetch(p, p->rtm, *out);
 }
 
 // One launch of rl_bounds_kernel over the rows the last trajectory stage read: its x, y and

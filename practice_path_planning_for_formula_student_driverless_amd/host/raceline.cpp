@@ -51,6 +51,10 @@
 //               also the winners' ticks from the sample K nodes before J (512; clipped to the row
 //               and to RL_RJN_MAX_NODES), at the raceline's own speed there, braking to V m/s (0)
 //               at sample J (rl_stop), in <base>_trajectory_<r>_stop.csv (the same columns)
+//   --retime-set key=value [--retime-set ...] [--retime-from S]  with --best K --mode mintime --trajectory-dt DT:
+//               the winners from sample S (0) at the raceline's own speed there, over the samples
+//               ahead, under this run's cfg with the given knobs replaced (rl_retime), in
+//               <base>_trajectory_<r>_retimed.csv (the same columns)
 //   --bounds    with --best K --trajectory-dt DT: also the free track width about every sample of
 //               the winners (rl_bounds, guard = cfg veh_width_m / 2 + safety_margin_m), in
 //               <base>_bounds_<r>.csv: i,x,y,nx,ny,lo,hi
@@ -1200,6 +1204,14 @@ static void compute_mintime_and_save(const string& base, const vector<Vec2>& cen
     if (C.debug_dump) debug_dump(base, center_for_opt, s0, L, closed_mode, res);
 }
 
+// --retime-set / --retime-from: the knobs that replace this run's cfg in the retime stage, and
+// the sample the winners start from (-1: not given)
+struct RetimeOpt {
+    vector<string> sets;
+    int from = -1;
+};
+static RetimeOpt g_retime;
+
 // B α-seeds in one launch (beyond the reference): one summary row per instance.
 static void batch_and_save(const string& base, const vector<Vec2>& center, double L, bool closed,
                            const vector<Vec2>& inner_from_mids, const vector<Vec2>& outer_from_mids, int B, int modes,
@@ -1270,7 +1282,9 @@ static void batch_and_save(const string& base, const vector<Vec2>& center, doubl
     const bool want_rjn = want_traj && start_speed >= 0.0;
     // --stop-sample: the stop stage needs the winners' whole rows as well
     const bool want_stp = want_traj && stop_sample >= 0;
-    const bool want_rows = want_rjn || want_stp;
+    // --retime-set: the retime stage needs the winners' whole rows as well
+    const bool want_rtm = want_traj && !g_retime.sets.empty();
+    const bool want_rows = want_rjn || want_stp || want_rtm;
     vector<double> wrow[4], tT(want_rows ? idx.size() : 0);      // heading, kappa, v, ax
     for (auto& col : wrow) col.resize(want_rows ? idx.size() * N : 0);
     auto run_best = [&]() {
@@ -1438,6 +1452,59 @@ static void batch_and_save(const string& base, const vector<Vec2>& center, doubl
             std::cerr << "[stop] winner " << r << " from sample " << at << " to " << stop_speed << " m/s at sample " << stop_sample
                       << ": stop: t_stop " << tstop[r] << " s, brake_node " << brake[r] << " of " << node[r] << ", v_end "
                       << vend[r] << " m/s\n";
+        }
+    }
+    // <base>_trajectory_<r>_retimed.csv: winner r from sample --retime-from at the raceline's own
+    // speed there, over the samples ahead, with the limits of this run's cfg after --retime-set
+    if (want_rtm) {
+        const size_t K = idx.size();
+        cfg::Config now = C;
+        for (const string& kv : g_retime.sets)
+            if (!cfg::set_knob(now, kv)) throw std::runtime_error("unknown cfg knob: " + kv);
+        const rl_cfg cn = cfg::to_abi(now);
+        const int at = std::max(g_retime.from, 0);
+        vector<double> pose(2 * K), v0(K), h(K, L / (double)N), rcol[7], tend(K), tloss(K);
+        vector<int32_t> row(K), hint(K, at), rcount(K), node(K), bind(K), feas(K);
+        for (size_t r = 0; r < K; ++r) {
+            pose[2 * r] = bx[r * N + at];
+            pose[2 * r + 1] = by[r * N + at];
+            v0[r] = wrow[2][r * N + at];
+            row[r] = (int32_t)r;
+        }
+        for (auto& col : rcol) col.resize(K * (size_t)traj_cap);
+        rl_rtm_query q;
+        std::memset(&q, 0, sizeof(q));
+        q.rj.pose_xy = pose.data(); q.rj.row = row.data(); q.rj.seg_hint = hint.data();
+        q.rj.Q = (int32_t)K; q.rj.window = 0; q.rj.M_cap = traj_cap; q.rj.dt = traj_dt;
+        q.rj.v0 = v0.data(); q.rj.cfg = &cn; q.rj.K_cap = RL_RJN_MAX_NODES;
+        rl_rtm rt;
+        std::memset(&rt, 0, sizeof(rt));
+        rt.s = rcol[0].data(); rt.x = rcol[1].data(); rt.y = rcol[2].data(); rt.heading = rcol[3].data();
+        rt.kappa = rcol[4].data(); rt.v = rcol[5].data(); rt.ax = rcol[6].data();
+        rt.count = rcount.data(); rt.end_node = node.data(); rt.bind_node = bind.data(); rt.feasible = feas.data();
+        rt.t_end = tend.data(); rt.t_loss = tloss.data();
+        gpu::check(rl_retime(bx.data(), by.data(), wrow[0].data(), wrow[1].data(), wrow[2].data(), wrow[3].data(), h.data(),
+                             (int32_t)N, (int32_t)K, closed ? 1 : 0, &q, gpu::device, &rt),
+                   "rl_retime");
+        std::cerr << std::setprecision(9);
+        for (size_t r = 0; r < K; ++r) {
+            if (node[r] < 0) throw std::runtime_error("retime: no node ahead of the pose");
+            const int64_t rows = rcount[r];
+            vector<double> tab((size_t)rows * 8);
+            for (int64_t m = 0; m < rows; ++m) {
+                tab[(size_t)m * 8] = (double)m * traj_dt;
+                for (int cc = 0; cc < 7; ++cc) tab[(size_t)m * 8 + 1 + cc] = rcol[cc][r * (size_t)traj_cap + (size_t)m];
+            }
+            vector<char> text((size_t)rows * 8 * 22 + 1);
+            int64_t len = 0;
+            gpu::check(rl_format_csv(tab.data(), rows, 8, gpu::device, text.data(), (int64_t)text.size(), &len, nullptr),
+                       "rl_format_csv");
+            io::Csv o(base + "_trajectory_" + std::to_string(r) + "_retimed.csv");
+            if (!o) throw std::runtime_error("save retimed trajectory failed");
+            o.f << "t,s,x,y,heading_rad,curvature,v_mps,ax_mps2\n";
+            o.f.write(text.data(), (std::streamsize)len);
+            std::cerr << "[retime] winner " << r << " from sample " << at << " over " << node[r] << " nodes: retime: t_end "
+                      << tend[r] << " s, t_loss " << tloss[r] << " s, bind_node " << bind[r] << ", feasible " << feas[r] << "\n";
         }
     }
     // <base>_bounds_<r>.csv: the room on either side of every sample of winner r along its unit
@@ -1633,6 +1700,25 @@ int run_from_centerline(const string& outPath, double L, double s0, const string
             return 2;
         }
     }
+    if (!pipeline::g_retime.sets.empty() || pipeline::g_retime.from != -1) {
+        // (the winners' whole rows: as for --start-speed)
+        if (pipeline::g_retime.sets.empty() || !(traj_dt > 0.0) || mode != "mintime") {
+            std::cerr << "[ERR] --retime-set key=value [--retime-from S] needs --seeds B --best K --mode mintime "
+                         "--trajectory-dt DT\n";
+            return 2;
+        }
+        const int N = (int)center_for_opt.size();
+        if (pipeline::g_retime.from != -1 && (pipeline::g_retime.from < 0 || pipeline::g_retime.from >= (closed_mode ? N : N - 1))) {
+            std::cerr << "[ERR] --retime-from S: a sample of the raceline with one ahead, 0.." << (closed_mode ? N : N - 1) - 1 << "\n";
+            return 2;
+        }
+        cfg::Config probe = C;
+        for (const string& kv : pipeline::g_retime.sets)
+            if (!cfg::set_knob(probe, kv)) {
+                std::cerr << "[ERR] --retime-set: unknown cfg knob: " << kv << "\n";
+                return 2;
+            }
+    }
     if (want_bounds && (!(traj_dt > 0.0) || best <= 0)) {
         std::cerr << "[ERR] --bounds needs --seeds B --best K --trajectory-dt DT\n";
         return 2;
@@ -1703,6 +1789,11 @@ int main(int argc, char** argv) {
                 stop_from = std::stoi(next());
                 if (stop_from == 0) stop_from = -1;                // (0 stands for "not given")
             }
+            else if (a == "--retime-set") pipeline::g_retime.sets.push_back(next());
+            else if (a == "--retime-from") {
+                pipeline::g_retime.from = std::stoi(next());
+                if (pipeline::g_retime.from == -1) pipeline::g_retime.from = -2;   // (-1 stands for "not given")
+            }
             else if (a == "--bounds") want_bounds = true;
             else if (a == "--device") gpu::device = std::stoi(next());
             else if (a == "--devices") {
@@ -1726,6 +1817,8 @@ int main(int argc, char** argv) {
                       << "         [--start-speed V]   with --mode mintime --trajectory-dt: the winners from sample 0 at V m/s\n"
                       << "         [--stop-sample J [--stop-speed V] [--stop-from K]]   with --mode mintime --trajectory-dt: the winners\n"
                       << "             from K (512) samples before J, braking to V (0) m/s at sample J\n"
+                      << "         [--retime-set key=value ... [--retime-from S]]   with --mode mintime --trajectory-dt: the winners\n"
+                      << "             from sample S (0) over the samples ahead, under the cfg with these knobs replaced\n"
                       << "         [--bounds]   with --best K --trajectory-dt: the free track width along the winners\n";
             return 1;
         }

@@ -1111,6 +1111,142 @@ def stop(x, y, heading, kappa, v, ax, h, closed: bool, poses, v0, cfg: RlCfg, st
     return _one_shot("rl_stop", rows, hs, N, B, closed, qc, Stop.alloc(P.shape[0], int(m_cap), dt, int(k_cap)), device)
 
 
+# ------------------------------------------------- retime: the speed profile under the car's limits now
+@dataclass
+class Retime(_FromTheCar):
+    """The retime stage's answer for Q poses (rl_rtm): Horizon's fields, with the ticks counted from
+    the car (t = m * dt) along the march over the nodes ahead, and end_node (the last node K, -1:
+    no answer), feasible (1: the car is inside the envelope of cfg), overspeed (nodes at which the
+    car is faster than the envelope), bind_node (the first node at which the envelope is below the
+    row's speed, -1: none), t_end (the time marched), t_loss (the time lost against the row's own
+    schedule over the window), v_excess (the largest excess over the envelope) [Q]; node_v, node_t,
+    node_b, node_c [Q, k_cap + 1]: the march's speeds and times, the envelope and the ceiling, the
+    entries after node_end(q) unspecified.  Where end_node is -1 only seg and count are specified."""
+
+    end_node: np.ndarray = None
+    overspeed: np.ndarray = None
+    feasible: np.ndarray = None
+    bind_node: np.ndarray = None
+    t_end: np.ndarray = None
+    t_loss: np.ndarray = None
+    v_excess: np.ndarray = None
+    node_v: np.ndarray = None
+    node_t: np.ndarray = None
+    node_b: np.ndarray = None
+    node_c: np.ndarray = None
+
+    @classmethod
+    def alloc(cls, Q: int, m_cap: int, dt: float, k_cap: int = 1) -> "Retime":
+        cols = {n: np.zeros((Q, m_cap)) for n in abi.TRAJ_COLS}
+        per = {n: np.zeros(Q) for n in abi.HZN_LOC + abi.RTM_SCAL}
+        ints = {n: np.zeros(Q, dtype=np.int32) for n in abi.RTM_INTS}
+        nodes = {n: np.zeros((Q, k_cap + 1)) for n in abi.RTM_NODES}
+        return cls(**cols, **per, **ints, **nodes, dt=float(dt))
+
+    def as_c(self) -> abi.RlRtm:
+        t = abi.RlRtm()
+        for n in abi.TRAJ_COLS + abi.HZN_LOC + abi.RTM_SCAL + abi.RTM_NODES:
+            setattr(t, n, _ptr(getattr(self, n), np.float64, n))
+        for n in abi.RTM_INTS:
+            setattr(t, n, _ptr(getattr(self, n), np.int32, n))
+        return t
+
+    def node_end(self, q: int) -> int:
+        """K: the last march node of query q (-1: no answer)."""
+        return int(self.end_node[q])
+
+
+def retime_host(x, y, heading, kappa, v, ax, h, closed: bool, poses, v0, cfg: RlCfg, row=None, seg_hint=None,
+                window: int = 0, dt: float = 0.05, m_cap: int = 64, k_cap: int = 1024, stamps=None) -> Retime:
+    """The specification of the retime stage (include/rl_abi.h) in NumPy; the kernel
+    equals it bit for bit.  The rows, poses, hints, stamps, v0 and cfg are rejoin_host's, and so
+    are the locate and the nodes 0 .. K = K_lim.  Per node the ceiling c is the lowest of cfg's
+    v_cap, its lateral limit sqrt(a_lat_max / |kappa|) and the row's speed r; the envelope b is
+    swept backward under c from b[K] = c[K] with cfg's braking; v0 is marched forward to K under b
+    (inside the envelope the envelope caps the speed, outside it the car brakes as hard as cfg
+    allows); and the ticks m * dt before t_end follow the march.  It is the reference's
+    velocity_profile_forward_backward over the nodes ahead, with the car's cfg, from the car's
+    speed."""
+    closed = bool(closed)
+    rows, hs, stamps, N, S, (P, rw, hint, V0) = _query_rows(
+        "retime", (x, y, heading, kappa, v, ax, h), closed,
+        lambda: _rjn_query(poses, v0, cfg, row, seg_hint, window, dt, m_cap, k_cap), stamps)
+    Q, dt, m_cap, W, k_cap = P.shape[0], float(dt), int(m_cap), int(window), int(k_cap)
+    consts = _rjn_consts(cfg)
+    v_cap, a_lat, k_eps = float(cfg.v_cap_mps), float(cfg.a_lat_max), float(cfg.kappa_eps)
+    out = Retime.alloc(Q, m_cap, dt, k_cap)
+    out.seg[:] = -1
+    out.end_node[:] = -1
+    tau_all = np.arange(m_cap, dtype=np.float64) * dt
+    for q in range(Q):
+        if S < 1:
+            continue
+        row6 = [a[rw[q]] for a in rows]
+        t, hb = stamps[rw[q]], float(hs[rw[q]])
+        T = t[S]
+        loc = _hzn_locate(row6[0], row6[1], t, hb, P[q, 0], P[q, 1], int(hint[q]), W, closed)
+        if loc is None:
+            continue
+        i0, u, t0 = int(loc[0]), float(loc[1]), loc[4]
+        K = min(k_cap, N if closed else N - 1 - i0)
+        if K < 1:
+            continue
+        out.seg[q], out.u[q], out.dist2[q], out.e[q], out.t0[q], out.s0[q] = loc
+        nodes = _, _, kap, r, d0 = _march_nodes(row6, i0, u, hb, K)
+        kl, rl_ = kap.tolist(), r.tolist()
+        c = [_smin(_smin(v_cap, math.sqrt(_fdiv(a_lat, _smax(abs(kk), k_eps)))), rk)     # the ceiling, per node
+             for kk, rk in zip(kl, rl_)]
+        b = [0.0] * (K + 1)                                 # the envelope, backward from the last node
+        b[K] = c[K]
+        for k in range(K - 1, -1, -1):
+            d, bn = (d0 if k == 0 else hb), b[k + 1]
+            a_brk = _ax_max_at(consts, bn, kl[k + 1])[1]
+            b[k] = _smin(c[k], math.sqrt(_smax(0.0, bn * bn + (2.0 * a_brk) * d)))
+        w, tt = [float(V0[q])], [0.0]                       # the march, forward to the last node
+        over, ve, bind = 0, 0.0, -1
+        for k in range(K + 1):
+            wk = w[k]
+            over += wk > b[k]
+            ve = _smax(ve, wk - b[k])
+            if bind < 0 and b[k] < rl_[k]:
+                bind = k
+            if k == K:
+                break
+            d = d0 if k == 0 else hb
+            up, dn = _march_step(consts, wk, kl[k], d)
+            wn = _smin(up, b[k + 1] if wk <= b[k] else _smax(dn, b[k + 1]))
+            w.append(wn)
+            tt.append(tt[k] + _fdiv(2.0 * d, _smax(1e-6, wk + wn)))
+        w, tt, b, c = np.array(w), np.array(tt), np.array(b), np.array(c)
+        out.node_v[q, :K + 1], out.node_t[q, :K + 1], out.node_b[q, :K + 1], out.node_c[q, :K + 1] = w, tt, b, c
+        tte = tt[K]
+        out.end_node[q], out.overspeed[q], out.feasible[q] = K, over, 1 if float(V0[q]) <= b[0] else 0
+        out.bind_node[q], out.t_end[q], out.v_excess[q] = bind, tte, ve
+        nk = i0 + K
+        c0 = nk // N
+        with np.errstate(all="ignore"):
+            out.t_loss[q] = tte - ((np.float64(c0) * T + t[nk - c0 * N]) - t0)
+            M1 = int(np.count_nonzero(tau_all < tte))           # (monotone in m: the kernel bisects)
+            out.count[q] = M1
+            if M1 > 0:
+                _march_ticks(out, q, M1, tau_all[:M1], tt, w, K, row6, nodes, i0, u, hb)
+    return out
+
+
+def _rtm_c(P, rw, hint, V0, cfg, window, dt, m_cap, k_cap) -> abi.RlRtmQuery:
+    return abi.RlRtmQuery(_rjn_c(P, rw, hint, V0, cfg, window, dt, m_cap, k_cap))
+
+
+def retime(x, y, heading, kappa, v, ax, h, closed: bool, poses, v0, cfg: RlCfg, row=None, seg_hint=None,
+           window: int = 0, dt: float = 0.05, m_cap: int = 64, k_cap: int = 1024, device: int = 0) -> Retime:
+    """retime_host on the GPU (rl_retime): the trajectory kernel stamps the B given rows, then the
+    retime kernel answers the Q poses; row[q] counts the given rows."""
+    rows, hs, (P, rw, hint, V0), B, N = _open_query(
+        "retime", (x, y, heading, kappa, v, ax, h), lambda: _rjn_query(poses, v0, cfg, row, seg_hint, window, dt, m_cap, k_cap))
+    return _one_shot("rl_retime", rows, hs, N, B, closed, _rtm_c(P, rw, hint, V0, cfg, window, dt, m_cap, k_cap),
+                     Retime.alloc(P.shape[0], int(m_cap), dt, int(k_cap)), device)
+
+
 # ------------------------------------------------- bounds: the free track width along the rows
 @dataclass
 class Bounds:
@@ -1483,6 +1619,34 @@ class Plan:
         if not nodes:
             t.node_v = t.node_t = t.node_b = None
         _check(_lib().rl_plan_fetch_stop(self._h, C.byref(t)))
+        return out
+
+    def retime(self, poses, v0, cfg: RlCfg, row=None, seg_hint=None, window: int = 0, dt: float = 0.05,
+               m_cap: int = 64, k_cap: int = 1024, stream_ptr: int = 0) -> None:
+        """Enqueue the retime stage after the last trajectory() (rl_plan_retime): rejoin()'s query,
+        answered with the speed profile of cfg (the car's limits now) over the k_cap samples
+        ahead: the path stays, the speeds are recomputed under cfg from v0 and never exceed the
+        row's.  The trajectory stage and the last horizon(), rejoin() and stop() stay as they
+        are."""
+        P, rw, hint, V0 = _rjn_query(poses, v0, cfg, row, seg_hint, window, dt, m_cap, k_cap)
+        self._rtm = None
+        qc = _rtm_c(P, rw, hint, V0, cfg, window, dt, m_cap, k_cap)
+        _check(_lib().rl_plan_retime(self._h, C.byref(qc), C.c_void_p(stream_ptr) if stream_ptr else None))
+        self._rtm = (P.shape[0], int(m_cap), float(dt), int(k_cap))
+
+    def fetch_retime(self, nodes: bool = True) -> Retime:
+        """Download the last retime() (rl_plan_fetch_retime); nodes=False leaves node_v, node_t,
+        node_b, node_c on the device."""
+        if getattr(self, "_rtm", None) is None:
+            t = abi.RlRtm()                 # (the library's own answer: no stage on this plan)
+            _check(_lib().rl_plan_fetch_retime(self._h, C.byref(t)))
+            raise ValueError("fetch_retime: no retime() on this plan")
+        Q, m_cap, dt, k_cap = self._rtm
+        out = Retime.alloc(Q, m_cap, dt, k_cap)
+        t = out.as_c()
+        if not nodes:
+            t.node_v = t.node_t = t.node_b = t.node_c = None
+        _check(_lib().rl_plan_fetch_retime(self._h, C.byref(t)))
         return out
 
     def bounds(self, veh_width: Optional[float] = None, margin: Optional[float] = None, stream_ptr: int = 0) -> None:

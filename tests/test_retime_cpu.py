@@ -1,0 +1,283 @@
+"""The retime stage's specification, raceline.retime_host, without a GPU: the march on
+a straight in closed form, a row under its own planning cfg reproduced bit for bit, the same row
+under a wet cfg, a car outside the envelope, the edges of the march, the argument checks, the
+packed blocks (tests/retime_layout_check.cpp) and the ABI's new structs and feature bit."""
+import ctypes as C
+import math
+import os
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+
+import oracle_lib as O
+import vpass_anchor_cases as VA
+from practice_path_planning_for_formula_student_driverless_amd import abi, raceline
+
+COLS, LOC = abi.TRAJ_COLS, abi.HZN_LOC
+HEADER = os.path.join(O.REPO, "include", "rl_abi.h")
+CSRC = os.path.join(O.REPO, "practice_path_planning_for_formula_student_driverless_amd", "csrc")
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+N_ROW, H_ROW = 401, 0.17
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+def path_of(kap, h):
+    """x, y, heading of a row with curvature kap and step h, from the origin along +x."""
+    psi = np.concatenate(([0.0], np.cumsum(kap[:-1] * h)))
+    x = np.concatenate(([0.0], np.cumsum(np.cos(psi[:-1]) * h)))
+    y = np.concatenate(([0.0], np.cumsum(np.sin(psi[:-1]) * h)))
+    return x, y, (psi + np.pi) % (2.0 * np.pi) - np.pi
+
+
+def sine_row(cfg):
+    """N = 401, h = 0.17, kappa = 0.08 sin(0.05 i), the speed the oracle's converged v-pass under cfg."""
+    kap = 0.08 * np.sin(0.05 * np.arange(N_ROW))
+    v, sweeps = VA.oracle_v(cfg, kap, H_ROW, 12)
+    assert sweeps < 12
+    x, y, psi = path_of(kap, H_ROW)
+    return (x, y, psi, kap, v, np.zeros(N_ROW)), H_ROW
+
+
+def ring(N=240, R=30.0, v=12.0):
+    a = 2.0 * np.pi * np.arange(N) / N
+    psi = (a + np.pi / 2.0 + np.pi) % (2.0 * np.pi) - np.pi
+    return (R * np.cos(a), R * np.sin(a), psi, np.full(N, 1.0 / R), np.full(N, v), np.zeros(N)), 2.0 * np.pi * R / N
+
+
+def wet_cfg(cfg):
+    """test_gpu_stop.py's wet cfg: mu = 0.8, and the lateral limit lowered to the total as well."""
+    wet = abi.RlCfg.from_buffer_copy(cfg)
+    abi.set_mu(wet, 0.8)
+    wet.a_lat_max = min(wet.a_lat_max, wet.a_total_max)
+    return wet
+
+
+def at(rows, i):
+    return [[rows[0][i], rows[1][i]]]
+
+
+def retime_at(rows, h, closed, i, v0, cfg, **kw):
+    """One pose on sample i (the hint keeps the locate there)."""
+    kw = {"dt": 0.05, "m_cap": 512, "k_cap": 1024, **kw}
+    return raceline.retime_host(*rows, h, closed, at(rows, i), v0, cfg, seg_hint=[i], window=0, **kw)
+
+
+# ------------------------------------------------------------------ straight row, no drag
+def test_a_straight_is_constant_acceleration_to_the_cap():
+    """r = +inf, no drag, rolling resistance or power limit, v_cap = 20: from rest w_k^2 = 2 a k h
+    with a = a_long_acc_cap until the cap, one partial step onto it, then the cap.  The trapezoid
+    is exact for constant acceleration, so t_end = sqrt(2 n h / a) + 2 h / (w_n + v_cap) +
+    (K - n - 1) h / v_cap with n the last node below the cap.  Each of the K = 400 steps rounds a
+    few times: 400 * 4 * 2^-53 = 1.8e-13 relative; 1e-12 leaves a factor of 5."""
+    cfg = abi.default_cfg()
+    cfg.Cd, cfg.c_rr, cfg.P_max_W, cfg.v_cap_mps = 0.0, 0.0, 0.0, 20.0
+    a, h, K = cfg.a_long_acc_cap, H_ROW, N_ROW - 1
+    assert a < cfg.a_total_max
+    z = np.zeros(N_ROW)
+    rows = (np.arange(N_ROW) * h, z, z, z, np.full(N_ROW, np.inf), z)
+    r = retime_at(rows, h, False, 0, 0.0, cfg)
+    assert r.end_node[0] == K and r.seg[0] == 0 and r.u[0] == 0.0 and r.feasible[0] == 1 and r.overspeed[0] == 0
+    assert r.bind_node[0] == 1 and r.v_excess[0] == 0.0       # r_0 is NaN (inf - inf), r_1 = +inf is above any envelope
+    n = int(math.floor(20.0 ** 2 / (2.0 * a * h)))
+    assert 10 < n < K - 10
+    k = np.arange(n + 1)
+    np.testing.assert_allclose(r.node_v[0, :n + 1] ** 2, 2.0 * a * k * h, rtol=1e-12, atol=0.0)
+    assert np.all(r.node_v[0, n + 1:K + 1] == 20.0) and np.all(r.node_b[0, :K + 1] == 20.0) and np.all(r.node_c[0, :K + 1] == 20.0)
+    t_end = math.sqrt(2.0 * n * h / a) + 2.0 * h / (math.sqrt(2.0 * a * n * h) + 20.0) + (K - n - 1) * h / 20.0
+    assert abs(r.t_end[0] - t_end) <= 1e-12 * t_end
+    assert r.node_t[0, K] == r.t_end[0] and r.t_loss[0] == r.t_end[0]       # r = +inf: the plan takes no time
+    assert r.count[0] == int(np.count_nonzero(np.arange(512) * 0.05 < r.t_end[0]))
+
+
+# ------------------------------------------------------------------ the planning cfg, and a wet one
+def test_a_row_under_its_own_planning_cfg_is_reproduced():
+    cfg = abi.default_cfg()
+    rows, h = sine_row(cfg)
+    v = rows[4]
+    r = retime_at(rows, h, False, 0, v[0], cfg)
+    K = N_ROW - 1
+    assert r.end_node[0] == K and r.feasible[0] == 1 and r.overspeed[0] == 0 and r.bind_node[0] == -1 and r.v_excess[0] == 0.0
+    np.testing.assert_array_equal(bits(r.node_b[0, :K + 1]), bits(v))
+    np.testing.assert_array_equal(bits(r.node_v[0, :K + 1]), bits(v))
+    np.testing.assert_array_equal(bits(r.node_c[0, :K + 1]), bits(v))       # r caps the ceiling
+    assert np.count_nonzero(np.diff(v) > 0) >= 10 and np.count_nonzero(np.diff(v) < 0) >= 10
+
+
+def test_the_same_row_under_a_wet_cfg():
+    cfg = abi.default_cfg()
+    wet = wet_cfg(cfg)
+    assert wet.a_lat_max < cfg.a_lat_max and wet.a_total_max < cfg.a_total_max
+    rows, h = sine_row(cfg)
+    kap, v = rows[3], rows[4]
+    b0 = retime_at(rows, h, False, 0, 0.0, wet).node_b[0, 0]
+    r = retime_at(rows, h, False, 0, b0, wet)
+    K = N_ROW - 1
+    w = r.node_v[0, :K + 1]
+    assert r.end_node[0] == K and r.feasible[0] == 1 and r.overspeed[0] == 0
+    assert r.bind_node[0] >= 0 and r.node_b[0, r.bind_node[0]] < v[r.bind_node[0]]
+    assert np.all(r.node_b[0, :r.bind_node[0]] >= v[:r.bind_node[0]])
+    assert np.all(w * w * np.abs(kap) <= wet.a_lat_max * (1.0 + 4e-16))      # (the root and its square: two roundings)
+    assert np.all(w <= v) and np.count_nonzero(w < v) >= 100
+    assert r.t_loss[0] > 0.0
+    dry = retime_at(rows, h, False, 0, v[0], cfg)
+    assert dry.bind_node[0] == -1 and r.t_loss[0] > dry.t_loss[0] and r.t_end[0] > dry.t_end[0]
+
+
+def test_a_car_outside_the_envelope_brakes_as_hard_as_the_cfg_allows():
+    cfg = abi.default_cfg()
+    wet = wet_cfg(cfg)
+    rows, h = sine_row(cfg)
+    b = retime_at(rows, h, False, 0, 0.0, wet).node_b[0]
+    r = retime_at(rows, h, False, 0, 1.5 * b[0], wet)
+    assert r.feasible[0] == 0 and r.overspeed[0] > 0 and r.v_excess[0] >= 0.5 * b[0]
+    np.testing.assert_array_equal(bits(r.node_b[0]), bits(b))               # the envelope does not depend on v0
+    up, dn = raceline._march_step(raceline._rjn_consts(wet), 1.5 * b[0], rows[3][0], h)
+    assert dn > b[1] and r.node_v[0, 1] == dn                               # the branch smax(dn, b_1), on dn
+    k = int(r.overspeed[0])
+    assert np.all(r.node_v[0, :k] > b[:k]) and np.all(r.node_v[0, k:N_ROW] <= b[k:N_ROW])   # back inside, and it stays there
+
+
+# ------------------------------------------------------------------ edges
+def test_k_cap_1():
+    rows, h = ring()
+    r = retime_at(rows, h, True, 7, 5.0, abi.default_cfg(), k_cap=1)
+    assert r.end_node[0] == 1 and r.node_v.shape == (1, 2) and r.node_b[0, 1] == r.node_c[0, 1]
+    assert r.count[0] == int(np.count_nonzero(np.arange(512) * 0.05 < r.t_end[0])) and r.count[0] >= 1
+
+
+def test_a_march_across_sample_0_on_a_closed_row():
+    rows, h = ring()
+    N = 240
+    cfg = abi.default_cfg()
+    r = retime_at(rows, h, True, N - 5, 12.0, cfg, k_cap=20)
+    assert r.end_node[0] == 20 and r.seg[0] == N - 5
+    m = int(r.count[0])
+    assert m >= 10 and np.all(np.diff(r.s[0, :m]) > 0.0) and r.s[0, m - 1] > N * h      # s runs on across the start line
+    # t_loss against the plan's schedule across the line: the row's own speed is feasible, so the
+    # loss is the trapezoid's difference to the stamps alone
+    assert abs(r.t_loss[0]) < 1e-9 and r.bind_node[0] == -1
+    whole = retime_at(rows, h, True, 3, 12.0, cfg)                 # K_cap 1024 > N: one lap, node K is sample 3 again
+    assert whole.end_node[0] == N and abs(whole.t_loss[0]) < 1e-9
+
+
+def test_an_open_row_that_ends_first():
+    cfg = abi.default_cfg()
+    rows, h = sine_row(cfg)
+    r = retime_at(rows, h, False, N_ROW - 4, rows[4][N_ROW - 4], cfg, k_cap=50)
+    assert r.end_node[0] == 3 and r.node_v.shape == (1, 51)
+    last = retime_at(rows, h, False, N_ROW - 2, 1.0, cfg)          # the last segment: one node ahead
+    assert last.end_node[0] == 1
+    beyond = raceline.retime_host(*rows, h, False, [[rows[0][-1] + 5.0, rows[1][-1]]], 1.0, cfg)   # past the end: u = 1
+    assert beyond.seg[0] == N_ROW - 2 and beyond.u[0] == 1.0 and beyond.end_node[0] == 1 and beyond.node_t[0, 1] == 0.0
+
+
+def test_nan_in_v_and_kappa():
+    cfg = abi.default_cfg()
+    rows, h = ring()
+    rows = [np.array(a) for a in rows]
+    rows[4][10:14] = np.nan                                         # a NaN r does not cap
+    r = retime_at(rows, h, True, 7, 5.0, cfg, k_cap=20)
+    assert r.end_node[0] == 20 and np.isfinite(r.node_v[0, :21]).all() and np.isfinite(r.node_b[0, :21]).all()
+    vk = math.sqrt(cfg.a_lat_max / (1.0 / 30.0))
+    assert np.all(r.node_c[0, 3:7] == min(cfg.v_cap_mps, vk)) and r.node_c[0, 2] == 12.0
+    rows[3][12] = np.nan                                            # a NaN kappa: v_kappa is NaN and does not cap either
+    r = retime_at(rows, h, True, 7, 5.0, cfg, k_cap=20)
+    assert r.end_node[0] == 20 and r.node_c[0, 5] == cfg.v_cap_mps
+
+
+def test_a_car_at_rest():
+    rows, h = ring()
+    r = retime_at(rows, h, True, 7, 1e-9, abi.default_cfg(), k_cap=30)
+    assert r.end_node[0] == 30 and r.feasible[0] == 1 and np.isfinite(r.node_t[0, :31]).all()
+    assert np.all(np.diff(r.node_v[0, :31]) >= 0.0) and r.node_v[0, 30] <= 12.0
+    m = int(r.count[0])
+    assert m >= 2 and np.isfinite(r.ax[0, :m]).all() and r.v[0, 0] == 1e-9
+
+
+# ------------------------------------------------------------------ the argument checks
+def test_argument_checks():
+    rows, h = ring()
+    P = at(rows, 7)
+    cfg = abi.default_cfg()
+    for fn in (raceline.retime_host, raceline.retime):  # the GPU entry point checks before it touches the library
+        for bad in (-1.0, float("nan"), float("inf"), [1.0, 2.0]):
+            with pytest.raises(ValueError):
+                fn(*rows, h, True, P, bad, cfg)
+        with pytest.raises(ValueError):
+            fn(*rows, h, True, P, 1.0, None)
+        with pytest.raises(ValueError):
+            fn(*rows, h, True, P, 1.0, cfg, dt=0.0)
+        with pytest.raises(ValueError):
+            fn(*rows, h, True, P, 1.0, cfg, window=-1)
+        for bad in (0, abi.RL_RJN_MAX_NODES + 1, 1.5):
+            with pytest.raises(ValueError):
+                fn(*rows, h, True, P, 1.0, cfg, k_cap=bad)
+    with pytest.raises(ValueError):
+        raceline.retime_host(*rows, h, True, P, 1.0, cfg, seg_hint=[240])
+    with pytest.raises(ValueError):
+        raceline.retime_host(*rows, h, True, P, 1.0, cfg, row=[1])
+    r = raceline.retime_host(*rows, h, True, [[float("nan"), 0.0]], 1.0, cfg)
+    assert r.seg[0] == -1 and r.count[0] == 0 and r.end_node[0] == -1
+
+
+# ------------------------------------------------------------------ the packed blocks
+def test_retime_layout(tmp_path):
+    """tests/retime_layout_check.cpp, a stand-alone program (its own main, host code only), built as
+    test_stop_layout_cpu.py builds its program: with AddressSanitizer and UBSan on the host side
+    where that links, without them otherwise, and the test says which."""
+    if not os.path.exists(HIPCC):
+        pytest.fail(f"{HIPCC} is missing: the layout check cannot be built (the library's build needs it too)")
+    src = os.path.join(O.REPO, "tests", "retime_layout_check.cpp")
+    flags = ["-O1", "-g", "-std=c++17", "--cuda-host-only", "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Werror",
+             "-I" + CSRC, "-I" + os.path.join(O.REPO, "include")]
+    sanitize = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all"]
+    exe = str(tmp_path / "retime_layout_check")
+    r = subprocess.run([HIPCC, *flags, *sanitize, src, "-o", exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    sanitized = r.returncode == 0
+    if not sanitized:
+        print("the sanitizer build failed, building without:\n" + r.stdout[-2000:])
+        subprocess.run([HIPCC, *flags, src, "-o", exe], check=True)
+    run = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    print(("with" if sanitized else "WITHOUT") + " -fsanitize=address,undefined:\n" + run.stdout)
+    assert run.returncode == 0, run.stdout
+    assert "retime layout ok" in run.stdout
+
+
+# ------------------------------------------------------------------ the ABI
+def test_header_library_and_bindings_announce_the_stage():
+    lib = abi.load_library()
+    assert abi.RL_FEATURE_RETIME == 32 and lib.rl_abi_features() & abi.RL_FEATURE_RETIME == 32
+    assert lib.rl_abi_version() == 6 and lib.rl_abi_minor() == 1
+    src = open(HEADER).read()
+    assert "#define RL_FEATURE_RETIME 32" in src
+    for name, _, argtypes in abi.DECLS_RTM:
+        assert name + "(" in src and getattr(lib, name).argtypes == argtypes
+    assert [d[0] for d in abi.DECLS_RTM] == ["rl_plan_retime", "rl_plan_fetch_retime", "rl_retime"]
+    earlier = abi.DECLS + abi.DECLS_EXT + abi.DECLS_HZN + abi.DECLS_RJN + abi.DECLS_STP + abi.DECLS_BND
+    assert not {d[0] for d in abi.DECLS_RTM} & {d[0] for d in earlier}
+
+
+def test_struct_layouts_match_c():
+    of = [n for n, _ in abi.RlRtm._fields_]
+    probe = ('#include <stdio.h>\n#include <stddef.h>\n#include "rl_abi.h"\nint main(void){\n'
+             '  printf("%zu %zu %zu\\n", sizeof(rl_rtm_query), sizeof(rl_rtm), offsetof(rl_rtm_query, rj));\n' +
+             "".join(f'  printf("%zu\\n", offsetof(rl_rtm, {n}));\n' for n in of) + "  return 0;\n}\n")
+    with tempfile.TemporaryDirectory() as d:
+        src = os.path.join(d, "p.c")
+        open(src, "w").write(probe)
+        exe = os.path.join(d, "p")
+        subprocess.run(["gcc", "-I", os.path.dirname(HEADER), src, "-o", exe], check=True)
+        vals = [int(x) for x in subprocess.run([exe], capture_output=True, text=True).stdout.split()]
+    assert vals[:3] == [C.sizeof(abi.RlRtmQuery), C.sizeof(abi.RlRtm), 0]
+    assert C.sizeof(abi.RlRtmQuery) == C.sizeof(abi.RlRjnQuery)
+    assert vals[3:] == [getattr(abi.RlRtm, n).offset for n in of]
+    # rl_rtm begins as rl_rjn does: the rejoin stage's fields' offsets, with the retime stage's names for two
+    rename = {"merge_node": "end_node", "t_merge": "t_end"}
+    for n, _ in abi.RlRjn._fields_:
+        assert getattr(abi.RlRtm, rename.get(n, n)).offset == getattr(abi.RlRjn, n).offset
+    assert set(of) == set(COLS + LOC + abi.RTM_SCAL + abi.RTM_INTS + abi.RTM_NODES)
