@@ -248,7 +248,7 @@ int rl_plan_bind_device_outputs(rl_plan* plan, int32_t which, const rl_out* dev_
  * rl_plan_horizon, 9 = the rejoin stage of the last rl_plan_rejoin, 10 = the stop stage of the
  * last rl_plan_stop, 11 = the bounds stage of the last rl_plan_bounds, 12 = the bounds at the
  * horizon stage's ticks of the last rl_plan_horizon_bounds, 13 = the retime stage of the last
- * rl_plan_retime. */
+ * rl_plan_retime, 14 = the recover stage of the last rl_plan_recover. */
 int rl_plan_kernel_ms(rl_plan* plan, int32_t idx, float* ms);
 /* The batch size the plan's kernel shape is chosen for (rl_kernel_shape's B); 0 = the plan's
  * own B (the default).  Shapes differ in the tree order of the J / decrease / lap sums, so
@@ -795,6 +795,106 @@ int rl_plan_fetch_horizon_bounds(rl_plan* plan, rl_hzn_bnd* out);
 int rl_bounds(const rl_problem* prob, const double* x, const double* y, int32_t B, double veh_width,
               double margin, int32_t device, rl_bnd* out);
 
+/* ------------------------------------------------- recover stage: a path from the car's offset back to the raceline
+ * Every stage above serves ticks whose x, y lie on the row: a car that is off the line by e gets
+ * ticks that start e to its side.  This stage serves the path back: a lateral offset profile from
+ * the car's e (and heading error) to zero over a merge length, kept inside the free width of the
+ * last bounds stage, the geometry of that offset path, the retime stage's speed pass on that
+ * geometry, and the ticks along it.  In fp64 without contraction; smax, smin, the row,
+ * ax_max_at, the march's step and time are the rejoin stage's:
+ *   locate, nodes   the rejoin stage's: seg = i, u, e, dist2, t0, s0; kappa_k, r_k, d_k,
+ *           n_k = i + k for k = 0..K, K = K_lim = min(K_cap, closed ? N : N-1-i), K_cap in
+ *           1..RL_RCV_MAX_NODES.  A NaN winner, S = 0 or K < 1: seg as located or -1,
+ *           end_node = -1, count = 0, nothing else is specified.  The stage reads the last
+ *           bounds stage's lo, hi, nx, ny of the query's row (below: at row index n_k mod N);
+ *           j = (i+1) mod N.
+ *   slope   dir_xy [Q][2] (optional): the car's direction of travel (hx, hy), finite, any length.
+ *           With (dx, dy) the located segment's direction P_j - P_i:
+ *           den = dx*hx + dy*hy, num = dx*hy - dy*hx,
+ *           g0 = den > 0 ? smin(1.0, smax(-1.0, num/den)) : (num < 0 ? -1.0 : (num > 0 ? 1.0 : 0.0)):
+ *           de/ds, capped at 45 degrees, without trigonometry.  dir_xy == NULL: g0 = 0.0.
+ *   offsets   D = merge_len[q], finite and > 0.  a_0 = 0.0, a_k = d_0 + (double)(k-1)*h,
+ *           z_k = smin(1.0, a_k / D), z3 = (z*z)*z,
+ *           qz = 1.0 + z3*(-10.0 + z*(15.0 - 6.0*z)), pz = z + z3*(-6.0 + z*(8.0 - 3.0*z)).
+ *           o_0 = e; for k >= 1: o_k = smin(hi_{n_k}, smax(lo_{n_k}, e*qz + (g0*D)*pz)): the
+ *           quintic with value e, slope g0 and no second derivative at the car and value, slope
+ *           and second derivative zero at D, clamped to the free width.  At z = 1 both
+ *           polynomials are exactly 0.  clamped = #{k in [1, K] : the clamp changed the value};
+ *           offtrack = !(lo0 <= e && e <= hi0) with lo0 = smax(lo_i, lo_j), hi0 = smin(hi_i, hi_j);
+ *           merge_node = the first k with z_k >= 1.0 (none in [0, K]: -1).
+ *   points   P_0 = (X0 + rx, Y0 + ry): (X0, Y0) the rejoin stage's node 0, (rx, ry) the locate's
+ *           residual (wx - u*dx, wy - u*dy).  P_k = (x_{n_k} + o_k*nx_{n_k}, y_{n_k} + o_k*ny_{n_k})
+ *           for k >= 1.
+ *   geometry   Segment k is on the line if o_k == 0.0 && o_{k+1} == 0.0: d'_k = d_k.  Otherwise
+ *           d'_k = sqrt(qx*qx + qy*qy), q = P_{k+1} - P_k.  Node k is on the line if o_m == 0.0
+ *           for every m of {k-1, k, k+1} within [0, K]: kappa'_k = kappa_k and psi_k is the rejoin
+ *           stage's node heading.  Otherwise, for 1 <= k <= K-1 with a = P_k - P_{k-1},
+ *           b = P_{k+1} - P_k, c = P_{k+1} - P_{k-1}: den = (d'_{k-1}*d'_k)*sqrt(cx*cx + cy*cy),
+ *           kappa'_k = den > 0 ? (2.0*(ax*by - ay*bx))/den : 0.0 (Menger), psi_k = atan2_cr(cy, cx).
+ *           End nodes off the line: kappa'_0 = kappa'_1 and kappa'_K = kappa'_{K-1} when K >= 2,
+ *           otherwise the row's; psi_0 = atan2_cr of P_1 - P_0, psi_K = atan2_cr of P_K - P_{K-1}.
+ *   ceiling, envelope, march, per query   the retime stage's, word for word, with kappa'_k for
+ *           kappa_k and d'_k for d_k: c_k, b_k, feasible, w_k, tt_k, overspeed, v_excess,
+ *           bind_node, end_node = K, t_end, t_loss.
+ *   ticks   tau_m = (double)m*dt.  count = #{m < M_cap : tau_m < tt_K}.  The rejoin stage's node
+ *           bisection over tt[0..K] gives k and u_m; x, y between P_k and P_{k+1}; heading along
+ *           the shorter arc between psi_k and psi_{k+1}; kappa between kappa'_k and kappa'_{k+1};
+ *           v and ax the march-tick expressions with d'_k; s = s_k + u_m*(s_{k+1} - s_k), the
+ *           station along the raceline as in the rejoin stage; offset = o_k + u_m*(o_{k+1} - o_k).
+ *           The stage never hands over to the row's own ticks.
+ * Anchor: a pose with e == 0.0 and g0 == 0.0 has every o_k == 0.0, every node and segment is on
+ * the line, and the stage is the retime stage bit for bit with offset all zeros.
+ * Known limits: the window ends at node K like the retime stage's, so a corner or the rest of the
+ * merge beyond node K is not foreseen.  A car far off the line with u near 1 gets a short, sharp
+ * first segment and is reported feasible = 0; it is not rescued.
+ * raceline.recover_host states the same in NumPy; the kernel equals it bit for bit except in
+ * heading where a node is off the line (atan2_cr is correctly rounded).  These are additions to
+ * ABI 6.1 that leave RL_ABI_MINOR as it is: RL_FEATURE_RECOVER announces them. */
+#define RL_RCV_MAX_NODES 512
+typedef struct rl_rcv_query {
+    rl_rjn_query   rj;           /* the rejoin stage's query; K_cap in 1..RL_RCV_MAX_NODES */
+    const double*  merge_len;    /* [Q] D, finite and > 0 */
+    const double*  dir_xy;       /* [Q][2] the car's direction of travel, finite; NULL: g0 = 0.0 */
+} rl_rcv_query;
+
+typedef struct rl_rcv {          /* caller-allocated; NULL fields skipped; it begins as rl_rtm does */
+    double *s, *x, *y, *heading, *kappa, *v, *ax;   /* [Q][M_cap]; ticks m >= count[q] are unspecified */
+    double *u, *t0, *s0, *e, *dist2;                /* [Q] */
+    int32_t *seg, *count;                           /* [Q] */
+    int32_t *end_node, *overspeed;                  /* [Q] */
+    double *t_end, *t_loss;                         /* [Q] */
+    double *node_v, *node_t;                        /* [Q][K_cap+1] w_k, tt_k; entries past K are unspecified;
+                                                       downloaded only when asked for */
+    int32_t *feasible, *bind_node;                  /* [Q] */
+    double *v_excess;                               /* [Q] */
+    double *node_b, *node_c;                        /* [Q][K_cap+1] b_k, c_k, as node_v */
+    double *offset;                                 /* [Q][M_cap] as the columns */
+    int32_t *clamped, *offtrack;                    /* [Q] */
+    int32_t *merge_node;                            /* [Q] */
+    double *lo0, *hi0;                              /* [Q] */
+    double *node_o, *node_k;                        /* [Q][K_cap+1] o_k, kappa'_k, as node_v */
+} rl_rcv;
+
+/* Enqueue the stage after the plan's last trajectory and bounds stages: rl_plan_retime's stream,
+ * validity and invalidation rules, and a later bounds stage invalidates it as well.  It leaves
+ * the results, the trajectory stage and the last horizon, rejoin, stop, retime and bounds stages
+ * untouched; its buffers are plan-owned (they count toward the plan cache's budget) and grow with
+ * Q, M_cap and K_cap.  The query's arrays and cfg are read before the call returns.
+ * rl_plan_kernel_ms index 14 is the stage.  RL_EINVAL before any device work for: every error of
+ * rl_plan_retime, K_cap > RL_RCV_MAX_NODES, a NULL merge_len, a merge_len[q] that is not finite
+ * or is <= 0, a dir_xy that is not finite, no valid bounds stage after the trajectory stage. */
+int rl_plan_recover(rl_plan* plan, const rl_rcv_query* query, void* hip_stream);
+/* Download the last recover stage (synchronises its stream) into the non-NULL fields of out.
+ * RL_EINVAL before a stage, or after a run, a trajectory or a bounds stage that followed it. */
+int rl_plan_fetch_recover(rl_plan* plan, rl_rcv* out);
+/* The same on B given rows [B][N] with steps h [B] and their bounds lo, hi, nx, ny [B][N] (host
+ * in, host out): the trajectory kernel for the stamps, then the recover kernel.  Errors as
+ * rl_retime's and rl_plan_recover's, and a NULL lo, hi, nx or ny. */
+int rl_recover(const double* x, const double* y, const double* heading, const double* kappa,
+               const double* v, const double* ax, const double* h, const double* lo, const double* hi,
+               const double* nx, const double* ny, int32_t N, int32_t B, int32_t closed,
+               const rl_rcv_query* query, int32_t device, rl_rcv* out);
+
 /* B lap evaluations of given paths: heading/curvature
  * (heading_curv_from_points_generic, ref:595-620) and velocity_profile_forward_backward
  * (ref:782-862) with h = L[b]/N on path b — the min-time driver's final step
@@ -876,6 +976,7 @@ int         rl_abi_minor(void);
 #define RL_FEATURE_STOP 8         /* bit 3: the stop stage */
 #define RL_FEATURE_BOUNDS 16      /* bit 4: the bounds stage */
 #define RL_FEATURE_RETIME 32      /* bit 5: the retime stage */
+#define RL_FEATURE_RECOVER 64     /* bit 6: the recover stage */
 int         rl_abi_features(void);
 /* samples per lane of the THROUGHPUT shape for N (4: N <= 256, 5: N <= 320, 8: N <= 4096;
  * 1 = the streaming kernel), or RL_ETOOBIG.  Batches small enough for a latency shape launch fewer samples per lane:

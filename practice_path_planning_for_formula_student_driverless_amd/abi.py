@@ -225,6 +225,29 @@ class RlRtm(C.Structure):
                 [(n, C.POINTER(C.c_double)) for n in RTM_SCAL[2:] + RTM_NODES[2:]])
 
 
+RL_FEATURE_RECOVER = 64    # rl_abi_features() bit 6: the recover stage
+RL_RCV_MAX_NODES = 512
+RCV_COLS = ("offset",)
+RCV_SCAL = RTM_SCAL + ("lo0", "hi0")
+RCV_INTS = RTM_INTS + ("clamped", "offtrack", "merge_node")
+RCV_NODES = RTM_NODES + ("node_o", "node_k")
+
+
+class RlRcvQuery(C.Structure):
+    """``rl_rcv_query`` — the ``rl_rjn_query``, then merge_len [Q] and the optional dir_xy [Q][2]."""
+
+    _fields_ = [("rj", RlRjnQuery), ("merge_len", C.POINTER(C.c_double)), ("dir_xy", C.POINTER(C.c_double))]
+
+
+class RlRcv(C.Structure):
+    """``rl_rcv`` — ``rl_rtm``'s layout, then offset [Q][M_cap], clamped, offtrack, merge_node, lo0,
+    hi0 [Q] and the optional node_o, node_k [Q][K_cap + 1]; NULL fields are skipped."""
+
+    _fields_ = (RlRtm._fields_ + [("offset", C.POINTER(C.c_double))] +
+                [(n, C.POINTER(C.c_int32)) for n in RCV_INTS[len(RTM_INTS):]] +
+                [(n, C.POINTER(C.c_double)) for n in RCV_SCAL[len(RTM_SCAL):] + RCV_NODES[len(RTM_NODES):]])
+
+
 RL_FEATURE_BOUNDS = 16     # rl_abi_features() bit 4: the bounds stage
 BND_ROWS = ("lo", "hi", "nx", "ny")
 HZN_BND = ("lo", "hi", "lo0", "hi0")
@@ -640,6 +663,14 @@ DECLS_RTM = [
     ("rl_retime", C.c_int, [_F64] * 7 + [C.c_int32, C.c_int32, C.c_int32, _RTMQ, C.c_int32, _RTM]),
 ]
 
+# the recover stage: bound only in a library whose rl_abi_features() has RL_FEATURE_RECOVER
+_RCV, _RCVQ = _P(RlRcv), _P(RlRcvQuery)
+DECLS_RCV = [
+    ("rl_plan_recover", C.c_int, [C.c_void_p, _RCVQ, C.c_void_p]),
+    ("rl_plan_fetch_recover", C.c_int, [C.c_void_p, _RCV]),
+    ("rl_recover", C.c_int, [_F64] * 11 + [C.c_int32, C.c_int32, C.c_int32, _RCVQ, C.c_int32, _RCV]),
+]
+
 
 def declare_optimize(fn) -> None:
     """rl_optimize's signature (the oracle's oracle_optimize shares it)."""
@@ -653,8 +684,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     """Load librl.so (the HIP path).  Raises if it is missing: there is no fallback; a library
     that lacks a function of DECLS or DECLS_EXT raises AttributeError naming it, and so does
     one that announces RL_FEATURE_HORIZON / RL_FEATURE_REJOIN / RL_FEATURE_STOP /
-    RL_FEATURE_BOUNDS / RL_FEATURE_RETIME and lacks a function of DECLS_HZN / DECLS_RJN / DECLS_STP /
-    DECLS_BND / DECLS_RTM."""
+    RL_FEATURE_BOUNDS / RL_FEATURE_RETIME / RL_FEATURE_RECOVER and lacks a function of DECLS_HZN /
+    DECLS_RJN / DECLS_STP / DECLS_BND / DECLS_RTM / DECLS_RCV."""
     global _LIB
     if _LIB is not None and path == LIB_PATH:
         return _LIB
@@ -682,6 +713,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         bind(DECLS_BND)
     if ext and lib.rl_abi_features() & RL_FEATURE_RETIME:
         bind(DECLS_RTM)
+    if ext and lib.rl_abi_features() & RL_FEATURE_RECOVER:
+        bind(DECLS_RCV)
     if path == LIB_PATH:
         _LIB = lib
     return lib

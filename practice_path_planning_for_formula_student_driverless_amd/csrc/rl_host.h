@@ -377,18 +377,18 @@ inline int queue_downloads(const std::vector<CopyJob>& jobs, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------ pose-query stages
-// The plan's side of one pose-query stage (horizon, rejoin, stop, retime).  The queries go up and the results
+// The plan's side of one pose-query stage (horizon, rejoin, stop, retime, recover).  The queries go up and the results
 // come down as one packed block each (in, out; rl_query.h has their layout), through one pinned
 // host block (pin) of the larger capacity; all three grow with Q, M_cap and K_cap.  ev[0] is
 // recorded after the upload, which reads pin, ev[1] after the kernel.  Q = 0: no stage since
 // the last run or trajectory stage; M, K (0 for the horizon) are that stage's M_cap and K_cap,
-// stop / retime whether its blocks have the stop / retime stage's arrays.
+// stop / retime / recover whether its blocks have the stop / retime / recover stage's arrays.
 struct QueryStage {
     char *in = nullptr, *out = nullptr, *pin = nullptr;
     size_t in_cap = 0, out_cap = 0;
     DevArena mem;                     // in, out: they count toward the plan's dev_bytes()
     int Q = 0, M = 0, K = 0;
-    bool stop = false, retime = false;
+    bool stop = false, retime = false, recover = false;
     double dt = 0;                    // that stage's tick step (the bounds stage's tick kernel reads it)
     hipEvent_t ev[2] = {nullptr, nullptr};
 
@@ -502,7 +502,7 @@ struct rl_plan {
     rl::DevArena traj_mem;
     int traj_cap_R = 0, traj_cap_M = 0, traj_R = 0, traj_M = 0;
     hipEvent_t ev_traj[2] = {nullptr, nullptr};
-    // pose-query stages (rl_plan_horizon, rl_plan_rejoin, rl_plan_stop, rl_plan_retime; rl::QueryStage): they read the last
+    // pose-query stages (rl_plan_horizon, rl_plan_rejoin, rl_plan_stop, rl_plan_retime, rl_plan_recover; rl::QueryStage): they read the last
     // trajectory stage through traj_q, that stage's launch parameters, which stay valid while
     // traj_R != 0 and the rows they point at are those the stamps were made from:
     // traj_sel_epoch / traj_lap_epoch are sel_epoch / lap_epoch (counted up by every selection /
@@ -511,7 +511,7 @@ struct rl_plan {
     rl::TrajParams traj_q{};
     int traj_mode = 0;
     uint32_t sel_epoch = 0, lap_epoch = 0, traj_sel_epoch = 0, traj_lap_epoch = 0;
-    rl::QueryStage hzn, rjn, stp, rtm;
+    rl::QueryStage hzn, rjn, stp, rtm, rcv;     // (rcv reads the bounds stage as well: drop_bounds_readers)
     // bounds stage (rl_plan_bounds, rl::BndParams): lo, hi, nx, ny [bnd_R][N] of the last
     // trajectory stage's rows, row for row, in buffers sized for bnd_cap_R rows; bnd_R = 0: no
     // stage since the last run or trajectory stage.  Its tick kernel (rl_plan_horizon_bounds)
@@ -529,7 +529,9 @@ struct rl_plan {
     hipEvent_t ev_hb[2] = {nullptr, nullptr};
     // a run or a trajectory stage invalidates the pose-query stages that read the one before,
     // and the bounds of its rows
-    void drop_queries() { hzn.Q = rjn.Q = stp.Q = rtm.Q = bnd_R = hb_Q = 0; }
+    void drop_queries() { hzn.Q = rjn.Q = stp.Q = rtm.Q = rcv.Q = bnd_R = hb_Q = 0; }
+    // a bounds stage invalidates what read the one before: the tick bounds and the recover stage
+    void drop_bounds_readers() { bnd_R = hb_Q = rcv.Q = 0; }
 
     template <class T>
     int alloc(T** p, size_t n) {
@@ -540,7 +542,7 @@ struct rl_plan {
     // device memory held (plan cache budget)
     size_t dev_bytes() const {
         return mem.bytes + sel_mem.bytes + lap_mem.bytes + traj_mem.bytes + hzn.mem.bytes + rjn.mem.bytes + stp.mem.bytes +
-               rtm.mem.bytes + bnd_mem.bytes + hb_mem.bytes;
+               rtm.mem.bytes + rcv.mem.bytes + bnd_mem.bytes + hb_mem.bytes;
     }
     // the stream of the last run or stage
     hipStream_t run_stream() const { return last_stream ? last_stream : own_stream; }
@@ -594,5 +596,12 @@ hipError_t query_launch(const StpParams& s, hipStream_t st);
 // the retime stage's kernel on a rejoin query's parameters s (query_params'), its cfg, and the
 // results' block `out` (device) laid out as L (L.retime set)
 hipError_t retime_launch(const StpParams& s, const rl_cfg& cfg, const QueryLayout& L, char* out, hipStream_t st);
+// argument checks of the recover entry points (no device call): check_rjn's with
+// K_cap <= RL_RCV_MAX_NODES, then merge_len and dir_xy
+int check_rcv(const rl_rcv_query* q, int32_t R, int32_t N, int32_t closed);
+// the recover stage's kernel on its query's rejoin parameters s (query_params'), the blocks in
+// and out (device) laid out as L (recover_layout's) and the bounds rows bnd (lo, hi, nx, ny, device)
+hipError_t recover_launch(const StpParams& s, const rl_rcv_query& q, const QueryLayout& L, const char* in, char* out,
+                          const double* const (&bnd)[4], hipStream_t st);
 
 }  // namespace rl

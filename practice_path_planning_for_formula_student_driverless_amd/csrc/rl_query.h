@@ -9,7 +9,9 @@
 // a layout with `retime` set has its extra arrays in the same places; without it no offset or
 // byte count moves.  No HIP call: a host compiler builds it without a device
 // (tests/test_query_layout_cpu.py, tests/test_stop_layout_cpu.py, tests/test_retime_cpu.py).
-// Not part of the public ABI.
+// The recover stage (§3q) is the retime stage with a merge length and a direction per query and
+// more results: recover_layout is the retime layout with its extra arrays, again each kind behind
+// the others of that kind (tests/test_recover_cpu.py).  Not part of the public ABI.
 #pragma once
 #include <cstddef>
 #include <cstring>
@@ -18,6 +20,7 @@
 #include "rl_rejoin.h"
 #include "rl_stop.h"
 #include "rl_retime.h"
+#include "rl_recover.h"
 
 namespace rl {
 
@@ -35,7 +38,11 @@ constexpr int QRY_NODES = 2;                  // node_v, node_t
 // t_merge and t_loss do.  A retime stage's results' block has as well: v_excess [Q] behind the
 // n_per doubles, feasible and bind_node [Q] behind the n_ints ints (all three in the head),
 // node_b and node_c [Q][K + 1] behind the node arrays.  Its end_node and t_end lie where the
-// rejoin stage's merge_node and t_merge do.
+// rejoin stage's merge_node and t_merge do.  A recover stage's blocks (recover_layout; `retime`
+// set as well) have as well: merge_len [Q] and dir [Q][2] behind hint; the column offset [Q][M]
+// behind the seven; lo0, hi0 [Q] behind the doubles and clamped, offtrack, merge_node [Q] and one
+// pad word per query (the node arrays stay 8-byte aligned) behind the ints (all in the head);
+// node_o, node_k [Q][K + 1] behind the node arrays.
 struct QueryLayout {
     size_t Q, M, K;
     size_t pose, v0, row, hint, in_bytes;
@@ -45,14 +52,18 @@ struct QueryLayout {
     size_t v_target, stop_sample, sper[STP_SCAL], sints[STP_INTS], node_b;
     bool retime;
     size_t rper[RTM_SCAL], rints[RTM_INTS], rnodes[RTM_NODES];
+    bool recover;
+    size_t merge_len, dir, offset, cper[RCV_SCAL], cints[RCV_INTS], cnodes[RCV_NODES];
 };
 
-inline QueryLayout query_layout(size_t Q, size_t M, size_t K, bool stop = false, bool retime = false) {
+// every stage's layout; `recover` adds the recover stage's arrays to a retime layout
+inline QueryLayout query_layout_of(size_t Q, size_t M, size_t K, bool stop, bool retime, bool recover) {
     QueryLayout L{};
     const bool rjn = K > 0;
     L.Q = Q; L.M = M; L.K = K;
     L.stop = stop;
     L.retime = retime;
+    L.recover = recover;
     L.n_per = HZN_LOC + (rjn ? RJN_SCAL : 0);
     L.n_ints = rjn ? QRY_INTS : 2;
     L.n_nodes = rjn ? QRY_NODES : 0;
@@ -64,22 +75,35 @@ inline QueryLayout query_layout(size_t Q, size_t M, size_t K, bool stop = false,
     L.hint = take(Q * 4);
     L.v_target = take(stop ? Q * 8 : 0);
     L.stop_sample = take(stop ? Q * 4 : 0);
+    L.merge_len = take(recover ? Q * 8 : 0);
+    L.dir = take(recover ? Q * 16 : 0);
     L.in_bytes = at;
     at = 0;
     for (auto& o : L.col) o = take(Q * M * 8);
+    L.offset = take(recover ? Q * M * 8 : 0);
     for (int c = 0; c < L.n_per; ++c) L.per[c] = take(Q * 8);
     for (auto& o : L.sper) o = take(stop ? Q * 8 : 0);
     for (auto& o : L.rper) o = take(retime ? Q * 8 : 0);
+    for (auto& o : L.cper) o = take(recover ? Q * 8 : 0);
     for (int c = 0; c < L.n_ints; ++c) L.ints[c] = take(Q * 4);
     for (auto& o : L.sints) o = take(stop ? Q * 4 : 0);
     for (auto& o : L.rints) o = take(retime ? Q * 4 : 0);
+    for (auto& o : L.cints) o = take(recover ? Q * 4 : 0);
+    static_assert(RCV_INTS % 2 == 1, "the pad below keeps the node arrays 8-byte aligned");
+    take(recover ? Q * 4 : 0);
     L.head_bytes = at;
     for (int c = 0; c < L.n_nodes; ++c) L.nodes[c] = take(Q * (K + 1) * 8);
     L.node_b = take(stop ? Q * (K + 1) * 8 : 0);
     for (auto& o : L.rnodes) o = take(retime ? Q * (K + 1) * 8 : 0);
+    for (auto& o : L.cnodes) o = take(recover ? Q * (K + 1) * 8 : 0);
     L.out_bytes = at;
     return L;
 }
+inline QueryLayout query_layout(size_t Q, size_t M, size_t K, bool stop = false, bool retime = false) {
+    return query_layout_of(Q, M, K, stop, retime, false);
+}
+// a recover stage's: the retime layout of a rejoin query with the recover stage's arrays
+inline QueryLayout recover_layout(size_t Q, size_t M, size_t K) { return query_layout_of(Q, M, K, false, true, true); }
 
 // a horizon query and its results in the rejoin forms: no v0, no cfg, K_cap = 0, the extra
 // fields NULL
@@ -233,5 +257,52 @@ inline void query_unpack(const char* block, const QueryLayout& L, const rl_rtm& 
         if (rnodes[c]) std::memcpy(rnodes[c], block + L.rnodes[c], L.Q * (L.K + 1) * 8);
 }
 inline bool query_wants_nodes(const rl_rtm& o) { return o.node_v || o.node_t || o.node_b || o.node_c; }
+
+// the recover stage: its query's rejoin part in the stop forms, its layout, the rest of its
+// queries' block (a NULL dir_xy leaves that part unread), its launch on the retime pointers t of
+// its query and the bounds rows bnd (lo, hi, nx, ny on the device), and its results
+inline QueryLayout recover_layout(const rl_rcv_query& q) {
+    return recover_layout((size_t)q.rj.Q, (size_t)q.rj.M_cap, (size_t)q.rj.K_cap);
+}
+inline void recover_pack(const rl_rcv_query& q, const QueryLayout& L, char* block) {
+    std::memcpy(block + L.merge_len, q.merge_len, L.Q * 8);
+    if (q.dir_xy) std::memcpy(block + L.dir, q.dir_xy, L.Q * 16);
+}
+inline RcvParams recover_pointers(const RtmParams& t, const rl_rcv_query& q, const QueryLayout& L, const char* in, char* out,
+                                  const double* const (&bnd)[4]) {
+    RcvParams c{};
+    c.rt = t;
+    c.merge_len = (const double*)(in + L.merge_len);
+    c.dir = q.dir_xy ? (const double*)(in + L.dir) : nullptr;
+    c.lo = bnd[0]; c.hi = bnd[1]; c.nx = bnd[2]; c.ny = bnd[3];
+    c.offset = (double*)(out + L.offset);
+    for (int k = 0; k < RCV_SCAL; ++k) c.scal[k] = (double*)(out + L.cper[k]);
+    c.clamped = (int32_t*)(out + L.cints[0]);
+    c.offtrack = (int32_t*)(out + L.cints[1]);
+    c.merge_node = (int32_t*)(out + L.cints[2]);
+    c.node_o = (double*)(out + L.cnodes[0]);
+    c.node_k = (double*)(out + L.cnodes[1]);
+    return c;
+}
+// the retime part of a recover stage's results (rl_rcv begins with rl_rtm's fields)
+inline rl_rtm as_rtm(const rl_rcv& o) {
+    return {o.s, o.x, o.y, o.heading, o.kappa, o.v, o.ax, o.u, o.t0, o.s0, o.e, o.dist2, o.seg, o.count,
+            o.end_node, o.overspeed, o.t_end, o.t_loss, o.node_v, o.node_t, o.feasible, o.bind_node, o.v_excess,
+            o.node_b, o.node_c};
+}
+inline void query_unpack(const char* block, const QueryLayout& L, const rl_rcv& o) {
+    query_unpack(block, L, as_rtm(o));
+    double* const cper[RCV_SCAL] = {o.lo0, o.hi0};
+    int32_t* const cints[RCV_INTS] = {o.clamped, o.offtrack, o.merge_node};
+    double* const cnodes[RCV_NODES] = {o.node_o, o.node_k};
+    if (o.offset) std::memcpy(o.offset, block + L.offset, L.Q * L.M * 8);
+    for (int c = 0; c < RCV_SCAL; ++c)
+        if (cper[c]) std::memcpy(cper[c], block + L.cper[c], L.Q * 8);
+    for (int c = 0; c < RCV_INTS; ++c)
+        if (cints[c]) std::memcpy(cints[c], block + L.cints[c], L.Q * 4);
+    for (int c = 0; c < RCV_NODES; ++c)
+        if (cnodes[c]) std::memcpy(cnodes[c], block + L.cnodes[c], L.Q * (L.K + 1) * 8);
+}
+inline bool query_wants_nodes(const rl_rcv& o) { return query_wants_nodes(as_rtm(o)) || o.node_o || o.node_k; }
 
 }  // namespace rl

@@ -80,52 +80,23 @@ __global__ __launch_bounds__(HZN_THREADS) void rl_retime_kernel(RtmParams tp) {
     const double d0 = mr.d0;
     march_stage(mr, tid, K, s_kap, s_r);
     __syncthreads();
-    for (int kk = tid; kk <= K; kk += HZN_THREADS) {
-        const double vk = sqrt(tp.a_lat_max / smax(fabs(s_kap[kk]), tp.kappa_eps));
-        s_c[kk] = smin(smin(tp.v_cap, vk), s_r[kk]);
-    }
+    for (int kk = tid; kk <= K; kk += HZN_THREADS) s_c[kk] = retime_ceiling(tp, s_kap[kk], s_r[kk]);
     __syncthreads();
     if (tid == 0) {
         const double v0 = rp.v0[k];
-        double e = s_c[K];                         // the envelope, backward from the last node
-        s_b[K] = e;
-        for (int kk = K - 1; kk >= 0; --kk) {
-            const double d = kk == 0 ? d0 : h;
-            const AxMax a = ax_max_at(rp.cfg, e, s_kap[kk + 1]);
-            e = smin(s_c[kk], sqrt(smax(0.0, e * e + (2.0 * a.brk) * d)));
-            s_b[kk] = e;
-        }
-        double w = v0, tt = 0.0, ve = 0.0;         // the march, forward to the last node
-        int over = 0, bn = -1;
-        s_w[0] = w;
-        s_tt[0] = 0.0;
-        for (int kk = 0;; ++kk) {
-            const double bk = s_b[kk];
-            over += w > bk;
-            ve = smax(ve, w - bk);
-            if (bn < 0 && bk < s_r[kk]) bn = kk;
-            if (kk == K) break;
-            const double d = kk == 0 ? d0 : h;
-            const Reach s = march_step(rp.cfg, w, s_kap[kk], d);
-            const double bn1 = s_b[kk + 1];
-            const double wn = smin(s.up, w <= bk ? bn1 : smax(s.dn, bn1));
-            tt = march_time(tt, d, w, wn);
-            s_w[kk + 1] = wn;
-            s_tt[kk + 1] = tt;
-            w = wn;
-        }
-        const double tte = tt;
+        const RtmPass ps = retime_pass(rp.cfg, v0, K, s_kap, s_r, s_c, s_b, s_w, s_tt, [&](int kk) { return kk == 0 ? d0 : h; });
+        const double tte = ps.tt;
         const int m1 = tick_end(0, p.M_cap, [&](int m) { return (double)m * p.dt < tte; });
         const double t0 = hzn_t0([&](int i) { return tg[i]; }, i0, f.u);
         const int nk = i0 + K, c0 = nk >= N ? 1 : 0;   // nk < 2N
         hzn_store_loc(p, k, f, i0, h, t0, m1);
         rp.merge_node[k] = K;
-        rp.overspeed[k] = over;
+        rp.overspeed[k] = ps.over;
         rp.scal[0][k] = tte;
         rp.scal[1][k] = tte - (((double)c0 * q.T[r] + tg[nk - c0 * N]) - t0);
         tp.feasible[k] = v0 <= s_b[0] ? 1 : 0;
-        tp.bind_node[k] = bn;
-        tp.v_excess[k] = ve;
+        tp.bind_node[k] = ps.bn;
+        tp.v_excess[k] = ps.ve;
         s_m1 = m1;
     }
     __syncthreads();

@@ -6,8 +6,9 @@
 // ticks from there.  Rejoin stage (rl_rejoin.hip): the same from the car's speed, along a
 // reachable profile.  Stop stage (rl_stop.hip): the same under a brake envelope, up
 // to a target sample.  Retime stage (rl_retime.hip): the reference's speed pass
-// over the nodes ahead, under the car's cfg.  These four pose-query stages share one enqueue and
-// one fetch routine.
+// over the nodes ahead, under the car's cfg.  Recover stage (rl_recover.hip): a path
+// from the car's offset back to the row inside the bounds stage's free width, and that speed pass
+// on it.  These five pose-query stages share one enqueue and one fetch routine.
 // Bounds stage (rl_bounds.hip): the free track width about the trajectory stage's
 // rows, and at the horizon stage's ticks.
 #include "rl_host.h"
@@ -126,6 +127,25 @@ hipError_t rl::query_launch(const StpParams& s, hipStream_t st) {
 
 hipError_t rl::retime_launch(const StpParams& s, const rl_cfg& cfg, const QueryLayout& L, char* out, hipStream_t st) {
     return rl::launch_retime(retime_pointers(s.rj, cfg, L, out), st);
+}
+
+int rl::check_rcv(const rl_rcv_query* q, int32_t R, int32_t N, int32_t closed) {
+    if (!q) return fail(RL_EINVAL, "recover: the query is NULL");
+    if (int rc = check_rjn(&q->rj, R, N, closed)) return rc;
+    if (q->rj.K_cap > RL_RCV_MAX_NODES) return fail(RL_EINVAL, "recover: K_cap must be 1..512");
+    if (!q->merge_len) return fail(RL_EINVAL, "recover: merge_len is NULL");
+    for (int32_t k = 0; k < q->rj.Q; ++k) {
+        if (!std::isfinite(q->merge_len[k]) || !(q->merge_len[k] > 0.0))
+            return fail(RL_EINVAL, "recover: a merge_len that is not finite or is <= 0");
+        if (q->dir_xy && (!std::isfinite(q->dir_xy[2 * (size_t)k]) || !std::isfinite(q->dir_xy[2 * (size_t)k + 1])))
+            return fail(RL_EINVAL, "recover: a dir_xy that is not finite");
+    }
+    return RL_OK;
+}
+
+hipError_t rl::recover_launch(const StpParams& s, const rl_rcv_query& q, const QueryLayout& L, const char* in, char* out,
+                              const double* const (&bnd)[4], hipStream_t st) {
+    return rl::launch_recover(recover_pointers(retime_pointers(s.rj, *q.rj.cfg, L, out), q, L, in, out, bnd), st);
 }
 
 namespace {
@@ -261,13 +281,15 @@ int select_impl(rl_plan* p, const rl_select* sel, int gs, bool by_lap, void* hip
     return RL_OK;
 }
 
-// rl_plan_horizon / rl_plan_rejoin / rl_plan_stop / rl_plan_retime (arguments checked; K_cap = 0:
-// the horizon; a stop_sample: the stop stage; retime: the retime stage of a rejoin query): one
-// launch of the stage's kernel on the last trajectory stage.
+// rl_plan_horizon / rl_plan_rejoin / rl_plan_stop / rl_plan_retime / rl_plan_recover (arguments
+// checked; K_cap = 0: the horizon; a stop_sample: the stop stage; retime: the retime stage of a
+// rejoin query; rcv: the recover stage's query, q its rejoin part, after a valid bounds stage):
+// one launch of the stage's kernel on the last trajectory stage.
 // The queries go up in one block, through s's pinned block, ahead of the kernel on the same
 // stream.
-int query_enqueue(rl_plan* p, QueryStage& s, const rl_stp_query& q, void* hip_stream, bool retime = false) {
-    const char* what = retime ? "retime" : q.stop_sample ? "stop" : q.rj.K_cap > 0 ? "rejoin" : "horizon";
+int query_enqueue(rl_plan* p, QueryStage& s, const rl_stp_query& q, void* hip_stream, bool retime = false,
+                  const rl_rcv_query* rcv = nullptr) {
+    const char* what = rcv ? "recover" : retime ? "retime" : q.stop_sample ? "stop" : q.rj.K_cap > 0 ? "rejoin" : "horizon";
     const std::string fn = std::string("rl_plan_") + what;
     if (p->traj_q.index && p->traj_sel_epoch != p->sel_epoch)
         return fail(RL_EINVAL, fn + ": a selection has replaced the winners the trajectory stage read");
@@ -282,17 +304,21 @@ int query_enqueue(rl_plan* p, QueryStage& s, const rl_stp_query& q, void* hip_st
     if (s.ev[0]) HIPCHK(hipEventSynchronize(s.ev[0]));
     s.Q = 0;
     if (&s == &p->hzn) p->hb_Q = 0;                    // the tick bounds of the horizon stage before
-    const QueryLayout L = query_layout(q, retime);
+    const QueryLayout L = rcv ? recover_layout(*rcv) : query_layout(q, retime);
     if (int rc = s.reserve(p->last_stream, L.in_bytes, L.out_bytes, what)) return rc;
     for (auto& e : s.ev)
         if (!e) HIPCHK(hipEventCreate(&e));
     if (st != run_st) HIPCHK(hipStreamWaitEvent(st, p->ev_traj[1], 0));
+    if (rcv) HIPCHK(hipStreamWaitEvent(st, p->ev_bnd[1], 0));      // (the bounds stage may be on another stream)
     p->last_stream = st;
     query_pack(q, L, s.pin);
+    if (rcv) recover_pack(*rcv, L, s.pin);
     HIPCHK(hipMemcpyAsync(s.in, s.pin, L.in_bytes, hipMemcpyHostToDevice, st));
     HIPCHK(hipEventRecord(s.ev[0], st));
     const StpParams sp = query_params(p->traj_q, q, L, s.in, s.out);
-    const hipError_t e = retime ? retime_launch(sp, *q.rj.cfg, L, s.out, st) : query_launch(sp, st);
+    const hipError_t e = rcv      ? recover_launch(sp, *rcv, L, s.in, s.out, {p->bnd[0], p->bnd[1], p->bnd[2], p->bnd[3]}, st)
+                         : retime ? retime_launch(sp, *q.rj.cfg, L, s.out, st)
+                                  : query_launch(sp, st);
     if (e != hipSuccess) return fail(RL_EHIP, std::string(what) + " launch: " + hipGetErrorString(e));
     HIPCHK(hipEventRecord(s.ev[1], st));
     s.Q = q.rj.Q;
@@ -300,6 +326,7 @@ int query_enqueue(rl_plan* p, QueryStage& s, const rl_stp_query& q, void* hip_st
     s.K = q.rj.K_cap;
     s.stop = L.stop;
     s.retime = L.retime;
+    s.recover = L.recover;
     s.dt = q.rj.dt;
     return RL_OK;
 }
@@ -340,15 +367,16 @@ int horizon_bounds_alloc(rl_plan* p, size_t Q, size_t M) {
     return RL_OK;
 }
 
-// rl_plan_fetch_horizon / rl_plan_fetch_rejoin / rl_plan_fetch_stop / rl_plan_fetch_retime (a valid
-// stage in s; Out: rl_stp, or rl_rtm for the retime stage): the results' block comes down through
-// the pinned block, without the node arrays if o asks for none
+// rl_plan_fetch_horizon / rl_plan_fetch_rejoin / rl_plan_fetch_stop / rl_plan_fetch_retime /
+// rl_plan_fetch_recover (a valid stage in s; Out: rl_stp, rl_rtm for the retime stage, rl_rcv for
+// the recover stage): the results' block comes down through the pinned block, without the node
+// arrays if o asks for none
 template <class Out>
 int query_fetch(rl_plan* p, QueryStage& s, const Out& o) {
     HIPCHK(hipSetDevice(p->device));
     hipStream_t st = p->run_stream();
     HIPCHK(hipStreamWaitEvent(st, s.ev[1], 0));         // (a later stage may have moved to another stream)
-    const QueryLayout L = query_layout((size_t)s.Q, (size_t)s.M, (size_t)s.K, s.stop, s.retime);
+    const QueryLayout L = query_layout_of((size_t)s.Q, (size_t)s.M, (size_t)s.K, s.stop, s.retime, s.recover);
     HIPCHK(hipMemcpyAsync(s.pin, s.out, query_wants_nodes(o) ? L.out_bytes : L.head_bytes, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     query_unpack(s.pin, L, o);
@@ -598,6 +626,25 @@ int rl_plan_fetch_retime(rl_plan* p, rl_rtm* out) {
     return query_fetch(p, p->rtm, *out);
 }
 
+// blocks of its own: the last horizon, rejoin, stop and retime stages stay as they are; it reads
+// the bounds stage's rows where they lie
+int rl_plan_recover(rl_plan* p, const rl_rcv_query* query, void* hip_stream) {
+    if (!p) return fail(RL_EINVAL, "plan is NULL");
+    if (!query) return fail(RL_EINVAL, "recover: the query is NULL");
+    if (!p->traj_R) return fail(RL_EINVAL, "rl_plan_recover: no trajectory stage since the plan's last run");
+    if (int rc = check_rcv(query, p->traj_R, p->N, p->closed)) return rc;
+    if (!p->bnd_R) return fail(RL_EINVAL, "rl_plan_recover: no bounds stage since the plan's last trajectory stage");
+    return query_enqueue(p, p->rcv, as_stp(query->rj), hip_stream, true, query);
+}
+
+int rl_plan_fetch_recover(rl_plan* p, rl_rcv* out) {
+    if (!p) return fail(RL_EINVAL, "plan is NULL");
+    if (!out) return fail(RL_EINVAL, "rl_plan_fetch_recover: out is NULL");
+    if (!p->rcv.Q || !p->traj_R || !p->bnd_R)
+        return fail(RL_EINVAL, "rl_plan_fetch_recover: no recover stage since the plan's last run, trajectory or bounds stage");
+    return query_fetch(p, p->rcv, *out);
+}
+
 // One launch of rl_bounds_kernel over the rows the last trajectory stage read: its x, y and
 // index, the plan's resident rings.  Buffers of its own: every other stage stays as it is.
 int rl_plan_bounds(rl_plan* p, const rl_bnd_query* query, void* hip_stream) {
@@ -612,11 +659,12 @@ int rl_plan_bounds(rl_plan* p, const rl_bnd_query* query, void* hip_stream) {
         return fail(RL_EINVAL, "rl_plan_bounds: a lap stage has rewritten the rows the trajectory stage read");
     HIPCHK(hipSetDevice(p->device));
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : p->run_stream();
-    p->bnd_R = p->hb_Q = 0;                            // (the tick bounds read the stage before this one)
+    p->drop_bounds_readers();                          // (the tick bounds and the recover stage read the stage before this one)
     if (int rc = bounds_alloc(p, p->traj_R)) return rc;
     for (auto& e : p->ev_bnd)
         if (!e) HIPCHK(hipEventCreate(&e));
     HIPCHK(hipStreamWaitEvent(st, p->ev_traj[1], 0));
+    if (p->rcv.ev[1]) HIPCHK(hipStreamWaitEvent(st, p->rcv.ev[1], 0));   // (a recover stage may still read the rows, on another stream)
     p->last_stream = st;
     HIPCHK(hipEventRecord(p->ev_bnd[0], st));
     const TrajParams& t = p->traj_q;

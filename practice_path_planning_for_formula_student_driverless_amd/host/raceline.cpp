@@ -55,6 +55,11 @@
 //               the winners from sample S (0) at the raceline's own speed there, over the samples
 //               ahead, under this run's cfg with the given knobs replaced (rl_retime), in
 //               <base>_trajectory_<r>_retimed.csv (the same columns)
+//   --recover-from X,Y [--recover-dir HX,HY] [--recover-len D] [--recover-speed V]  with --best K --mode mintime
+//               --trajectory-dt DT --bounds: a car at (X, Y) heading (HX, HY) (along the raceline) doing V m/s (the
+//               raceline's speed at its nearest sample) on a path back to each winner within D (20) m along it, inside
+//               the free width of --bounds, under this run's cfg (rl_recover), in <base>_trajectory_<r>_recover.csv
+//               (the same columns and offset_m)
 //   --bounds    with --best K --trajectory-dt DT: also the free track width about every sample of
 //               the winners (rl_bounds, guard = cfg veh_width_m / 2 + safety_margin_m), in
 //               <base>_bounds_<r>.csv: i,x,y,nx,ny,lo,hi
@@ -1212,6 +1217,15 @@ struct RetimeOpt {
 };
 static RetimeOpt g_retime;
 
+// --recover-from / --recover-dir / --recover-len / --recover-speed: the car's position, its
+// direction of travel (has_dir), the merge length and its speed (< 0: the raceline's at its
+// nearest sample)
+struct RecoverOpt {
+    bool given = false, has_dir = false;
+    double x = 0, y = 0, hx = 0, hy = 0, len = 20.0, speed = -1.0;
+};
+static RecoverOpt g_recover;
+
 // B α-seeds in one launch (beyond the reference): one summary row per instance.
 static void batch_and_save(const string& base, const vector<Vec2>& center, double L, bool closed,
                            const vector<Vec2>& inner_from_mids, const vector<Vec2>& outer_from_mids, int B, int modes,
@@ -1284,7 +1298,9 @@ static void batch_and_save(const string& base, const vector<Vec2>& center, doubl
     const bool want_stp = want_traj && stop_sample >= 0;
     // --retime-set: the retime stage needs the winners' whole rows as well
     const bool want_rtm = want_traj && !g_retime.sets.empty();
-    const bool want_rows = want_rjn || want_stp || want_rtm;
+    // --recover-from: the recover stage needs the winners' whole rows as well
+    const bool want_rcv = want_traj && g_recover.given;
+    const bool want_rows = want_rjn || want_stp || want_rtm || want_rcv;
     vector<double> wrow[4], tT(want_rows ? idx.size() : 0);      // heading, kappa, v, ax
     for (auto& col : wrow) col.resize(want_rows ? idx.size() * N : 0);
     auto run_best = [&]() {
@@ -1528,6 +1544,62 @@ static void batch_and_save(const string& base, const vector<Vec2>& center, doubl
                     << col[1][at] << "\n";
             }
         }
+        // <base>_trajectory_<r>_recover.csv: the car of --recover-from on its way back to winner r
+        if (want_rcv) {
+            const rl_cfg cn = cfg::to_abi(C);
+            vector<double> pose(2 * K), dir(2 * K), v0(K), len(K, g_recover.len), h(K, L / (double)N), rcol[8], tend(K), e(K);
+            vector<int32_t> row(K), rcount(K), node(K), feas(K), clamped(K), offtrack(K), merge(K);
+            for (size_t r = 0; r < K; ++r) {
+                pose[2 * r] = g_recover.x; pose[2 * r + 1] = g_recover.y;
+                dir[2 * r] = g_recover.hx; dir[2 * r + 1] = g_recover.hy;
+                row[r] = (int32_t)r;
+                size_t near = 0;                                 // the winner's sample nearest the car
+                double best_d = INFINITY;
+                for (size_t i = 0; i < N; ++i) {
+                    const double ddx = bx[r * N + i] - g_recover.x, ddy = by[r * N + i] - g_recover.y, d2 = ddx * ddx + ddy * ddy;
+                    if (d2 < best_d) { best_d = d2; near = i; }
+                }
+                v0[r] = g_recover.speed >= 0.0 ? g_recover.speed : wrow[2][r * N + near];
+            }
+            for (auto& c : rcol) c.resize(K * (size_t)traj_cap);
+            rl_rcv_query q;
+            std::memset(&q, 0, sizeof(q));
+            q.rj.pose_xy = pose.data(); q.rj.row = row.data();
+            q.rj.Q = (int32_t)K; q.rj.window = 0; q.rj.M_cap = traj_cap; q.rj.dt = traj_dt;
+            q.rj.v0 = v0.data(); q.rj.cfg = &cn; q.rj.K_cap = RL_RCV_MAX_NODES;
+            q.merge_len = len.data(); q.dir_xy = g_recover.has_dir ? dir.data() : nullptr;
+            rl_rcv rc;
+            std::memset(&rc, 0, sizeof(rc));
+            rc.s = rcol[0].data(); rc.x = rcol[1].data(); rc.y = rcol[2].data(); rc.heading = rcol[3].data();
+            rc.kappa = rcol[4].data(); rc.v = rcol[5].data(); rc.ax = rcol[6].data(); rc.offset = rcol[7].data();
+            rc.count = rcount.data(); rc.end_node = node.data(); rc.feasible = feas.data(); rc.t_end = tend.data(); rc.e = e.data();
+            rc.clamped = clamped.data(); rc.offtrack = offtrack.data(); rc.merge_node = merge.data();
+            gpu::check(rl_recover(bx.data(), by.data(), wrow[0].data(), wrow[1].data(), wrow[2].data(), wrow[3].data(), h.data(),
+                                  col[0].data(), col[1].data(), col[2].data(), col[3].data(), (int32_t)N, (int32_t)K, closed ? 1 : 0,
+                                  &q, gpu::device, &rc),
+                       "rl_recover");
+            std::cerr << std::setprecision(9);
+            for (size_t r = 0; r < K; ++r) {
+                if (node[r] < 0) throw std::runtime_error("recover: no node ahead of the pose");
+                const int64_t rows = rcount[r];
+                vector<double> tab((size_t)rows * 9);
+                for (int64_t m = 0; m < rows; ++m) {
+                    tab[(size_t)m * 9] = (double)m * traj_dt;
+                    for (int cc = 0; cc < 8; ++cc) tab[(size_t)m * 9 + 1 + cc] = rcol[cc][r * (size_t)traj_cap + (size_t)m];
+                }
+                vector<char> text((size_t)rows * 9 * 22 + 1);
+                int64_t tlen = 0;
+                gpu::check(rl_format_csv(tab.data(), rows, 9, gpu::device, text.data(), (int64_t)text.size(), &tlen, nullptr),
+                           "rl_format_csv");
+                io::Csv o(base + "_trajectory_" + std::to_string(r) + "_recover.csv");
+                if (!o) throw std::runtime_error("save recover trajectory failed");
+                o.f << "t,s,x,y,heading_rad,curvature,v_mps,ax_mps2,offset_m\n";
+                o.f.write(text.data(), (std::streamsize)tlen);
+                std::cerr << "[recover] winner " << r << ": e " << e[r] << " m, " << node[r] << " nodes, merge_node " << merge[r]
+                          << ", clamped " << clamped[r] << ", offtrack " << offtrack[r] << ", feasible " << feas[r] << ", t_end "
+                          << tend[r] << " s\n";
+            }
+        }
     }
     std::cerr << "[best] " << (mt || score_lap ? "lap_time_s" : "curvature_score") << " of the " << best << " best of B=" << B << ":";
     std::cerr << std::setprecision(9);
@@ -1719,6 +1791,18 @@ int run_from_centerline(const string& outPath, double L, double s0, const string
                 return 2;
             }
     }
+    if (pipeline::g_recover.given && (!(traj_dt > 0.0) || mode != "mintime" || !want_bounds || best <= 0)) {
+        std::cerr << "[ERR] --recover-from X,Y needs --seeds B --best K --mode mintime --trajectory-dt DT --bounds\n";
+        return 2;
+    }
+    if (pipeline::g_recover.given) {
+        const auto& g = pipeline::g_recover;
+        if (!std::isfinite(g.x) || !std::isfinite(g.y) || !std::isfinite(g.hx) || !std::isfinite(g.hy) || !std::isfinite(g.len) ||
+            !(g.len > 0.0) || !std::isfinite(g.speed)) {
+            std::cerr << "[ERR] --recover-from / --recover-dir need finite numbers, --recover-len D > 0\n";
+            return 2;
+        }
+    }
     if (want_bounds && (!(traj_dt > 0.0) || best <= 0)) {
         std::cerr << "[ERR] --bounds needs --seeds B --best K --trajectory-dt DT\n";
         return 2;
@@ -1794,6 +1878,17 @@ int main(int argc, char** argv) {
                 pipeline::g_retime.from = std::stoi(next());
                 if (pipeline::g_retime.from == -1) pipeline::g_retime.from = -2;   // (-1 stands for "not given")
             }
+            else if (a == "--recover-from" || a == "--recover-dir") {
+                const string xy = next();
+                const size_t comma = xy.find(',');
+                if (comma == string::npos) throw std::runtime_error(a + " needs two numbers X,Y");
+                const double u = std::stod(xy.substr(0, comma)), w = std::stod(xy.substr(comma + 1));
+                auto& g = pipeline::g_recover;
+                if (a == "--recover-from") { g.given = true; g.x = u; g.y = w; }
+                else { g.has_dir = true; g.hx = u; g.hy = w; }
+            }
+            else if (a == "--recover-len") pipeline::g_recover.len = std::stod(next());
+            else if (a == "--recover-speed") pipeline::g_recover.speed = std::stod(next());
             else if (a == "--bounds") want_bounds = true;
             else if (a == "--device") gpu::device = std::stoi(next());
             else if (a == "--devices") {
@@ -1819,6 +1914,8 @@ int main(int argc, char** argv) {
                       << "             from K (512) samples before J, braking to V (0) m/s at sample J\n"
                       << "         [--retime-set key=value ... [--retime-from S]]   with --mode mintime --trajectory-dt: the winners\n"
                       << "             from sample S (0) over the samples ahead, under the cfg with these knobs replaced\n"
+                      << "         [--recover-from X,Y [--recover-dir HX,HY] [--recover-len D] [--recover-speed V]]   with --mode mintime\n"
+                      << "             --trajectory-dt --bounds: a path from the car at X,Y back to the winners within D (20) m\n"
                       << "         [--bounds]   with --best K --trajectory-dt: the free track width along the winners\n";
             return 1;
         }

@@ -824,17 +824,12 @@ def _march_step(consts: tuple, wk: float, kap_k: float, d: float) -> tuple:
     return math.sqrt(_smax(0.0, wk * wk + (2.0 * a_acc) * d)), math.sqrt(_smax(0.0, wk * wk - (2.0 * a_brk) * d))
 
 
-def _march_ticks(out, q: int, M1: int, tau, tt, w, kend: int, row6, nodes, i0: int, u: float, hb: float) -> None:
-    """The seven columns of the ticks tau[:M1] of query q on the march w, tt over the nodes
-    0 .. kend, nodes = _march_nodes' (the device's march_columns)."""
+def _node_values(row6, nodes, i0: int, u: float, hb: float, s0) -> tuple:
+    """(x, y, psi, s) of the march nodes, nodes = _march_nodes': node 0 the located point (s0 its
+    arc length), node k >= 1 sample n_k (the device's march_node)."""
     X, Y, PSI = row6[:3]
-    n, idx, kap, _, d0 = nodes
+    n, idx = nodes[:2]
     j0 = (i0 + 1) % X.shape[0]
-    a = _bisect_nodes(tt, tau, kend)
-    b = a + 1
-    um = (tau - tt[a]) / (tt[b] - tt[a])
-    d = np.where(a == 0, d0, hb)
-    # the nodes' values: node 0 the located point, node k >= 1 sample n_k
     dp0 = PSI[j0] - PSI[i0]
     dp0 = dp0 - 2.0 * np.pi if dp0 > np.pi else (dp0 + 2.0 * np.pi if dp0 < -np.pi else dp0)
     nx, ny, npsi = X[idx].copy(), Y[idx].copy(), PSI[idx].copy()
@@ -842,7 +837,19 @@ def _march_ticks(out, q: int, M1: int, tau, tt, w, kend: int, row6, nodes, i0: i
     nx[0] = X[i0] + u * (X[j0] - X[i0])
     ny[0] = Y[i0] + u * (Y[j0] - Y[i0])
     npsi[0] = PSI[i0] + u * dp0
-    ns[0] = out.s0[q]
+    ns[0] = s0
+    return nx, ny, npsi, ns
+
+
+def _node_ticks(out, q: int, M1: int, tau, tt, w, kend: int, values, kap, d) -> np.ndarray:
+    """The seven columns of the ticks tau[:M1] of query q on the march w, tt over the nodes
+    0 .. kend with values = (x, y, psi, s), curvatures kap and d [kend] apart (the device's
+    march_columns).  Returns the ticks' nodes a and parameters um [2, M1]."""
+    nx, ny, npsi, ns = values
+    a = _bisect_nodes(tt, tau, kend)
+    b = a + 1
+    um = (tau - tt[a]) / (tt[b] - tt[a])
+    d = d[a]
     dp = npsi[b] - npsi[a]
     dp = np.where(dp > np.pi, dp - 2.0 * np.pi, np.where(dp < -np.pi, dp + 2.0 * np.pi, dp))
     out.s[q, :M1] = ns[a] + um * (ns[b] - ns[a])
@@ -852,6 +859,15 @@ def _march_ticks(out, q: int, M1: int, tau, tt, w, kend: int, row6, nodes, i0: i
     out.kappa[q, :M1] = kap[a] + um * (kap[b] - kap[a])
     out.v[q, :M1] = w[a] + um * (w[b] - w[a])
     out.ax[q, :M1] = np.where(d > 0.0, (w[b] * w[b] - w[a] * w[a]) / (2.0 * d), 0.0)
+    return a, um
+
+
+def _march_ticks(out, q: int, M1: int, tau, tt, w, kend: int, row6, nodes, i0: int, u: float, hb: float) -> None:
+    """The seven columns of the ticks tau[:M1] of query q on the march w, tt over the nodes
+    0 .. kend, nodes = _march_nodes' (the device's march_columns)."""
+    kap, d0 = nodes[2], nodes[4]
+    d = np.concatenate(([d0], np.full(max(kend - 1, 0), hb)))
+    _node_ticks(out, q, M1, tau, tt, w, kend, _node_values(row6, nodes, i0, u, hb, out.s0[q]), kap, d)
 
 
 def rejoin_host(x, y, heading, kappa, v, ax, h, closed: bool, poses, v0, cfg: RlCfg, row=None, seg_hint=None,
@@ -1156,6 +1172,37 @@ class Retime(_FromTheCar):
         return int(self.end_node[q])
 
 
+def _retime_pass(consts: tuple, cfg: RlCfg, v0: float, kap, r, d) -> tuple:
+    """The retime stage's ceiling, envelope and march over the nodes 0 .. K of curvatures kap and
+    row speeds r [K + 1], d [K] apart, from v0: (w, tt, b, c [K + 1], overspeed, v_excess,
+    bind_node) (the device's retime_ceiling and retime_pass)."""
+    v_cap, a_lat, k_eps = float(cfg.v_cap_mps), float(cfg.a_lat_max), float(cfg.kappa_eps)
+    kl, rl_, K = np.asarray(kap).tolist(), np.asarray(r).tolist(), len(d)
+    c = [_smin(_smin(v_cap, math.sqrt(_fdiv(a_lat, _smax(abs(kk), k_eps)))), rk)     # the ceiling, per node
+         for kk, rk in zip(kl, rl_)]
+    b = [0.0] * (K + 1)                                 # the envelope, backward from the last node
+    b[K] = c[K]
+    for k in range(K - 1, -1, -1):
+        bn = b[k + 1]
+        a_brk = _ax_max_at(consts, bn, kl[k + 1])[1]
+        b[k] = _smin(c[k], math.sqrt(_smax(0.0, bn * bn + (2.0 * a_brk) * d[k])))
+    w, tt = [v0], [0.0]                                 # the march, forward to the last node
+    over, ve, bind = 0, 0.0, -1
+    for k in range(K + 1):
+        wk = w[k]
+        over += wk > b[k]
+        ve = _smax(ve, wk - b[k])
+        if bind < 0 and b[k] < rl_[k]:
+            bind = k
+        if k == K:
+            break
+        up, dn = _march_step(consts, wk, kl[k], d[k])
+        wn = _smin(up, b[k + 1] if wk <= b[k] else _smax(dn, b[k + 1]))
+        w.append(wn)
+        tt.append(tt[k] + _fdiv(2.0 * d[k], _smax(1e-6, wk + wn)))
+    return np.array(w), np.array(tt), np.array(b), np.array(c), over, ve, bind
+
+
 def retime_host(x, y, heading, kappa, v, ax, h, closed: bool, poses, v0, cfg: RlCfg, row=None, seg_hint=None,
                 window: int = 0, dt: float = 0.05, m_cap: int = 64, k_cap: int = 1024, stamps=None) -> Retime:
     """The specification of the retime stage (include/rl_abi.h) in NumPy; the kernel
@@ -1173,7 +1220,6 @@ def retime_host(x, y, heading, kappa, v, ax, h, closed: bool, poses, v0, cfg: Rl
         lambda: _rjn_query(poses, v0, cfg, row, seg_hint, window, dt, m_cap, k_cap), stamps)
     Q, dt, m_cap, W, k_cap = P.shape[0], float(dt), int(m_cap), int(window), int(k_cap)
     consts = _rjn_consts(cfg)
-    v_cap, a_lat, k_eps = float(cfg.v_cap_mps), float(cfg.a_lat_max), float(cfg.kappa_eps)
     out = Retime.alloc(Q, m_cap, dt, k_cap)
     out.seg[:] = -1
     out.end_node[:] = -1
@@ -1193,31 +1239,7 @@ def retime_host(x, y, heading, kappa, v, ax, h, closed: bool, poses, v0, cfg: Rl
             continue
         out.seg[q], out.u[q], out.dist2[q], out.e[q], out.t0[q], out.s0[q] = loc
         nodes = _, _, kap, r, d0 = _march_nodes(row6, i0, u, hb, K)
-        kl, rl_ = kap.tolist(), r.tolist()
-        c = [_smin(_smin(v_cap, math.sqrt(_fdiv(a_lat, _smax(abs(kk), k_eps)))), rk)     # the ceiling, per node
-             for kk, rk in zip(kl, rl_)]
-        b = [0.0] * (K + 1)                                 # the envelope, backward from the last node
-        b[K] = c[K]
-        for k in range(K - 1, -1, -1):
-            d, bn = (d0 if k == 0 else hb), b[k + 1]
-            a_brk = _ax_max_at(consts, bn, kl[k + 1])[1]
-            b[k] = _smin(c[k], math.sqrt(_smax(0.0, bn * bn + (2.0 * a_brk) * d)))
-        w, tt = [float(V0[q])], [0.0]                       # the march, forward to the last node
-        over, ve, bind = 0, 0.0, -1
-        for k in range(K + 1):
-            wk = w[k]
-            over += wk > b[k]
-            ve = _smax(ve, wk - b[k])
-            if bind < 0 and b[k] < rl_[k]:
-                bind = k
-            if k == K:
-                break
-            d = d0 if k == 0 else hb
-            up, dn = _march_step(consts, wk, kl[k], d)
-            wn = _smin(up, b[k + 1] if wk <= b[k] else _smax(dn, b[k + 1]))
-            w.append(wn)
-            tt.append(tt[k] + _fdiv(2.0 * d, _smax(1e-6, wk + wn)))
-        w, tt, b, c = np.array(w), np.array(tt), np.array(b), np.array(c)
+        w, tt, b, c, over, ve, bind = _retime_pass(consts, cfg, float(V0[q]), kap, r, [d0] + [hb] * (K - 1))
         out.node_v[q, :K + 1], out.node_t[q, :K + 1], out.node_b[q, :K + 1], out.node_c[q, :K + 1] = w, tt, b, c
         tte = tt[K]
         out.end_node[q], out.overspeed[q], out.feasible[q] = K, over, 1 if float(V0[q]) <= b[0] else 0
@@ -1374,6 +1396,252 @@ def bounds(prob: Problem, x, y, veh_width: float, margin: float, device: int = 0
     out = Bounds.alloc(B, N)
     p, oc = prob.as_c(), out.as_c()
     _check(_lib().rl_bounds(C.byref(p), abi.dptr(X), abi.dptr(Y), B, w, m, int(device), C.byref(oc)))
+    return out
+
+
+# ------------------------------------------------- recover: a path from the car's offset back to the row
+@dataclass
+class Recover(Retime):
+    """The recover stage's answer for Q poses (rl_rcv): Retime's fields on the offset path (x, y,
+    heading, kappa of the ticks leave the row; s stays the station along the row), and offset
+    [Q, M_cap] (the ticks' lateral offset), clamped (nodes at which the free width cut the offset
+    profile), offtrack (1: the car itself is outside lo0 .. hi0), merge_node (the first node on
+    the row again, -1: not within the window), lo0, hi0 (the room at the car) [Q]; node_o, node_k
+    [Q, k_cap + 1]: the nodes' offsets and the path's curvatures there."""
+
+    offset: np.ndarray = None
+    clamped: np.ndarray = None
+    offtrack: np.ndarray = None
+    merge_node: np.ndarray = None
+    lo0: np.ndarray = None
+    hi0: np.ndarray = None
+    node_o: np.ndarray = None
+    node_k: np.ndarray = None
+    node_psi: np.ndarray = None   # [Q, k_cap + 1] the nodes' headings (host side: recover_host fills it, the library does not)
+
+    @classmethod
+    def alloc(cls, Q: int, m_cap: int, dt: float, k_cap: int = 1) -> "Recover":
+        cols = {n: np.zeros((Q, m_cap)) for n in abi.TRAJ_COLS + abi.RCV_COLS}
+        per = {n: np.zeros(Q) for n in abi.HZN_LOC + abi.RCV_SCAL}
+        ints = {n: np.zeros(Q, dtype=np.int32) for n in abi.RCV_INTS}
+        nodes = {n: np.zeros((Q, k_cap + 1)) for n in abi.RCV_NODES + ("node_psi",)}
+        return cls(**cols, **per, **ints, **nodes, dt=float(dt))
+
+    def as_c(self) -> abi.RlRcv:
+        t = abi.RlRcv()
+        for n in abi.TRAJ_COLS + abi.RCV_COLS + abi.HZN_LOC + abi.RCV_SCAL + abi.RCV_NODES:
+            setattr(t, n, _ptr(getattr(self, n), np.float64, n))
+        for n in abi.RCV_INTS:
+            setattr(t, n, _ptr(getattr(self, n), np.int32, n))
+        return t
+
+    def row(self, q: int) -> dict:
+        """Retime's ticks of query q, and their offset."""
+        out = super().row(q)
+        out["offset"] = self.offset[q, :int(self.count[q])]
+        return out
+
+
+def _rcv_query(poses, v0, cfg, merge_len, dir_xy, row, seg_hint, window, dt, m_cap, k_cap) -> tuple:
+    if int(k_cap) != k_cap or not 1 <= int(k_cap) <= abi.RL_RCV_MAX_NODES:
+        raise ValueError(f"recover: k_cap must be 1..{abi.RL_RCV_MAX_NODES}, got {k_cap}")
+    P, rw, hint, V0 = _rjn_query(poses, v0, cfg, row, seg_hint, window, dt, m_cap, k_cap)
+    Q = P.shape[0]
+    D = np.asarray(merge_len, dtype=np.float64)
+    if D.ndim == 0:
+        D = np.broadcast_to(D, (Q,))
+    if D.shape != (Q,):
+        raise ValueError(f"recover: merge_len must be a number or [Q={Q}] numbers, got shape {D.shape}")
+    D = np.ascontiguousarray(D)
+    if not np.all(np.isfinite(D)) or np.any(D <= 0.0):
+        raise ValueError("recover: merge_len must be finite and > 0")
+    H = None
+    if dir_xy is not None:
+        H = np.asarray(dir_xy, dtype=np.float64)
+        if H.shape == (2,):
+            H = np.broadcast_to(H, (Q, 2))
+        if H.shape != (Q, 2):
+            raise ValueError(f"recover: dir_xy must be [2] or [Q={Q}, 2], got shape {H.shape}")
+        H = np.ascontiguousarray(H)
+        if not np.all(np.isfinite(H)):
+            raise ValueError("recover: dir_xy must be finite")
+    return P, rw, hint, V0, D, H
+
+
+def _rcv_c(P, rw, hint, V0, D, H, cfg, window, dt, m_cap, k_cap) -> abi.RlRcvQuery:
+    return abi.RlRcvQuery(_rjn_c(P, rw, hint, V0, cfg, window, dt, m_cap, k_cap), _ptr(D, np.float64, "merge_len"),
+                          None if H is None else _ptr(H, np.float64, "dir_xy"))
+
+
+def _rcv_bounds(what: str, rows, closed: bool, lo, hi, nx, ny) -> tuple:
+    """lo, hi, nx, ny as contiguous float64 [B, N] for the rows; nx, ny None: normals_host's."""
+    B, N = rows[0].shape
+    if nx is None or ny is None:
+        nx, ny = normals_host(rows[0], rows[1], closed)
+    out = []
+    for name, a in zip(abi.BND_ROWS, (lo, hi, nx, ny)):
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.shape == (N,) and B == 1:
+            a = a[None]
+        if a.shape != (B, N):
+            raise ValueError(f"{what}: {name} must be [B={B}, N={N}], got {a.shape}")
+        out.append(a)
+    return tuple(out)
+
+
+def _rcv_slope(dx, dy, hx, hy) -> float:
+    """g0: de/ds of a car heading (hx, hy) on a segment of direction (dx, dy), capped at 45 degrees."""
+    den, num = dx * hx + dy * hy, dx * hy - dy * hx
+    if den > 0.0:
+        return _smin(1.0, _smax(-1.0, _fdiv(num, den)))
+    return -1.0 if num < 0.0 else (1.0 if num > 0.0 else 0.0)
+
+
+def _rcv_quintics(z: float) -> tuple:
+    """(qz, pz) at z in [0, 1]: the quintics with q(0) = 1, p'(0) = 1 and every other value, slope
+    and second derivative at 0 and 1 zero; both are exactly 0.0 at z = 1."""
+    z3 = (z * z) * z
+    return 1.0 + z3 * (-10.0 + z * (15.0 - 6.0 * z)), z + z3 * (-6.0 + z * (8.0 - 3.0 * z))
+
+
+def _rcv_geometry(o, px, py, d_row, kap_row, psi_row) -> tuple:
+    """(d', kappa', psi) of the offset path through the points px, py [K + 1] with offsets o: the
+    row's d_row [K], kap_row and psi_row [K + 1] where the path is on the line, the points'
+    chords, Menger curvature and chord directions where it is not (§3q "geometry")."""
+    K = len(o) - 1
+    zero = [ok == 0.0 for ok in o]
+    with np.errstate(all="ignore"):
+        d = [d_row[k] if zero[k] and zero[k + 1] else
+             float(np.sqrt((px[k + 1] - px[k]) * (px[k + 1] - px[k]) + (py[k + 1] - py[k]) * (py[k + 1] - py[k])))
+             for k in range(K)]
+
+        def on_line(k):
+            return zero[k] and (k == 0 or zero[k - 1]) and (k == K or zero[k + 1])
+
+        def inner(k):
+            if on_line(k):
+                return kap_row[k]
+            ax_, ay_ = px[k] - px[k - 1], py[k] - py[k - 1]
+            bx_, by_ = px[k + 1] - px[k], py[k + 1] - py[k]
+            cx_, cy_ = px[k + 1] - px[k - 1], py[k + 1] - py[k - 1]
+            den = (d[k - 1] * d[k]) * float(np.sqrt(cx_ * cx_ + cy_ * cy_))
+            return _fdiv(2.0 * (ax_ * by_ - ay_ * bx_), den) if den > 0.0 else 0.0
+
+        kap, psi = [0.0] * (K + 1), [0.0] * (K + 1)
+        for k in range(K + 1):
+            if 0 < k < K:
+                kap[k] = inner(k)
+            elif K < 2 or on_line(k):
+                kap[k] = kap_row[k]
+            else:
+                kap[k] = inner(1 if k == 0 else K - 1)
+            if on_line(k):
+                psi[k] = psi_row[k]
+            else:
+                a, b = max(k - 1, 0), min(k + 1, K)
+                psi[k] = math.atan2(py[b] - py[a], px[b] - px[a])
+    return np.array(d, dtype=np.float64), np.array(kap, dtype=np.float64), np.array(psi, dtype=np.float64)
+
+
+def recover_host(x, y, heading, kappa, v, ax, h, closed: bool, lo, hi, poses, v0, cfg: RlCfg, merge_len, dir_xy=None,
+                 nx=None, ny=None, row=None, seg_hint=None, window: int = 0, dt: float = 0.05, m_cap: int = 64,
+                 k_cap: int = 512, stamps=None) -> Recover:
+    """The specification of the recover stage (include/rl_abi.h) in NumPy; the kernel
+    equals it bit for bit (heading off the line: to the rounding of math.atan2).  The rows, poses,
+    hints, stamps, v0 and cfg are retime_host's, and so are the locate and the nodes 0 .. K.  lo,
+    hi [B, N] are the rows' free width (the bounds stage's) and nx, ny their unit normals (None:
+    normals_host's).  From the car's offset e and slope (dir_xy: its direction of travel; None:
+    along the row) a quintic offset profile runs to zero over merge_len metres along the row,
+    clamped to lo .. hi at every node; the nodes moved along their normals are the path, whose
+    chords, Menger curvatures and chord directions replace the row's d, kappa and heading where it
+    is off the line; retime_host's ceiling, envelope and march run on that geometry, and the
+    ticks m * dt before t_end follow the path.  A pose on the line heading along it gets
+    retime_host's answer bit for bit."""
+    closed = bool(closed)
+    rows, hs, stamps, N, S, (P, rw, hint, V0, D, H) = _query_rows(
+        "recover", (x, y, heading, kappa, v, ax, h), closed,
+        lambda: _rcv_query(poses, v0, cfg, merge_len, dir_xy, row, seg_hint, window, dt, m_cap, k_cap), stamps)
+    LO, HI, NX, NY = _rcv_bounds("recover", rows, closed, lo, hi, nx, ny)
+    Q, dt, m_cap, W, k_cap = P.shape[0], float(dt), int(m_cap), int(window), int(k_cap)
+    consts = _rjn_consts(cfg)
+    out = Recover.alloc(Q, m_cap, dt, k_cap)
+    out.seg[:] = -1
+    out.end_node[:] = -1
+    tau_all = np.arange(m_cap, dtype=np.float64) * dt
+    for q in range(Q):
+        if S < 1:
+            continue
+        row6 = [a[rw[q]] for a in rows]
+        X, Y = row6[:2]
+        blo, bhi, bnx, bny = (a[rw[q]] for a in (LO, HI, NX, NY))
+        t, hb = stamps[rw[q]], float(hs[rw[q]])
+        T = t[S]
+        px, py = P[q, 0], P[q, 1]
+        loc = _hzn_locate(X, Y, t, hb, px, py, int(hint[q]), W, closed)
+        if loc is None:
+            continue
+        i0, u, t0 = int(loc[0]), float(loc[1]), loc[4]
+        K = min(k_cap, N if closed else N - 1 - i0)
+        if K < 1:
+            continue
+        out.seg[q], out.u[q], out.dist2[q], out.e[q], out.t0[q], out.s0[q] = loc
+        e, Dq, j0 = float(loc[3]), float(D[q]), (i0 + 1) % N
+        nodes = n, idx, kap, r, d0 = _march_nodes(row6, i0, u, hb, K)
+        with np.errstate(all="ignore"):
+            dx, dy, wx, wy = float(X[j0] - X[i0]), float(Y[j0] - Y[i0]), float(px - X[i0]), float(py - Y[i0])
+            g0 = 0.0 if H is None else _rcv_slope(dx, dy, float(H[q, 0]), float(H[q, 1]))
+            gD = g0 * Dq
+            o, ncl, mg = [e], 0, -1                                    # offsets and clamp
+            for k in range(1, K + 1):
+                z = _smin(1.0, _fdiv(float(d0) + float(k - 1) * hb, Dq))
+                qz, pz = _rcv_quintics(z)
+                raw = e * qz + gD * pz
+                ok = _smin(float(bhi[idx[k]]), _smax(float(blo[idx[k]]), raw))
+                o.append(ok)
+                ncl += ok != raw
+                if mg < 0 and z >= 1.0:
+                    mg = k
+            lo0, hi0 = _smax(float(blo[i0]), float(blo[j0])), _smin(float(bhi[i0]), float(bhi[j0]))
+            values = nxv, nyv, npsi, ns = _node_values(row6, nodes, i0, u, hb, out.s0[q])
+            o = np.array(o, dtype=np.float64)
+            ppx, ppy = X[idx] + o * bnx[idx], Y[idx] + o * bny[idx]    # points
+            ppx[0], ppy[0] = nxv[0] + (wx - u * dx), nyv[0] + (wy - u * dy)
+            d_row = np.concatenate(([d0], np.full(K - 1, hb)))
+            dp, kp, psi = _rcv_geometry(o.tolist(), ppx.tolist(), ppy.tolist(), d_row.tolist(), kap.tolist(), npsi.tolist())
+        w, tt, b, c, over, ve, bind = _retime_pass(consts, cfg, float(V0[q]), kp, r, dp.tolist())
+        out.node_v[q, :K + 1], out.node_t[q, :K + 1], out.node_b[q, :K + 1], out.node_c[q, :K + 1] = w, tt, b, c
+        out.node_o[q, :K + 1], out.node_k[q, :K + 1], out.node_psi[q, :K + 1] = o, kp, psi
+        tte = tt[K]
+        out.end_node[q], out.overspeed[q], out.feasible[q] = K, over, 1 if float(V0[q]) <= b[0] else 0
+        out.bind_node[q], out.t_end[q], out.v_excess[q] = bind, tte, ve
+        out.clamped[q], out.merge_node[q], out.offtrack[q] = ncl, mg, 0 if (lo0 <= e and e <= hi0) else 1
+        out.lo0[q], out.hi0[q] = lo0, hi0
+        nk = i0 + K
+        c0 = nk // N
+        with np.errstate(all="ignore"):
+            out.t_loss[q] = tte - ((np.float64(c0) * T + t[nk - c0 * N]) - t0)
+            M1 = int(np.count_nonzero(tau_all < tte))           # (monotone in m: the kernel bisects)
+            out.count[q] = M1
+            if M1 > 0:
+                a, um = _node_ticks(out, q, M1, tau_all[:M1], tt, w, K, (ppx, ppy, psi, ns), kp, dp)
+                out.offset[q, :M1] = o[a] + um * (o[a + 1] - o[a])
+    return out
+
+
+def recover(x, y, heading, kappa, v, ax, h, closed: bool, lo, hi, poses, v0, cfg: RlCfg, merge_len, dir_xy=None,
+            nx=None, ny=None, row=None, seg_hint=None, window: int = 0, dt: float = 0.05, m_cap: int = 64,
+            k_cap: int = 512, device: int = 0) -> Recover:
+    """recover_host on the GPU (rl_recover): the trajectory kernel stamps the B given rows, then
+    the recover kernel answers the Q poses on them and their bounds; row[q] counts the given rows."""
+    rows, hs, (P, rw, hint, V0, D, H), B, N = _open_query(
+        "recover", (x, y, heading, kappa, v, ax, h),
+        lambda: _rcv_query(poses, v0, cfg, merge_len, dir_xy, row, seg_hint, window, dt, m_cap, k_cap))
+    bnd = _rcv_bounds("recover", rows, bool(closed), lo, hi, nx, ny)
+    out = Recover.alloc(P.shape[0], int(m_cap), dt, int(k_cap))
+    qc, oc = _rcv_c(P, rw, hint, V0, D, H, cfg, window, dt, m_cap, k_cap), out.as_c()
+    _check(_lib().rl_recover(*[_ptr(a, np.float64, "row") for a in rows], _ptr(hs, np.float64, "h"),
+                             *[_ptr(a, np.float64, "bounds") for a in bnd], N, B, 1 if closed else 0, C.byref(qc),
+                             int(device), C.byref(oc)))
     return out
 
 
@@ -1647,6 +1915,35 @@ class Plan:
         if not nodes:
             t.node_v = t.node_t = t.node_b = t.node_c = None
         _check(_lib().rl_plan_fetch_retime(self._h, C.byref(t)))
+        return out
+
+    def recover(self, poses, v0, cfg: RlCfg, merge_len, dir_xy=None, row=None, seg_hint=None, window: int = 0,
+                dt: float = 0.05, m_cap: int = 64, k_cap: int = 512, stream_ptr: int = 0) -> None:
+        """Enqueue the recover stage after the last trajectory() and bounds() (rl_plan_recover):
+        retime()'s query with a merge length (a number or [Q], metres along the row) and optionally
+        the car's direction of travel dir_xy ([2] or [Q, 2]), answered with a path from the car's
+        offset back to the row inside the bounds stage's free width and cfg's speed profile on
+        it.  Every other stage stays as it is; a later bounds() invalidates it."""
+        P, rw, hint, V0, D, H = _rcv_query(poses, v0, cfg, merge_len, dir_xy, row, seg_hint, window, dt, m_cap, k_cap)
+        self._rcv = None
+        qc = _rcv_c(P, rw, hint, V0, D, H, cfg, window, dt, m_cap, k_cap)
+        _check(_lib().rl_plan_recover(self._h, C.byref(qc), C.c_void_p(stream_ptr) if stream_ptr else None))
+        self._rcv = (P.shape[0], int(m_cap), float(dt), int(k_cap))
+
+    def fetch_recover(self, nodes: bool = True) -> Recover:
+        """Download the last recover() (rl_plan_fetch_recover); nodes=False leaves the node arrays
+        on the device."""
+        if getattr(self, "_rcv", None) is None:
+            t = abi.RlRcv()                 # (the library's own answer: no stage on this plan)
+            _check(_lib().rl_plan_fetch_recover(self._h, C.byref(t)))
+            raise ValueError("fetch_recover: no recover() on this plan")
+        Q, m_cap, dt, k_cap = self._rcv
+        out = Recover.alloc(Q, m_cap, dt, k_cap)
+        t = out.as_c()
+        if not nodes:
+            for n in abi.RCV_NODES:
+                setattr(t, n, None)
+        _check(_lib().rl_plan_fetch_recover(self._h, C.byref(t)))
         return out
 
     def bounds(self, veh_width: Optional[float] = None, margin: Optional[float] = None, stream_ptr: int = 0) -> None:
