@@ -248,7 +248,8 @@ int rl_plan_bind_device_outputs(rl_plan* plan, int32_t which, const rl_out* dev_
  * rl_plan_horizon, 9 = the rejoin stage of the last rl_plan_rejoin, 10 = the stop stage of the
  * last rl_plan_stop, 11 = the bounds stage of the last rl_plan_bounds, 12 = the bounds at the
  * horizon stage's ticks of the last rl_plan_horizon_bounds, 13 = the retime stage of the last
- * rl_plan_retime, 14 = the recover stage of the last rl_plan_recover. */
+ * rl_plan_retime, 14 = the recover stage of the last rl_plan_recover, 15 = the fan stage of the
+ * last rl_plan_recover_fan. */
 int rl_plan_kernel_ms(rl_plan* plan, int32_t idx, float* ms);
 /* The batch size the plan's kernel shape is chosen for (rl_kernel_shape's B); 0 = the plan's
  * own B (the default).  Shapes differ in the tree order of the J / decrease / lap sums, so
@@ -895,6 +896,82 @@ int rl_recover(const double* x, const double* y, const double* heading, const do
                const double* nx, const double* ny, int32_t N, int32_t B, int32_t closed,
                const rl_rcv_query* query, int32_t device, rl_rcv* out);
 
+/* ------------------------------------------------- fan stage: several merge lengths per pose, the best one served
+ * The recover stage's caller chooses merge_len before knowing what it costs: feasible, clamped,
+ * merge_node and t_end are known only after the stage has run.  This stage evaluates C merge
+ * lengths for each pose on the device, ranks them in an exact order and serves the winner's
+ * results with a small table of every candidate's per-query values.
+ *   query   the recover stage's, with merge_len [Q][C], C = n_cand in 1..RL_FAN_MAX_CAND, K_cap in
+ *           1..RL_RCV_MAX_NODES, Q*C <= RL_HZN_MAX_QUERIES, every merge_len[q][c] finite and > 0;
+ *           duplicate lengths are allowed.
+ *   candidates   candidate c of query q is the recover stage's answer for query q with
+ *           D = merge_len[q][c], word for word.  All candidates of a query share the locate (seg,
+ *           u, e, dist2, t0, s0), K, lo0, hi0 and offtrack.
+ *   class   g = 0: feasible && clamped == 0 && merge_node >= 0; g = 1: feasible && merge_node >= 0;
+ *           g = 2: feasible; g = 3: otherwise.
+ *   order   ascending in (g, isnan(t_end), t_end, c), with plain < on doubles and no tolerance;
+ *           best[q] is the first candidate in that order: the path that is drivable from the car's
+ *           speed, was not cut by the track's edge and is on the row again inside the window; among
+ *           such paths the one that reaches node K soonest, and the earlier candidate on a tie.
+ *   empty   a query that the recover stage answers with end_node = -1 has best = -1; seg, count = 0
+ *           and end_node = -1 are as the recover stage specifies them, nothing else is specified.
+ *   results   every field of rl_rcv, holding the winner's values (the node arrays downloaded only
+ *           when asked for), then best [Q] and the table [Q][C].  Losers' ticks and node arrays
+ *           never leave the device.
+ * Anchors: with C = 1 the stage is the recover stage bit for bit.  For any C the winner's fields
+ * equal rl_recover's for merge_len[q][best[q]] bit for bit, heading included, and table row c equals
+ * the per-query values of rl_recover with merge_len[q][c].  A pose on the row with g0 == 0 has
+ * equal t_end for every D, so best = 0 except where a class differs through merge_node.
+ * raceline.recover_fan_host states the same in NumPy (recover_host C times, then
+ * raceline.fan_order).  These are additions to ABI 6.1 that leave RL_ABI_MINOR as it is:
+ * RL_FEATURE_FAN announces them. */
+#define RL_FAN_MAX_CAND 16
+typedef struct rl_fan_query {
+    rl_rcv_query   rc;           /* the recover stage's query, its merge_len [Q][n_cand] */
+    int32_t        n_cand;       /* C, 1..RL_FAN_MAX_CAND; Q*C <= RL_HZN_MAX_QUERIES */
+    int32_t        _pad;
+} rl_fan_query;
+
+typedef struct rl_fan {          /* caller-allocated; NULL fields skipped; it begins as rl_rcv does */
+    double *s, *x, *y, *heading, *kappa, *v, *ax;   /* [Q][M_cap]; ticks m >= count[q] are unspecified */
+    double *u, *t0, *s0, *e, *dist2;                /* [Q] */
+    int32_t *seg, *count;                           /* [Q] */
+    int32_t *end_node, *overspeed;                  /* [Q] */
+    double *t_end, *t_loss;                         /* [Q] */
+    double *node_v, *node_t;                        /* [Q][K_cap+1] as rl_rcv's; downloaded only when asked for */
+    int32_t *feasible, *bind_node;                  /* [Q] */
+    double *v_excess;                               /* [Q] */
+    double *node_b, *node_c;                        /* [Q][K_cap+1] as node_v */
+    double *offset;                                 /* [Q][M_cap] as the columns */
+    int32_t *clamped, *offtrack;                    /* [Q] */
+    int32_t *merge_node;                            /* [Q] */
+    double *lo0, *hi0;                              /* [Q] */
+    double *node_o, *node_k;                        /* [Q][K_cap+1] as node_v */
+    int32_t *best;                                  /* [Q] the winner's c; -1: an empty query */
+    int32_t *cand_class, *cand_feasible, *cand_clamped, *cand_merge_node, *cand_overspeed,
+            *cand_bind_node;                        /* [Q][C] */
+    double *cand_t_end, *cand_t_loss, *cand_v_excess;   /* [Q][C] */
+} rl_fan;
+
+/* Enqueue the stage after the plan's last trajectory and bounds stages: rl_plan_recover's stream,
+ * validity and invalidation rules (a later run, trajectory or bounds stage invalidates it).  It
+ * leaves the results, the trajectory stage and the last horizon, rejoin, stop, retime, recover and
+ * bounds stages untouched; its buffers, the candidates' scratch block among them, are plan-owned
+ * (they count toward the plan cache's budget) and grow with Q, C, M_cap and K_cap.  The query's
+ * arrays and cfg are read before the call returns.  rl_plan_kernel_ms index 15 is the stage (both
+ * kernels).  RL_EINVAL before any device work for: every error of rl_plan_recover, n_cand outside
+ * 1..RL_FAN_MAX_CAND, Q*n_cand > RL_HZN_MAX_QUERIES, a merge_len[q][c] that is not finite or is <= 0. */
+int rl_plan_recover_fan(rl_plan* plan, const rl_fan_query* query, void* hip_stream);
+/* Download the last fan stage (synchronises its stream) into the non-NULL fields of out.
+ * RL_EINVAL before a stage, or after a run, a trajectory or a bounds stage that followed it. */
+int rl_plan_fetch_recover_fan(rl_plan* plan, rl_fan* out);
+/* The same on B given rows and their bounds, as rl_recover.  Errors as rl_recover's and
+ * rl_plan_recover_fan's. */
+int rl_recover_fan(const double* x, const double* y, const double* heading, const double* kappa,
+                   const double* v, const double* ax, const double* h, const double* lo, const double* hi,
+                   const double* nx, const double* ny, int32_t N, int32_t B, int32_t closed,
+                   const rl_fan_query* query, int32_t device, rl_fan* out);
+
 /* B lap evaluations of given paths: heading/curvature
  * (heading_curv_from_points_generic, ref:595-620) and velocity_profile_forward_backward
  * (ref:782-862) with h = L[b]/N on path b — the min-time driver's final step
@@ -977,6 +1054,7 @@ int         rl_abi_minor(void);
 #define RL_FEATURE_BOUNDS 16      /* bit 4: the bounds stage */
 #define RL_FEATURE_RETIME 32      /* bit 5: the retime stage */
 #define RL_FEATURE_RECOVER 64     /* bit 6: the recover stage */
+#define RL_FEATURE_FAN 128        /* bit 7: the fan stage */
 int         rl_abi_features(void);
 /* samples per lane of the THROUGHPUT shape for N (4: N <= 256, 5: N <= 320, 8: N <= 4096;
  * 1 = the streaming kernel), or RL_ETOOBIG.  Batches small enough for a latency shape launch fewer samples per lane:

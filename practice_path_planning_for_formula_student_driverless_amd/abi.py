@@ -248,6 +248,27 @@ class RlRcv(C.Structure):
                 [(n, C.POINTER(C.c_double)) for n in RCV_SCAL[len(RTM_SCAL):] + RCV_NODES[len(RTM_NODES):]])
 
 
+RL_FEATURE_FAN = 128       # rl_abi_features() bit 7: the fan stage
+RL_FAN_MAX_CAND = 16
+FAN_TAB_INTS = ("cand_class", "cand_feasible", "cand_clamped", "cand_merge_node", "cand_overspeed", "cand_bind_node")
+FAN_TAB_SCAL = ("cand_t_end", "cand_t_loss", "cand_v_excess")
+
+
+class RlFanQuery(C.Structure):
+    """``rl_fan_query`` — the ``rl_rcv_query`` with merge_len [Q][n_cand], then n_cand."""
+
+    _fields_ = [("rc", RlRcvQuery), ("n_cand", C.c_int32), ("_pad", C.c_int32)]
+
+
+class RlFan(C.Structure):
+    """``rl_fan`` — ``rl_rcv``'s layout holding the winner's values, then best [Q] and the table
+    [Q][C]: class, feasible, clamped, merge_node, overspeed, bind_node, t_end, t_loss, v_excess of
+    every candidate; NULL fields are skipped."""
+
+    _fields_ = (RlRcv._fields_ + [("best", C.POINTER(C.c_int32))] +
+                [(n, C.POINTER(C.c_int32)) for n in FAN_TAB_INTS] + [(n, C.POINTER(C.c_double)) for n in FAN_TAB_SCAL])
+
+
 RL_FEATURE_BOUNDS = 16     # rl_abi_features() bit 4: the bounds stage
 BND_ROWS = ("lo", "hi", "nx", "ny")
 HZN_BND = ("lo", "hi", "lo0", "hi0")
@@ -670,6 +691,13 @@ DECLS_RCV = [
     ("rl_plan_fetch_recover", C.c_int, [C.c_void_p, _RCV]),
     ("rl_recover", C.c_int, [_F64] * 11 + [C.c_int32, C.c_int32, C.c_int32, _RCVQ, C.c_int32, _RCV]),
 ]
+# the fan stage: bound only in a library whose rl_abi_features() has RL_FEATURE_FAN
+_FAN, _FANQ = _P(RlFan), _P(RlFanQuery)
+DECLS_FAN = [
+    ("rl_plan_recover_fan", C.c_int, [C.c_void_p, _FANQ, C.c_void_p]),
+    ("rl_plan_fetch_recover_fan", C.c_int, [C.c_void_p, _FAN]),
+    ("rl_recover_fan", C.c_int, [_F64] * 11 + [C.c_int32, C.c_int32, C.c_int32, _FANQ, C.c_int32, _FAN]),
+]
 
 
 def declare_optimize(fn) -> None:
@@ -684,8 +712,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     """Load librl.so (the HIP path).  Raises if it is missing: there is no fallback; a library
     that lacks a function of DECLS or DECLS_EXT raises AttributeError naming it, and so does
     one that announces RL_FEATURE_HORIZON / RL_FEATURE_REJOIN / RL_FEATURE_STOP /
-    RL_FEATURE_BOUNDS / RL_FEATURE_RETIME / RL_FEATURE_RECOVER and lacks a function of DECLS_HZN /
-    DECLS_RJN / DECLS_STP / DECLS_BND / DECLS_RTM / DECLS_RCV."""
+    RL_FEATURE_BOUNDS / RL_FEATURE_RETIME / RL_FEATURE_RECOVER / RL_FEATURE_FAN and lacks a function
+    of DECLS_HZN / DECLS_RJN / DECLS_STP / DECLS_BND / DECLS_RTM / DECLS_RCV / DECLS_FAN."""
     global _LIB
     if _LIB is not None and path == LIB_PATH:
         return _LIB
@@ -715,6 +743,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         bind(DECLS_RTM)
     if ext and lib.rl_abi_features() & RL_FEATURE_RECOVER:
         bind(DECLS_RCV)
+    if ext and lib.rl_abi_features() & RL_FEATURE_FAN:
+        bind(DECLS_FAN)
     if path == LIB_PATH:
         _LIB = lib
     return lib

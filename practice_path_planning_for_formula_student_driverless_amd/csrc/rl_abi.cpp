@@ -38,19 +38,25 @@ int rows_on_device(DevArena& mem, const std::string& fn, const double* const (&i
 // rl_horizon / rl_rejoin / rl_stop / rl_retime / rl_recover (arguments checked, the device selected;
 // K_cap = 0: the horizon; a stop_sample: the stop stage; Out = rl_rtm: the retime stage of a rejoin
 // query; Out = rl_rcv: the recover stage, rcv its query, q that query's rejoin part and bnd the
-// rows' bounds lo, hi, nx, ny [B][N] on the host): the
+// rows' bounds lo, hi, nx, ny [B][N] on the host; Out = rl_fan: the fan stage, rcv its query's
+// recover part with n_cand merge lengths per query): the
 // trajectory kernel for the stamps of the host rows (one tick per row, not downloaded), then the
 // stage's kernel on them; `row` counts the B given rows
 template <class Out>
 int query_rows(const std::string& fn, const double* const (&in)[6], const double* h, int32_t N, int32_t B, int32_t closed,
-               const rl_stp_query& q, const Out& out, const rl_rcv_query* rcv = nullptr, const double* const* bnd = nullptr) {
-    constexpr bool recover = std::is_same<Out, rl_rcv>::value;
+               const rl_stp_query& q, const Out& out, const rl_rcv_query* rcv = nullptr, const double* const* bnd = nullptr,
+               int n_cand = 0) {
+    constexpr bool fan = std::is_same<Out, rl_fan>::value;
+    constexpr bool recover = std::is_same<Out, rl_rcv>::value || fan;
     constexpr bool retime = std::is_same<Out, rl_rtm>::value;
     DevArena mem;
     rl::TrajParams t;
     if (int rc = rows_on_device(mem, fn, in, h, N, B, closed, q.rj.dt, 1, &t)) return rc;
-    const QueryLayout L = recover ? recover_layout(*rcv) : query_layout(q, retime);
+    const QueryLayout L = fan       ? fan_layout((size_t)q.rj.Q, (size_t)q.rj.M_cap, (size_t)q.rj.K_cap, (size_t)n_cand)
+                          : recover ? recover_layout(*rcv)
+                                    : query_layout(q, retime);
     double* d_bnd[4] = {};
+    char* d_scratch = fan ? mem.get<char>(L.scratch_bytes) : nullptr;
     if (recover)
         for (auto& d : d_bnd) d = mem.get<double>((size_t)B * (size_t)N);
     char* d_qry = mem.get<char>(L.in_bytes);
@@ -65,7 +71,7 @@ int query_rows(const std::string& fn, const double* const (&in)[6], const double
             return fail(RL_EHIP, fn + ": upload");
     if (rl::launch_trajectory(t, nullptr) != hipSuccess) return fail(RL_EHIP, fn + ": trajectory kernel");
     const StpParams sp = query_params(t, q, L, d_qry, d_res);
-    const hipError_t e = recover  ? recover_launch(sp, *rcv, L, d_qry, d_res, {d_bnd[0], d_bnd[1], d_bnd[2], d_bnd[3]}, nullptr)
+    const hipError_t e = recover  ? recover_launch(sp, *rcv, L, d_qry, d_res, {d_bnd[0], d_bnd[1], d_bnd[2], d_bnd[3]}, nullptr, d_scratch)
                          : retime ? retime_launch(sp, *q.rj.cfg, L, d_res, nullptr)
                                   : query_launch(sp, nullptr);
     if (e != hipSuccess || hipDeviceSynchronize() != hipSuccess)
@@ -85,7 +91,7 @@ int rl_abi_version(void) { return RL_ABI_VERSION; }
 int rl_abi_minor(void) { return RL_ABI_MINOR; }
 int rl_abi_features(void) {
     return RL_FEATURE_TRAJECTORY | RL_FEATURE_HORIZON | RL_FEATURE_REJOIN | RL_FEATURE_STOP | RL_FEATURE_BOUNDS |
-           RL_FEATURE_RETIME | RL_FEATURE_RECOVER;
+           RL_FEATURE_RETIME | RL_FEATURE_RECOVER | RL_FEATURE_FAN;
 }
 
 int rl_device_count(void) {
@@ -479,6 +485,20 @@ int rl_recover(const double* x, const double* y, const double* heading, const do
     if (int rc = select_device(device)) return rc;
     const double* const bnd[4] = {lo, hi, nx, ny};
     return query_rows("rl_recover", {x, y, heading, kappa, v, ax}, h, N, B, closed, as_stp(query->rj), *out, query, bnd);
+}
+
+int rl_recover_fan(const double* x, const double* y, const double* heading, const double* kappa, const double* v,
+                   const double* ax, const double* h, const double* lo, const double* hi, const double* nx, const double* ny,
+                   int32_t N, int32_t B, int32_t closed, const rl_fan_query* query, int32_t device, rl_fan* out) {
+    if (!x || !y || !heading || !kappa || !v || !ax || !h || !lo || !hi || !nx || !ny || !query || !out)
+        return fail(RL_EINVAL, "rl_recover_fan: an input row, h, a bounds row, the query or out is NULL");
+    if (B < 1 || N < 0) return fail(RL_EINVAL, "rl_recover_fan: B < 1 or N < 0");
+    if (N > rl::RL_STREAM_MAX_N) return fail(RL_ETOOBIG, "rl_recover_fan: N exceeds 1048576");
+    if (int rc = check_fan(query, B, N, closed ? 1 : 0)) return rc;
+    if (int rc = select_device(device)) return rc;
+    const double* const bnd[4] = {lo, hi, nx, ny};
+    return query_rows("rl_recover_fan", {x, y, heading, kappa, v, ax}, h, N, B, closed, as_stp(query->rc.rj), *out, &query->rc, bnd,
+                      query->n_cand);
 }
 
 // rank host scores with rl_rank_kernel (rl_select.hip)

@@ -382,12 +382,15 @@ inline int queue_downloads(const std::vector<CopyJob>& jobs, hipStream_t st) {
 // host block (pin) of the larger capacity; all three grow with Q, M_cap and K_cap.  ev[0] is
 // recorded after the upload, which reads pin, ev[1] after the kernel.  Q = 0: no stage since
 // the last run or trajectory stage; M, K (0 for the horizon) are that stage's M_cap and K_cap,
-// stop / retime / recover whether its blocks have the stop / retime / recover stage's arrays.
+// stop / retime / recover whether its blocks have the stop / retime / recover stage's arrays, C
+// the candidates per query of a fan stage (0 for every other).  The fan stage has a scratch block
+// on the device as well, which never comes down.
 struct QueryStage {
-    char *in = nullptr, *out = nullptr, *pin = nullptr;
-    size_t in_cap = 0, out_cap = 0;
+    char *in = nullptr, *out = nullptr, *pin = nullptr, *scratch = nullptr;
+    size_t in_cap = 0, out_cap = 0, scratch_cap = 0;
     DevArena mem;                     // in, out: they count toward the plan's dev_bytes()
-    int Q = 0, M = 0, K = 0;
+    DevArena scratch_mem;             // scratch: it counts as well
+    int Q = 0, M = 0, K = 0, C = 0;
     bool stop = false, retime = false, recover = false;
     double dt = 0;                    // that stage's tick step (the bounds stage's tick kernel reads it)
     hipEvent_t ev[2] = {nullptr, nullptr};
@@ -400,6 +403,9 @@ struct QueryStage {
     }
     void release() {
         release_blocks();
+        scratch_mem.release();
+        scratch = nullptr;
+        scratch_cap = 0;
         for (auto& e : ev) {
             if (e) hipEventDestroy(e);
             e = nullptr;
@@ -426,6 +432,22 @@ struct QueryStage {
         out_cap = oc;
         return RL_OK;
     }
+    // a scratch block of at least `bytes`; it only grows
+    int reserve_scratch(hipStream_t last_stream, size_t bytes, const char* what) {
+        if (scratch && bytes <= scratch_cap) return RL_OK;
+        if (last_stream) HIPCHK(hipStreamSynchronize(last_stream));
+        scratch_mem.release();
+        scratch_cap = 0;
+        scratch = scratch_mem.get<char>(bytes);
+        if (!scratch_mem.ok()) {
+            scratch_mem.release();
+            scratch = nullptr;
+            return fail(RL_ENOMEM, std::string("allocation of the ") + what + " scratch block failed");
+        }
+        scratch_cap = bytes;
+        return RL_OK;
+    }
+    size_t dev_bytes() const { return mem.bytes + scratch_mem.bytes; }
 };
 
 }  // namespace rl
@@ -511,7 +533,7 @@ struct rl_plan {
     rl::TrajParams traj_q{};
     int traj_mode = 0;
     uint32_t sel_epoch = 0, lap_epoch = 0, traj_sel_epoch = 0, traj_lap_epoch = 0;
-    rl::QueryStage hzn, rjn, stp, rtm, rcv;     // (rcv reads the bounds stage as well: drop_bounds_readers)
+    rl::QueryStage hzn, rjn, stp, rtm, rcv, fan;   // (rcv and fan read the bounds stage as well: drop_bounds_readers)
     // bounds stage (rl_plan_bounds, rl::BndParams): lo, hi, nx, ny [bnd_R][N] of the last
     // trajectory stage's rows, row for row, in buffers sized for bnd_cap_R rows; bnd_R = 0: no
     // stage since the last run or trajectory stage.  Its tick kernel (rl_plan_horizon_bounds)
@@ -529,9 +551,9 @@ struct rl_plan {
     hipEvent_t ev_hb[2] = {nullptr, nullptr};
     // a run or a trajectory stage invalidates the pose-query stages that read the one before,
     // and the bounds of its rows
-    void drop_queries() { hzn.Q = rjn.Q = stp.Q = rtm.Q = rcv.Q = bnd_R = hb_Q = 0; }
-    // a bounds stage invalidates what read the one before: the tick bounds and the recover stage
-    void drop_bounds_readers() { bnd_R = hb_Q = rcv.Q = 0; }
+    void drop_queries() { hzn.Q = rjn.Q = stp.Q = rtm.Q = rcv.Q = fan.Q = bnd_R = hb_Q = 0; }
+    // a bounds stage invalidates what read the one before: the tick bounds, the recover and the fan stage
+    void drop_bounds_readers() { bnd_R = hb_Q = rcv.Q = fan.Q = 0; }
 
     template <class T>
     int alloc(T** p, size_t n) {
@@ -542,7 +564,7 @@ struct rl_plan {
     // device memory held (plan cache budget)
     size_t dev_bytes() const {
         return mem.bytes + sel_mem.bytes + lap_mem.bytes + traj_mem.bytes + hzn.mem.bytes + rjn.mem.bytes + stp.mem.bytes +
-               rtm.mem.bytes + rcv.mem.bytes + bnd_mem.bytes + hb_mem.bytes;
+               rtm.mem.bytes + rcv.mem.bytes + fan.dev_bytes() + bnd_mem.bytes + hb_mem.bytes;
     }
     // the stream of the last run or stage
     hipStream_t run_stream() const { return last_stream ? last_stream : own_stream; }
@@ -601,7 +623,11 @@ hipError_t retime_launch(const StpParams& s, const rl_cfg& cfg, const QueryLayou
 int check_rcv(const rl_rcv_query* q, int32_t R, int32_t N, int32_t closed);
 // the recover stage's kernel on its query's rejoin parameters s (query_params'), the blocks in
 // and out (device) laid out as L (recover_layout's) and the bounds rows bnd (lo, hi, nx, ny, device)
+// L a fan_layout (L.C > 0) and a scratch block of L.scratch_bytes (device): the fan stage's kernels
 hipError_t recover_launch(const StpParams& s, const rl_rcv_query& q, const QueryLayout& L, const char* in, char* out,
-                          const double* const (&bnd)[4], hipStream_t st);
+                          const double* const (&bnd)[4], hipStream_t st, char* scratch = nullptr);
+// argument checks of the fan entry points (no device call): check_rcv's with merge_len [Q][n_cand],
+// n_cand and Q*n_cand
+int check_fan(const rl_fan_query* q, int32_t R, int32_t N, int32_t closed);
 
 }  // namespace rl

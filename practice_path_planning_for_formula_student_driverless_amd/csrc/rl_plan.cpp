@@ -198,6 +198,7 @@ int rl_plan_destroy(rl_plan* plan) {
     plan->stp.release();
     plan->rtm.release();
     plan->rcv.release();
+    plan->fan.release();
     plan->bnd_mem.release();
     plan->hb_mem.release();
     for (auto& e : plan->ev_bnd)
@@ -439,8 +440,8 @@ int rl_plan_kernel_ms(rl_plan* p, int32_t idx, float* ms) {
     hipEvent_t a, b;
     const bool mc = p->modes & RL_MODE_MINCURV, mt = p->modes & RL_MODE_MINTIME;
     // 8: the horizon stage; 9: the rejoin stage; 10: the stop stage; 13: the retime stage; 14: the
-    // recover stage (which a bounds stage invalidates as well)
-    const rl::QueryStage& stage = idx == 14 ? p->rcv : idx == 13 ? p->rtm : idx == 10 ? p->stp : idx == 9 ? p->rjn : p->hzn;
+    // recover stage, 15: the fan stage (which a bounds stage invalidates as well)
+    const rl::QueryStage& stage = idx == 15 ? p->fan : idx == 14 ? p->rcv : idx == 13 ? p->rtm : idx == 10 ? p->stp : idx == 9 ? p->rjn : p->hzn;
     if (idx == 0) { a = p->ev[0]; b = p->ev[3]; }
     else if (idx == 3 && p->sel_mode) {
         a = p->ev_sel[0];
@@ -458,7 +459,7 @@ int rl_plan_kernel_ms(rl_plan* p, int32_t idx, float* ms) {
         b = p->ev_traj[1];
         HIPCHK(hipEventSynchronize(b));
     }
-    else if (((idx >= 8 && idx <= 10) || idx == 13 || (idx == 14 && p->bnd_R)) && stage.Q && p->traj_R) {
+    else if (((idx >= 8 && idx <= 10) || idx == 13 || ((idx == 14 || idx == 15) && p->bnd_R)) && stage.Q && p->traj_R) {
         a = stage.ev[0];
         b = stage.ev[1];
         HIPCHK(hipEventSynchronize(b));

@@ -11,7 +11,10 @@
 // (tests/test_query_layout_cpu.py, tests/test_stop_layout_cpu.py, tests/test_retime_cpu.py).
 // The recover stage (§3q) is the retime stage with a merge length and a direction per query and
 // more results: recover_layout is the retime layout with its extra arrays, again each kind behind
-// the others of that kind (tests/test_recover_cpu.py).  Not part of the public ABI.
+// the others of that kind (tests/test_recover_cpu.py).  The fan stage (§3r) is the recover stage
+// with C merge lengths per query and a table of the candidates: fan_layout is the recover layout
+// with merge_len [Q][C] and the table behind the others of its kind, and a scratch block for the
+// candidates beside the two (tests/test_recover_fan_cpu.py).  Not part of the public ABI.
 #pragma once
 #include <cstddef>
 #include <cstring>
@@ -21,6 +24,7 @@
 #include "rl_stop.h"
 #include "rl_retime.h"
 #include "rl_recover.h"
+#include "rl_recover_fan.h"
 
 namespace rl {
 
@@ -42,7 +46,11 @@ constexpr int QRY_NODES = 2;                  // node_v, node_t
 // set as well) have as well: merge_len [Q] and dir [Q][2] behind hint; the column offset [Q][M]
 // behind the seven; lo0, hi0 [Q] behind the doubles and clamped, offtrack, merge_node [Q] and one
 // pad word per query (the node arrays stay 8-byte aligned) behind the ints (all in the head);
-// node_o, node_k [Q][K + 1] behind the node arrays.
+// node_o, node_k [Q][K + 1] behind the node arrays.  A fan stage's blocks (fan_layout; C > 0, and
+// `retime` and `recover` set) have merge_len [Q][C]; the table's doubles [Q][C] behind the doubles;
+// best [Q], the table's ints [Q][C] and one more pad word per query behind the recover stage's pad
+// (all in the head).  Its scratch block (scratch_bytes, on the device only) is the results' block
+// of a recover stage of Q*C queries without ticks, then P.x, P.y, d', psi [Q*C][K + 1].
 struct QueryLayout {
     size_t Q, M, K;
     size_t pose, v0, row, hint, in_bytes;
@@ -54,11 +62,15 @@ struct QueryLayout {
     size_t rper[RTM_SCAL], rints[RTM_INTS], rnodes[RTM_NODES];
     bool recover;
     size_t merge_len, dir, offset, cper[RCV_SCAL], cints[RCV_INTS], cnodes[RCV_NODES];
+    size_t C;                                  // candidates per query; 0: no fan stage's
+    size_t best, tper[FAN_TAB_SCAL], tints[FAN_TAB_INTS], scratch_bytes;
 };
 
-// every stage's layout; `recover` adds the recover stage's arrays to a retime layout
-inline QueryLayout query_layout_of(size_t Q, size_t M, size_t K, bool stop, bool retime, bool recover) {
+// every stage's layout; `recover` adds the recover stage's arrays to a retime layout, C > 0 the
+// fan stage's to a recover layout
+inline QueryLayout query_layout_of(size_t Q, size_t M, size_t K, bool stop, bool retime, bool recover, size_t C = 0) {
     QueryLayout L{};
+    L.C = C;
     const bool rjn = K > 0;
     L.Q = Q; L.M = M; L.K = K;
     L.stop = stop;
@@ -75,7 +87,7 @@ inline QueryLayout query_layout_of(size_t Q, size_t M, size_t K, bool stop, bool
     L.hint = take(Q * 4);
     L.v_target = take(stop ? Q * 8 : 0);
     L.stop_sample = take(stop ? Q * 4 : 0);
-    L.merge_len = take(recover ? Q * 8 : 0);
+    L.merge_len = take(recover ? Q * (C ? C : 1) * 8 : 0);
     L.dir = take(recover ? Q * 16 : 0);
     L.in_bytes = at;
     at = 0;
@@ -85,18 +97,24 @@ inline QueryLayout query_layout_of(size_t Q, size_t M, size_t K, bool stop, bool
     for (auto& o : L.sper) o = take(stop ? Q * 8 : 0);
     for (auto& o : L.rper) o = take(retime ? Q * 8 : 0);
     for (auto& o : L.cper) o = take(recover ? Q * 8 : 0);
+    for (auto& o : L.tper) o = take(Q * C * 8);
     for (int c = 0; c < L.n_ints; ++c) L.ints[c] = take(Q * 4);
     for (auto& o : L.sints) o = take(stop ? Q * 4 : 0);
     for (auto& o : L.rints) o = take(retime ? Q * 4 : 0);
     for (auto& o : L.cints) o = take(recover ? Q * 4 : 0);
     static_assert(RCV_INTS % 2 == 1, "the pad below keeps the node arrays 8-byte aligned");
     take(recover ? Q * 4 : 0);
+    L.best = take(C ? Q * 4 : 0);
+    for (auto& o : L.tints) o = take(Q * C * 4);
+    static_assert(FAN_TAB_INTS % 2 == 0, "best and the pad below keep the node arrays 8-byte aligned");
+    take(C ? Q * 4 : 0);
     L.head_bytes = at;
     for (int c = 0; c < L.n_nodes; ++c) L.nodes[c] = take(Q * (K + 1) * 8);
     L.node_b = take(stop ? Q * (K + 1) * 8 : 0);
     for (auto& o : L.rnodes) o = take(retime ? Q * (K + 1) * 8 : 0);
     for (auto& o : L.cnodes) o = take(recover ? Q * (K + 1) * 8 : 0);
     L.out_bytes = at;
+    if (C) L.scratch_bytes = query_layout_of(Q * C, 0, K, false, true, true).out_bytes + FAN_XNODES * (Q * C) * (K + 1) * 8;
     return L;
 }
 inline QueryLayout query_layout(size_t Q, size_t M, size_t K, bool stop = false, bool retime = false) {
@@ -264,8 +282,9 @@ inline bool query_wants_nodes(const rl_rtm& o) { return o.node_v || o.node_t || 
 inline QueryLayout recover_layout(const rl_rcv_query& q) {
     return recover_layout((size_t)q.rj.Q, (size_t)q.rj.M_cap, (size_t)q.rj.K_cap);
 }
+// (a fan stage's merge_len is [Q][C])
 inline void recover_pack(const rl_rcv_query& q, const QueryLayout& L, char* block) {
-    std::memcpy(block + L.merge_len, q.merge_len, L.Q * 8);
+    std::memcpy(block + L.merge_len, q.merge_len, L.Q * (L.C ? L.C : 1) * 8);
     if (q.dir_xy) std::memcpy(block + L.dir, q.dir_xy, L.Q * 16);
 }
 inline RcvParams recover_pointers(const RtmParams& t, const rl_rcv_query& q, const QueryLayout& L, const char* in, char* out,
@@ -304,5 +323,62 @@ inline void query_unpack(const char* block, const QueryLayout& L, const rl_rcv& 
         if (cnodes[c]) std::memcpy(cnodes[c], block + L.cnodes[c], L.Q * (L.K + 1) * 8);
 }
 inline bool query_wants_nodes(const rl_rcv& o) { return query_wants_nodes(as_rtm(o)) || o.node_o || o.node_k; }
+
+// the fan stage: its layout, its launch on the recover pointers w of its query in the blocks in
+// and out (recover_pointers') and the scratch block (device), and its results
+inline QueryLayout fan_layout(size_t Q, size_t M, size_t K, size_t C) { return query_layout_of(Q, M, K, false, true, true, C); }
+inline QueryLayout fan_layout(const rl_fan_query& q) {
+    return fan_layout((size_t)q.rc.rj.Q, (size_t)q.rc.rj.M_cap, (size_t)q.rc.rj.K_cap, (size_t)q.n_cand);
+}
+inline FanParams fan_pointers(const RcvParams& w, const rl_cfg& cfg, const QueryLayout& L, char* out, char* scratch) {
+    FanParams f{};
+    f.win = w;
+    f.C = (int32_t)L.C;
+    f.best = (int32_t*)(out + L.best);
+    for (int c = 0; c < FAN_TAB_INTS; ++c) f.tab_i[c] = (int32_t*)(out + L.tints[c]);
+    for (int c = 0; c < FAN_TAB_SCAL; ++c) f.tab_d[c] = (double*)(out + L.tper[c]);
+    // the candidates: the same query, the results of Q*C queries in the scratch block
+    const QueryLayout S = recover_layout(L.Q * L.C, 0, L.K);
+    rl_rjn_query sq{};
+    sq.dt = w.rt.rj.hz.dt;
+    sq.Q = (int32_t)(L.Q * L.C); sq.window = w.rt.rj.hz.window; sq.M_cap = w.rt.rj.hz.M_cap; sq.K_cap = w.rt.rj.K_cap;
+    RjnParams r = query_pointers(sq, S, scratch, scratch);   // (the query pointers are replaced below)
+    r.hz.src = w.rt.rj.hz.src;
+    r.hz.pose = w.rt.rj.hz.pose; r.hz.row = w.rt.rj.hz.row; r.hz.hint = w.rt.rj.hz.hint;
+    r.cfg = w.rt.rj.cfg;
+    r.v0 = w.rt.rj.v0;
+    RcvParams c{};
+    c.rt = retime_pointers(r, cfg, S, scratch);
+    c.merge_len = w.merge_len; c.dir = w.dir;
+    c.lo = w.lo; c.hi = w.hi; c.nx = w.nx; c.ny = w.ny;
+    c.offset = nullptr;                        // no ticks (S.M == 0: the columns have no bytes either)
+    for (int k = 0; k < RCV_SCAL; ++k) c.scal[k] = (double*)(scratch + S.cper[k]);
+    c.clamped = (int32_t*)(scratch + S.cints[0]);
+    c.offtrack = (int32_t*)(scratch + S.cints[1]);
+    c.merge_node = (int32_t*)(scratch + S.cints[2]);
+    c.node_o = (double*)(scratch + S.cnodes[0]);
+    c.node_k = (double*)(scratch + S.cnodes[1]);
+    f.cand = c;
+    for (int k = 0; k < FAN_XNODES; ++k) f.xnode[k] = (double*)(scratch + S.out_bytes + (size_t)k * (L.Q * L.C) * (L.K + 1) * 8);
+    return f;
+}
+// the recover part of a fan stage's results (rl_fan begins with rl_rcv's fields)
+inline rl_rcv as_rcv(const rl_fan& o) {
+    return {o.s, o.x, o.y, o.heading, o.kappa, o.v, o.ax, o.u, o.t0, o.s0, o.e, o.dist2, o.seg, o.count,
+            o.end_node, o.overspeed, o.t_end, o.t_loss, o.node_v, o.node_t, o.feasible, o.bind_node, o.v_excess,
+            o.node_b, o.node_c, o.offset, o.clamped, o.offtrack, o.merge_node, o.lo0, o.hi0, o.node_o, o.node_k};
+}
+inline void query_unpack(const char* block, const QueryLayout& L, const rl_fan& o) {
+    query_unpack(block, L, as_rcv(o));
+    int32_t* const tints[FAN_TAB_INTS] = {o.cand_class, o.cand_feasible, o.cand_clamped, o.cand_merge_node, o.cand_overspeed,
+                                          o.cand_bind_node};
+    double* const tper[FAN_TAB_SCAL] = {o.cand_t_end, o.cand_t_loss, o.cand_v_excess};
+    if (o.best) std::memcpy(o.best, block + L.best, L.Q * 4);
+    for (int c = 0; c < FAN_TAB_INTS; ++c)
+        if (tints[c]) std::memcpy(tints[c], block + L.tints[c], L.Q * L.C * 4);
+    for (int c = 0; c < FAN_TAB_SCAL; ++c)
+        if (tper[c]) std::memcpy(tper[c], block + L.tper[c], L.Q * L.C * 8);
+}
+inline bool query_wants_nodes(const rl_fan& o) { return query_wants_nodes(as_rcv(o)); }
 
 }  // namespace rl

@@ -8,7 +8,8 @@
 // to a target sample.  Retime stage (rl_retime.hip): the reference's speed pass
 // over the nodes ahead, under the car's cfg.  Recover stage (rl_recover.hip): a path
 // from the car's offset back to the row inside the bounds stage's free width, and that speed pass
-// on it.  These five pose-query stages share one enqueue and one fetch routine.
+// on it.  Fan stage (rl_recover_fan.hip): the recover stage for C merge lengths per
+// pose, and the best one served.  These six pose-query stages share one enqueue and one fetch routine.
 // Bounds stage (rl_bounds.hip): the free track width about the trajectory stage's
 // rows, and at the horizon stage's ticks.
 #include "rl_host.h"
@@ -129,23 +130,40 @@ hipError_t rl::retime_launch(const StpParams& s, const rl_cfg& cfg, const QueryL
     return rl::launch_retime(retime_pointers(s.rj, cfg, L, out), st);
 }
 
-int rl::check_rcv(const rl_rcv_query* q, int32_t R, int32_t N, int32_t closed) {
+namespace {
+
+// check_rcv, or with `fan` check_fan: C merge lengths per query
+int check_rcv_of(const rl_rcv_query* q, int32_t R, int32_t N, int32_t closed, bool fan, int32_t C) {
     if (!q) return fail(RL_EINVAL, "recover: the query is NULL");
     if (int rc = check_rjn(&q->rj, R, N, closed)) return rc;
     if (q->rj.K_cap > RL_RCV_MAX_NODES) return fail(RL_EINVAL, "recover: K_cap must be 1..512");
     if (!q->merge_len) return fail(RL_EINVAL, "recover: merge_len is NULL");
+    if (fan && (C < 1 || C > RL_FAN_MAX_CAND)) return fail(RL_EINVAL, "recover fan: n_cand must be 1..16");
+    if (fan && (int64_t)q->rj.Q * C > RL_HZN_MAX_QUERIES) return fail(RL_EINVAL, "recover fan: Q*n_cand must be <= 65536");
+    const size_t per = fan ? (size_t)C : 1;
     for (int32_t k = 0; k < q->rj.Q; ++k) {
-        if (!std::isfinite(q->merge_len[k]) || !(q->merge_len[k] > 0.0))
-            return fail(RL_EINVAL, "recover: a merge_len that is not finite or is <= 0");
+        for (size_t c = 0; c < per; ++c)
+            if (!std::isfinite(q->merge_len[k * per + c]) || !(q->merge_len[k * per + c] > 0.0))
+                return fail(RL_EINVAL, "recover: a merge_len that is not finite or is <= 0");
         if (q->dir_xy && (!std::isfinite(q->dir_xy[2 * (size_t)k]) || !std::isfinite(q->dir_xy[2 * (size_t)k + 1])))
             return fail(RL_EINVAL, "recover: a dir_xy that is not finite");
     }
     return RL_OK;
 }
 
+}  // namespace
+
+int rl::check_rcv(const rl_rcv_query* q, int32_t R, int32_t N, int32_t closed) { return check_rcv_of(q, R, N, closed, false, 1); }
+
+int rl::check_fan(const rl_fan_query* q, int32_t R, int32_t N, int32_t closed) {
+    if (!q) return fail(RL_EINVAL, "recover fan: the query is NULL");
+    return check_rcv_of(&q->rc, R, N, closed, true, q->n_cand);
+}
+
 hipError_t rl::recover_launch(const StpParams& s, const rl_rcv_query& q, const QueryLayout& L, const char* in, char* out,
-                              const double* const (&bnd)[4], hipStream_t st) {
-    return rl::launch_recover(recover_pointers(retime_pointers(s.rj, *q.rj.cfg, L, out), q, L, in, out, bnd), st);
+                              const double* const (&bnd)[4], hipStream_t st, char* scratch) {
+    const RcvParams c = recover_pointers(retime_pointers(s.rj, *q.rj.cfg, L, out), q, L, in, out, bnd);
+    return L.C ? rl::launch_recover_fan(fan_pointers(c, *q.rj.cfg, L, out, scratch), st) : rl::launch_recover(c, st);
 }
 
 namespace {
@@ -283,13 +301,14 @@ int select_impl(rl_plan* p, const rl_select* sel, int gs, bool by_lap, void* hip
 
 // rl_plan_horizon / rl_plan_rejoin / rl_plan_stop / rl_plan_retime / rl_plan_recover (arguments
 // checked; K_cap = 0: the horizon; a stop_sample: the stop stage; retime: the retime stage of a
-// rejoin query; rcv: the recover stage's query, q its rejoin part, after a valid bounds stage):
+// rejoin query; rcv: the recover stage's query, q its rejoin part, after a valid bounds stage;
+// n_cand > 0: the fan stage, rcv its query's recover part):
 // one launch of the stage's kernel on the last trajectory stage.
 // The queries go up in one block, through s's pinned block, ahead of the kernel on the same
 // stream.
 int query_enqueue(rl_plan* p, QueryStage& s, const rl_stp_query& q, void* hip_stream, bool retime = false,
-                  const rl_rcv_query* rcv = nullptr) {
-    const char* what = rcv ? "recover" : retime ? "retime" : q.stop_sample ? "stop" : q.rj.K_cap > 0 ? "rejoin" : "horizon";
+                  const rl_rcv_query* rcv = nullptr, int n_cand = 0) {
+    const char* what = n_cand ? "recover_fan" : rcv ? "recover" : retime ? "retime" : q.stop_sample ? "stop" : q.rj.K_cap > 0 ? "rejoin" : "horizon";
     const std::string fn = std::string("rl_plan_") + what;
     if (p->traj_q.index && p->traj_sel_epoch != p->sel_epoch)
         return fail(RL_EINVAL, fn + ": a selection has replaced the winners the trajectory stage read");
@@ -304,8 +323,12 @@ int query_enqueue(rl_plan* p, QueryStage& s, const rl_stp_query& q, void* hip_st
     if (s.ev[0]) HIPCHK(hipEventSynchronize(s.ev[0]));
     s.Q = 0;
     if (&s == &p->hzn) p->hb_Q = 0;                    // the tick bounds of the horizon stage before
-    const QueryLayout L = rcv ? recover_layout(*rcv) : query_layout(q, retime);
+    const QueryLayout L = n_cand ? fan_layout((size_t)q.rj.Q, (size_t)q.rj.M_cap, (size_t)q.rj.K_cap, (size_t)n_cand)
+                          : rcv  ? recover_layout(*rcv)
+                                 : query_layout(q, retime);
     if (int rc = s.reserve(p->last_stream, L.in_bytes, L.out_bytes, what)) return rc;
+    if (n_cand)
+        if (int rc = s.reserve_scratch(p->last_stream, L.scratch_bytes, what)) return rc;
     for (auto& e : s.ev)
         if (!e) HIPCHK(hipEventCreate(&e));
     if (st != run_st) HIPCHK(hipStreamWaitEvent(st, p->ev_traj[1], 0));
@@ -316,7 +339,7 @@ int query_enqueue(rl_plan* p, QueryStage& s, const rl_stp_query& q, void* hip_st
     HIPCHK(hipMemcpyAsync(s.in, s.pin, L.in_bytes, hipMemcpyHostToDevice, st));
     HIPCHK(hipEventRecord(s.ev[0], st));
     const StpParams sp = query_params(p->traj_q, q, L, s.in, s.out);
-    const hipError_t e = rcv      ? recover_launch(sp, *rcv, L, s.in, s.out, {p->bnd[0], p->bnd[1], p->bnd[2], p->bnd[3]}, st)
+    const hipError_t e = rcv      ? recover_launch(sp, *rcv, L, s.in, s.out, {p->bnd[0], p->bnd[1], p->bnd[2], p->bnd[3]}, st, s.scratch)
                          : retime ? retime_launch(sp, *q.rj.cfg, L, s.out, st)
                                   : query_launch(sp, st);
     if (e != hipSuccess) return fail(RL_EHIP, std::string(what) + " launch: " + hipGetErrorString(e));
@@ -327,6 +350,7 @@ int query_enqueue(rl_plan* p, QueryStage& s, const rl_stp_query& q, void* hip_st
     s.stop = L.stop;
     s.retime = L.retime;
     s.recover = L.recover;
+    s.C = n_cand;
     s.dt = q.rj.dt;
     return RL_OK;
 }
@@ -368,15 +392,15 @@ int horizon_bounds_alloc(rl_plan* p, size_t Q, size_t M) {
 }
 
 // rl_plan_fetch_horizon / rl_plan_fetch_rejoin / rl_plan_fetch_stop / rl_plan_fetch_retime /
-// rl_plan_fetch_recover (a valid stage in s; Out: rl_stp, rl_rtm for the retime stage, rl_rcv for
-// the recover stage): the results' block comes down through the pinned block, without the node
-// arrays if o asks for none
+// rl_plan_fetch_recover / rl_plan_fetch_recover_fan (a valid stage in s; Out: rl_stp, rl_rtm for
+// the retime stage, rl_rcv for the recover stage, rl_fan for the fan stage): the results' block
+// comes down through the pinned block, without the node arrays if o asks for none
 template <class Out>
 int query_fetch(rl_plan* p, QueryStage& s, const Out& o) {
     HIPCHK(hipSetDevice(p->device));
     hipStream_t st = p->run_stream();
     HIPCHK(hipStreamWaitEvent(st, s.ev[1], 0));         // (a later stage may have moved to another stream)
-    const QueryLayout L = query_layout_of((size_t)s.Q, (size_t)s.M, (size_t)s.K, s.stop, s.retime, s.recover);
+    const QueryLayout L = query_layout_of((size_t)s.Q, (size_t)s.M, (size_t)s.K, s.stop, s.retime, s.recover, (size_t)s.C);
     HIPCHK(hipMemcpyAsync(s.pin, s.out, query_wants_nodes(o) ? L.out_bytes : L.head_bytes, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     query_unpack(s.pin, L, o);
@@ -645,6 +669,25 @@ int rl_plan_fetch_recover(rl_plan* p, rl_rcv* out) {
     return query_fetch(p, p->rcv, *out);
 }
 
+// blocks of its own, and the candidates' scratch block: every other stage stays as it is; it
+// reads the bounds stage's rows where they lie
+int rl_plan_recover_fan(rl_plan* p, const rl_fan_query* query, void* hip_stream) {
+    if (!p) return fail(RL_EINVAL, "plan is NULL");
+    if (!query) return fail(RL_EINVAL, "recover fan: the query is NULL");
+    if (!p->traj_R) return fail(RL_EINVAL, "rl_plan_recover_fan: no trajectory stage since the plan's last run");
+    if (int rc = check_fan(query, p->traj_R, p->N, p->closed)) return rc;
+    if (!p->bnd_R) return fail(RL_EINVAL, "rl_plan_recover_fan: no bounds stage since the plan's last trajectory stage");
+    return query_enqueue(p, p->fan, as_stp(query->rc.rj), hip_stream, true, &query->rc, query->n_cand);
+}
+
+int rl_plan_fetch_recover_fan(rl_plan* p, rl_fan* out) {
+    if (!p) return fail(RL_EINVAL, "plan is NULL");
+    if (!out) return fail(RL_EINVAL, "rl_plan_fetch_recover_fan: out is NULL");
+    if (!p->fan.Q || !p->traj_R || !p->bnd_R)
+        return fail(RL_EINVAL, "rl_plan_fetch_recover_fan: no fan stage since the plan's last run, trajectory or bounds stage");
+    return query_fetch(p, p->fan, *out);
+}
+
 // One launch of rl_bounds_kernel over the rows the last trajectory stage read: its x, y and
 // index, the plan's resident rings.  Buffers of its own: every other stage stays as it is.
 int rl_plan_bounds(rl_plan* p, const rl_bnd_query* query, void* hip_stream) {
@@ -665,6 +708,7 @@ int rl_plan_bounds(rl_plan* p, const rl_bnd_query* query, void* hip_stream) {
         if (!e) HIPCHK(hipEventCreate(&e));
     HIPCHK(hipStreamWaitEvent(st, p->ev_traj[1], 0));
     if (p->rcv.ev[1]) HIPCHK(hipStreamWaitEvent(st, p->rcv.ev[1], 0));   // (a recover stage may still read the rows, on another stream)
+    if (p->fan.ev[1]) HIPCHK(hipStreamWaitEvent(st, p->fan.ev[1], 0));   // (and so may a fan stage)
     p->last_stream = st;
     HIPCHK(hipEventRecord(p->ev_bnd[0], st));
     const TrajParams& t = p->traj_q;

@@ -55,7 +55,7 @@
 //               the winners from sample S (0) at the raceline's own speed there, over the samples
 //               ahead, under this run's cfg with the given knobs replaced (rl_retime), in
 //               <base>_trajectory_<r>_retimed.csv (the same columns)
-//   --recover-from X,Y [--recover-dir HX,HY] [--recover-len D] [--recover-speed V]  with --best K --mode mintime
+//   --recover-from X,Y [--recover-dir HX,HY] [--recover-len D | --recover-fan D1,D2,...] [--recover-speed V]  with --best K --mode mintime
 //               --trajectory-dt DT --bounds: a car at (X, Y) heading (HX, HY) (along the raceline) doing V m/s (the
 //               raceline's speed at its nearest sample) on a path back to each winner within D (20) m along it, inside
 //               the free width of --bounds, under this run's cfg (rl_recover), in <base>_trajectory_<r>_recover.csv
@@ -1219,10 +1219,11 @@ static RetimeOpt g_retime;
 
 // --recover-from / --recover-dir / --recover-len / --recover-speed: the car's position, its
 // direction of travel (has_dir), the merge length and its speed (< 0: the raceline's at its
-// nearest sample)
+// nearest sample); --recover-fan: several merge lengths instead of one, the best one served
 struct RecoverOpt {
     bool given = false, has_dir = false;
     double x = 0, y = 0, hx = 0, hy = 0, len = 20.0, speed = -1.0;
+    std::vector<double> fan;
 };
 static RecoverOpt g_recover;
 
@@ -1574,13 +1575,40 @@ static void batch_and_save(const string& base, const vector<Vec2>& center, doubl
             rc.kappa = rcol[4].data(); rc.v = rcol[5].data(); rc.ax = rcol[6].data(); rc.offset = rcol[7].data();
             rc.count = rcount.data(); rc.end_node = node.data(); rc.feasible = feas.data(); rc.t_end = tend.data(); rc.e = e.data();
             rc.clamped = clamped.data(); rc.offtrack = offtrack.data(); rc.merge_node = merge.data();
-            gpu::check(rl_recover(bx.data(), by.data(), wrow[0].data(), wrow[1].data(), wrow[2].data(), wrow[3].data(), h.data(),
-                                  col[0].data(), col[1].data(), col[2].data(), col[3].data(), (int32_t)N, (int32_t)K, closed ? 1 : 0,
-                                  &q, gpu::device, &rc),
-                       "rl_recover");
+            // --recover-fan: the same query with C merge lengths per winner (rl_recover_fan); rc then holds the best one's answer
+            const size_t nC = g_recover.fan.size();
+            vector<double> flen(K * nC), ct_end(K * nC);
+            vector<int32_t> fbest(K), cclass(K * nC), cfeas(K * nC), cclamped(K * nC), cmerge(K * nC);
+            if (nC) {
+                for (size_t r = 0; r < K; ++r) std::copy(g_recover.fan.begin(), g_recover.fan.end(), flen.begin() + (std::ptrdiff_t)(r * nC));
+                rl_fan_query fq;
+                std::memset(&fq, 0, sizeof(fq));
+                fq.rc = q;
+                fq.rc.merge_len = flen.data();
+                fq.n_cand = (int32_t)nC;
+                rl_fan fo;
+                std::memset(&fo, 0, sizeof(fo));
+                std::memcpy(&fo, &rc, sizeof(rc));               // (rl_fan begins as rl_rcv does)
+                fo.best = fbest.data(); fo.cand_class = cclass.data(); fo.cand_feasible = cfeas.data();
+                fo.cand_clamped = cclamped.data(); fo.cand_merge_node = cmerge.data(); fo.cand_t_end = ct_end.data();
+                gpu::check(rl_recover_fan(bx.data(), by.data(), wrow[0].data(), wrow[1].data(), wrow[2].data(), wrow[3].data(), h.data(),
+                                          col[0].data(), col[1].data(), col[2].data(), col[3].data(), (int32_t)N, (int32_t)K,
+                                          closed ? 1 : 0, &fq, gpu::device, &fo),
+                           "rl_recover_fan");
+            } else {
+                gpu::check(rl_recover(bx.data(), by.data(), wrow[0].data(), wrow[1].data(), wrow[2].data(), wrow[3].data(), h.data(),
+                                      col[0].data(), col[1].data(), col[2].data(), col[3].data(), (int32_t)N, (int32_t)K, closed ? 1 : 0,
+                                      &q, gpu::device, &rc),
+                           "rl_recover");
+            }
             std::cerr << std::setprecision(9);
             for (size_t r = 0; r < K; ++r) {
                 if (node[r] < 0) throw std::runtime_error("recover: no node ahead of the pose");
+                for (size_t c = 0; c < nC; ++c)
+                    std::cerr << "[recover-fan] winner " << r << " candidate " << c << ": len " << flen[r * nC + c] << " m, class "
+                              << cclass[r * nC + c] << ", feasible " << cfeas[r * nC + c] << ", clamped " << cclamped[r * nC + c]
+                              << ", merge_node " << cmerge[r * nC + c] << ", t_end " << ct_end[r * nC + c] << " s\n";
+                if (nC) std::cerr << "[recover-fan] winner " << r << ": best " << fbest[r] << " (len " << flen[r * nC + (size_t)fbest[r]] << " m)\n";
                 const int64_t rows = rcount[r];
                 vector<double> tab((size_t)rows * 9);
                 for (int64_t m = 0; m < rows; ++m) {
@@ -1802,6 +1830,15 @@ int run_from_centerline(const string& outPath, double L, double s0, const string
             std::cerr << "[ERR] --recover-from / --recover-dir need finite numbers, --recover-len D > 0\n";
             return 2;
         }
+        bool fan_ok = g.fan.size() <= (size_t)RL_FAN_MAX_CAND;
+        for (double d : g.fan) fan_ok = fan_ok && std::isfinite(d) && d > 0.0;
+        if (!fan_ok) {
+            std::cerr << "[ERR] --recover-fan needs 1.." << RL_FAN_MAX_CAND << " finite lengths D1,D2,... > 0\n";
+            return 2;
+        }
+    } else if (!pipeline::g_recover.fan.empty()) {
+        std::cerr << "[ERR] --recover-fan D1,D2,... needs --recover-from X,Y\n";
+        return 2;
     }
     if (want_bounds && (!(traj_dt > 0.0) || best <= 0)) {
         std::cerr << "[ERR] --bounds needs --seeds B --best K --trajectory-dt DT\n";
@@ -1888,6 +1925,13 @@ int main(int argc, char** argv) {
                 else { g.has_dir = true; g.hx = u; g.hy = w; }
             }
             else if (a == "--recover-len") pipeline::g_recover.len = std::stod(next());
+            else if (a == "--recover-fan") {                                        // (replaces --recover-len)
+                std::stringstream list(next());
+                string item;
+                pipeline::g_recover.fan.clear();
+                while (std::getline(list, item, ',')) pipeline::g_recover.fan.push_back(std::stod(item));
+                if (pipeline::g_recover.fan.empty()) throw std::runtime_error("--recover-fan needs lengths D1,D2,...");
+            }
             else if (a == "--recover-speed") pipeline::g_recover.speed = std::stod(next());
             else if (a == "--bounds") want_bounds = true;
             else if (a == "--device") gpu::device = std::stoi(next());
@@ -1914,7 +1958,7 @@ int main(int argc, char** argv) {
                       << "             from K (512) samples before J, braking to V (0) m/s at sample J\n"
                       << "         [--retime-set key=value ... [--retime-from S]]   with --mode mintime --trajectory-dt: the winners\n"
                       << "             from sample S (0) over the samples ahead, under the cfg with these knobs replaced\n"
-                      << "         [--recover-from X,Y [--recover-dir HX,HY] [--recover-len D] [--recover-speed V]]   with --mode mintime\n"
+                      << "         [--recover-from X,Y [--recover-dir HX,HY] [--recover-len D | --recover-fan D1,D2,...] [--recover-speed V]]   with --mode mintime\n"
                       << "             --trajectory-dt --bounds: a path from the car at X,Y back to the winners within D (20) m\n"
                       << "         [--bounds]   with --best K --trajectory-dt: the free track width along the winners\n";
             return 1;

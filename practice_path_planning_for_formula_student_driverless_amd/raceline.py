@@ -1645,6 +1645,133 @@ def recover(x, y, heading, kappa, v, ax, h, closed: bool, lo, hi, poses, v0, cfg
     return out
 
 
+# ------------------------------------------------- fan: several merge lengths per pose, the best one served
+@dataclass
+class RecoverFan(Recover):
+    """The fan stage's answer for Q poses and C merge lengths each (rl_fan): Recover's fields hold
+    the winner's values; best [Q] is the winner's candidate (-1: an empty query); cand_class,
+    cand_feasible, cand_clamped, cand_merge_node, cand_overspeed, cand_bind_node, cand_t_end,
+    cand_t_loss, cand_v_excess [Q, C] are every candidate's per-query values."""
+
+    best: np.ndarray = None
+    cand_class: np.ndarray = None
+    cand_feasible: np.ndarray = None
+    cand_clamped: np.ndarray = None
+    cand_merge_node: np.ndarray = None
+    cand_overspeed: np.ndarray = None
+    cand_bind_node: np.ndarray = None
+    cand_t_end: np.ndarray = None
+    cand_t_loss: np.ndarray = None
+    cand_v_excess: np.ndarray = None
+
+    @classmethod
+    def alloc(cls, Q: int, m_cap: int, dt: float, k_cap: int = 1, n_cand: int = 1) -> "RecoverFan":
+        base = Recover.alloc(Q, m_cap, dt, k_cap)
+        tab = {n: np.zeros((Q, n_cand), dtype=np.int32) for n in abi.FAN_TAB_INTS}
+        tab.update({n: np.zeros((Q, n_cand)) for n in abi.FAN_TAB_SCAL})
+        return cls(**{f: getattr(base, f) for f in base.__dataclass_fields__}, best=np.zeros(Q, dtype=np.int32), **tab)
+
+    def as_c(self) -> abi.RlFan:
+        t, r = abi.RlFan(), super().as_c()
+        for n, _ in abi.RlRcv._fields_:
+            setattr(t, n, getattr(r, n))
+        for n in ("best",) + abi.FAN_TAB_INTS:
+            setattr(t, n, _ptr(getattr(self, n), np.int32, n))
+        for n in abi.FAN_TAB_SCAL:
+            setattr(t, n, _ptr(getattr(self, n), np.float64, n))
+        return t
+
+
+def fan_order(feasible, clamped, merge_node, t_end) -> tuple:
+    """The fan stage's order alone.  For tables [Q, C] (or [C]) of the candidates' feasible,
+    clamped, merge_node and t_end: cls, the classes (0: feasible, not clamped and merged; 1:
+    feasible and merged; 2: feasible; 3: otherwise), and best [Q] (or a number), the first
+    candidate ascending in (cls, isnan(t_end), t_end, c), with plain < on doubles."""
+    fe, cl, mn = (np.asarray(a) for a in (feasible, clamped, merge_node))
+    te = np.asarray(t_end, dtype=np.float64)
+    one = te.ndim == 1
+    fe, cl, mn, te = (np.atleast_2d(a) for a in (fe, cl, mn, te))
+    if not (fe.shape == cl.shape == mn.shape == te.shape) or te.shape[1] < 1:
+        raise ValueError(f"fan_order: the four tables must have one shape [Q, C >= 1], got {fe.shape}, {cl.shape}, {mn.shape}, {te.shape}")
+    cls = np.where(fe == 0, 3, np.where(mn < 0, 2, np.where(cl != 0, 1, 0))).astype(np.int32)
+    best = np.zeros(te.shape[0], dtype=np.int32)
+    for q in range(te.shape[0]):
+        b = 0
+        for c in range(1, te.shape[1]):
+            ka = (int(cls[q, c]), bool(np.isnan(te[q, c])))
+            kb = (int(cls[q, b]), bool(np.isnan(te[q, b])))
+            if ka < kb or (ka == kb and te[q, c] < te[q, b]):
+                b = c
+        best[q] = b
+    return (cls[0], int(best[0])) if one else (cls, best)
+
+
+def _fan_query(poses, v0, cfg, merge_lens, dir_xy, row, seg_hint, window, dt, m_cap, k_cap) -> tuple:
+    """_rcv_query's arrays with D [Q, C] from merge_lens [C] or [Q, C]."""
+    Q = np.asarray(poses, dtype=np.float64).reshape(-1, 2).shape[0] if np.size(poses) else 0
+    D = np.asarray(merge_lens, dtype=np.float64)
+    if D.ndim == 1:
+        D = np.broadcast_to(D, (Q, D.shape[0]))
+    if D.ndim != 2 or D.shape[0] != Q or not 1 <= D.shape[1] <= abi.RL_FAN_MAX_CAND:
+        raise ValueError(f"recover_fan: merge_lens must be [C] or [Q={Q}, C] with C in 1..{abi.RL_FAN_MAX_CAND}, got shape {D.shape}")
+    if Q * D.shape[1] > abi.RL_HZN_MAX_QUERIES:
+        raise ValueError(f"recover_fan: Q*C must be <= {abi.RL_HZN_MAX_QUERIES}, got {Q * D.shape[1]}")
+    D = np.ascontiguousarray(D)
+    if not np.all(np.isfinite(D)) or np.any(D <= 0.0):
+        raise ValueError("recover_fan: merge_lens must be finite and > 0")
+    P, rw, hint, V0, _, H = _rcv_query(poses, v0, cfg, D[:, 0], dir_xy, row, seg_hint, window, dt, m_cap, k_cap)
+    return P, rw, hint, V0, D, H
+
+
+def _fan_c(P, rw, hint, V0, D, H, cfg, window, dt, m_cap, k_cap) -> abi.RlFanQuery:
+    return abi.RlFanQuery(_rcv_c(P, rw, hint, V0, D, H, cfg, window, dt, m_cap, k_cap), D.shape[1], 0)
+
+
+def recover_fan_host(x, y, heading, kappa, v, ax, h, closed: bool, lo, hi, poses, v0, cfg: RlCfg, merge_lens, dir_xy=None,
+                     nx=None, ny=None, row=None, seg_hint=None, window: int = 0, dt: float = 0.05, m_cap: int = 64,
+                     k_cap: int = 512, stamps=None) -> RecoverFan:
+    """The specification of the fan stage (include/rl_abi.h) in NumPy: recover_host
+    once per candidate length (merge_lens [C] or [Q, C]), fan_order on the candidates' feasible,
+    clamped, merge_node and t_end, and every field of the winner.  An empty query (end_node = -1)
+    has best = -1, seg and count = 0 as recover_host gives them and nothing else specified."""
+    P, rw, hint, V0, D, H = _fan_query(poses, v0, cfg, merge_lens, dir_xy, row, seg_hint, window, dt, m_cap, k_cap)
+    Q, Cn = D.shape
+    cands = [recover_host(x, y, heading, kappa, v, ax, h, closed, lo, hi, P, V0, cfg, D[:, c], H, nx, ny, rw, hint, window,
+                          dt, m_cap, k_cap, stamps) for c in range(Cn)]
+    out = RecoverFan.alloc(Q, int(m_cap), dt, int(k_cap), Cn)
+    table = {"cand_feasible": "feasible", "cand_clamped": "clamped", "cand_merge_node": "merge_node",
+             "cand_overspeed": "overspeed", "cand_bind_node": "bind_node", "cand_t_end": "t_end", "cand_t_loss": "t_loss",
+             "cand_v_excess": "v_excess"}
+    for name, src in table.items():
+        getattr(out, name)[:] = np.stack([getattr(r, src) for r in cands], axis=1)
+    out.cand_class[:], out.best[:] = fan_order(out.cand_feasible, out.cand_clamped, out.cand_merge_node, out.cand_t_end)
+    fields = [f for f in Recover.__dataclass_fields__ if isinstance(getattr(out, f), np.ndarray)]
+    for q in range(Q):
+        if cands[0].end_node[q] < 0:                   # (every candidate shares the locate)
+            out.best[q] = -1
+        win = cands[max(int(out.best[q]), 0)]
+        for f in fields:
+            getattr(out, f)[q] = getattr(win, f)[q]
+    return out
+
+
+def recover_fan(x, y, heading, kappa, v, ax, h, closed: bool, lo, hi, poses, v0, cfg: RlCfg, merge_lens, dir_xy=None,
+                nx=None, ny=None, row=None, seg_hint=None, window: int = 0, dt: float = 0.05, m_cap: int = 64,
+                k_cap: int = 512, device: int = 0) -> RecoverFan:
+    """recover_fan_host on the GPU (rl_recover_fan): the trajectory kernel stamps the B given
+    rows, then the fan stage's kernels answer the Q poses with C merge lengths each."""
+    rows, hs, (P, rw, hint, V0, D, H), B, N = _open_query(
+        "recover_fan", (x, y, heading, kappa, v, ax, h),
+        lambda: _fan_query(poses, v0, cfg, merge_lens, dir_xy, row, seg_hint, window, dt, m_cap, k_cap))
+    bnd = _rcv_bounds("recover_fan", rows, bool(closed), lo, hi, nx, ny)
+    out = RecoverFan.alloc(P.shape[0], int(m_cap), dt, int(k_cap), D.shape[1])
+    qc, oc = _fan_c(P, rw, hint, V0, D, H, cfg, window, dt, m_cap, k_cap), out.as_c()
+    _check(_lib().rl_recover_fan(*[_ptr(a, np.float64, "row") for a in rows], _ptr(hs, np.float64, "h"),
+                                 *[_ptr(a, np.float64, "bounds") for a in bnd], N, B, 1 if closed else 0, C.byref(qc),
+                                 int(device), C.byref(oc)))
+    return out
+
+
 def path_lengths(x, y, closed: bool, device: int = 0) -> np.ndarray:
     """L [B]: the debug dump's path_length (ref:1443-1448) of B paths given as rows x [B, N],
     y [B, N], summed on the GPU in the reference's order (rl_path_lengths): L[b] equals
@@ -1944,6 +2071,34 @@ class Plan:
             for n in abi.RCV_NODES:
                 setattr(t, n, None)
         _check(_lib().rl_plan_fetch_recover(self._h, C.byref(t)))
+        return out
+
+    def recover_fan(self, poses, v0, cfg: RlCfg, merge_lens, dir_xy=None, row=None, seg_hint=None, window: int = 0,
+                    dt: float = 0.05, m_cap: int = 64, k_cap: int = 512, stream_ptr: int = 0) -> None:
+        """Enqueue the fan stage after the last trajectory() and bounds() (rl_plan_recover_fan):
+        recover()'s query with C merge lengths per pose (merge_lens [C] or [Q, C]); every length is
+        answered as recover() would, the candidates of a pose are ranked on the device in
+        fan_order's order and the winner is served.  Every other stage stays as it is; a later
+        bounds() invalidates it."""
+        P, rw, hint, V0, D, H = _fan_query(poses, v0, cfg, merge_lens, dir_xy, row, seg_hint, window, dt, m_cap, k_cap)
+        self._fan = None
+        qc = _fan_c(P, rw, hint, V0, D, H, cfg, window, dt, m_cap, k_cap)
+        _check(_lib().rl_plan_recover_fan(self._h, C.byref(qc), C.c_void_p(stream_ptr) if stream_ptr else None))
+        self._fan = (P.shape[0], int(m_cap), float(dt), int(k_cap), D.shape[1])
+
+    def fetch_recover_fan(self, nodes: bool = True) -> RecoverFan:
+        """Download the last recover_fan() (rl_plan_fetch_recover_fan): the winner's fields, best
+        and the candidates' table; nodes=False leaves the node arrays on the device."""
+        if getattr(self, "_fan", None) is None:
+            t = abi.RlFan()                 # (the library's own answer: no stage on this plan)
+            _check(_lib().rl_plan_fetch_recover_fan(self._h, C.byref(t)))
+            raise ValueError("fetch_recover_fan: no recover_fan() on this plan")
+        out = RecoverFan.alloc(*self._fan)
+        t = out.as_c()
+        if not nodes:
+            for n in abi.RCV_NODES:
+                setattr(t, n, None)
+        _check(_lib().rl_plan_fetch_recover_fan(self._h, C.byref(t)))
         return out
 
     def bounds(self, veh_width: Optional[float] = None, margin: Optional[float] = None, stream_ptr: int = 0) -> None:
