@@ -642,29 +642,27 @@ DECLS_EXT = [
     ("rl_trajectory", C.c_int, [_F64] * 7 + [C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32, _TRAJ]),
 ]
 
-# the horizon stage: bound only in a library whose rl_abi_features() has RL_FEATURE_HORIZON
-_HZN, _HZNQ = _P(RlHzn), _P(RlHznQuery)
-DECLS_HZN = [
-    ("rl_plan_horizon", C.c_int, [C.c_void_p, _HZNQ, C.c_void_p]),
-    ("rl_plan_fetch_horizon", C.c_int, [C.c_void_p, _HZN]),
-    ("rl_horizon", C.c_int, [_F64] * 7 + [C.c_int32, C.c_int32, C.c_int32, _HZNQ, C.c_int32, _HZN]),
-]
+# The pose-query stages, one row each: name (rl_plan_<name>, rl_plan_fetch_<name>, rl_<name>), feature
+# bit, query struct, results struct, and the row arguments of the one-shot (x, y, heading, kappa, v,
+# ax, h; with lo, hi, nx, ny for a stage that reads the bounds: 11).  A stage is bound only in a
+# library whose rl_abi_features() has its bit.
+QUERY_STAGES = (
+    ("horizon", RL_FEATURE_HORIZON, RlHznQuery, RlHzn, 7),
+    ("rejoin", RL_FEATURE_REJOIN, RlRjnQuery, RlRjn, 7),
+    ("stop", RL_FEATURE_STOP, RlStpQuery, RlStp, 7),
+    ("retime", RL_FEATURE_RETIME, RlRtmQuery, RlRtm, 7),
+    ("recover", RL_FEATURE_RECOVER, RlRcvQuery, RlRcv, 11),
+    ("recover_fan", RL_FEATURE_FAN, RlFanQuery, RlFan, 11),
+)
 
-# the rejoin stage: bound only in a library whose rl_abi_features() has RL_FEATURE_REJOIN
-_RJN, _RJNQ = _P(RlRjn), _P(RlRjnQuery)
-DECLS_RJN = [
-    ("rl_plan_rejoin", C.c_int, [C.c_void_p, _RJNQ, C.c_void_p]),
-    ("rl_plan_fetch_rejoin", C.c_int, [C.c_void_p, _RJN]),
-    ("rl_rejoin", C.c_int, [_F64] * 7 + [C.c_int32, C.c_int32, C.c_int32, _RJNQ, C.c_int32, _RJN]),
-]
 
-# the stop stage: bound only in a library whose rl_abi_features() has RL_FEATURE_STOP
-_STP, _STPQ = _P(RlStp), _P(RlStpQuery)
-DECLS_STP = [
-    ("rl_plan_stop", C.c_int, [C.c_void_p, _STPQ, C.c_void_p]),
-    ("rl_plan_fetch_stop", C.c_int, [C.c_void_p, _STP]),
-    ("rl_stop", C.c_int, [_F64] * 7 + [C.c_int32, C.c_int32, C.c_int32, _STPQ, C.c_int32, _STP]),
-]
+def _stage_decls(name, _feature, query, results, n_rows) -> list:
+    return [("rl_plan_" + name, C.c_int, [C.c_void_p, _P(query), C.c_void_p]),
+            ("rl_plan_fetch_" + name, C.c_int, [C.c_void_p, _P(results)]),
+            ("rl_" + name, C.c_int, [_F64] * n_rows + [C.c_int32, C.c_int32, C.c_int32, _P(query), C.c_int32, _P(results)])]
+
+
+DECLS_HZN, DECLS_RJN, DECLS_STP, DECLS_RTM, DECLS_RCV, DECLS_FAN = (_stage_decls(*st) for st in QUERY_STAGES)
 
 # the bounds stage: bound only in a library whose rl_abi_features() has RL_FEATURE_BOUNDS
 _BND, _BNDQ, _HZNBND = _P(RlBnd), _P(RlBndQuery), _P(RlHznBnd)
@@ -674,29 +672,6 @@ DECLS_BND = [
     ("rl_plan_horizon_bounds", C.c_int, [C.c_void_p, C.c_void_p]),
     ("rl_plan_fetch_horizon_bounds", C.c_int, [C.c_void_p, _HZNBND]),
     ("rl_bounds", C.c_int, [_P(RlProblem), _F64, _F64, C.c_int32, C.c_double, C.c_double, C.c_int32, _BND]),
-]
-
-# the retime stage: bound only in a library whose rl_abi_features() has RL_FEATURE_RETIME
-_RTM, _RTMQ = _P(RlRtm), _P(RlRtmQuery)
-DECLS_RTM = [
-    ("rl_plan_retime", C.c_int, [C.c_void_p, _RTMQ, C.c_void_p]),
-    ("rl_plan_fetch_retime", C.c_int, [C.c_void_p, _RTM]),
-    ("rl_retime", C.c_int, [_F64] * 7 + [C.c_int32, C.c_int32, C.c_int32, _RTMQ, C.c_int32, _RTM]),
-]
-
-# the recover stage: bound only in a library whose rl_abi_features() has RL_FEATURE_RECOVER
-_RCV, _RCVQ = _P(RlRcv), _P(RlRcvQuery)
-DECLS_RCV = [
-    ("rl_plan_recover", C.c_int, [C.c_void_p, _RCVQ, C.c_void_p]),
-    ("rl_plan_fetch_recover", C.c_int, [C.c_void_p, _RCV]),
-    ("rl_recover", C.c_int, [_F64] * 11 + [C.c_int32, C.c_int32, C.c_int32, _RCVQ, C.c_int32, _RCV]),
-]
-# the fan stage: bound only in a library whose rl_abi_features() has RL_FEATURE_FAN
-_FAN, _FANQ = _P(RlFan), _P(RlFanQuery)
-DECLS_FAN = [
-    ("rl_plan_recover_fan", C.c_int, [C.c_void_p, _FANQ, C.c_void_p]),
-    ("rl_plan_fetch_recover_fan", C.c_int, [C.c_void_p, _FAN]),
-    ("rl_recover_fan", C.c_int, [_F64] * 11 + [C.c_int32, C.c_int32, C.c_int32, _FANQ, C.c_int32, _FAN]),
 ]
 
 
@@ -731,20 +706,12 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
                 fn.argtypes = argtypes
 
     bind(DECLS + ext)
-    if ext and lib.rl_abi_features() & RL_FEATURE_HORIZON:
-        bind(DECLS_HZN)
-    if ext and lib.rl_abi_features() & RL_FEATURE_REJOIN:
-        bind(DECLS_RJN)
-    if ext and lib.rl_abi_features() & RL_FEATURE_STOP:
-        bind(DECLS_STP)
-    if ext and lib.rl_abi_features() & RL_FEATURE_BOUNDS:
+    features = lib.rl_abi_features() if ext else 0
+    for st in QUERY_STAGES:
+        if features & st[1]:
+            bind(_stage_decls(*st))
+    if features & RL_FEATURE_BOUNDS:
         bind(DECLS_BND)
-    if ext and lib.rl_abi_features() & RL_FEATURE_RETIME:
-        bind(DECLS_RTM)
-    if ext and lib.rl_abi_features() & RL_FEATURE_RECOVER:
-        bind(DECLS_RCV)
-    if ext and lib.rl_abi_features() & RL_FEATURE_FAN:
-        bind(DECLS_FAN)
     if path == LIB_PATH:
         _LIB = lib
     return lib

@@ -2,8 +2,6 @@
 // plan, the cfg defaults, and the one-shot entry points that upload, run one kernel and
 // download.  Plans are in rl_plan.cpp, their stages in rl_stages.cpp, rl_optimize and the
 // plan cache in rl_cache.cpp.  The compute path is the gfx950 kernels; there is no CPU fallback.
-#include <type_traits>
-
 #include "rl_host.h"
 
 using namespace rl;
@@ -35,51 +33,59 @@ int rows_on_device(DevArena& mem, const std::string& fn, const double* const (&i
     return RL_OK;
 }
 
-// rl_horizon / rl_rejoin / rl_stop / rl_retime / rl_recover (arguments checked, the device selected;
-// K_cap = 0: the horizon; a stop_sample: the stop stage; Out = rl_rtm: the retime stage of a rejoin
-// query; Out = rl_rcv: the recover stage, rcv its query, q that query's rejoin part and bnd the
-// rows' bounds lo, hi, nx, ny [B][N] on the host; Out = rl_fan: the fan stage, rcv its query's
-// recover part with n_cand merge lengths per query): the
-// trajectory kernel for the stamps of the host rows (one tick per row, not downloaded), then the
-// stage's kernel on them; `row` counts the B given rows
-template <class Out>
+// every pose-query stage's one-shot rl_<name> (arguments checked, the device selected; out: the
+// kind's results struct; bnd: the rows' bounds lo, hi, nx, ny [B][N] on the host, for a kind that
+// reads them): the trajectory kernel for the stamps of the host rows (one tick per row, not
+// downloaded), then the kind's kernel on them; `row` counts the B given rows
 int query_rows(const std::string& fn, const double* const (&in)[6], const double* h, int32_t N, int32_t B, int32_t closed,
-               const rl_stp_query& q, const Out& out, const rl_rcv_query* rcv = nullptr, const double* const* bnd = nullptr,
-               int n_cand = 0) {
-    constexpr bool fan = std::is_same<Out, rl_fan>::value;
-    constexpr bool recover = std::is_same<Out, rl_rcv>::value || fan;
-    constexpr bool retime = std::is_same<Out, rl_rtm>::value;
+               QueryKind kind, const QueryView& q, const void* out, const double* const (&bnd)[4]) {
+    const bool bounds = kind_info(kind).reads_bounds;
     DevArena mem;
     rl::TrajParams t;
     if (int rc = rows_on_device(mem, fn, in, h, N, B, closed, q.rj.dt, 1, &t)) return rc;
-    const QueryLayout L = fan       ? fan_layout((size_t)q.rj.Q, (size_t)q.rj.M_cap, (size_t)q.rj.K_cap, (size_t)n_cand)
-                          : recover ? recover_layout(*rcv)
-                                    : query_layout(q, retime);
+    const QueryLayout L = query_layout_of(kind, q);
     double* d_bnd[4] = {};
-    char* d_scratch = fan ? mem.get<char>(L.scratch_bytes) : nullptr;
-    if (recover)
+    char* d_scratch = L.scratch_bytes ? mem.get<char>(L.scratch_bytes) : nullptr;
+    if (bounds)
         for (auto& d : d_bnd) d = mem.get<double>((size_t)B * (size_t)N);
     char* d_qry = mem.get<char>(L.in_bytes);
     char* d_res = mem.get<char>(L.out_bytes);
     if (!mem.ok()) return fail(RL_ENOMEM, fn + ": hipMalloc failed");
     std::vector<char> block(std::max(L.in_bytes, L.out_bytes));
     query_pack(q, L, block.data());
-    if (recover) recover_pack(*rcv, L, block.data());
     if (hipMemcpy(d_qry, block.data(), L.in_bytes, hipMemcpyHostToDevice) != hipSuccess) return fail(RL_EHIP, fn + ": upload");
-    for (int c = 0; recover && c < 4; ++c)
+    for (int c = 0; bounds && c < 4; ++c)
         if (hipMemcpy(d_bnd[c], bnd[c], (size_t)B * (size_t)N * 8, hipMemcpyHostToDevice) != hipSuccess)
             return fail(RL_EHIP, fn + ": upload");
     if (rl::launch_trajectory(t, nullptr) != hipSuccess) return fail(RL_EHIP, fn + ": trajectory kernel");
-    const StpParams sp = query_params(t, q, L, d_qry, d_res);
-    const hipError_t e = recover  ? recover_launch(sp, *rcv, L, d_qry, d_res, {d_bnd[0], d_bnd[1], d_bnd[2], d_bnd[3]}, nullptr, d_scratch)
-                         : retime ? retime_launch(sp, *q.rj.cfg, L, d_res, nullptr)
-                                  : query_launch(sp, nullptr);
+    const hipError_t e = query_launch(L, q, t, d_qry, d_res, {d_bnd[0], d_bnd[1], d_bnd[2], d_bnd[3]}, d_scratch, nullptr);
     if (e != hipSuccess || hipDeviceSynchronize() != hipSuccess)
         return fail(RL_EHIP, fn + ": kernel");
-    if (hipMemcpy(block.data(), d_res, query_wants_nodes(out) ? L.out_bytes : L.head_bytes, hipMemcpyDeviceToHost) != hipSuccess)
+    if (hipMemcpy(block.data(), d_res, query_wants_nodes(kind, out) ? L.out_bytes : L.head_bytes, hipMemcpyDeviceToHost) != hipSuccess)
         return fail(RL_EHIP, fn + ": download");
     query_unpack(block.data(), L, out);
     return RL_OK;
+}
+
+// the checked prologue of every rl_<name>: rows = x, y, heading, kappa, v, ax, h and, for a kind
+// that reads the bounds, lo, hi, nx, ny
+template <QueryKind kind, class Query, class Out>
+int one_shot(const double* const (&rows)[11], int32_t N, int32_t B, int32_t closed, const Query* query, int32_t device, Out* out) {
+    static_assert(sizeof(Out) == kKinds[(int)kind].n_fields * sizeof(void*), "out is the kind's results struct");
+    const KindInfo& k = kind_info(kind);
+    const std::string fn = std::string("rl_") + k.name;
+    bool null = !query || !out;
+    for (int c = 0; c < (k.reads_bounds ? 11 : 7); ++c) null = null || !rows[c];
+    if (null)
+        return fail(RL_EINVAL, fn + (k.reads_bounds ? ": an input row, h, a bounds row, the query or out is NULL"
+                                                    : ": an input row, h, the query or out is NULL"));
+    if (B < 1 || N < 0) return fail(RL_EINVAL, fn + ": B < 1 or N < 0");
+    if (N > rl::RL_STREAM_MAX_N) return fail(RL_ETOOBIG, fn + ": N exceeds 1048576");
+    const QueryView q = query_view(*query);
+    if (int rc = check_query(kind, q, B, N, closed ? 1 : 0)) return rc;
+    if (int rc = select_device(device)) return rc;
+    return query_rows(fn, {rows[0], rows[1], rows[2], rows[3], rows[4], rows[5]}, rows[6], N, B, closed, kind, q, out,
+                      {rows[7], rows[8], rows[9], rows[10]});
 }
 
 }  // namespace
@@ -426,79 +432,41 @@ int rl_trajectory(const double* x, const double* y, const double* heading, const
     return RL_OK;
 }
 
+// the pose-query stages on host rows: one_shot with the kind
 int rl_horizon(const double* x, const double* y, const double* heading, const double* kappa, const double* v,
                const double* ax, const double* h, int32_t N, int32_t B, int32_t closed, const rl_hzn_query* query,
                int32_t device, rl_hzn* out) {
-    if (!x || !y || !heading || !kappa || !v || !ax || !h || !query || !out)
-        return fail(RL_EINVAL, "rl_horizon: an input row, h, the query or out is NULL");
-    if (B < 1 || N < 0) return fail(RL_EINVAL, "rl_horizon: B < 1 or N < 0");
-    if (N > rl::RL_STREAM_MAX_N) return fail(RL_ETOOBIG, "rl_horizon: N exceeds 1048576");
-    if (int rc = check_hzn(query, B, N, closed ? 1 : 0)) return rc;
-    if (int rc = select_device(device)) return rc;
-    return query_rows("rl_horizon", {x, y, heading, kappa, v, ax}, h, N, B, closed, as_stp(as_rjn(*query)), as_stp(as_rjn(*out)));
+    return one_shot<QueryKind::Horizon>({x, y, heading, kappa, v, ax, h, nullptr, nullptr, nullptr, nullptr}, N, B, closed, query, device, out);
 }
 
 int rl_rejoin(const double* x, const double* y, const double* heading, const double* kappa, const double* v,
               const double* ax, const double* h, int32_t N, int32_t B, int32_t closed, const rl_rjn_query* query,
               int32_t device, rl_rjn* out) {
-    if (!x || !y || !heading || !kappa || !v || !ax || !h || !query || !out)
-        return fail(RL_EINVAL, "rl_rejoin: an input row, h, the query or out is NULL");
-    if (B < 1 || N < 0) return fail(RL_EINVAL, "rl_rejoin: B < 1 or N < 0");
-    if (N > rl::RL_STREAM_MAX_N) return fail(RL_ETOOBIG, "rl_rejoin: N exceeds 1048576");
-    if (int rc = check_rjn(query, B, N, closed ? 1 : 0)) return rc;
-    if (int rc = select_device(device)) return rc;
-    return query_rows("rl_rejoin", {x, y, heading, kappa, v, ax}, h, N, B, closed, as_stp(*query), as_stp(*out));
+    return one_shot<QueryKind::Rejoin>({x, y, heading, kappa, v, ax, h, nullptr, nullptr, nullptr, nullptr}, N, B, closed, query, device, out);
 }
 
 int rl_stop(const double* x, const double* y, const double* heading, const double* kappa, const double* v,
             const double* ax, const double* h, int32_t N, int32_t B, int32_t closed, const rl_stp_query* query,
             int32_t device, rl_stp* out) {
-    if (!x || !y || !heading || !kappa || !v || !ax || !h || !query || !out)
-        return fail(RL_EINVAL, "rl_stop: an input row, h, the query or out is NULL");
-    if (B < 1 || N < 0) return fail(RL_EINVAL, "rl_stop: B < 1 or N < 0");
-    if (N > rl::RL_STREAM_MAX_N) return fail(RL_ETOOBIG, "rl_stop: N exceeds 1048576");
-    if (int rc = check_stp(query, B, N, closed ? 1 : 0)) return rc;
-    if (int rc = select_device(device)) return rc;
-    return query_rows("rl_stop", {x, y, heading, kappa, v, ax}, h, N, B, closed, *query, *out);
+    return one_shot<QueryKind::Stop>({x, y, heading, kappa, v, ax, h, nullptr, nullptr, nullptr, nullptr}, N, B, closed, query, device, out);
 }
 
 int rl_retime(const double* x, const double* y, const double* heading, const double* kappa, const double* v,
               const double* ax, const double* h, int32_t N, int32_t B, int32_t closed, const rl_rtm_query* query,
               int32_t device, rl_rtm* out) {
-    if (!x || !y || !heading || !kappa || !v || !ax || !h || !query || !out)
-        return fail(RL_EINVAL, "rl_retime: an input row, h, the query or out is NULL");
-    if (B < 1 || N < 0) return fail(RL_EINVAL, "rl_retime: B < 1 or N < 0");
-    if (N > rl::RL_STREAM_MAX_N) return fail(RL_ETOOBIG, "rl_retime: N exceeds 1048576");
-    if (int rc = check_rjn(&query->rj, B, N, closed ? 1 : 0)) return rc;
-    if (int rc = select_device(device)) return rc;
-    return query_rows("rl_retime", {x, y, heading, kappa, v, ax}, h, N, B, closed, as_stp(query->rj), *out);
+    return one_shot<QueryKind::Retime>({x, y, heading, kappa, v, ax, h, nullptr, nullptr, nullptr, nullptr}, N, B, closed, query, device, out);
 }
 
 int rl_recover(const double* x, const double* y, const double* heading, const double* kappa, const double* v,
                const double* ax, const double* h, const double* lo, const double* hi, const double* nx, const double* ny,
                int32_t N, int32_t B, int32_t closed, const rl_rcv_query* query, int32_t device, rl_rcv* out) {
-    if (!x || !y || !heading || !kappa || !v || !ax || !h || !lo || !hi || !nx || !ny || !query || !out)
-        return fail(RL_EINVAL, "rl_recover: an input row, h, a bounds row, the query or out is NULL");
-    if (B < 1 || N < 0) return fail(RL_EINVAL, "rl_recover: B < 1 or N < 0");
-    if (N > rl::RL_STREAM_MAX_N) return fail(RL_ETOOBIG, "rl_recover: N exceeds 1048576");
-    if (int rc = check_rcv(query, B, N, closed ? 1 : 0)) return rc;
-    if (int rc = select_device(device)) return rc;
-    const double* const bnd[4] = {lo, hi, nx, ny};
-    return query_rows("rl_recover", {x, y, heading, kappa, v, ax}, h, N, B, closed, as_stp(query->rj), *out, query, bnd);
+    return one_shot<QueryKind::Recover>({x, y, heading, kappa, v, ax, h, lo, hi, nx, ny}, N, B, closed, query, device, out);
 }
 
 int rl_recover_fan(const double* x, const double* y, const double* heading, const double* kappa, const double* v,
                    const double* ax, const double* h, const double* lo, const double* hi, const double* nx, const double* ny,
                    int32_t N, int32_t B, int32_t closed, const rl_fan_query* query, int32_t device, rl_fan* out) {
-    if (!x || !y || !heading || !kappa || !v || !ax || !h || !lo || !hi || !nx || !ny || !query || !out)
-        return fail(RL_EINVAL, "rl_recover_fan: an input row, h, a bounds row, the query or out is NULL");
-    if (B < 1 || N < 0) return fail(RL_EINVAL, "rl_recover_fan: B < 1 or N < 0");
-    if (N > rl::RL_STREAM_MAX_N) return fail(RL_ETOOBIG, "rl_recover_fan: N exceeds 1048576");
-    if (int rc = check_fan(query, B, N, closed ? 1 : 0)) return rc;
-    if (int rc = select_device(device)) return rc;
-    const double* const bnd[4] = {lo, hi, nx, ny};
-    return query_rows("rl_recover_fan", {x, y, heading, kappa, v, ax}, h, N, B, closed, as_stp(query->rc.rj), *out, &query->rc, bnd,
-                      query->n_cand);
+    return one_shot<QueryKind::Fan>({x, y, heading, kappa, v, ax, h, lo, hi, nx, ny}, N, B, closed, query, device, out);
 }
 
 // rank host scores with rl_rank_kernel (rl_select.hip)

@@ -377,21 +377,20 @@ inline int queue_downloads(const std::vector<CopyJob>& jobs, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------ pose-query stages
-// The plan's side of one pose-query stage (horizon, rejoin, stop, retime, recover).  The queries go up and the results
-// come down as one packed block each (in, out; rl_query.h has their layout), through one pinned
-// host block (pin) of the larger capacity; all three grow with Q, M_cap and K_cap.  ev[0] is
-// recorded after the upload, which reads pin, ev[1] after the kernel.  Q = 0: no stage since
-// the last run or trajectory stage; M, K (0 for the horizon) are that stage's M_cap and K_cap,
-// stop / retime / recover whether its blocks have the stop / retime / recover stage's arrays, C
-// the candidates per query of a fan stage (0 for every other).  The fan stage has a scratch block
-// on the device as well, which never comes down.
+// The plan's side of one pose-query stage; a plan has one per QueryKind (rl_query.h).  The queries
+// go up and the results come down as one packed block each (in, out; rl_query.h has their layout),
+// through one pinned host block (pin) of the larger capacity; all three grow with Q, M_cap and
+// K_cap.  ev[0] is recorded after the upload, which reads pin, ev[1] after the kernel.  Q = 0: no
+// stage since the last run or trajectory stage; M, K (0 for the horizon) and C (the candidates per
+// query of a fan stage, 0 for every other) are that stage's M_cap, K_cap and n_cand: with the
+// stage's kind they give its layout again.  The fan stage has a scratch block on the device as
+// well, which never comes down.
 struct QueryStage {
     char *in = nullptr, *out = nullptr, *pin = nullptr, *scratch = nullptr;
     size_t in_cap = 0, out_cap = 0, scratch_cap = 0;
     DevArena mem;                     // in, out: they count toward the plan's dev_bytes()
     DevArena scratch_mem;             // scratch: it counts as well
     int Q = 0, M = 0, K = 0, C = 0;
-    bool stop = false, retime = false, recover = false;
     double dt = 0;                    // that stage's tick step (the bounds stage's tick kernel reads it)
     hipEvent_t ev[2] = {nullptr, nullptr};
 
@@ -524,7 +523,7 @@ struct rl_plan {
     rl::DevArena traj_mem;
     int traj_cap_R = 0, traj_cap_M = 0, traj_R = 0, traj_M = 0;
     hipEvent_t ev_traj[2] = {nullptr, nullptr};
-    // pose-query stages (rl_plan_horizon, rl_plan_rejoin, rl_plan_stop, rl_plan_retime, rl_plan_recover; rl::QueryStage): they read the last
+    // pose-query stages (rl::QueryStage, one per rl::QueryKind): they read the last
     // trajectory stage through traj_q, that stage's launch parameters, which stay valid while
     // traj_R != 0 and the rows they point at are those the stamps were made from:
     // traj_sel_epoch / traj_lap_epoch are sel_epoch / lap_epoch (counted up by every selection /
@@ -533,7 +532,8 @@ struct rl_plan {
     rl::TrajParams traj_q{};
     int traj_mode = 0;
     uint32_t sel_epoch = 0, lap_epoch = 0, traj_sel_epoch = 0, traj_lap_epoch = 0;
-    rl::QueryStage hzn, rjn, stp, rtm, rcv, fan;   // (rcv and fan read the bounds stage as well: drop_bounds_readers)
+    rl::QueryStage qs[rl::QUERY_KINDS];            // by kind (some read the bounds stage as well: drop_bounds_readers)
+    rl::QueryStage& stage(rl::QueryKind k) { return qs[(int)k]; }
     // bounds stage (rl_plan_bounds, rl::BndParams): lo, hi, nx, ny [bnd_R][N] of the last
     // trajectory stage's rows, row for row, in buffers sized for bnd_cap_R rows; bnd_R = 0: no
     // stage since the last run or trajectory stage.  Its tick kernel (rl_plan_horizon_bounds)
@@ -551,9 +551,16 @@ struct rl_plan {
     hipEvent_t ev_hb[2] = {nullptr, nullptr};
     // a run or a trajectory stage invalidates the pose-query stages that read the one before,
     // and the bounds of its rows
-    void drop_queries() { hzn.Q = rjn.Q = stp.Q = rtm.Q = rcv.Q = fan.Q = bnd_R = hb_Q = 0; }
-    // a bounds stage invalidates what read the one before: the tick bounds, the recover and the fan stage
-    void drop_bounds_readers() { bnd_R = hb_Q = rcv.Q = fan.Q = 0; }
+    void drop_queries() {
+        for (auto& s : qs) s.Q = 0;
+        bnd_R = hb_Q = 0;
+    }
+    // a bounds stage invalidates what read the one before: the tick bounds and the stages whose kind reads_bounds
+    void drop_bounds_readers() {
+        for (int k = 0; k < rl::QUERY_KINDS; ++k)
+            if (rl::kKinds[k].reads_bounds) qs[k].Q = 0;
+        bnd_R = hb_Q = 0;
+    }
 
     template <class T>
     int alloc(T** p, size_t n) {
@@ -563,8 +570,9 @@ struct rl_plan {
     int nomem() const { return rl::fail(RL_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(mem.err)); }
     // device memory held (plan cache budget)
     size_t dev_bytes() const {
-        return mem.bytes + sel_mem.bytes + lap_mem.bytes + traj_mem.bytes + hzn.mem.bytes + rjn.mem.bytes + stp.mem.bytes +
-               rtm.mem.bytes + rcv.mem.bytes + fan.dev_bytes() + bnd_mem.bytes + hb_mem.bytes;
+        size_t n = mem.bytes + sel_mem.bytes + lap_mem.bytes + traj_mem.bytes + bnd_mem.bytes + hb_mem.bytes;
+        for (const auto& s : qs) n += s.dev_bytes();
+        return n;
     }
     // the stream of the last run or stage
     hipStream_t run_stream() const { return last_stream ? last_stream : own_stream; }
@@ -600,34 +608,13 @@ void sel_jobs(const rl_plan* p, int32_t* index, double* score, double* all_score
 int check_traj(double dt, int32_t M_cap);
 // the copies that download the last trajectory stage of p into the non-NULL fields of t
 void traj_jobs(const rl_plan* p, const rl_traj* t, std::vector<CopyJob>& jobs);
-// argument checks shared by the horizon entry points (no device call): the queries against a
-// trajectory stage of R rows of N samples
-int check_hzn(const rl_hzn_query* q, int32_t R, int32_t N, int32_t closed);
-// argument checks shared by the rejoin entry points (no device call): check_hzn's, then v0, cfg
-// and K_cap
-int check_rjn(const rl_rjn_query* q, int32_t R, int32_t N, int32_t closed);
-// argument checks shared by the stop entry points (no device call): check_rjn's, then
-// stop_sample and v_target
-int check_stp(const rl_stp_query* q, int32_t R, int32_t N, int32_t closed);
-// the launch parameters of q on the blocks `in` and `out` (device) laid out as L, reading the
-// trajectory stage src: rl_query.h's pointers, and for a rejoin or stop query ax_max_at's
-// constants
-StpParams query_params(const TrajParams& src, const rl_stp_query& q, const QueryLayout& L, char* in, char* out);
-// the stage's kernel for those parameters: a stop_sample: stop; K_cap > 0: rejoin; else horizon
-hipError_t query_launch(const StpParams& s, hipStream_t st);
-// the retime stage's kernel on a rejoin query's parameters s (query_params'), its cfg, and the
-// results' block `out` (device) laid out as L (L.retime set)
-hipError_t retime_launch(const StpParams& s, const rl_cfg& cfg, const QueryLayout& L, char* out, hipStream_t st);
-// argument checks of the recover entry points (no device call): check_rjn's with
-// K_cap <= RL_RCV_MAX_NODES, then merge_len and dir_xy
-int check_rcv(const rl_rcv_query* q, int32_t R, int32_t N, int32_t closed);
-// the recover stage's kernel on its query's rejoin parameters s (query_params'), the blocks in
-// and out (device) laid out as L (recover_layout's) and the bounds rows bnd (lo, hi, nx, ny, device)
-// L a fan_layout (L.C > 0) and a scratch block of L.scratch_bytes (device): the fan stage's kernels
-hipError_t recover_launch(const StpParams& s, const rl_rcv_query& q, const QueryLayout& L, const char* in, char* out,
-                          const double* const (&bnd)[4], hipStream_t st, char* scratch = nullptr);
-// argument checks of the fan entry points (no device call): check_rcv's with merge_len [Q][n_cand],
-// n_cand and Q*n_cand
-int check_fan(const rl_fan_query* q, int32_t R, int32_t N, int32_t closed);
+// argument checks of the pose-query entry points (no device call): the kind's query, NULL-checked
+// by the caller, against a trajectory stage of R rows of N samples
+int check_query(QueryKind kind, const QueryView& q, int32_t R, int32_t N, int32_t closed);
+// the kind's kernel on q, the blocks `in` and `out` (device) laid out as L, reading the trajectory
+// stage src: rl_query.h's pointers, and for every kind but the horizon ax_max_at's constants.  bnd:
+// the bounds rows lo, hi, nx, ny (device) of a kind that reads them; scratch: the fan stage's block
+hipError_t query_launch(const QueryLayout& L, const QueryView& q, const TrajParams& src, char* in, char* out,
+                        const double* const (&bnd)[4], char* scratch, hipStream_t st);
 
 }  // namespace rl

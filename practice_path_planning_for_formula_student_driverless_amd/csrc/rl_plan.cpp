@@ -193,12 +193,7 @@ int rl_plan_destroy(rl_plan* plan) {
     plan->traj_mem.release();
     for (auto& e : plan->ev_traj)
         if (e) hipEventDestroy(e);
-    plan->hzn.release();
-    plan->rjn.release();
-    plan->stp.release();
-    plan->rtm.release();
-    plan->rcv.release();
-    plan->fan.release();
+    for (auto& s : plan->qs) s.release();
     plan->bnd_mem.release();
     plan->hb_mem.release();
     for (auto& e : plan->ev_bnd)
@@ -439,9 +434,10 @@ int rl_plan_kernel_ms(rl_plan* p, int32_t idx, float* ms) {
     // idx 0: whole run; 1: min-curv kernel; 2: min-time kernel; 3: the selection stage
     hipEvent_t a, b;
     const bool mc = p->modes & RL_MODE_MINCURV, mt = p->modes & RL_MODE_MINTIME;
-    // 8: the horizon stage; 9: the rejoin stage; 10: the stop stage; 13: the retime stage; 14: the
-    // recover stage, 15: the fan stage (which a bounds stage invalidates as well)
-    const rl::QueryStage& stage = idx == 15 ? p->fan : idx == 14 ? p->rcv : idx == 13 ? p->rtm : idx == 10 ? p->stp : idx == 9 ? p->rjn : p->hzn;
+    // 8..10, 13..15: the pose-query stages, by kKinds' ms_index (a bounds stage invalidates those that read it as well)
+    const rl::QueryStage* stage = nullptr;
+    for (int k = 0; k < rl::QUERY_KINDS; ++k)
+        if (rl::kKinds[k].ms_index == idx && (!rl::kKinds[k].reads_bounds || p->bnd_R)) stage = &p->qs[k];
     if (idx == 0) { a = p->ev[0]; b = p->ev[3]; }
     else if (idx == 3 && p->sel_mode) {
         a = p->ev_sel[0];
@@ -459,9 +455,9 @@ int rl_plan_kernel_ms(rl_plan* p, int32_t idx, float* ms) {
         b = p->ev_traj[1];
         HIPCHK(hipEventSynchronize(b));
     }
-    else if (((idx >= 8 && idx <= 10) || idx == 13 || ((idx == 14 || idx == 15) && p->bnd_R)) && stage.Q && p->traj_R) {
-        a = stage.ev[0];
-        b = stage.ev[1];
+    else if (stage && stage->Q && p->traj_R) {
+        a = stage->ev[0];
+        b = stage->ev[1];
         HIPCHK(hipEventSynchronize(b));
     }
     else if (idx == 11 && p->bnd_R && p->traj_R) {      // 11: the bounds stage

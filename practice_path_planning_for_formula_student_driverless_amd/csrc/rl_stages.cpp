@@ -9,7 +9,9 @@
 // over the nodes ahead, under the car's cfg.  Recover stage (rl_recover.hip): a path
 // from the car's offset back to the row inside the bounds stage's free width, and that speed pass
 // on it.  Fan stage (rl_recover_fan.hip): the recover stage for C merge lengths per
-// pose, and the best one served.  These six pose-query stages share one enqueue and one fetch routine.
+// pose, and the best one served.  These six pose-query stages are the kinds of rl_query.h's table:
+// they share one checked prologue, one enqueue (query_enqueue), one launch switch (query_launch) and
+// one fetch (query_fetch), and their entry points are one-line forwards that name the kind.
 // Bounds stage (rl_bounds.hip): the free track width about the trajectory stage's
 // rows, and at the horizon stage's ticks.
 #include "rl_host.h"
@@ -67,103 +69,113 @@ void rl::traj_jobs(const rl_plan* p, const rl_traj* t, std::vector<CopyJob>& job
     add_job(jobs, t->count, p->traj_count, R * 4);
 }
 
-int rl::check_hzn(const rl_hzn_query* q, int32_t R, int32_t N, int32_t closed) {
-    if (!q || !q->pose_xy) return fail(RL_EINVAL, "horizon: the query or its pose_xy is NULL");
-    if (q->Q < 1 || q->Q > RL_HZN_MAX_QUERIES) return fail(RL_EINVAL, "horizon: Q must be 1..65536");
-    if (q->window < 0) return fail(RL_EINVAL, "horizon: window < 0");
-    if (int rc = check_traj(q->dt, q->M_cap)) return rc;
+namespace {
+
+// the horizon part of every kind's query: the sizes, and the rows and hints against a trajectory
+// stage of R rows of N samples
+int check_hzn(const rl_rjn_query& q, int32_t R, int32_t N, int32_t closed) {
+    if (!q.pose_xy) return fail(RL_EINVAL, "horizon: the query or its pose_xy is NULL");
+    if (q.Q < 1 || q.Q > RL_HZN_MAX_QUERIES) return fail(RL_EINVAL, "horizon: Q must be 1..65536");
+    if (q.window < 0) return fail(RL_EINVAL, "horizon: window < 0");
+    if (int rc = check_traj(q.dt, q.M_cap)) return rc;
     if (N < 1) return fail(RL_EINVAL, "horizon: N == 0 (no row)");
     const int32_t S = closed ? N : N - 1;
-    for (int32_t k = 0; k < q->Q; ++k) {
-        const int32_t r = q->row ? q->row[k] : 0, g = q->seg_hint ? q->seg_hint[k] : -1;
+    for (int32_t k = 0; k < q.Q; ++k) {
+        const int32_t r = q.row ? q.row[k] : 0, g = q.seg_hint ? q.seg_hint[k] : -1;
         if (r < 0 || r >= R) return fail(RL_EINVAL, "horizon: a row outside the trajectory stage's [0, R)");
         if (g < -1 || g >= S) return fail(RL_EINVAL, "horizon: a seg_hint outside [-1, S)");
     }
     return RL_OK;
 }
 
-int rl::check_rjn(const rl_rjn_query* q, int32_t R, int32_t N, int32_t closed) {
-    if (!q) return fail(RL_EINVAL, "rejoin: the query is NULL");
-    const rl_hzn_query hq{q->pose_xy, q->row, q->seg_hint, q->Q, q->window, q->M_cap, 0, q->dt};
-    if (int rc = check_hzn(&hq, R, N, closed)) return rc;
-    if (!q->v0 || !q->cfg) return fail(RL_EINVAL, "rejoin: v0 or cfg is NULL");
-    if (q->K_cap < 1 || q->K_cap > RL_RJN_MAX_NODES) return fail(RL_EINVAL, "rejoin: K_cap must be 1..1024");
-    for (int32_t k = 0; k < q->Q; ++k)
-        if (!std::isfinite(q->v0[k]) || q->v0[k] < 0.0) return fail(RL_EINVAL, "rejoin: a v0 that is not finite or is < 0");
+// check_hzn's, then v0, cfg and K_cap
+int check_rjn(const rl_rjn_query& q, int32_t R, int32_t N, int32_t closed) {
+    if (int rc = check_hzn(q, R, N, closed)) return rc;
+    if (!q.v0 || !q.cfg) return fail(RL_EINVAL, "rejoin: v0 or cfg is NULL");
+    if (q.K_cap < 1 || q.K_cap > RL_RJN_MAX_NODES) return fail(RL_EINVAL, "rejoin: K_cap must be 1..1024");
+    for (int32_t k = 0; k < q.Q; ++k)
+        if (!std::isfinite(q.v0[k]) || q.v0[k] < 0.0) return fail(RL_EINVAL, "rejoin: a v0 that is not finite or is < 0");
     return RL_OK;
 }
 
-int rl::check_stp(const rl_stp_query* q, int32_t R, int32_t N, int32_t closed) {
-    if (!q) return fail(RL_EINVAL, "stop: the query is NULL");
-    if (int rc = check_rjn(&q->rj, R, N, closed)) return rc;
-    if (!q->stop_sample) return fail(RL_EINVAL, "stop: stop_sample is NULL");
-    for (int32_t k = 0; k < q->rj.Q; ++k) {
-        if (q->stop_sample[k] < 0 || q->stop_sample[k] >= N) return fail(RL_EINVAL, "stop: a stop_sample outside [0, N)");
-        if (q->v_target && (!std::isfinite(q->v_target[k]) || q->v_target[k] < 0.0))
+// check_rjn's, then stop_sample and v_target
+int check_stp(const QueryView& q, int32_t R, int32_t N, int32_t closed) {
+    if (int rc = check_rjn(q.rj, R, N, closed)) return rc;
+    if (!q.stop_sample) return fail(RL_EINVAL, "stop: stop_sample is NULL");
+    for (int32_t k = 0; k < q.rj.Q; ++k) {
+        if (q.stop_sample[k] < 0 || q.stop_sample[k] >= N) return fail(RL_EINVAL, "stop: a stop_sample outside [0, N)");
+        if (q.v_target && (!std::isfinite(q.v_target[k]) || q.v_target[k] < 0.0))
             return fail(RL_EINVAL, "stop: a v_target that is not finite or is < 0");
     }
     return RL_OK;
 }
 
-StpParams rl::query_params(const TrajParams& src, const rl_stp_query& q, const QueryLayout& L, char* in, char* out) {
-    StpParams s = query_pointers(q, L, in, out);
-    RjnParams& r = s.rj;
+// check_rjn's with K_cap <= RL_RCV_MAX_NODES, then merge_len and dir_xy; with `fan` merge_len is
+// [Q][n_cand], and n_cand and Q*n_cand are checked
+int check_rcv(const QueryView& q, int32_t R, int32_t N, int32_t closed, bool fan) {
+    const int32_t C = q.n_cand;
+    if (int rc = check_rjn(q.rj, R, N, closed)) return rc;
+    if (q.rj.K_cap > RL_RCV_MAX_NODES) return fail(RL_EINVAL, "recover: K_cap must be 1..512");
+    if (!q.merge_len) return fail(RL_EINVAL, "recover: merge_len is NULL");
+    if (fan && (C < 1 || C > RL_FAN_MAX_CAND)) return fail(RL_EINVAL, "recover fan: n_cand must be 1..16");
+    if (fan && (int64_t)q.rj.Q * C > RL_HZN_MAX_QUERIES) return fail(RL_EINVAL, "recover fan: Q*n_cand must be <= 65536");
+    const size_t per = fan ? (size_t)C : 1;
+    for (int32_t k = 0; k < q.rj.Q; ++k) {
+        for (size_t c = 0; c < per; ++c)
+            if (!std::isfinite(q.merge_len[k * per + c]) || !(q.merge_len[k * per + c] > 0.0))
+                return fail(RL_EINVAL, "recover: a merge_len that is not finite or is <= 0");
+        if (q.dir_xy && (!std::isfinite(q.dir_xy[2 * (size_t)k]) || !std::isfinite(q.dir_xy[2 * (size_t)k + 1])))
+            return fail(RL_EINVAL, "recover: a dir_xy that is not finite");
+    }
+    return RL_OK;
+}
+
+// query_pointers of q, reading the trajectory stage src, and for every kind but the horizon
+// ax_max_at's constant prefixes, as the optimisers' VConst evaluates them
+RjnParams query_params(const TrajParams& src, const rl_rjn_query& q, const QueryLayout& L, char* in, char* out) {
+    RjnParams r = query_pointers(q, L, in, out);
     r.hz.src = src;
-    if (!q.rj.cfg) return s;                           // a horizon query
-    // ax_max_at's constant prefixes, as the optimisers' VConst evaluates them
-    const rl_cfg& C = *q.rj.cfg;
+    if (!q.cfg) return r;                              // a horizon query
+    const rl_cfg& C = *q.cfg;
     const double a_total = C.use_total_ge_lat ? smax_h(C.a_total_max, C.a_lat_max) : C.a_total_max;
     r.cfg.a_total2 = a_total * a_total;
     r.cfg.kFd = 0.5 * C.rho_air * C.Cd * C.A_front_m2;
     r.cfg.Fr = C.mass_kg * 9.81 * C.c_rr;
     r.cfg.mass = C.mass_kg; r.cfg.Pmax = C.P_max_W;
     r.cfg.acc_cap = C.a_long_acc_cap; r.cfg.brk_cap = C.a_long_brake_cap;
-    return s;
-}
-
-hipError_t rl::query_launch(const StpParams& s, hipStream_t st) {
-    if (s.stop_sample) return rl::launch_stop(s, st);
-    return s.rj.K_cap > 0 ? rl::launch_rejoin(s.rj, st) : rl::launch_horizon(s.rj.hz, st);
-}
-
-hipError_t rl::retime_launch(const StpParams& s, const rl_cfg& cfg, const QueryLayout& L, char* out, hipStream_t st) {
-    return rl::launch_retime(retime_pointers(s.rj, cfg, L, out), st);
-}
-
-namespace {
-
-// check_rcv, or with `fan` check_fan: C merge lengths per query
-int check_rcv_of(const rl_rcv_query* q, int32_t R, int32_t N, int32_t closed, bool fan, int32_t C) {
-    if (!q) return fail(RL_EINVAL, "recover: the query is NULL");
-    if (int rc = check_rjn(&q->rj, R, N, closed)) return rc;
-    if (q->rj.K_cap > RL_RCV_MAX_NODES) return fail(RL_EINVAL, "recover: K_cap must be 1..512");
-    if (!q->merge_len) return fail(RL_EINVAL, "recover: merge_len is NULL");
-    if (fan && (C < 1 || C > RL_FAN_MAX_CAND)) return fail(RL_EINVAL, "recover fan: n_cand must be 1..16");
-    if (fan && (int64_t)q->rj.Q * C > RL_HZN_MAX_QUERIES) return fail(RL_EINVAL, "recover fan: Q*n_cand must be <= 65536");
-    const size_t per = fan ? (size_t)C : 1;
-    for (int32_t k = 0; k < q->rj.Q; ++k) {
-        for (size_t c = 0; c < per; ++c)
-            if (!std::isfinite(q->merge_len[k * per + c]) || !(q->merge_len[k * per + c] > 0.0))
-                return fail(RL_EINVAL, "recover: a merge_len that is not finite or is <= 0");
-        if (q->dir_xy && (!std::isfinite(q->dir_xy[2 * (size_t)k]) || !std::isfinite(q->dir_xy[2 * (size_t)k + 1])))
-            return fail(RL_EINVAL, "recover: a dir_xy that is not finite");
-    }
-    return RL_OK;
+    return r;
 }
 
 }  // namespace
 
-int rl::check_rcv(const rl_rcv_query* q, int32_t R, int32_t N, int32_t closed) { return check_rcv_of(q, R, N, closed, false, 1); }
-
-int rl::check_fan(const rl_fan_query* q, int32_t R, int32_t N, int32_t closed) {
-    if (!q) return fail(RL_EINVAL, "recover fan: the query is NULL");
-    return check_rcv_of(&q->rc, R, N, closed, true, q->n_cand);
+int rl::check_query(QueryKind kind, const QueryView& q, int32_t R, int32_t N, int32_t closed) {
+    switch (kind) {
+    case QueryKind::Horizon: return check_hzn(q.rj, R, N, closed);
+    case QueryKind::Rejoin:
+    case QueryKind::Retime: return check_rjn(q.rj, R, N, closed);
+    case QueryKind::Stop: return check_stp(q, R, N, closed);
+    case QueryKind::Recover: return check_rcv(q, R, N, closed, false);
+    case QueryKind::Fan: return check_rcv(q, R, N, closed, true);
+    }
+    return fail(RL_EINVAL, "unknown pose-query stage");
 }
 
-hipError_t rl::recover_launch(const StpParams& s, const rl_rcv_query& q, const QueryLayout& L, const char* in, char* out,
-                              const double* const (&bnd)[4], hipStream_t st, char* scratch) {
-    const RcvParams c = recover_pointers(retime_pointers(s.rj, *q.rj.cfg, L, out), q, L, in, out, bnd);
-    return L.C ? rl::launch_recover_fan(fan_pointers(c, *q.rj.cfg, L, out, scratch), st) : rl::launch_recover(c, st);
+hipError_t rl::query_launch(const QueryLayout& L, const QueryView& q, const TrajParams& src, char* in, char* out,
+                            const double* const (&bnd)[4], char* scratch, hipStream_t st) {
+    const RjnParams r = query_params(src, q.rj, L, in, out);
+    switch (L.kind) {
+    case QueryKind::Horizon: return rl::launch_horizon(r.hz, st);
+    case QueryKind::Rejoin: return rl::launch_rejoin(r, st);
+    case QueryKind::Stop: return rl::launch_stop(stop_pointers(r, L, in, out), st);
+    case QueryKind::Retime: return rl::launch_retime(retime_pointers(r, *q.rj.cfg, L, out), st);
+    case QueryKind::Recover:
+    case QueryKind::Fan: {
+        const RcvParams c = recover_pointers(retime_pointers(r, *q.rj.cfg, L, out), q.dir_xy != nullptr, L, in, out, bnd);
+        return L.kind == QueryKind::Fan ? rl::launch_recover_fan(fan_pointers(c, *q.rj.cfg, L, out, scratch), st)
+                                        : rl::launch_recover(c, st);
+    }
+    }
+    return hipErrorInvalidValue;
 }
 
 namespace {
@@ -299,17 +311,13 @@ int select_impl(rl_plan* p, const rl_select* sel, int gs, bool by_lap, void* hip
     return RL_OK;
 }
 
-// rl_plan_horizon / rl_plan_rejoin / rl_plan_stop / rl_plan_retime / rl_plan_recover (arguments
-// checked; K_cap = 0: the horizon; a stop_sample: the stop stage; retime: the retime stage of a
-// rejoin query; rcv: the recover stage's query, q its rejoin part, after a valid bounds stage;
-// n_cand > 0: the fan stage, rcv its query's recover part):
-// one launch of the stage's kernel on the last trajectory stage.
-// The queries go up in one block, through s's pinned block, ahead of the kernel on the same
-// stream.
-int query_enqueue(rl_plan* p, QueryStage& s, const rl_stp_query& q, void* hip_stream, bool retime = false,
-                  const rl_rcv_query* rcv = nullptr, int n_cand = 0) {
-    const char* what = n_cand ? "recover_fan" : rcv ? "recover" : retime ? "retime" : q.stop_sample ? "stop" : q.rj.K_cap > 0 ? "rejoin" : "horizon";
-    const std::string fn = std::string("rl_plan_") + what;
+// every pose-query stage's rl_plan_<name> (arguments checked; a kind that reads the bounds stage
+// after a valid one): one launch of the kind's kernel on the last trajectory stage.  The queries go
+// up in one block, through the stage's pinned block, ahead of the kernel on the same stream.
+int query_enqueue(rl_plan* p, QueryKind kind, const QueryView& q, void* hip_stream) {
+    const KindInfo& k = kind_info(kind);
+    QueryStage& s = p->stage(kind);
+    const std::string fn = std::string("rl_plan_") + k.name;
     if (p->traj_q.index && p->traj_sel_epoch != p->sel_epoch)
         return fail(RL_EINVAL, fn + ": a selection has replaced the winners the trajectory stage read");
     if (p->traj_mode == RL_MODE_MINCURV && p->traj_lap_epoch != p->lap_epoch)
@@ -322,35 +330,26 @@ int query_enqueue(rl_plan* p, QueryStage& s, const rl_stp_query& q, void* hip_st
     // recorded is complete).
     if (s.ev[0]) HIPCHK(hipEventSynchronize(s.ev[0]));
     s.Q = 0;
-    if (&s == &p->hzn) p->hb_Q = 0;                    // the tick bounds of the horizon stage before
-    const QueryLayout L = n_cand ? fan_layout((size_t)q.rj.Q, (size_t)q.rj.M_cap, (size_t)q.rj.K_cap, (size_t)n_cand)
-                          : rcv  ? recover_layout(*rcv)
-                                 : query_layout(q, retime);
-    if (int rc = s.reserve(p->last_stream, L.in_bytes, L.out_bytes, what)) return rc;
-    if (n_cand)
-        if (int rc = s.reserve_scratch(p->last_stream, L.scratch_bytes, what)) return rc;
+    if (kind == QueryKind::Horizon) p->hb_Q = 0;       // the tick bounds of the horizon stage before
+    const QueryLayout L = query_layout_of(kind, q);
+    if (int rc = s.reserve(p->last_stream, L.in_bytes, L.out_bytes, k.name)) return rc;
+    if (L.scratch_bytes)
+        if (int rc = s.reserve_scratch(p->last_stream, L.scratch_bytes, k.name)) return rc;
     for (auto& e : s.ev)
         if (!e) HIPCHK(hipEventCreate(&e));
     if (st != run_st) HIPCHK(hipStreamWaitEvent(st, p->ev_traj[1], 0));
-    if (rcv) HIPCHK(hipStreamWaitEvent(st, p->ev_bnd[1], 0));      // (the bounds stage may be on another stream)
+    if (k.reads_bounds) HIPCHK(hipStreamWaitEvent(st, p->ev_bnd[1], 0));   // (the bounds stage may be on another stream)
     p->last_stream = st;
     query_pack(q, L, s.pin);
-    if (rcv) recover_pack(*rcv, L, s.pin);
     HIPCHK(hipMemcpyAsync(s.in, s.pin, L.in_bytes, hipMemcpyHostToDevice, st));
     HIPCHK(hipEventRecord(s.ev[0], st));
-    const StpParams sp = query_params(p->traj_q, q, L, s.in, s.out);
-    const hipError_t e = rcv      ? recover_launch(sp, *rcv, L, s.in, s.out, {p->bnd[0], p->bnd[1], p->bnd[2], p->bnd[3]}, st, s.scratch)
-                         : retime ? retime_launch(sp, *q.rj.cfg, L, s.out, st)
-                                  : query_launch(sp, st);
-    if (e != hipSuccess) return fail(RL_EHIP, std::string(what) + " launch: " + hipGetErrorString(e));
+    const hipError_t e = query_launch(L, q, p->traj_q, s.in, s.out, {p->bnd[0], p->bnd[1], p->bnd[2], p->bnd[3]}, s.scratch, st);
+    if (e != hipSuccess) return fail(RL_EHIP, std::string(k.name) + " launch: " + hipGetErrorString(e));
     HIPCHK(hipEventRecord(s.ev[1], st));
     s.Q = q.rj.Q;
     s.M = q.rj.M_cap;
     s.K = q.rj.K_cap;
-    s.stop = L.stop;
-    s.retime = L.retime;
-    s.recover = L.recover;
-    s.C = n_cand;
+    s.C = q.n_cand;
     s.dt = q.rj.dt;
     return RL_OK;
 }
@@ -391,20 +390,45 @@ int horizon_bounds_alloc(rl_plan* p, size_t Q, size_t M) {
     return RL_OK;
 }
 
-// rl_plan_fetch_horizon / rl_plan_fetch_rejoin / rl_plan_fetch_stop / rl_plan_fetch_retime /
-// rl_plan_fetch_recover / rl_plan_fetch_recover_fan (a valid stage in s; Out: rl_stp, rl_rtm for
-// the retime stage, rl_rcv for the recover stage, rl_fan for the fan stage): the results' block
-// comes down through the pinned block, without the node arrays if o asks for none
-template <class Out>
-int query_fetch(rl_plan* p, QueryStage& s, const Out& o) {
+// every pose-query stage's rl_plan_fetch_<name> (a valid stage of `kind`; o: the kind's results
+// struct): the results' block comes down through the pinned block, without the node arrays if o
+// asks for none
+int query_fetch(rl_plan* p, QueryKind kind, const void* o) {
+    QueryStage& s = p->stage(kind);
     HIPCHK(hipSetDevice(p->device));
     hipStream_t st = p->run_stream();
     HIPCHK(hipStreamWaitEvent(st, s.ev[1], 0));         // (a later stage may have moved to another stream)
-    const QueryLayout L = query_layout_of((size_t)s.Q, (size_t)s.M, (size_t)s.K, s.stop, s.retime, s.recover, (size_t)s.C);
-    HIPCHK(hipMemcpyAsync(s.pin, s.out, query_wants_nodes(o) ? L.out_bytes : L.head_bytes, hipMemcpyDeviceToHost, st));
+    const QueryLayout L = query_layout_of(kind, (size_t)s.Q, (size_t)s.M, (size_t)s.K, (size_t)s.C);
+    HIPCHK(hipMemcpyAsync(s.pin, s.out, query_wants_nodes(kind, o) ? L.out_bytes : L.head_bytes, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     query_unpack(s.pin, L, o);
     return RL_OK;
+}
+
+// the checked prologue of every rl_plan_<name>: blocks of the kind's own, so every other stage
+// stays as it is; a kind that reads the bounds stage reads its rows where they lie
+template <QueryKind kind, class Query>
+int plan_stage(rl_plan* p, const Query* query, void* hip_stream) {
+    const KindInfo& k = kind_info(kind);
+    if (!p) return fail(RL_EINVAL, "plan is NULL");
+    if (!query) return fail(RL_EINVAL, k.null_query);
+    const std::string fn = std::string("rl_plan_") + k.name;
+    if (!p->traj_R) return fail(RL_EINVAL, fn + ": no trajectory stage since the plan's last run");
+    const QueryView q = query_view(*query);
+    if (int rc = check_query(kind, q, p->traj_R, p->N, p->closed)) return rc;
+    if (k.reads_bounds && !p->bnd_R) return fail(RL_EINVAL, fn + ": no bounds stage since the plan's last trajectory stage");
+    return query_enqueue(p, kind, q, hip_stream);
+}
+
+// the checked prologue of every rl_plan_fetch_<name>
+template <QueryKind kind, class Out>
+int plan_fetch(rl_plan* p, const Out* out) {
+    static_assert(sizeof(Out) == kKinds[(int)kind].n_fields * sizeof(void*), "out is the kind's results struct");
+    const KindInfo& k = kind_info(kind);
+    if (!p) return fail(RL_EINVAL, "plan is NULL");
+    if (!out) return fail(RL_EINVAL, std::string("rl_plan_fetch_") + k.name + ": out is NULL");
+    if (!p->stage(kind).Q || !p->traj_R || (k.reads_bounds && !p->bnd_R)) return fail(RL_EINVAL, k.fetch_none);
+    return query_fetch(p, kind, out);
 }
 
 }  // namespace
@@ -583,110 +607,19 @@ int rl_plan_fetch_trajectory(rl_plan* p, rl_traj* out) {
     return RL_OK;
 }
 
-int rl_plan_horizon(rl_plan* p, const rl_hzn_query* query, void* hip_stream) {
-    if (!p) return fail(RL_EINVAL, "plan is NULL");
-    if (!query) return fail(RL_EINVAL, "horizon: the query or its pose_xy is NULL");
-    if (!p->traj_R) return fail(RL_EINVAL, "rl_plan_horizon: no trajectory stage since the plan's last run");
-    if (int rc = check_hzn(query, p->traj_R, p->N, p->closed)) return rc;
-    return query_enqueue(p, p->hzn, as_stp(as_rjn(*query)), hip_stream);
-}
-
-int rl_plan_fetch_horizon(rl_plan* p, rl_hzn* out) {
-    if (!p) return fail(RL_EINVAL, "plan is NULL");
-    if (!out) return fail(RL_EINVAL, "rl_plan_fetch_horizon: out is NULL");
-    if (!p->hzn.Q || !p->traj_R)
-        return fail(RL_EINVAL, "rl_plan_fetch_horizon: no horizon stage since the plan's last run or trajectory stage");
-    return query_fetch(p, p->hzn, as_stp(as_rjn(*out)));
-}
-
-// blocks of its own: the last horizon stage stays as it is
-int rl_plan_rejoin(rl_plan* p, const rl_rjn_query* query, void* hip_stream) {
-    if (!p) return fail(RL_EINVAL, "plan is NULL");
-    if (!query) return fail(RL_EINVAL, "rejoin: the query is NULL");
-    if (!p->traj_R) return fail(RL_EINVAL, "rl_plan_rejoin: no trajectory stage since the plan's last run");
-    if (int rc = check_rjn(query, p->traj_R, p->N, p->closed)) return rc;
-    return query_enqueue(p, p->rjn, as_stp(*query), hip_stream);
-}
-
-int rl_plan_fetch_rejoin(rl_plan* p, rl_rjn* out) {
-    if (!p) return fail(RL_EINVAL, "plan is NULL");
-    if (!out) return fail(RL_EINVAL, "rl_plan_fetch_rejoin: out is NULL");
-    if (!p->rjn.Q || !p->traj_R)
-        return fail(RL_EINVAL, "rl_plan_fetch_rejoin: no rejoin stage since the plan's last run or trajectory stage");
-    return query_fetch(p, p->rjn, as_stp(*out));
-}
-
-// blocks of its own: the last horizon and rejoin stages stay as they are
-int rl_plan_stop(rl_plan* p, const rl_stp_query* query, void* hip_stream) {
-    if (!p) return fail(RL_EINVAL, "plan is NULL");
-    if (!query) return fail(RL_EINVAL, "stop: the query is NULL");
-    if (!p->traj_R) return fail(RL_EINVAL, "rl_plan_stop: no trajectory stage since the plan's last run");
-    if (int rc = check_stp(query, p->traj_R, p->N, p->closed)) return rc;
-    return query_enqueue(p, p->stp, *query, hip_stream);
-}
-
-int rl_plan_fetch_stop(rl_plan* p, rl_stp* out) {
-    if (!p) return fail(RL_EINVAL, "plan is NULL");
-    if (!out) return fail(RL_EINVAL, "rl_plan_fetch_stop: out is NULL");
-    if (!p->stp.Q || !p->traj_R)
-        return fail(RL_EINVAL, "rl_plan_fetch_stop: no stop stage since the plan's last run or trajectory stage");
-    return query_fetch(p, p->stp, *out);
-}
-
-// blocks of its own: the last horizon, rejoin and stop stages stay as they are
-int rl_plan_retime(rl_plan* p, const rl_rtm_query* query, void* hip_stream) {
-    if (!p) return fail(RL_EINVAL, "plan is NULL");
-    if (!query) return fail(RL_EINVAL, "retime: the query is NULL");
-    if (!p->traj_R) return fail(RL_EINVAL, "rl_plan_retime: no trajectory stage since the plan's last run");
-    if (int rc = check_rjn(&query->rj, p->traj_R, p->N, p->closed)) return rc;
-    return query_enqueue(p, p->rtm, as_stp(query->rj), hip_stream, true);
-}
-
-int rl_plan_fetch_retime(rl_plan* p, rl_rtm* out) {
-    if (!p) return fail(RL_EINVAL, "plan is NULL");
-    if (!out) return fail(RL_EINVAL, "rl_plan_fetch_retime: out is NULL");
-    if (!p->rtm.Q || !p->traj_R)
-        return fail(RL_EINVAL, "rl_plan_fetch_retime: no retime stage since the plan's last run or trajectory stage");
-    return query_fetch(p, p->rtm, *out);
-}
-
-// blocks of its own: the last horizon, rejoin, stop and retime stages stay as they are; it reads
-// the bounds stage's rows where they lie
-int rl_plan_recover(rl_plan* p, const rl_rcv_query* query, void* hip_stream) {
-    if (!p) return fail(RL_EINVAL, "plan is NULL");
-    if (!query) return fail(RL_EINVAL, "recover: the query is NULL");
-    if (!p->traj_R) return fail(RL_EINVAL, "rl_plan_recover: no trajectory stage since the plan's last run");
-    if (int rc = check_rcv(query, p->traj_R, p->N, p->closed)) return rc;
-    if (!p->bnd_R) return fail(RL_EINVAL, "rl_plan_recover: no bounds stage since the plan's last trajectory stage");
-    return query_enqueue(p, p->rcv, as_stp(query->rj), hip_stream, true, query);
-}
-
-int rl_plan_fetch_recover(rl_plan* p, rl_rcv* out) {
-    if (!p) return fail(RL_EINVAL, "plan is NULL");
-    if (!out) return fail(RL_EINVAL, "rl_plan_fetch_recover: out is NULL");
-    if (!p->rcv.Q || !p->traj_R || !p->bnd_R)
-        return fail(RL_EINVAL, "rl_plan_fetch_recover: no recover stage since the plan's last run, trajectory or bounds stage");
-    return query_fetch(p, p->rcv, *out);
-}
-
-// blocks of its own, and the candidates' scratch block: every other stage stays as it is; it
-// reads the bounds stage's rows where they lie
-int rl_plan_recover_fan(rl_plan* p, const rl_fan_query* query, void* hip_stream) {
-    if (!p) return fail(RL_EINVAL, "plan is NULL");
-    if (!query) return fail(RL_EINVAL, "recover fan: the query is NULL");
-    if (!p->traj_R) return fail(RL_EINVAL, "rl_plan_recover_fan: no trajectory stage since the plan's last run");
-    if (int rc = check_fan(query, p->traj_R, p->N, p->closed)) return rc;
-    if (!p->bnd_R) return fail(RL_EINVAL, "rl_plan_recover_fan: no bounds stage since the plan's last trajectory stage");
-    return query_enqueue(p, p->fan, as_stp(query->rc.rj), hip_stream, true, &query->rc, query->n_cand);
-}
-
-int rl_plan_fetch_recover_fan(rl_plan* p, rl_fan* out) {
-    if (!p) return fail(RL_EINVAL, "plan is NULL");
-    if (!out) return fail(RL_EINVAL, "rl_plan_fetch_recover_fan: out is NULL");
-    if (!p->fan.Q || !p->traj_R || !p->bnd_R)
-        return fail(RL_EINVAL, "rl_plan_fetch_recover_fan: no fan stage since the plan's last run, trajectory or bounds stage");
-    return query_fetch(p, p->fan, *out);
-}
+// the pose-query stages: plan_stage and plan_fetch with the kind
+int rl_plan_horizon(rl_plan* p, const rl_hzn_query* query, void* hip_stream) { return plan_stage<QueryKind::Horizon>(p, query, hip_stream); }
+int rl_plan_fetch_horizon(rl_plan* p, rl_hzn* out) { return plan_fetch<QueryKind::Horizon>(p, out); }
+int rl_plan_rejoin(rl_plan* p, const rl_rjn_query* query, void* hip_stream) { return plan_stage<QueryKind::Rejoin>(p, query, hip_stream); }
+int rl_plan_fetch_rejoin(rl_plan* p, rl_rjn* out) { return plan_fetch<QueryKind::Rejoin>(p, out); }
+int rl_plan_stop(rl_plan* p, const rl_stp_query* query, void* hip_stream) { return plan_stage<QueryKind::Stop>(p, query, hip_stream); }
+int rl_plan_fetch_stop(rl_plan* p, rl_stp* out) { return plan_fetch<QueryKind::Stop>(p, out); }
+int rl_plan_retime(rl_plan* p, const rl_rtm_query* query, void* hip_stream) { return plan_stage<QueryKind::Retime>(p, query, hip_stream); }
+int rl_plan_fetch_retime(rl_plan* p, rl_rtm* out) { return plan_fetch<QueryKind::Retime>(p, out); }
+int rl_plan_recover(rl_plan* p, const rl_rcv_query* query, void* hip_stream) { return plan_stage<QueryKind::Recover>(p, query, hip_stream); }
+int rl_plan_fetch_recover(rl_plan* p, rl_rcv* out) { return plan_fetch<QueryKind::Recover>(p, out); }
+int rl_plan_recover_fan(rl_plan* p, const rl_fan_query* query, void* hip_stream) { return plan_stage<QueryKind::Fan>(p, query, hip_stream); }
+int rl_plan_fetch_recover_fan(rl_plan* p, rl_fan* out) { return plan_fetch<QueryKind::Fan>(p, out); }
 
 // One launch of rl_bounds_kernel over the rows the last trajectory stage read: its x, y and
 // index, the plan's resident rings.  Buffers of its own: every other stage stays as it is.
@@ -707,8 +640,8 @@ int rl_plan_bounds(rl_plan* p, const rl_bnd_query* query, void* hip_stream) {
     for (auto& e : p->ev_bnd)
         if (!e) HIPCHK(hipEventCreate(&e));
     HIPCHK(hipStreamWaitEvent(st, p->ev_traj[1], 0));
-    if (p->rcv.ev[1]) HIPCHK(hipStreamWaitEvent(st, p->rcv.ev[1], 0));   // (a recover stage may still read the rows, on another stream)
-    if (p->fan.ev[1]) HIPCHK(hipStreamWaitEvent(st, p->fan.ev[1], 0));   // (and so may a fan stage)
+    for (int k = 0; k < QUERY_KINDS; ++k)              // (a recover or fan stage may still read the rows, on another stream)
+        if (kKinds[k].reads_bounds && p->qs[k].ev[1]) HIPCHK(hipStreamWaitEvent(st, p->qs[k].ev[1], 0));
     p->last_stream = st;
     HIPCHK(hipEventRecord(p->ev_bnd[0], st));
     const TrajParams& t = p->traj_q;
@@ -746,11 +679,11 @@ int rl_plan_fetch_bounds(rl_plan* p, rl_bnd* out) {
 // block and the bounds stage's rows: no upload.
 int rl_plan_horizon_bounds(rl_plan* p, void* hip_stream) {
     if (!p) return fail(RL_EINVAL, "plan is NULL");
-    if (!p->traj_R || !p->hzn.Q || !p->bnd_R)
+    if (!p->traj_R || !p->stage(QueryKind::Horizon).Q || !p->bnd_R)
         return fail(RL_EINVAL, "rl_plan_horizon_bounds: no horizon stage and bounds stage since the plan's last trajectory stage");
     HIPCHK(hipSetDevice(p->device));
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : p->run_stream();
-    const QueryStage& s = p->hzn;
+    const QueryStage& s = p->stage(QueryKind::Horizon);
     p->hb_Q = 0;
     if (int rc = horizon_bounds_alloc(p, (size_t)s.Q, (size_t)s.M)) return rc;
     for (auto& e : p->ev_hb)
@@ -763,7 +696,7 @@ int rl_plan_horizon_bounds(rl_plan* p, void* hip_stream) {
     rl_rjn_query q{};
     q.Q = s.Q; q.M_cap = s.M; q.dt = s.dt;
     rl::HznBndParams h{};
-    h.hz = query_pointers(q, query_layout((size_t)s.Q, (size_t)s.M, 0), s.in, s.out).hz;
+    h.hz = query_pointers(q, query_layout_of(QueryKind::Horizon, (size_t)s.Q, (size_t)s.M, 0), s.in, s.out).hz;
     h.hz.src = p->traj_q;
     h.lo = p->bnd[0]; h.hi = p->bnd[1];
     h.tlo = p->hb[0]; h.thi = p->hb[1]; h.lo0 = p->hb[2]; h.hi0 = p->hb[3];

@@ -445,18 +445,29 @@ class Horizon:
     count: np.ndarray
     dt: float
 
-    @classmethod
-    def alloc(cls, Q: int, m_cap: int, dt: float) -> "Horizon":
-        cols = {n: np.zeros((Q, m_cap)) for n in abi.TRAJ_COLS}
-        loc = {n: np.zeros(Q) for n in abi.HZN_LOC}
-        return cls(**cols, **loc, seg=np.zeros(Q, dtype=np.int32), count=np.zeros(Q, dtype=np.int32), dt=float(dt))
+    # What a pose-query result class holds, by shape: _C its ctypes struct, whose fields are _COLS
+    # float64 [Q, m_cap], _PER float64 [Q], _INTS int32 [Q], _NODES float64 [Q, k_cap + 1] and the
+    # candidates' _TAB_PER float64 and _TAB_INTS int32 [Q, n_cand]; _HOST_INTS and _HOST_NODES are
+    # filled on the host side only.  Subclasses declare the tuples and inherit alloc and as_c.
+    _C = abi.RlHzn
+    _COLS = abi.TRAJ_COLS
+    _PER = abi.HZN_LOC
+    _INTS = ("seg", "count")
+    _NODES = _TAB_PER = _TAB_INTS = _HOST_INTS = _HOST_NODES = ()
 
-    def as_c(self) -> abi.RlHzn:
-        t = abi.RlHzn()
-        for n in abi.TRAJ_COLS + abi.HZN_LOC:
+    @classmethod
+    def alloc(cls, Q: int, m_cap: int, dt: float, k_cap: int = 1, n_cand: int = 1):
+        groups = ((cls._COLS, (Q, m_cap), np.float64), (cls._PER, (Q,), np.float64), (cls._INTS + cls._HOST_INTS, (Q,), np.int32),
+                  (cls._NODES + cls._HOST_NODES, (Q, k_cap + 1), np.float64), (cls._TAB_INTS, (Q, n_cand), np.int32),
+                  (cls._TAB_PER, (Q, n_cand), np.float64))
+        return cls(**{n: np.zeros(shape, dtype=t) for names, shape, t in groups for n in names}, dt=float(dt))
+
+    def as_c(self):
+        t = self._C()
+        for n in self._COLS + self._PER + self._NODES + self._TAB_PER:
             setattr(t, n, _ptr(getattr(self, n), np.float64, n))
-        t.seg = _ptr(self.seg, np.int32, "seg")
-        t.count = _ptr(self.count, np.int32, "count")
+        for n in self._INTS + self._TAB_INTS:
+            setattr(t, n, _ptr(getattr(self, n), np.int32, n))
         return t
 
     def row(self, q: int) -> dict:
@@ -704,21 +715,11 @@ class Rejoin(_FromTheCar):
     node_t: np.ndarray = None
     k_lim: np.ndarray = None      # [Q] nodes the march may take (host side: from seg, N and closed)
 
-    @classmethod
-    def alloc(cls, Q: int, m_cap: int, dt: float, k_cap: int = 1) -> "Rejoin":
-        cols = {n: np.zeros((Q, m_cap)) for n in abi.TRAJ_COLS}
-        per = {n: np.zeros(Q) for n in abi.HZN_LOC + abi.RJN_SCAL}
-        ints = {n: np.zeros(Q, dtype=np.int32) for n in abi.RJN_INTS}
-        nodes = {n: np.zeros((Q, k_cap + 1)) for n in abi.RJN_NODES}
-        return cls(**cols, **per, **ints, **nodes, k_lim=np.zeros(Q, dtype=np.int32), dt=float(dt))
-
-    def as_c(self) -> abi.RlRjn:
-        t = abi.RlRjn()
-        for n in abi.TRAJ_COLS + abi.HZN_LOC + abi.RJN_SCAL + abi.RJN_NODES:
-            setattr(t, n, _ptr(getattr(self, n), np.float64, n))
-        for n in abi.RJN_INTS:
-            setattr(t, n, _ptr(getattr(self, n), np.int32, n))
-        return t
+    _C = abi.RlRjn
+    _PER = abi.HZN_LOC + abi.RJN_SCAL
+    _INTS = abi.RJN_INTS
+    _NODES = abi.RJN_NODES
+    _HOST_INTS = ("k_lim",)
 
     def set_k_lim(self, N: int, closed: bool) -> None:
         room = np.full(self.seg.shape, N) if closed else N - 1 - self.seg
@@ -984,21 +985,10 @@ class Stop(_FromTheCar):
     node_t: np.ndarray = None
     node_b: np.ndarray = None
 
-    @classmethod
-    def alloc(cls, Q: int, m_cap: int, dt: float, k_cap: int = 1) -> "Stop":
-        cols = {n: np.zeros((Q, m_cap)) for n in abi.TRAJ_COLS}
-        per = {n: np.zeros(Q) for n in abi.HZN_LOC + abi.STP_SCAL}
-        ints = {n: np.zeros(Q, dtype=np.int32) for n in abi.STP_INTS}
-        nodes = {n: np.zeros((Q, k_cap + 1)) for n in abi.STP_NODES}
-        return cls(**cols, **per, **ints, **nodes, dt=float(dt))
-
-    def as_c(self) -> abi.RlStp:
-        t = abi.RlStp()
-        for n in abi.TRAJ_COLS + abi.HZN_LOC + abi.STP_SCAL + abi.STP_NODES:
-            setattr(t, n, _ptr(getattr(self, n), np.float64, n))
-        for n in abi.STP_INTS:
-            setattr(t, n, _ptr(getattr(self, n), np.int32, n))
-        return t
+    _C = abi.RlStp
+    _PER = abi.HZN_LOC + abi.STP_SCAL
+    _INTS = abi.STP_INTS
+    _NODES = abi.STP_NODES
 
     def node_end(self, q: int) -> int:
         """K_s: the target's march node of query q (-1: out of range)."""
@@ -1151,21 +1141,10 @@ class Retime(_FromTheCar):
     node_b: np.ndarray = None
     node_c: np.ndarray = None
 
-    @classmethod
-    def alloc(cls, Q: int, m_cap: int, dt: float, k_cap: int = 1) -> "Retime":
-        cols = {n: np.zeros((Q, m_cap)) for n in abi.TRAJ_COLS}
-        per = {n: np.zeros(Q) for n in abi.HZN_LOC + abi.RTM_SCAL}
-        ints = {n: np.zeros(Q, dtype=np.int32) for n in abi.RTM_INTS}
-        nodes = {n: np.zeros((Q, k_cap + 1)) for n in abi.RTM_NODES}
-        return cls(**cols, **per, **ints, **nodes, dt=float(dt))
-
-    def as_c(self) -> abi.RlRtm:
-        t = abi.RlRtm()
-        for n in abi.TRAJ_COLS + abi.HZN_LOC + abi.RTM_SCAL + abi.RTM_NODES:
-            setattr(t, n, _ptr(getattr(self, n), np.float64, n))
-        for n in abi.RTM_INTS:
-            setattr(t, n, _ptr(getattr(self, n), np.int32, n))
-        return t
+    _C = abi.RlRtm
+    _PER = abi.HZN_LOC + abi.RTM_SCAL
+    _INTS = abi.RTM_INTS
+    _NODES = abi.RTM_NODES
 
     def node_end(self, q: int) -> int:
         """K: the last march node of query q (-1: no answer)."""
@@ -1419,21 +1398,12 @@ class Recover(Retime):
     node_k: np.ndarray = None
     node_psi: np.ndarray = None   # [Q, k_cap + 1] the nodes' headings (host side: recover_host fills it, the library does not)
 
-    @classmethod
-    def alloc(cls, Q: int, m_cap: int, dt: float, k_cap: int = 1) -> "Recover":
-        cols = {n: np.zeros((Q, m_cap)) for n in abi.TRAJ_COLS + abi.RCV_COLS}
-        per = {n: np.zeros(Q) for n in abi.HZN_LOC + abi.RCV_SCAL}
-        ints = {n: np.zeros(Q, dtype=np.int32) for n in abi.RCV_INTS}
-        nodes = {n: np.zeros((Q, k_cap + 1)) for n in abi.RCV_NODES + ("node_psi",)}
-        return cls(**cols, **per, **ints, **nodes, dt=float(dt))
-
-    def as_c(self) -> abi.RlRcv:
-        t = abi.RlRcv()
-        for n in abi.TRAJ_COLS + abi.RCV_COLS + abi.HZN_LOC + abi.RCV_SCAL + abi.RCV_NODES:
-            setattr(t, n, _ptr(getattr(self, n), np.float64, n))
-        for n in abi.RCV_INTS:
-            setattr(t, n, _ptr(getattr(self, n), np.int32, n))
-        return t
+    _C = abi.RlRcv
+    _COLS = abi.TRAJ_COLS + abi.RCV_COLS
+    _PER = abi.HZN_LOC + abi.RCV_SCAL
+    _INTS = abi.RCV_INTS
+    _NODES = abi.RCV_NODES
+    _HOST_NODES = ("node_psi",)
 
     def row(self, q: int) -> dict:
         """Retime's ticks of query q, and their offset."""
@@ -1664,22 +1634,10 @@ class RecoverFan(Recover):
     cand_t_loss: np.ndarray = None
     cand_v_excess: np.ndarray = None
 
-    @classmethod
-    def alloc(cls, Q: int, m_cap: int, dt: float, k_cap: int = 1, n_cand: int = 1) -> "RecoverFan":
-        base = Recover.alloc(Q, m_cap, dt, k_cap)
-        tab = {n: np.zeros((Q, n_cand), dtype=np.int32) for n in abi.FAN_TAB_INTS}
-        tab.update({n: np.zeros((Q, n_cand)) for n in abi.FAN_TAB_SCAL})
-        return cls(**{f: getattr(base, f) for f in base.__dataclass_fields__}, best=np.zeros(Q, dtype=np.int32), **tab)
-
-    def as_c(self) -> abi.RlFan:
-        t, r = abi.RlFan(), super().as_c()
-        for n, _ in abi.RlRcv._fields_:
-            setattr(t, n, getattr(r, n))
-        for n in ("best",) + abi.FAN_TAB_INTS:
-            setattr(t, n, _ptr(getattr(self, n), np.int32, n))
-        for n in abi.FAN_TAB_SCAL:
-            setattr(t, n, _ptr(getattr(self, n), np.float64, n))
-        return t
+    _C = abi.RlFan
+    _INTS = abi.RCV_INTS + ("best",)
+    _TAB_INTS = abi.FAN_TAB_INTS
+    _TAB_PER = abi.FAN_TAB_SCAL
 
 
 def fan_order(feasible, clamped, merge_node, t_end) -> tuple:
@@ -1804,6 +1762,10 @@ def rank_scores(scores, k: int, group_size: Optional[int] = None, device: int = 
     index = np.zeros((B // group_size, k), dtype=np.int32)
     _check(_lib().rl_rank_scores(abi.dptr(sc), B, int(group_size), int(k), int(device), abi.iptr(index)))
     return index
+
+
+_STAGE_RESULTS = {"horizon": Horizon, "rejoin": Rejoin, "stop": Stop, "retime": Retime, "recover": Recover,
+                  "recover_fan": RecoverFan}
 
 
 class Plan:
@@ -1934,6 +1896,31 @@ class Plan:
         _check(_lib().rl_plan_fetch_trajectory(self._h, C.byref(t)))
         return out
 
+    # The pose-query stages (abi.QUERY_STAGES): `kind` names the C entry points rl_plan_<kind> and
+    # rl_plan_fetch_<kind>, the public methods <kind>() and fetch_<kind>() and, in _STAGE_RESULTS,
+    # the result class.  The shape of the last enqueued stage of each kind (the arguments of the
+    # class's alloc) is what its fetch allocates; None: no stage, or one that failed.
+    def _stage_enqueue(self, kind: str, qc, shape: tuple, stream_ptr: int = 0) -> None:
+        shapes = self.__dict__.setdefault("_stage_shapes", {})
+        shapes[kind] = None
+        _check(getattr(_lib(), "rl_plan_" + kind)(self._h, C.byref(qc), C.c_void_p(stream_ptr) if stream_ptr else None))
+        shapes[kind] = shape
+
+    def _stage_fetch(self, kind: str, nodes: bool):
+        cls, fetch = _STAGE_RESULTS[kind], getattr(_lib(), "rl_plan_fetch_" + kind)
+        shape = self.__dict__.get("_stage_shapes", {}).get(kind)
+        if shape is None:
+            t = cls._C()                    # (the library's own answer: no stage on this plan)
+            _check(fetch(self._h, C.byref(t)))
+            raise ValueError(f"fetch_{kind}: no {kind}() on this plan")
+        out = cls.alloc(*shape)
+        t = out.as_c()
+        if not nodes:
+            for n in cls._NODES:
+                setattr(t, n, None)
+        _check(fetch(self._h, C.byref(t)))
+        return out
+
     def horizon(self, poses, row=None, seg_hint=None, window: int = 0, dt: float = 0.05, m_cap: int = 64,
                 stream_ptr: int = 0) -> None:
         """Enqueue the horizon stage after the last trajectory() (rl_plan_horizon): locate the
@@ -1942,22 +1929,11 @@ class Plan:
         across the start line on a closed track.  As often as the caller likes without another
         run(); the trajectory stage stays as it is."""
         P, rw, hint = _hzn_query(poses, row, seg_hint, window, dt, m_cap)
-        self._hzn = None
-        qc = _hzn_c(P, rw, hint, window, dt, m_cap)
-        _check(_lib().rl_plan_horizon(self._h, C.byref(qc), C.c_void_p(stream_ptr) if stream_ptr else None))
-        self._hzn = (P.shape[0], int(m_cap), float(dt))
+        self._stage_enqueue("horizon", _hzn_c(P, rw, hint, window, dt, m_cap), (P.shape[0], int(m_cap), float(dt)), stream_ptr)
 
     def fetch_horizon(self) -> Horizon:
         """Download the last horizon() (rl_plan_fetch_horizon)."""
-        if getattr(self, "_hzn", None) is None:
-            t = abi.RlHzn()                 # (the library's own answer: no stage on this plan)
-            _check(_lib().rl_plan_fetch_horizon(self._h, C.byref(t)))
-            raise ValueError("fetch_horizon: no horizon() on this plan")
-        Q, m_cap, dt = self._hzn
-        out = Horizon.alloc(Q, m_cap, dt)
-        t = out.as_c()
-        _check(_lib().rl_plan_fetch_horizon(self._h, C.byref(t)))
-        return out
+        return self._stage_fetch("horizon", True)
 
     def rejoin(self, poses, v0, cfg: RlCfg, row=None, seg_hint=None, window: int = 0, dt: float = 0.05,
                m_cap: int = 64, k_cap: int = 1024, stream_ptr: int = 0) -> None:
@@ -1967,24 +1943,13 @@ class Plan:
         meets the row's own, at most k_cap samples ahead.  The trajectory stage and the last
         horizon() stay as they are."""
         P, rw, hint, V0 = _rjn_query(poses, v0, cfg, row, seg_hint, window, dt, m_cap, k_cap)
-        self._rjn = None
-        qc = _rjn_c(P, rw, hint, V0, cfg, window, dt, m_cap, k_cap)
-        _check(_lib().rl_plan_rejoin(self._h, C.byref(qc), C.c_void_p(stream_ptr) if stream_ptr else None))
-        self._rjn = (P.shape[0], int(m_cap), float(dt), int(k_cap))
+        self._stage_enqueue("rejoin", _rjn_c(P, rw, hint, V0, cfg, window, dt, m_cap, k_cap),
+                            (P.shape[0], int(m_cap), float(dt), int(k_cap)), stream_ptr)
 
     def fetch_rejoin(self, nodes: bool = True) -> Rejoin:
         """Download the last rejoin() (rl_plan_fetch_rejoin); nodes=False leaves node_v, node_t on
         the device."""
-        if getattr(self, "_rjn", None) is None:
-            t = abi.RlRjn()                 # (the library's own answer: no stage on this plan)
-            _check(_lib().rl_plan_fetch_rejoin(self._h, C.byref(t)))
-            raise ValueError("fetch_rejoin: no rejoin() on this plan")
-        Q, m_cap, dt, k_cap = self._rjn
-        out = Rejoin.alloc(Q, m_cap, dt, k_cap)
-        t = out.as_c()
-        if not nodes:
-            t.node_v = t.node_t = None
-        _check(_lib().rl_plan_fetch_rejoin(self._h, C.byref(t)))
+        out = self._stage_fetch("rejoin", nodes)
         out.set_k_lim(self.N, bool(self._keep[0].closed))
         return out
 
@@ -1996,25 +1961,13 @@ class Plan:
         samples ahead.  The trajectory stage and the last horizon() and rejoin() stay as they
         are."""
         P, rw, hint, V0, J, VT = _stp_query(poses, v0, cfg, stop_sample, v_target, row, seg_hint, window, dt, m_cap, k_cap)
-        self._stp = None
-        qc = _stp_c(P, rw, hint, V0, cfg, J, None if v_target is None else VT, window, dt, m_cap, k_cap)
-        _check(_lib().rl_plan_stop(self._h, C.byref(qc), C.c_void_p(stream_ptr) if stream_ptr else None))
-        self._stp = (P.shape[0], int(m_cap), float(dt), int(k_cap))
+        self._stage_enqueue("stop", _stp_c(P, rw, hint, V0, cfg, J, None if v_target is None else VT, window, dt, m_cap, k_cap),
+                            (P.shape[0], int(m_cap), float(dt), int(k_cap)), stream_ptr)
 
     def fetch_stop(self, nodes: bool = True) -> Stop:
         """Download the last stop() (rl_plan_fetch_stop); nodes=False leaves node_v, node_t, node_b
         on the device."""
-        if getattr(self, "_stp", None) is None:
-            t = abi.RlStp()                 # (the library's own answer: no stage on this plan)
-            _check(_lib().rl_plan_fetch_stop(self._h, C.byref(t)))
-            raise ValueError("fetch_stop: no stop() on this plan")
-        Q, m_cap, dt, k_cap = self._stp
-        out = Stop.alloc(Q, m_cap, dt, k_cap)
-        t = out.as_c()
-        if not nodes:
-            t.node_v = t.node_t = t.node_b = None
-        _check(_lib().rl_plan_fetch_stop(self._h, C.byref(t)))
-        return out
+        return self._stage_fetch("stop", nodes)
 
     def retime(self, poses, v0, cfg: RlCfg, row=None, seg_hint=None, window: int = 0, dt: float = 0.05,
                m_cap: int = 64, k_cap: int = 1024, stream_ptr: int = 0) -> None:
@@ -2024,25 +1977,13 @@ class Plan:
         row's.  The trajectory stage and the last horizon(), rejoin() and stop() stay as they
         are."""
         P, rw, hint, V0 = _rjn_query(poses, v0, cfg, row, seg_hint, window, dt, m_cap, k_cap)
-        self._rtm = None
-        qc = _rtm_c(P, rw, hint, V0, cfg, window, dt, m_cap, k_cap)
-        _check(_lib().rl_plan_retime(self._h, C.byref(qc), C.c_void_p(stream_ptr) if stream_ptr else None))
-        self._rtm = (P.shape[0], int(m_cap), float(dt), int(k_cap))
+        self._stage_enqueue("retime", _rtm_c(P, rw, hint, V0, cfg, window, dt, m_cap, k_cap),
+                            (P.shape[0], int(m_cap), float(dt), int(k_cap)), stream_ptr)
 
     def fetch_retime(self, nodes: bool = True) -> Retime:
         """Download the last retime() (rl_plan_fetch_retime); nodes=False leaves node_v, node_t,
         node_b, node_c on the device."""
-        if getattr(self, "_rtm", None) is None:
-            t = abi.RlRtm()                 # (the library's own answer: no stage on this plan)
-            _check(_lib().rl_plan_fetch_retime(self._h, C.byref(t)))
-            raise ValueError("fetch_retime: no retime() on this plan")
-        Q, m_cap, dt, k_cap = self._rtm
-        out = Retime.alloc(Q, m_cap, dt, k_cap)
-        t = out.as_c()
-        if not nodes:
-            t.node_v = t.node_t = t.node_b = t.node_c = None
-        _check(_lib().rl_plan_fetch_retime(self._h, C.byref(t)))
-        return out
+        return self._stage_fetch("retime", nodes)
 
     def recover(self, poses, v0, cfg: RlCfg, merge_len, dir_xy=None, row=None, seg_hint=None, window: int = 0,
                 dt: float = 0.05, m_cap: int = 64, k_cap: int = 512, stream_ptr: int = 0) -> None:
@@ -2052,26 +1993,13 @@ class Plan:
         offset back to the row inside the bounds stage's free width and cfg's speed profile on
         it.  Every other stage stays as it is; a later bounds() invalidates it."""
         P, rw, hint, V0, D, H = _rcv_query(poses, v0, cfg, merge_len, dir_xy, row, seg_hint, window, dt, m_cap, k_cap)
-        self._rcv = None
-        qc = _rcv_c(P, rw, hint, V0, D, H, cfg, window, dt, m_cap, k_cap)
-        _check(_lib().rl_plan_recover(self._h, C.byref(qc), C.c_void_p(stream_ptr) if stream_ptr else None))
-        self._rcv = (P.shape[0], int(m_cap), float(dt), int(k_cap))
+        self._stage_enqueue("recover", _rcv_c(P, rw, hint, V0, D, H, cfg, window, dt, m_cap, k_cap),
+                            (P.shape[0], int(m_cap), float(dt), int(k_cap)), stream_ptr)
 
     def fetch_recover(self, nodes: bool = True) -> Recover:
         """Download the last recover() (rl_plan_fetch_recover); nodes=False leaves the node arrays
         on the device."""
-        if getattr(self, "_rcv", None) is None:
-            t = abi.RlRcv()                 # (the library's own answer: no stage on this plan)
-            _check(_lib().rl_plan_fetch_recover(self._h, C.byref(t)))
-            raise ValueError("fetch_recover: no recover() on this plan")
-        Q, m_cap, dt, k_cap = self._rcv
-        out = Recover.alloc(Q, m_cap, dt, k_cap)
-        t = out.as_c()
-        if not nodes:
-            for n in abi.RCV_NODES:
-                setattr(t, n, None)
-        _check(_lib().rl_plan_fetch_recover(self._h, C.byref(t)))
-        return out
+        return self._stage_fetch("recover", nodes)
 
     def recover_fan(self, poses, v0, cfg: RlCfg, merge_lens, dir_xy=None, row=None, seg_hint=None, window: int = 0,
                     dt: float = 0.05, m_cap: int = 64, k_cap: int = 512, stream_ptr: int = 0) -> None:
@@ -2081,25 +2009,13 @@ class Plan:
         fan_order's order and the winner is served.  Every other stage stays as it is; a later
         bounds() invalidates it."""
         P, rw, hint, V0, D, H = _fan_query(poses, v0, cfg, merge_lens, dir_xy, row, seg_hint, window, dt, m_cap, k_cap)
-        self._fan = None
-        qc = _fan_c(P, rw, hint, V0, D, H, cfg, window, dt, m_cap, k_cap)
-        _check(_lib().rl_plan_recover_fan(self._h, C.byref(qc), C.c_void_p(stream_ptr) if stream_ptr else None))
-        self._fan = (P.shape[0], int(m_cap), float(dt), int(k_cap), D.shape[1])
+        self._stage_enqueue("recover_fan", _fan_c(P, rw, hint, V0, D, H, cfg, window, dt, m_cap, k_cap),
+                            (P.shape[0], int(m_cap), float(dt), int(k_cap), D.shape[1]), stream_ptr)
 
     def fetch_recover_fan(self, nodes: bool = True) -> RecoverFan:
         """Download the last recover_fan() (rl_plan_fetch_recover_fan): the winner's fields, best
         and the candidates' table; nodes=False leaves the node arrays on the device."""
-        if getattr(self, "_fan", None) is None:
-            t = abi.RlFan()                 # (the library's own answer: no stage on this plan)
-            _check(_lib().rl_plan_fetch_recover_fan(self._h, C.byref(t)))
-            raise ValueError("fetch_recover_fan: no recover_fan() on this plan")
-        out = RecoverFan.alloc(*self._fan)
-        t = out.as_c()
-        if not nodes:
-            for n in abi.RCV_NODES:
-                setattr(t, n, None)
-        _check(_lib().rl_plan_fetch_recover_fan(self._h, C.byref(t)))
-        return out
+        return self._stage_fetch("recover_fan", nodes)
 
     def bounds(self, veh_width: Optional[float] = None, margin: Optional[float] = None, stream_ptr: int = 0) -> None:
         """Enqueue the bounds stage after the last trajectory() (rl_plan_bounds): the free track
@@ -2129,7 +2045,7 @@ class Plan:
         the last bounds() of the same trajectory(); nothing is uploaded."""
         self._hbnd = None
         _check(_lib().rl_plan_horizon_bounds(self._h, C.c_void_p(stream_ptr) if stream_ptr else None))
-        self._hbnd = getattr(self, "_hzn", None)
+        self._hbnd = self.__dict__.get("_stage_shapes", {}).get("horizon")
 
     def fetch_horizon_bounds(self) -> HorizonBounds:
         """Download the last horizon_bounds() (rl_plan_fetch_horizon_bounds)."""

@@ -1,7 +1,7 @@
 """The fan stage's specification without a GPU: raceline.fan_order on constructed
 tables, raceline.recover_fan_host against recover_host on the two rows of recover_cases with the
 candidate set of recover_fan_cases, the argument checks of the C entry point (which come before any
-device work: there is no device here), the packed blocks (tests/recover_fan_layout_check.cpp) and
+device work: there is no device here), the packed blocks (tests/query_layout_check.cpp as "recover_fan") and
 the ABI's new structs, constants and feature bit."""
 import ctypes as C
 import os
@@ -11,6 +11,7 @@ import tempfile
 import numpy as np
 import pytest
 
+import layout_check as LC
 import oracle_lib as O
 import recover_cases as RC
 import recover_fan_cases as FC
@@ -18,8 +19,6 @@ from practice_path_planning_for_formula_student_driverless_amd import abi, racel
 from recover_cases import bits
 
 HEADER = os.path.join(O.REPO, "include", "rl_abi.h")
-CSRC = os.path.join(O.REPO, "practice_path_planning_for_formula_student_driverless_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 NAN = float("nan")
 
 
@@ -200,25 +199,12 @@ def test_c_abi_argument_checks_come_before_any_device_work():
 
 # ------------------------------------------------------------------ the packed blocks
 def test_recover_fan_layout(tmp_path):
-    """tests/recover_fan_layout_check.cpp, a stand-alone program (its own main, host code only), built
-    as test_recover_cpu.py builds its program: with AddressSanitizer and UBSan on the host side where
+    """tests/query_layout_check.cpp run as "recover_fan", a stand-alone program (its own main, host code
+    only), built by tests/layout_check.py: with AddressSanitizer and UBSan on the host side where
     that links, without them otherwise, and the test says which."""
-    if not os.path.exists(HIPCC):
-        pytest.fail(f"{HIPCC} is missing: the layout check cannot be built (the library's build needs it too)")
-    src = os.path.join(O.REPO, "tests", "recover_fan_layout_check.cpp")
-    flags = ["-O1", "-g", "-std=c++17", "--cuda-host-only", "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Werror",
-             "-I" + CSRC, "-I" + os.path.join(O.REPO, "include")]
-    sanitize = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all"]
-    exe = str(tmp_path / "recover_fan_layout_check")
-    r = subprocess.run([HIPCC, *flags, *sanitize, src, "-o", exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    sanitized = r.returncode == 0
-    if not sanitized:
-        print("the sanitizer build failed, building without:\n" + r.stdout[-2000:])
-        subprocess.run([HIPCC, *flags, src, "-o", exe], check=True)
-    run = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    print(("with" if sanitized else "WITHOUT") + " -fsanitize=address,undefined:\n" + run.stdout)
-    assert run.returncode == 0, run.stdout
-    assert "recover fan layout ok" in run.stdout
+    if not os.path.exists(LC.HIPCC):
+        pytest.fail(f"{LC.HIPCC} is missing: the layout check cannot be built (the library's build needs it too)")
+    assert "recover_fan layout ok" in LC.run_stage(tmp_path, "recover_fan")
 
 
 # ------------------------------------------------------------------ the ABI
