@@ -84,6 +84,7 @@
 #include <iostream>
 #include <limits>
 #include <map>
+#include <optional>
 #include <queue>
 #include <random>
 #include <sstream>
@@ -1209,13 +1210,25 @@ static void compute_mintime_and_save(const string& base, const vector<Vec2>& cen
     if (C.debug_dump) debug_dump(base, center_for_opt, s0, L, closed_mode, res);
 }
 
-// --retime-set / --retime-from: the knobs that replace this run's cfg in the retime stage, and
-// the sample the winners start from (-1: not given)
+// ---- the centreline form: fsd_raceline centerline.csv [options] ----
+// BatchOpt is every option of the form: main fills it, check_options (below) validates it and
+// fills the defaults in, and nothing else holds option state.  A stage with a switch of its own
+// has one field group here, one check there and one stage_* function called from batch_and_save.
+// An option that can be left out is a std::optional.
+
+// --stop-sample J [--stop-speed V] [--stop-from K]: the target sample, the speed there (0) and
+// the samples before it that the winners start from (512)
+struct StopOpt {
+    std::optional<int> sample, from;
+    std::optional<double> speed;
+};
+
+// --retime-set / --retime-from: the knobs that replace this run's cfg in the retime stage, in
+// the order given, and the sample the winners start from (0)
 struct RetimeOpt {
     vector<string> sets;
-    int from = -1;
+    std::optional<int> from;
 };
-static RetimeOpt g_retime;
 
 // --recover-from / --recover-dir / --recover-len / --recover-speed: the car's position, its
 // direction of travel (has_dir), the merge length and its speed (< 0: the raceline's at its
@@ -1225,34 +1238,113 @@ struct RecoverOpt {
     double x = 0, y = 0, hx = 0, hy = 0, len = 20.0, speed = -1.0;
     std::vector<double> fan;
 };
-static RecoverOpt g_recover;
 
-// B α-seeds in one launch (beyond the reference): one summary row per instance.
-static void batch_and_save(const string& base, const vector<Vec2>& center, double L, bool closed,
-                           const vector<Vec2>& inner_from_mids, const vector<Vec2>& outer_from_mids, int B, int modes,
-                           int repeat, int best, bool score_lap, double traj_dt, int traj_cap, double start_speed,
-                           int stop_sample, double stop_speed, int stop_from, bool want_bounds) {
+struct BatchOpt {
+    std::optional<double> L;                 // --L (else the last s of <base>_with_geom.csv)
+    double s0 = 0.0;
+    string mode = "both", score;             // --mode, --score
+    int B = 0, repeat = 0, best = 0;         // --seeds, --repeat, --best (0: none)
+    double traj_dt = 0.0;                    // --trajectory-dt (0: no ticks)
+    int traj_cap = 0;                        // --trajectory-cap (0: 4096)
+    std::optional<double> start_speed;       // --start-speed: the rejoin stage
+    StopOpt stop;
+    RetimeOpt retime;
+    RecoverOpt recover;
+    bool bounds = false;                     // --bounds
+
+    int modes() const {
+        return mode == "mincurv" ? RL_MODE_MINCURV : mode == "mintime" ? RL_MODE_MINTIME : RL_MODE_MINCURV | RL_MODE_MINTIME;
+    }
+    bool mintime() const { return modes() & RL_MODE_MINTIME; }
+    bool score_lap() const { return score == "lap"; }
+    bool ticks() const { return traj_dt > 0.0 && best > 0; }
+    // the rejoin, stop, retime and recover stages need the winners' whole rows and the laps T
+    bool rows() const { return ticks() && (start_speed || stop.sample || !retime.sets.empty() || recover.given); }
+};
+
+// What the form reads: <base>.csv as loaded, the optimisers' input made of it, and the rings.
+struct Track {
+    string base;
+    vector<Vec2> center, path, inner, outer;
+    bool closed = true;
+};
+
+template <class T>
+static T zeroed() {
+    T t;
+    std::memset(&t, 0, sizeof(t));
+    return t;
+}
+
+// The tick columns of one stage's answer, [rows][cap] each: s, x, y, heading, kappa, v, ax,
+// then offset where the stage has one.  The first count[r] ticks of row r are valid.
+struct Ticks {
+    vector<vector<double>> col;
+    vector<int32_t> count;
+    size_t cap = 0;
+    Ticks() = default;
+    Ticks(int n, size_t rows, int cap_) : col((size_t)n, vector<double>(rows * (size_t)cap_)), count(rows), cap((size_t)cap_) {}
+};
+// (rl_traj, rl_rjn, rl_stp, rl_rtm, rl_rcv and rl_fan name these fields alike)
+template <class Out>
+static void bind_ticks(Ticks& t, Out& out) {
+    out.s = t.col[0].data(); out.x = t.col[1].data(); out.y = t.col[2].data(); out.heading = t.col[3].data();
+    out.kappa = t.col[4].data(); out.v = t.col[5].data(); out.ax = t.col[6].data();
+    out.count = t.count.data();
+}
+// <base>_trajectory_<r><suffix>.csv: one row per tick of row r, t = m * dt in front of the
+// columns, the numbers formatted on the GPU
+static void write_ticks(const string& base, size_t r, const string& suffix, const string& what, const Ticks& t, double dt) {
+    const int64_t rows = t.count[r];
+    const size_t w = t.col.size() + 1;
+    vector<double> tab((size_t)rows * w);
+    for (int64_t m = 0; m < rows; ++m) {
+        tab[(size_t)m * w] = (double)m * dt;
+        for (size_t cc = 0; cc + 1 < w; ++cc) tab[(size_t)m * w + 1 + cc] = t.col[cc][r * t.cap + (size_t)m];
+    }
+    vector<char> text((size_t)rows * w * 22 + 1);
+    int64_t len = 0;
+    gpu::check(rl_format_csv(tab.data(), rows, (int32_t)w, gpu::device, text.data(), (int64_t)text.size(), &len, nullptr),
+               "rl_format_csv");
+    io::Csv o(base + "_trajectory_" + std::to_string(r) + suffix + ".csv");
+    if (!o) throw std::runtime_error("save " + what + " failed");
+    o.f << "t,s,x,y,heading_rad,curvature,v_mps,ax_mps2" << (w > 8 ? ",offset_m" : "") << "\n";
+    o.f.write(text.data(), (std::streamsize)len);
+}
+
+// The batch: the problem as the ABI takes it, B α-seeds, and what the run leaves on the host.
+struct Batch {
+    gpu::Packed pk;
+    rl_cfg c;
+    vector<uint64_t> seeds;
+    vector<double> lap, al, x, y;
+    vector<int32_t> ev;
+    Batch(const Track& t, const BatchOpt& o)
+        : pk(gpu::pack(t.path, t.closed ? edges::ringEdges(t.inner) : edges::polylineEdges(t.inner),
+                       t.closed ? edges::ringEdges(t.outer) : edges::polylineEdges(t.outer), cfg::get().veh_width_m, *o.L,
+                       t.closed)),
+          c(cfg::to_abi(cfg::get())), seeds((size_t)o.B), lap((size_t)o.B), al((size_t)o.B * t.path.size()), x(al.size()),
+          y(al.size()), ev((size_t)o.B * cfg::get().max_outer_iters) {
+        for (int b = 0; b < o.B; ++b) seeds[b] = (uint64_t)b;
+    }
+    Batch(const Batch&) = delete;            // (pk.prob points into pk)
+};
+
+// One launch of the batch (beyond the reference), --repeat's timing, --devices' sharding.
+static void run_batch(Batch& b, const BatchOpt& o) {
     auto& C = cfg::get();
-    SegVec innerE = closed ? edges::ringEdges(inner_from_mids) : edges::polylineEdges(inner_from_mids);
-    SegVec outerE = closed ? edges::ringEdges(outer_from_mids) : edges::polylineEdges(outer_from_mids);
-    auto pk = gpu::pack(center, innerE, outerE, C.veh_width_m, L, closed);
-    rl_cfg c = cfg::to_abi(C);
-    vector<uint64_t> seeds(B);
-    for (int b = 0; b < B; ++b) seeds[b] = (uint64_t)b;
-    const size_t BN = (size_t)B * center.size();
-    vector<double> lap(B), al(BN), x(BN), y(BN);
-    vector<int32_t> ev((size_t)B * C.max_outer_iters);
-    rl_out o;
-    std::memset(&o, 0, sizeof(o));
-    o.x = x.data(); o.y = y.data(); o.alpha_last = al.data(); o.evals = ev.data();
-    const bool mt = modes & RL_MODE_MINTIME;
-    if (mt) o.lap = lap.data();
+    const int B = o.B, modes = o.modes();
+    int repeat = o.repeat;
+    rl_out out = zeroed<rl_out>();
+    out.x = b.x.data(); out.y = b.y.data(); out.alpha_last = b.al.data(); out.evals = b.ev.data();
+    const bool mt = o.mintime();
+    if (mt) out.lap = b.lap.data();
     rl_plan* plan = nullptr;
     if (!gpu::devices.empty()) {
         // sharded over the listed devices (one mode per call: the summary reads one)
         auto call = [&]() {
-            gpu::check(rl_optimize_multi(&pk.prob, &c, 1, seeds.data(), B, gpu::devices.data(),
-                                         (int32_t)gpu::devices.size(), mt ? nullptr : &o, mt ? &o : nullptr),
+            gpu::check(rl_optimize_multi(&b.pk.prob, &b.c, 1, b.seeds.data(), B, gpu::devices.data(),
+                                         (int32_t)gpu::devices.size(), mt ? nullptr : &out, mt ? &out : nullptr),
                        "rl_optimize_multi");
         };
         call();
@@ -1266,9 +1358,9 @@ static void batch_and_save(const string& base, const vector<Vec2>& center, doubl
         }
         repeat = 0;
     } else {
-        gpu::check(rl_plan_create(&plan, gpu::device, &pk.prob, &c, 1, seeds.data(), B, modes), "rl_plan_create");
+        gpu::check(rl_plan_create(&plan, gpu::device, &b.pk.prob, &b.c, 1, b.seeds.data(), B, modes), "rl_plan_create");
         gpu::check(rl_plan_run(plan, nullptr), "rl_plan_run");
-        gpu::check(rl_plan_fetch(plan, mt ? nullptr : &o, mt ? &o : nullptr), "rl_plan_fetch");
+        gpu::check(rl_plan_fetch(plan, mt ? nullptr : &out, mt ? &out : nullptr), "rl_plan_fetch");
     }
     if (repeat > 0) {
         auto t0 = std::chrono::steady_clock::now();
@@ -1281,357 +1373,312 @@ static void batch_and_save(const string& base, const vector<Vec2>& center, doubl
                   << " ms -> " << outers * repeat / wall << " PGD outer-iters/s\n";
     }
     if (plan) rl_plan_destroy(plan);
-    // --best K: the K best seeds of the batch, ranked and compacted on the GPU; only their
-    // rows are downloaded.  One file per rank, x,y rows like <base>_raceline.csv.
-    // (--score lap: before the summary, whose lap column is the lap stage's)
-    const size_t N = center.size();
-    vector<int32_t> idx((size_t)std::max(best, 0));
-    vector<double> sc(idx.size()), bx(idx.size() * N), by(idx.size() * N);
-    // --trajectory-dt: the winners' trajectories, resampled on the GPU in the same call
-    const bool want_traj = traj_dt > 0.0 && best > 0;
-    const size_t RM = want_traj ? idx.size() * (size_t)traj_cap : 0;
-    vector<double> tcol[7];
-    for (auto& col : tcol) col.resize(RM);
-    vector<int32_t> tcount(want_traj ? idx.size() : 0);
-    // --start-speed: the rejoin stage needs the winners' whole rows and the laps T
-    const bool want_rjn = want_traj && start_speed >= 0.0;
-    // --stop-sample: the stop stage needs the winners' whole rows as well
-    const bool want_stp = want_traj && stop_sample >= 0;
-    // --retime-set: the retime stage needs the winners' whole rows as well
-    const bool want_rtm = want_traj && !g_retime.sets.empty();
-    // --recover-from: the recover stage needs the winners' whole rows as well
-    const bool want_rcv = want_traj && g_recover.given;
-    const bool want_rows = want_rjn || want_stp || want_rtm || want_rcv;
-    vector<double> wrow[4], tT(want_rows ? idx.size() : 0);      // heading, kappa, v, ax
-    for (auto& col : wrow) col.resize(want_rows ? idx.size() * N : 0);
-    auto run_best = [&]() {
-        rl_select sel;
-        std::memset(&sel, 0, sizeof(sel));
-        sel.mode = modes;
-        sel.k = best;
-        sel.group_size = 0;
-        rl_out ob;
-        std::memset(&ob, 0, sizeof(ob));
-        ob.x = bx.data();
-        ob.y = by.data();
-        if (want_traj) {
-            rl_traj tj;
-            std::memset(&tj, 0, sizeof(tj));
-            tj.s = tcol[0].data(); tj.x = tcol[1].data(); tj.y = tcol[2].data(); tj.heading = tcol[3].data();
-            tj.kappa = tcol[4].data(); tj.v = tcol[5].data(); tj.ax = tcol[6].data();
-            tj.count = tcount.data();
-            if (want_rows) {
-                ob.heading = wrow[0].data(); ob.kappa = wrow[1].data(); ob.v = wrow[2].data(); ob.ax = wrow[3].data();
-                tj.T = tT.data();
-            }
-            gpu::check(rl_optimize_best_trajectory(&pk.prob, &c, 1, seeds.data(), B, &sel,
-                                                   score_lap ? RL_SCORE_LAP : RL_SCORE_DEFAULT, idx.data(), sc.data(),
-                                                   score_lap ? lap.data() : nullptr, &ob, traj_dt, traj_cap, &tj),
-                       "rl_optimize_best_trajectory");
-        } else if (score_lap)
-            gpu::check(rl_optimize_best_scored(&pk.prob, &c, 1, seeds.data(), B, &sel, RL_SCORE_LAP, idx.data(),
-                                               sc.data(), lap.data(), &ob),
-                       "rl_optimize_best_scored");
-        else
-            gpu::check(rl_optimize_best(&pk.prob, &c, 1, seeds.data(), B, &sel, idx.data(), sc.data(), nullptr, &ob),
-                       "rl_optimize_best");
-    };
-    if (best > 0 && score_lap) run_best();
+}
+
+// <base>_batch_summary.csv: one row per instance
+static void save_summary(const string& base, const Batch& b, const BatchOpt& o) {
+    auto& C = cfg::get();
+    const size_t N = (size_t)b.pk.prob.N;
     io::Csv fo(base + "_batch_summary.csv");
     fo.f << "seed,lap_time_s,mean_abs_alpha_last,evals_total\n";
-    for (int b = 0; b < B; ++b) {
+    for (int i = 0; i < o.B; ++i) {
         double s = 0;
-        for (size_t i = 0; i < center.size(); ++i) s += std::fabs(al[b * center.size() + i]);
+        for (size_t k = 0; k < N; ++k) s += std::fabs(b.al[i * N + k]);
         long et = 0;
-        for (int k = 0; k < C.max_outer_iters; ++k) et += ev[(size_t)b * C.max_outer_iters + k];
-        fo.f << b << "," << (mt || score_lap ? lap[b] : 0.0) << "," << s / std::max<size_t>(1, center.size()) << "," << et << "\n";
+        for (int k = 0; k < C.max_outer_iters; ++k) et += b.ev[(size_t)i * C.max_outer_iters + k];
+        fo.f << i << "," << (o.mintime() || o.score_lap() ? b.lap[i] : 0.0) << "," << s / std::max<size_t>(1, N) << "," << et << "\n";
     }
-    if (best <= 0) return;
-    if (!score_lap) run_best();
-    for (int r = 0; r < best; ++r) {
+}
+
+// --best K: the K best seeds of the batch, ranked and compacted on the GPU; only their rows are
+// downloaded.  K rows of N samples a step h apart: seed index, score, x, y; with the stages
+// that need them (BatchOpt::rows) heading, kappa, v, ax and the laps T; with --trajectory-dt
+// the winners' ticks, resampled on the GPU in the same call.
+struct Winners {
+    size_t K = 0, N = 0;
+    bool closed = true;
+    vector<int32_t> idx;
+    vector<double> sc, bx, by, h, row[4], T;
+    Ticks traj;
+};
+
+static Winners run_best(const Track& t, const BatchOpt& o, Batch& b) {
+    Winners w;
+    w.K = (size_t)o.best; w.N = t.path.size(); w.closed = t.closed;
+    w.idx.resize(w.K); w.sc.resize(w.K); w.bx.resize(w.K * w.N); w.by.resize(w.K * w.N);
+    w.h.assign(w.K, *o.L / (double)w.N);
+    rl_select sel = zeroed<rl_select>();
+    sel.mode = o.modes();
+    sel.k = o.best;
+    sel.group_size = 0;
+    rl_out ob = zeroed<rl_out>();
+    ob.x = w.bx.data();
+    ob.y = w.by.data();
+    const int score = o.score_lap() ? RL_SCORE_LAP : RL_SCORE_DEFAULT;
+    double* laps = o.score_lap() ? b.lap.data() : nullptr;         // (--score lap: every seed's lap, for the summary)
+    if (o.ticks()) {
+        w.traj = Ticks(7, w.K, o.traj_cap);
+        rl_traj tj = zeroed<rl_traj>();
+        bind_ticks(w.traj, tj);
+        if (o.rows()) {
+            for (auto& col : w.row) col.resize(w.K * w.N);
+            w.T.resize(w.K);
+            ob.heading = w.row[0].data(); ob.kappa = w.row[1].data(); ob.v = w.row[2].data(); ob.ax = w.row[3].data();
+            tj.T = w.T.data();
+        }
+        gpu::check(rl_optimize_best_trajectory(&b.pk.prob, &b.c, 1, b.seeds.data(), o.B, &sel, score, w.idx.data(), w.sc.data(),
+                                               laps, &ob, o.traj_dt, o.traj_cap, &tj),
+                   "rl_optimize_best_trajectory");
+    } else if (o.score_lap())
+        gpu::check(rl_optimize_best_scored(&b.pk.prob, &b.c, 1, b.seeds.data(), o.B, &sel, RL_SCORE_LAP, w.idx.data(),
+                                           w.sc.data(), laps, &ob),
+                   "rl_optimize_best_scored");
+    else
+        gpu::check(rl_optimize_best(&b.pk.prob, &b.c, 1, b.seeds.data(), o.B, &sel, w.idx.data(), w.sc.data(), nullptr, &ob),
+                   "rl_optimize_best");
+    return w;
+}
+
+// <base>_best<r>_raceline.csv: one file per rank, x,y rows like <base>_raceline.csv
+static void save_best(const string& base, const Winners& w) {
+    for (size_t r = 0; r < w.K; ++r) {
         io::Csv o(base + "_best" + std::to_string(r) + "_raceline.csv");
         if (!o) throw std::runtime_error("save best raceline failed");
-        for (size_t i = 0; i < N; ++i) o.f << bx[r * N + i] << "," << by[r * N + i] << "\n";
-        if (C.emit_closed_duplicate && N > 0) o.f << bx[r * N] << "," << by[r * N] << "\n";
+        for (size_t i = 0; i < w.N; ++i) o.f << w.bx[r * w.N + i] << "," << w.by[r * w.N + i] << "\n";
+        if (cfg::get().emit_closed_duplicate && w.N > 0) o.f << w.bx[r * w.N] << "," << w.by[r * w.N] << "\n";
     }
-    // <base>_trajectory_<r>.csv: one row per tick of winner r, the numbers formatted on the GPU
-    for (int r = 0; want_traj && r < best; ++r) {
-        const int64_t rows = tcount[r];
-        vector<double> tab((size_t)rows * 8);
-        for (int64_t m = 0; m < rows; ++m) {
-            tab[(size_t)m * 8] = (double)m * traj_dt;
-            for (int cc = 0; cc < 7; ++cc) tab[(size_t)m * 8 + 1 + cc] = tcol[cc][(size_t)r * traj_cap + (size_t)m];
-        }
-        vector<char> text((size_t)rows * 8 * 22 + 1);
-        int64_t len = 0;
-        gpu::check(rl_format_csv(tab.data(), rows, 8, gpu::device, text.data(), (int64_t)text.size(), &len, nullptr),
-                   "rl_format_csv");
-        io::Csv o(base + "_trajectory_" + std::to_string(r) + ".csv");
-        if (!o) throw std::runtime_error("save trajectory failed");
-        o.f << "t,s,x,y,heading_rad,curvature,v_mps,ax_mps2\n";
-        o.f.write(text.data(), (std::streamsize)len);
+}
+
+// The part of a pose query that every stage shares: one pose per winner, winner r on row r.
+struct PoseQuery {
+    vector<double> pose, v0;
+    vector<int32_t> row, hint;               // (hint left empty: every segment)
+    explicit PoseQuery(size_t K) : pose(2 * K), v0(K), row(K) {
+        for (size_t r = 0; r < K; ++r) row[r] = (int32_t)r;
     }
-    // <base>_trajectory_<r>_from_v0.csv: winner r from sample 0 at --start-speed, along the speed
-    // profile it can reach with the limits of this run's cfg, until that meets the raceline's own
-    if (want_rjn) {
-        const size_t K = idx.size();
-        vector<double> pose(2 * K), v0(K, start_speed), h(K, L / (double)N), rcol[7], tloss(K);
-        vector<int32_t> row(K), hint(K, 0), rcount(K), merge(K);
-        for (size_t r = 0; r < K; ++r) {
-            pose[2 * r] = bx[r * N];
-            pose[2 * r + 1] = by[r * N];
-            row[r] = (int32_t)r;
+    // every winner at its own sample `at`, at its own speed there
+    void at_sample(const Winners& w, size_t at) {
+        for (size_t r = 0; r < w.K; ++r) {
+            pose[2 * r] = w.bx[r * w.N + at];
+            pose[2 * r + 1] = w.by[r * w.N + at];
+            v0[r] = w.row[2][r * w.N + at];
         }
-        for (auto& col : rcol) col.resize(K * (size_t)traj_cap);
-        rl_rjn_query q;
-        std::memset(&q, 0, sizeof(q));
-        q.pose_xy = pose.data(); q.row = row.data(); q.seg_hint = hint.data();
-        q.Q = (int32_t)K; q.window = 0; q.M_cap = traj_cap; q.dt = traj_dt;
-        q.v0 = v0.data(); q.cfg = &c; q.K_cap = RL_RJN_MAX_NODES;
-        rl_rjn rj;
-        std::memset(&rj, 0, sizeof(rj));
-        rj.s = rcol[0].data(); rj.x = rcol[1].data(); rj.y = rcol[2].data(); rj.heading = rcol[3].data();
-        rj.kappa = rcol[4].data(); rj.v = rcol[5].data(); rj.ax = rcol[6].data();
-        rj.count = rcount.data(); rj.merge_node = merge.data(); rj.t_loss = tloss.data();
-        gpu::check(rl_rejoin(bx.data(), by.data(), wrow[0].data(), wrow[1].data(), wrow[2].data(), wrow[3].data(), h.data(),
-                             (int32_t)N, (int32_t)K, closed ? 1 : 0, &q, gpu::device, &rj),
-                   "rl_rejoin");
-        std::cerr << std::setprecision(9);
-        for (size_t r = 0; r < K; ++r) {
-            const int64_t rows = rcount[r];
-            vector<double> tab((size_t)rows * 8);
-            for (int64_t m = 0; m < rows; ++m) {
-                tab[(size_t)m * 8] = (double)m * traj_dt;
-                for (int cc = 0; cc < 7; ++cc) tab[(size_t)m * 8 + 1 + cc] = rcol[cc][r * (size_t)traj_cap + (size_t)m];
-            }
-            vector<char> text((size_t)rows * 8 * 22 + 1);
-            int64_t len = 0;
-            gpu::check(rl_format_csv(tab.data(), rows, 8, gpu::device, text.data(), (int64_t)text.size(), &len, nullptr),
-                       "rl_format_csv");
-            io::Csv o(base + "_trajectory_" + std::to_string(r) + "_from_v0.csv");
-            if (!o) throw std::runtime_error("save rejoin trajectory failed");
-            o.f << "t,s,x,y,heading_rad,curvature,v_mps,ax_mps2\n";
-            o.f.write(text.data(), (std::streamsize)len);
-            std::cerr << "[rejoin] winner " << r << " from " << start_speed << " m/s: merge node " << merge[r]
-                      << ", standing-start lap " << tT[r] + tloss[r] << " s (flying " << tT[r] << " s)\n";
-        }
+        hint.assign(w.K, (int32_t)at);
     }
-    // <base>_trajectory_<r>_stop.csv: winner r from the sample --stop-from nodes before
-    // --stop-sample, at the raceline's own speed there, braking to --stop-speed at that sample
-    // with the limits of this run's cfg
-    if (want_stp) {
-        const size_t K = idx.size();
-        // the nodes between the pose and the target: what the row and the stage allow
-        int from = std::min(stop_from, (int)RL_RJN_MAX_NODES);
-        from = std::min(from, closed ? (int)N : stop_sample);
-        const int at = ((stop_sample - from) % (int)N + (int)N) % (int)N;   // (open rows: stop_sample - from >= 0)
-        vector<double> pose(2 * K), v0(K), vt(K, stop_speed), h(K, L / (double)N), rcol[7], tstop(K), vend(K);
-        vector<int32_t> row(K), hint(K, at), target(K, stop_sample), rcount(K), node(K), brake(K);
-        for (size_t r = 0; r < K; ++r) {
-            pose[2 * r] = bx[r * N + at];
-            pose[2 * r + 1] = by[r * N + at];
-            v0[r] = wrow[2][r * N + at];
-            row[r] = (int32_t)r;
-        }
-        for (auto& col : rcol) col.resize(K * (size_t)traj_cap);
-        rl_stp_query q;
-        std::memset(&q, 0, sizeof(q));
-        q.rj.pose_xy = pose.data(); q.rj.row = row.data(); q.rj.seg_hint = hint.data();
-        q.rj.Q = (int32_t)K; q.rj.window = 0; q.rj.M_cap = traj_cap; q.rj.dt = traj_dt;
-        q.rj.v0 = v0.data(); q.rj.cfg = &c; q.rj.K_cap = RL_RJN_MAX_NODES;
-        q.stop_sample = target.data(); q.v_target = vt.data();
-        rl_stp sp;
-        std::memset(&sp, 0, sizeof(sp));
-        sp.s = rcol[0].data(); sp.x = rcol[1].data(); sp.y = rcol[2].data(); sp.heading = rcol[3].data();
-        sp.kappa = rcol[4].data(); sp.v = rcol[5].data(); sp.ax = rcol[6].data();
-        sp.count = rcount.data(); sp.stop_node = node.data(); sp.brake_node = brake.data();
-        sp.t_stop = tstop.data(); sp.v_end = vend.data();
-        gpu::check(rl_stop(bx.data(), by.data(), wrow[0].data(), wrow[1].data(), wrow[2].data(), wrow[3].data(), h.data(),
-                           (int32_t)N, (int32_t)K, closed ? 1 : 0, &q, gpu::device, &sp),
-                   "rl_stop");
-        std::cerr << std::setprecision(9);
-        for (size_t r = 0; r < K; ++r) {
-            if (node[r] < 0) throw std::runtime_error("stop: the target is not among the nodes ahead of the pose");
-            const int64_t rows = rcount[r];
-            vector<double> tab((size_t)rows * 8);
-            for (int64_t m = 0; m < rows; ++m) {
-                tab[(size_t)m * 8] = (double)m * traj_dt;
-                for (int cc = 0; cc < 7; ++cc) tab[(size_t)m * 8 + 1 + cc] = rcol[cc][r * (size_t)traj_cap + (size_t)m];
-            }
-            vector<char> text((size_t)rows * 8 * 22 + 1);
-            int64_t len = 0;
-            gpu::check(rl_format_csv(tab.data(), rows, 8, gpu::device, text.data(), (int64_t)text.size(), &len, nullptr),
-                       "rl_format_csv");
-            io::Csv o(base + "_trajectory_" + std::to_string(r) + "_stop.csv");
-            if (!o) throw std::runtime_error("save stop trajectory failed");
-            o.f << "t,s,x,y,heading_rad,curvature,v_mps,ax_mps2\n";
-            o.f.write(text.data(), (std::streamsize)len);
-            std::cerr << "[stop] winner " << r << " from sample " << at << " to " << stop_speed << " m/s at sample " << stop_sample
-                      << ": stop: t_stop " << tstop[r] << " s, brake_node " << brake[r] << " of " << node[r] << ", v_end "
-                      << vend[r] << " m/s\n";
-        }
+    void fill(rl_rjn_query& q, const BatchOpt& o, const rl_cfg* c, int32_t K_cap) const {
+        q.pose_xy = pose.data(); q.row = row.data(); q.seg_hint = hint.empty() ? nullptr : hint.data();
+        q.Q = (int32_t)row.size(); q.window = 0; q.M_cap = o.traj_cap; q.dt = o.traj_dt;
+        q.v0 = v0.data(); q.cfg = c; q.K_cap = K_cap;
     }
-    // <base>_trajectory_<r>_retimed.csv: winner r from sample --retime-from at the raceline's own
-    // speed there, over the samples ahead, with the limits of this run's cfg after --retime-set
-    if (want_rtm) {
-        const size_t K = idx.size();
-        cfg::Config now = C;
-        for (const string& kv : g_retime.sets)
-            if (!cfg::set_knob(now, kv)) throw std::runtime_error("unknown cfg knob: " + kv);
-        const rl_cfg cn = cfg::to_abi(now);
-        const int at = std::max(g_retime.from, 0);
-        vector<double> pose(2 * K), v0(K), h(K, L / (double)N), rcol[7], tend(K), tloss(K);
-        vector<int32_t> row(K), hint(K, at), rcount(K), node(K), bind(K), feas(K);
-        for (size_t r = 0; r < K; ++r) {
-            pose[2 * r] = bx[r * N + at];
-            pose[2 * r + 1] = by[r * N + at];
-            v0[r] = wrow[2][r * N + at];
-            row[r] = (int32_t)r;
-        }
-        for (auto& col : rcol) col.resize(K * (size_t)traj_cap);
-        rl_rtm_query q;
-        std::memset(&q, 0, sizeof(q));
-        q.rj.pose_xy = pose.data(); q.rj.row = row.data(); q.rj.seg_hint = hint.data();
-        q.rj.Q = (int32_t)K; q.rj.window = 0; q.rj.M_cap = traj_cap; q.rj.dt = traj_dt;
-        q.rj.v0 = v0.data(); q.rj.cfg = &cn; q.rj.K_cap = RL_RJN_MAX_NODES;
-        rl_rtm rt;
-        std::memset(&rt, 0, sizeof(rt));
-        rt.s = rcol[0].data(); rt.x = rcol[1].data(); rt.y = rcol[2].data(); rt.heading = rcol[3].data();
-        rt.kappa = rcol[4].data(); rt.v = rcol[5].data(); rt.ax = rcol[6].data();
-        rt.count = rcount.data(); rt.end_node = node.data(); rt.bind_node = bind.data(); rt.feasible = feas.data();
-        rt.t_end = tend.data(); rt.t_loss = tloss.data();
-        gpu::check(rl_retime(bx.data(), by.data(), wrow[0].data(), wrow[1].data(), wrow[2].data(), wrow[3].data(), h.data(),
-                             (int32_t)N, (int32_t)K, closed ? 1 : 0, &q, gpu::device, &rt),
-                   "rl_retime");
-        std::cerr << std::setprecision(9);
-        for (size_t r = 0; r < K; ++r) {
-            if (node[r] < 0) throw std::runtime_error("retime: no node ahead of the pose");
-            const int64_t rows = rcount[r];
-            vector<double> tab((size_t)rows * 8);
-            for (int64_t m = 0; m < rows; ++m) {
-                tab[(size_t)m * 8] = (double)m * traj_dt;
-                for (int cc = 0; cc < 7; ++cc) tab[(size_t)m * 8 + 1 + cc] = rcol[cc][r * (size_t)traj_cap + (size_t)m];
-            }
-            vector<char> text((size_t)rows * 8 * 22 + 1);
-            int64_t len = 0;
-            gpu::check(rl_format_csv(tab.data(), rows, 8, gpu::device, text.data(), (int64_t)text.size(), &len, nullptr),
-                       "rl_format_csv");
-            io::Csv o(base + "_trajectory_" + std::to_string(r) + "_retimed.csv");
-            if (!o) throw std::runtime_error("save retimed trajectory failed");
-            o.f << "t,s,x,y,heading_rad,curvature,v_mps,ax_mps2\n";
-            o.f.write(text.data(), (std::streamsize)len);
-            std::cerr << "[retime] winner " << r << " from sample " << at << " over " << node[r] << " nodes: retime: t_end "
-                      << tend[r] << " s, t_loss " << tloss[r] << " s, bind_node " << bind[r] << ", feasible " << feas[r] << "\n";
-        }
-    }
-    // <base>_bounds_<r>.csv: the room on either side of every sample of winner r along its unit
-    // normal (+n left of travel), with this run's vehicle width and safety margin
-    if (want_traj && want_bounds) {
-        const size_t K = idx.size();
-        vector<double> col[4];                                   // lo, hi, nx, ny
-        for (auto& a : col) a.resize(K * N);
-        rl_bnd bd;
-        std::memset(&bd, 0, sizeof(bd));
-        bd.lo = col[0].data(); bd.hi = col[1].data(); bd.nx = col[2].data(); bd.ny = col[3].data();
-        gpu::check(rl_bounds(&pk.prob, bx.data(), by.data(), (int32_t)K, C.veh_width_m, C.safety_margin_m, gpu::device, &bd),
-                   "rl_bounds");
-        for (size_t r = 0; r < K; ++r) {
-            io::Csv o(base + "_bounds_" + std::to_string(r) + ".csv");
-            if (!o) throw std::runtime_error("save bounds failed");
-            o.f << "i,x,y,nx,ny,lo,hi\n";
-            for (size_t i = 0; i < N; ++i) {
-                const size_t at = r * N + i;
-                o.f << i << "," << bx[at] << "," << by[at] << "," << col[2][at] << "," << col[3][at] << "," << col[0][at] << ","
-                    << col[1][at] << "\n";
-            }
-        }
-        // <base>_trajectory_<r>_recover.csv: the car of --recover-from on its way back to winner r
-        if (want_rcv) {
-            const rl_cfg cn = cfg::to_abi(C);
-            vector<double> pose(2 * K), dir(2 * K), v0(K), len(K, g_recover.len), h(K, L / (double)N), rcol[8], tend(K), e(K);
-            vector<int32_t> row(K), rcount(K), node(K), feas(K), clamped(K), offtrack(K), merge(K);
-            for (size_t r = 0; r < K; ++r) {
-                pose[2 * r] = g_recover.x; pose[2 * r + 1] = g_recover.y;
-                dir[2 * r] = g_recover.hx; dir[2 * r + 1] = g_recover.hy;
-                row[r] = (int32_t)r;
-                size_t near = 0;                                 // the winner's sample nearest the car
-                double best_d = INFINITY;
-                for (size_t i = 0; i < N; ++i) {
-                    const double ddx = bx[r * N + i] - g_recover.x, ddy = by[r * N + i] - g_recover.y, d2 = ddx * ddx + ddy * ddy;
-                    if (d2 < best_d) { best_d = d2; near = i; }
-                }
-                v0[r] = g_recover.speed >= 0.0 ? g_recover.speed : wrow[2][r * N + near];
-            }
-            for (auto& c : rcol) c.resize(K * (size_t)traj_cap);
-            rl_rcv_query q;
-            std::memset(&q, 0, sizeof(q));
-            q.rj.pose_xy = pose.data(); q.rj.row = row.data();
-            q.rj.Q = (int32_t)K; q.rj.window = 0; q.rj.M_cap = traj_cap; q.rj.dt = traj_dt;
-            q.rj.v0 = v0.data(); q.rj.cfg = &cn; q.rj.K_cap = RL_RCV_MAX_NODES;
-            q.merge_len = len.data(); q.dir_xy = g_recover.has_dir ? dir.data() : nullptr;
-            rl_rcv rc;
-            std::memset(&rc, 0, sizeof(rc));
-            rc.s = rcol[0].data(); rc.x = rcol[1].data(); rc.y = rcol[2].data(); rc.heading = rcol[3].data();
-            rc.kappa = rcol[4].data(); rc.v = rcol[5].data(); rc.ax = rcol[6].data(); rc.offset = rcol[7].data();
-            rc.count = rcount.data(); rc.end_node = node.data(); rc.feasible = feas.data(); rc.t_end = tend.data(); rc.e = e.data();
-            rc.clamped = clamped.data(); rc.offtrack = offtrack.data(); rc.merge_node = merge.data();
-            // --recover-fan: the same query with C merge lengths per winner (rl_recover_fan); rc then holds the best one's answer
-            const size_t nC = g_recover.fan.size();
-            vector<double> flen(K * nC), ct_end(K * nC);
-            vector<int32_t> fbest(K), cclass(K * nC), cfeas(K * nC), cclamped(K * nC), cmerge(K * nC);
-            if (nC) {
-                for (size_t r = 0; r < K; ++r) std::copy(g_recover.fan.begin(), g_recover.fan.end(), flen.begin() + (std::ptrdiff_t)(r * nC));
-                rl_fan_query fq;
-                std::memset(&fq, 0, sizeof(fq));
-                fq.rc = q;
-                fq.rc.merge_len = flen.data();
-                fq.n_cand = (int32_t)nC;
-                rl_fan fo;
-                std::memset(&fo, 0, sizeof(fo));
-                std::memcpy(&fo, &rc, sizeof(rc));               // (rl_fan begins as rl_rcv does)
-                fo.best = fbest.data(); fo.cand_class = cclass.data(); fo.cand_feasible = cfeas.data();
-                fo.cand_clamped = cclamped.data(); fo.cand_merge_node = cmerge.data(); fo.cand_t_end = ct_end.data();
-                gpu::check(rl_recover_fan(bx.data(), by.data(), wrow[0].data(), wrow[1].data(), wrow[2].data(), wrow[3].data(), h.data(),
-                                          col[0].data(), col[1].data(), col[2].data(), col[3].data(), (int32_t)N, (int32_t)K,
-                                          closed ? 1 : 0, &fq, gpu::device, &fo),
-                           "rl_recover_fan");
-            } else {
-                gpu::check(rl_recover(bx.data(), by.data(), wrow[0].data(), wrow[1].data(), wrow[2].data(), wrow[3].data(), h.data(),
-                                      col[0].data(), col[1].data(), col[2].data(), col[3].data(), (int32_t)N, (int32_t)K, closed ? 1 : 0,
-                                      &q, gpu::device, &rc),
-                           "rl_recover");
-            }
-            std::cerr << std::setprecision(9);
-            for (size_t r = 0; r < K; ++r) {
-                if (node[r] < 0) throw std::runtime_error("recover: no node ahead of the pose");
-                for (size_t c = 0; c < nC; ++c)
-                    std::cerr << "[recover-fan] winner " << r << " candidate " << c << ": len " << flen[r * nC + c] << " m, class "
-                              << cclass[r * nC + c] << ", feasible " << cfeas[r * nC + c] << ", clamped " << cclamped[r * nC + c]
-                              << ", merge_node " << cmerge[r * nC + c] << ", t_end " << ct_end[r * nC + c] << " s\n";
-                if (nC) std::cerr << "[recover-fan] winner " << r << ": best " << fbest[r] << " (len " << flen[r * nC + (size_t)fbest[r]] << " m)\n";
-                const int64_t rows = rcount[r];
-                vector<double> tab((size_t)rows * 9);
-                for (int64_t m = 0; m < rows; ++m) {
-                    tab[(size_t)m * 9] = (double)m * traj_dt;
-                    for (int cc = 0; cc < 8; ++cc) tab[(size_t)m * 9 + 1 + cc] = rcol[cc][r * (size_t)traj_cap + (size_t)m];
-                }
-                vector<char> text((size_t)rows * 9 * 22 + 1);
-                int64_t tlen = 0;
-                gpu::check(rl_format_csv(tab.data(), rows, 9, gpu::device, text.data(), (int64_t)text.size(), &tlen, nullptr),
-                           "rl_format_csv");
-                io::Csv o(base + "_trajectory_" + std::to_string(r) + "_recover.csv");
-                if (!o) throw std::runtime_error("save recover trajectory failed");
-                o.f << "t,s,x,y,heading_rad,curvature,v_mps,ax_mps2,offset_m\n";
-                o.f.write(text.data(), (std::streamsize)tlen);
-                std::cerr << "[recover] winner " << r << ": e " << e[r] << " m, " << node[r] << " nodes, merge_node " << merge[r]
-                          << ", clamped " << clamped[r] << ", offtrack " << offtrack[r] << ", feasible " << feas[r] << ", t_end "
-                          << tend[r] << " s\n";
-            }
-        }
-    }
-    std::cerr << "[best] " << (mt || score_lap ? "lap_time_s" : "curvature_score") << " of the " << best << " best of B=" << B << ":";
+};
+
+// f = rl_rejoin, rl_stop, rl_retime on the winners' rows; rl_recover, rl_recover_fan with the
+// rows' bounds after them
+template <class F, class Q, class Out, class... Bnd>
+static void on_rows(F f, const char* what, const Winners& w, const Q& q, Out& out, const Bnd*... bnd) {
+    gpu::check(f(w.bx.data(), w.by.data(), w.row[0].data(), w.row[1].data(), w.row[2].data(), w.row[3].data(), w.h.data(), bnd...,
+                 (int32_t)w.N, (int32_t)w.K, w.closed ? 1 : 0, &q, gpu::device, &out),
+               what);
+}
+
+// <base>_trajectory_<r>_from_v0.csv: winner r from sample 0 at --start-speed, along the speed
+// profile it can reach with the limits of this run's cfg, until that meets the raceline's own
+static void stage_rejoin(const string& base, const BatchOpt& o, const Winners& w) {
+    const rl_cfg c = cfg::to_abi(cfg::get());
+    PoseQuery pq(w.K);
+    pq.at_sample(w, 0);
+    pq.v0.assign(w.K, *o.start_speed);
+    rl_rjn_query q = zeroed<rl_rjn_query>();
+    pq.fill(q, o, &c, RL_RJN_MAX_NODES);
+    Ticks t(7, w.K, o.traj_cap);
+    vector<double> tloss(w.K);
+    vector<int32_t> merge(w.K);
+    rl_rjn rj = zeroed<rl_rjn>();
+    bind_ticks(t, rj);
+    rj.merge_node = merge.data(); rj.t_loss = tloss.data();
+    on_rows(rl_rejoin, "rl_rejoin", w, q, rj);
     std::cerr << std::setprecision(9);
-    for (int r = 0; r < best; ++r) std::cerr << " seed " << seeds[idx[r]] << " = " << sc[r];
+    for (size_t r = 0; r < w.K; ++r) {
+        write_ticks(base, r, "_from_v0", "rejoin trajectory", t, o.traj_dt);
+        std::cerr << "[rejoin] winner " << r << " from " << *o.start_speed << " m/s: merge node " << merge[r]
+                  << ", standing-start lap " << w.T[r] + tloss[r] << " s (flying " << w.T[r] << " s)\n";
+    }
+}
+
+// <base>_trajectory_<r>_stop.csv: winner r from the sample --stop-from nodes before
+// --stop-sample, at the raceline's own speed there, braking to --stop-speed at that sample
+// with the limits of this run's cfg
+static void stage_stop(const string& base, const BatchOpt& o, const Winners& w) {
+    const rl_cfg c = cfg::to_abi(cfg::get());
+    const int N = (int)w.N, J = *o.stop.sample;
+    // the nodes between the pose and the target: what the row and the stage allow
+    int from = std::min(*o.stop.from, (int)RL_RJN_MAX_NODES);
+    from = std::min(from, w.closed ? N : J);
+    const int at = ((J - from) % N + N) % N;                       // (open rows: J - from >= 0)
+    PoseQuery pq(w.K);
+    pq.at_sample(w, (size_t)at);
+    vector<double> vt(w.K, *o.stop.speed), tstop(w.K), vend(w.K);
+    vector<int32_t> target(w.K, J), node(w.K), brake(w.K);
+    rl_stp_query q = zeroed<rl_stp_query>();
+    pq.fill(q.rj, o, &c, RL_RJN_MAX_NODES);
+    q.stop_sample = target.data(); q.v_target = vt.data();
+    Ticks t(7, w.K, o.traj_cap);
+    rl_stp sp = zeroed<rl_stp>();
+    bind_ticks(t, sp);
+    sp.stop_node = node.data(); sp.brake_node = brake.data(); sp.t_stop = tstop.data(); sp.v_end = vend.data();
+    on_rows(rl_stop, "rl_stop", w, q, sp);
+    std::cerr << std::setprecision(9);
+    for (size_t r = 0; r < w.K; ++r) {
+        if (node[r] < 0) throw std::runtime_error("stop: the target is not among the nodes ahead of the pose");
+        write_ticks(base, r, "_stop", "stop trajectory", t, o.traj_dt);
+        std::cerr << "[stop] winner " << r << " from sample " << at << " to " << *o.stop.speed << " m/s at sample " << J
+                  << ": stop: t_stop " << tstop[r] << " s, brake_node " << brake[r] << " of " << node[r] << ", v_end "
+                  << vend[r] << " m/s\n";
+    }
+}
+
+// <base>_trajectory_<r>_retimed.csv: winner r from sample --retime-from at the raceline's own
+// speed there, over the samples ahead, with the limits of this run's cfg after --retime-set
+static void stage_retime(const string& base, const BatchOpt& o, const Winners& w) {
+    cfg::Config now = cfg::get();
+    for (const string& kv : o.retime.sets)
+        if (!cfg::set_knob(now, kv)) throw std::runtime_error("unknown cfg knob: " + kv);
+    const rl_cfg cn = cfg::to_abi(now);
+    const int at = o.retime.from.value_or(0);
+    PoseQuery pq(w.K);
+    pq.at_sample(w, (size_t)at);
+    vector<double> tend(w.K), tloss(w.K);
+    vector<int32_t> node(w.K), bind(w.K), feas(w.K);
+    rl_rtm_query q = zeroed<rl_rtm_query>();
+    pq.fill(q.rj, o, &cn, RL_RJN_MAX_NODES);
+    Ticks t(7, w.K, o.traj_cap);
+    rl_rtm rt = zeroed<rl_rtm>();
+    bind_ticks(t, rt);
+    rt.end_node = node.data(); rt.bind_node = bind.data(); rt.feasible = feas.data();
+    rt.t_end = tend.data(); rt.t_loss = tloss.data();
+    on_rows(rl_retime, "rl_retime", w, q, rt);
+    std::cerr << std::setprecision(9);
+    for (size_t r = 0; r < w.K; ++r) {
+        if (node[r] < 0) throw std::runtime_error("retime: no node ahead of the pose");
+        write_ticks(base, r, "_retimed", "retimed trajectory", t, o.traj_dt);
+        std::cerr << "[retime] winner " << r << " from sample " << at << " over " << node[r] << " nodes: retime: t_end "
+                  << tend[r] << " s, t_loss " << tloss[r] << " s, bind_node " << bind[r] << ", feasible " << feas[r] << "\n";
+    }
+}
+
+// <base>_bounds_<r>.csv: the room on either side of every sample of winner r along its unit
+// normal (+n left of travel), with this run's vehicle width and safety margin
+struct Bounds {
+    vector<double> lo, hi, nx, ny;           // [K][N]
+};
+static Bounds stage_bounds(const string& base, const rl_problem& prob, const Winners& w) {
+    auto& C = cfg::get();
+    Bounds b;
+    for (auto* a : {&b.lo, &b.hi, &b.nx, &b.ny}) a->resize(w.K * w.N);
+    rl_bnd bd = zeroed<rl_bnd>();
+    bd.lo = b.lo.data(); bd.hi = b.hi.data(); bd.nx = b.nx.data(); bd.ny = b.ny.data();
+    gpu::check(rl_bounds(&prob, w.bx.data(), w.by.data(), (int32_t)w.K, C.veh_width_m, C.safety_margin_m, gpu::device, &bd),
+               "rl_bounds");
+    for (size_t r = 0; r < w.K; ++r) {
+        io::Csv o(base + "_bounds_" + std::to_string(r) + ".csv");
+        if (!o) throw std::runtime_error("save bounds failed");
+        o.f << "i,x,y,nx,ny,lo,hi\n";
+        for (size_t i = 0; i < w.N; ++i) {
+            const size_t at = r * w.N + i;
+            o.f << i << "," << w.bx[at] << "," << w.by[at] << "," << b.nx[at] << "," << b.ny[at] << "," << b.lo[at] << ","
+                << b.hi[at] << "\n";
+        }
+    }
+    return b;
+}
+
+// <base>_trajectory_<r>_recover.csv: the car of --recover-from on its way back to winner r,
+// inside the winner's bounds
+static void stage_recover(const string& base, const BatchOpt& o, const Winners& w, const Bounds& b) {
+    const RecoverOpt& g = o.recover;
+    const size_t K = w.K, N = w.N;
+    const rl_cfg c = cfg::to_abi(cfg::get());
+    PoseQuery pq(K);
+    vector<double> dir(2 * K), len(K, g.len), tend(K), e(K);
+    vector<int32_t> node(K), feas(K), clamped(K), offtrack(K), merge(K);
+    for (size_t r = 0; r < K; ++r) {
+        pq.pose[2 * r] = g.x; pq.pose[2 * r + 1] = g.y;
+        dir[2 * r] = g.hx; dir[2 * r + 1] = g.hy;
+        size_t near = 0;                                         // the winner's sample nearest the car
+        double best_d = INFINITY;
+        for (size_t i = 0; i < N; ++i) {
+            const double ddx = w.bx[r * N + i] - g.x, ddy = w.by[r * N + i] - g.y, d2 = ddx * ddx + ddy * ddy;
+            if (d2 < best_d) { best_d = d2; near = i; }
+        }
+        pq.v0[r] = g.speed >= 0.0 ? g.speed : w.row[2][r * N + near];
+    }
+    rl_rcv_query q = zeroed<rl_rcv_query>();
+    pq.fill(q.rj, o, &c, RL_RCV_MAX_NODES);
+    q.merge_len = len.data(); q.dir_xy = g.has_dir ? dir.data() : nullptr;
+    Ticks t(8, K, o.traj_cap);
+    rl_rcv rc = zeroed<rl_rcv>();
+    bind_ticks(t, rc);
+    rc.offset = t.col[7].data();
+    rc.end_node = node.data(); rc.feasible = feas.data(); rc.t_end = tend.data(); rc.e = e.data();
+    rc.clamped = clamped.data(); rc.offtrack = offtrack.data(); rc.merge_node = merge.data();
+    // --recover-fan: the same query with C merge lengths per winner (rl_recover_fan); rc then holds the best one's answer
+    const size_t nC = g.fan.size();
+    vector<double> flen(K * nC), ct_end(K * nC);
+    vector<int32_t> fbest(K), cclass(K * nC), cfeas(K * nC), cclamped(K * nC), cmerge(K * nC);
+    if (nC) {
+        for (size_t r = 0; r < K; ++r) std::copy(g.fan.begin(), g.fan.end(), flen.begin() + (std::ptrdiff_t)(r * nC));
+        rl_fan_query fq = zeroed<rl_fan_query>();
+        fq.rc = q;
+        fq.rc.merge_len = flen.data();
+        fq.n_cand = (int32_t)nC;
+        rl_fan fo = zeroed<rl_fan>();
+        std::memcpy(&fo, &rc, sizeof(rc));                       // (rl_fan begins as rl_rcv does)
+        fo.best = fbest.data(); fo.cand_class = cclass.data(); fo.cand_feasible = cfeas.data();
+        fo.cand_clamped = cclamped.data(); fo.cand_merge_node = cmerge.data(); fo.cand_t_end = ct_end.data();
+        on_rows(rl_recover_fan, "rl_recover_fan", w, fq, fo, b.lo.data(), b.hi.data(), b.nx.data(), b.ny.data());
+    } else {
+        on_rows(rl_recover, "rl_recover", w, q, rc, b.lo.data(), b.hi.data(), b.nx.data(), b.ny.data());
+    }
+    std::cerr << std::setprecision(9);
+    for (size_t r = 0; r < K; ++r) {
+        if (node[r] < 0) throw std::runtime_error("recover: no node ahead of the pose");
+        for (size_t k = 0; k < nC; ++k)
+            std::cerr << "[recover-fan] winner " << r << " candidate " << k << ": len " << flen[r * nC + k] << " m, class "
+                      << cclass[r * nC + k] << ", feasible " << cfeas[r * nC + k] << ", clamped " << cclamped[r * nC + k]
+                      << ", merge_node " << cmerge[r * nC + k] << ", t_end " << ct_end[r * nC + k] << " s\n";
+        if (nC) std::cerr << "[recover-fan] winner " << r << ": best " << fbest[r] << " (len " << flen[r * nC + (size_t)fbest[r]] << " m)\n";
+        write_ticks(base, r, "_recover", "recover trajectory", t, o.traj_dt);
+        std::cerr << "[recover] winner " << r << ": e " << e[r] << " m, " << node[r] << " nodes, merge_node " << merge[r]
+                  << ", clamped " << clamped[r] << ", offtrack " << offtrack[r] << ", feasible " << feas[r] << ", t_end "
+                  << tend[r] << " s\n";
+    }
+}
+
+// B α-seeds in one launch (beyond the reference): one summary row per instance, then the
+// winners' files and the stages that were asked for, in this order.
+static void batch_and_save(const Track& t, const BatchOpt& o) {
+    Batch b(t, o);
+    run_batch(b, o);
+    Winners w;
+    if (o.best > 0 && o.score_lap()) w = run_best(t, o, b);        // (before the summary, whose lap column is the lap stage's)
+    save_summary(t.base, b, o);
+    if (o.best <= 0) return;
+    if (!o.score_lap()) w = run_best(t, o, b);
+    save_best(t.base, w);
+    if (o.ticks()) {
+        for (size_t r = 0; r < w.K; ++r) write_ticks(t.base, r, "", "trajectory", w.traj, o.traj_dt);
+        if (o.start_speed) stage_rejoin(t.base, o, w);
+        if (o.stop.sample) stage_stop(t.base, o, w);
+        if (!o.retime.sets.empty()) stage_retime(t.base, o, w);
+        if (o.bounds) {
+            const Bounds bd = stage_bounds(t.base, b.pk.prob, w);
+            if (o.recover.given) stage_recover(t.base, o, w, bd);
+        }
+    }
+    std::cerr << "[best] " << (o.mintime() || o.score_lap() ? "lap_time_s" : "curvature_score") << " of the " << o.best
+              << " best of B=" << o.B << ":";
+    std::cerr << std::setprecision(9);
+    for (size_t r = 0; r < w.K; ++r) std::cerr << " seed " << b.seeds[w.idx[r]] << " = " << w.sc[r];
     std::cerr << "\n";
 }
 }  // namespace pipeline
@@ -1722,149 +1769,102 @@ int run_pipeline(const string& innerPath, const string& outerPath, const string&
     return 0;
 }
 
-// Steps 7-8 from the reference's step-6 files.
-int run_from_centerline(const string& outPath, double L, double s0, const string& mode, int B, int repeat, int best,
-                        const string& score, double traj_dt, int traj_cap, double start_speed, int stop_sample,
-                        double stop_speed, int stop_from, bool want_bounds) {
-    auto& C = cfg::get();
-    const string base = io::dropExt(outPath);
-    const bool closed_mode = C.is_closed_track;
-    const auto center = io::loadCSV_XY(outPath);
-    const auto inner = io::loadCSV_XY(base + "_inner_from_mids.csv");
-    const auto outer = io::loadCSV_XY(base + "_outer_from_mids.csv");
-    if (std::isnan(L)) L = last_s_of(base + "_with_geom.csv");
-    if (center.size() < 2 || inner.size() < 2 || outer.size() < 2 || !(L > 0)) {
-        std::cerr << "[ERR] need centerline, inner/outer_from_mids and L (--L or <base>_with_geom.csv)\n";
-        return 2;
+// Every check of the centreline form's inputs and options, in the one order they run in, with
+// the defaults of what was left out filled in on the way.  The text of the first one that
+// fails, or nothing.  No GPU call precedes it.
+std::optional<string> check_options(const pipeline::Track& t, pipeline::BatchOpt& o) {
+    using std::to_string;
+    const int N = (int)t.path.size();
+    const bool ticks = o.traj_dt > 0.0, mintime = o.mode == "mintime";
+    if (t.center.size() < 2 || t.inner.size() < 2 || t.outer.size() < 2 || !(*o.L > 0))
+        return "need centerline, inner/outer_from_mids and L (--L or <base>_with_geom.csv)";
+    if (!o.score.empty()) {
+        if (o.score != "lap" && o.score != "default") return "--score default|lap";
+        if (o.best <= 0 || o.B <= 0) return "--score needs --seeds B --best K";
+        if (o.score == "lap" && o.mode != "mincurv")
+            return "--score lap needs --mode mincurv (the min-time score is the lap already)";
     }
-    const vector<Vec2> center_for_opt = opt_input(center, closed_mode);
-    if (!score.empty()) {
-        if (score != "lap" && score != "default") {
-            std::cerr << "[ERR] --score default|lap\n";
-            return 2;
-        }
-        if (best <= 0 || B <= 0) {
-            std::cerr << "[ERR] --score needs --seeds B --best K\n";
-            return 2;
-        }
-        if (score == "lap" && mode != "mincurv") {
-            std::cerr << "[ERR] --score lap needs --mode mincurv (the min-time score is the lap already)\n";
-            return 2;
-        }
+    if (o.traj_dt != 0.0 || o.traj_cap != 0) {
+        if (o.best <= 0 || o.B <= 0) return "--trajectory-dt needs --seeds B --best K";
+        if (o.traj_cap == 0) o.traj_cap = 4096;
+        if (!ticks || !std::isfinite(o.traj_dt) || o.traj_cap < 1 || o.traj_cap > RL_TRAJ_MAX_TICKS)
+            return "--trajectory-dt DT > 0 [--trajectory-cap M, 1.." + to_string(RL_TRAJ_MAX_TICKS) + "]";
     }
-    if (traj_dt != 0.0 || traj_cap != 0) {
-        if (best <= 0 || B <= 0) {
-            std::cerr << "[ERR] --trajectory-dt needs --seeds B --best K\n";
-            return 2;
-        }
-        if (traj_cap == 0) traj_cap = 4096;
-        if (!(traj_dt > 0.0) || !std::isfinite(traj_dt) || traj_cap < 1 || traj_cap > RL_TRAJ_MAX_TICKS) {
-            std::cerr << "[ERR] --trajectory-dt DT > 0 [--trajectory-cap M, 1.." << RL_TRAJ_MAX_TICKS << "]\n";
-            return 2;
-        }
-    }
-    if (!std::isnan(start_speed)) {
+    if (o.start_speed) {
         // (the winners' whole rows come down with a min-time selection; a min-curvature one has
         // its heading and curvature in the lap stage, which the one-shot call does not download)
-        if (!(traj_dt > 0.0) || mode != "mintime") {
-            std::cerr << "[ERR] --start-speed needs --seeds B --best K --mode mintime --trajectory-dt DT\n";
-            return 2;
-        }
-        if (!std::isfinite(start_speed) || start_speed < 0.0) {
-            std::cerr << "[ERR] --start-speed V: finite and >= 0\n";
-            return 2;
-        }
-    } else {
-        start_speed = -1.0;
+        if (!ticks || !mintime) return "--start-speed needs --seeds B --best K --mode mintime --trajectory-dt DT";
+        if (!std::isfinite(*o.start_speed) || *o.start_speed < 0.0) return "--start-speed V: finite and >= 0";
     }
-    if (stop_sample != -1 || !std::isnan(stop_speed) || stop_from != 0) {
+    if (o.stop.sample || o.stop.speed || o.stop.from) {
         // (the winners' whole rows: as for --start-speed)
-        if (stop_sample == -1 || !(traj_dt > 0.0) || mode != "mintime") {
-            std::cerr << "[ERR] --stop-sample J [--stop-speed V] [--stop-from K] needs --seeds B --best K --mode mintime "
-                         "--trajectory-dt DT\n";
-            return 2;
-        }
-        const int N = (int)center_for_opt.size();
-        if (stop_sample < (closed_mode ? 0 : 1) || stop_sample >= N) {
-            std::cerr << "[ERR] --stop-sample J: a sample of the raceline, " << (closed_mode ? 0 : 1) << ".." << N - 1 << "\n";
-            return 2;
-        }
-        if (std::isnan(stop_speed)) stop_speed = 0.0;
-        if (!std::isfinite(stop_speed) || stop_speed < 0.0) {
-            std::cerr << "[ERR] --stop-speed V: finite and >= 0\n";
-            return 2;
-        }
-        if (stop_from == 0) stop_from = 512;
-        if (stop_from < 1) {
-            std::cerr << "[ERR] --stop-from K: >= 1\n";
-            return 2;
-        }
+        if (!o.stop.sample || !ticks || !mintime)
+            return "--stop-sample J [--stop-speed V] [--stop-from K] needs --seeds B --best K --mode mintime "
+                   "--trajectory-dt DT";
+        if (*o.stop.sample < (t.closed ? 0 : 1) || *o.stop.sample >= N)
+            return "--stop-sample J: a sample of the raceline, " + to_string(t.closed ? 0 : 1) + ".." + to_string(N - 1);
+        if (!o.stop.speed) o.stop.speed = 0.0;
+        if (!std::isfinite(*o.stop.speed) || *o.stop.speed < 0.0) return "--stop-speed V: finite and >= 0";
+        if (!o.stop.from) o.stop.from = 512;
+        if (*o.stop.from < 1) return "--stop-from K: >= 1";
     }
-    if (!pipeline::g_retime.sets.empty() || pipeline::g_retime.from != -1) {
+    if (!o.retime.sets.empty() || o.retime.from) {
         // (the winners' whole rows: as for --start-speed)
-        if (pipeline::g_retime.sets.empty() || !(traj_dt > 0.0) || mode != "mintime") {
-            std::cerr << "[ERR] --retime-set key=value [--retime-from S] needs --seeds B --best K --mode mintime "
-                         "--trajectory-dt DT\n";
-            return 2;
-        }
-        const int N = (int)center_for_opt.size();
-        if (pipeline::g_retime.from != -1 && (pipeline::g_retime.from < 0 || pipeline::g_retime.from >= (closed_mode ? N : N - 1))) {
-            std::cerr << "[ERR] --retime-from S: a sample of the raceline with one ahead, 0.." << (closed_mode ? N : N - 1) - 1 << "\n";
-            return 2;
-        }
-        cfg::Config probe = C;
-        for (const string& kv : pipeline::g_retime.sets)
-            if (!cfg::set_knob(probe, kv)) {
-                std::cerr << "[ERR] --retime-set: unknown cfg knob: " << kv << "\n";
-                return 2;
-            }
+        if (o.retime.sets.empty() || !ticks || !mintime)
+            return "--retime-set key=value [--retime-from S] needs --seeds B --best K --mode mintime "
+                   "--trajectory-dt DT";
+        const int ahead = t.closed ? N : N - 1;
+        if (o.retime.from && (*o.retime.from < 0 || *o.retime.from >= ahead))
+            return "--retime-from S: a sample of the raceline with one ahead, 0.." + to_string(ahead - 1);
+        cfg::Config probe = cfg::get();
+        for (const string& kv : o.retime.sets)
+            if (!cfg::set_knob(probe, kv)) return "--retime-set: unknown cfg knob: " + kv;
     }
-    if (pipeline::g_recover.given && (!(traj_dt > 0.0) || mode != "mintime" || !want_bounds || best <= 0)) {
-        std::cerr << "[ERR] --recover-from X,Y needs --seeds B --best K --mode mintime --trajectory-dt DT --bounds\n";
-        return 2;
-    }
-    if (pipeline::g_recover.given) {
-        const auto& g = pipeline::g_recover;
+    const pipeline::RecoverOpt& g = o.recover;
+    if (g.given && (!ticks || !mintime || !o.bounds || o.best <= 0))
+        return "--recover-from X,Y needs --seeds B --best K --mode mintime --trajectory-dt DT --bounds";
+    if (g.given) {
         if (!std::isfinite(g.x) || !std::isfinite(g.y) || !std::isfinite(g.hx) || !std::isfinite(g.hy) || !std::isfinite(g.len) ||
-            !(g.len > 0.0) || !std::isfinite(g.speed)) {
-            std::cerr << "[ERR] --recover-from / --recover-dir need finite numbers, --recover-len D > 0\n";
-            return 2;
-        }
+            !(g.len > 0.0) || !std::isfinite(g.speed))
+            return "--recover-from / --recover-dir need finite numbers, --recover-len D > 0";
         bool fan_ok = g.fan.size() <= (size_t)RL_FAN_MAX_CAND;
         for (double d : g.fan) fan_ok = fan_ok && std::isfinite(d) && d > 0.0;
-        if (!fan_ok) {
-            std::cerr << "[ERR] --recover-fan needs 1.." << RL_FAN_MAX_CAND << " finite lengths D1,D2,... > 0\n";
-            return 2;
-        }
-    } else if (!pipeline::g_recover.fan.empty()) {
-        std::cerr << "[ERR] --recover-fan D1,D2,... needs --recover-from X,Y\n";
+        if (!fan_ok) return "--recover-fan needs 1.." + to_string(RL_FAN_MAX_CAND) + " finite lengths D1,D2,... > 0";
+    } else if (!g.fan.empty()) {
+        return "--recover-fan D1,D2,... needs --recover-from X,Y";
+    }
+    if (o.bounds && (!ticks || o.best <= 0)) return "--bounds needs --seeds B --best K --trajectory-dt DT";
+    if (o.B > 0) {
+        if (o.best > 0 && o.mode != "mincurv" && !mintime) return "--best needs --mode mincurv or --mode mintime";
+        if (o.best > o.B || o.best > RL_SELECT_MAX_K) return "--best K: K <= min(B, " + to_string(RL_SELECT_MAX_K) + ")";
+    }
+    return std::nullopt;
+}
+
+// Steps 7-8 from the reference's step-6 files.
+int run_from_centerline(const string& outPath, const pipeline::BatchOpt& given) {
+    pipeline::BatchOpt o = given;
+    pipeline::Track t;
+    t.base = io::dropExt(outPath);
+    t.closed = cfg::get().is_closed_track;
+    t.center = io::loadCSV_XY(outPath);
+    t.inner = io::loadCSV_XY(t.base + "_inner_from_mids.csv");
+    t.outer = io::loadCSV_XY(t.base + "_outer_from_mids.csv");
+    t.path = opt_input(t.center, t.closed);
+    if (!o.L) o.L = last_s_of(t.base + "_with_geom.csv");
+    if (const auto bad = check_options(t, o)) {
+        std::cerr << "[ERR] " << *bad << "\n";
         return 2;
     }
-    if (want_bounds && (!(traj_dt > 0.0) || best <= 0)) {
-        std::cerr << "[ERR] --bounds needs --seeds B --best K --trajectory-dt DT\n";
-        return 2;
-    }
-    if (B > 0) {
-        const int modes = mode == "mincurv" ? RL_MODE_MINCURV
-                                            : mode == "mintime" ? RL_MODE_MINTIME : RL_MODE_MINCURV | RL_MODE_MINTIME;
-        if (best > 0 && mode != "mincurv" && mode != "mintime") {
-            std::cerr << "[ERR] --best needs --mode mincurv or --mode mintime\n";
-            return 2;
-        }
-        if (best > B || best > RL_SELECT_MAX_K) {
-            std::cerr << "[ERR] --best K: K <= min(B, " << RL_SELECT_MAX_K << ")\n";
-            return 2;
-        }
-        pipeline::batch_and_save(base, center_for_opt, L, closed_mode, inner, outer, B, modes, repeat, best,
-                                 score == "lap", traj_dt, traj_cap, start_speed, stop_sample, stop_speed, stop_from,
-                                 want_bounds);
+    if (o.B > 0) {
+        pipeline::batch_and_save(t, o);
         return 0;
     }
     auto t0 = Clock::now();
-    if (mode != "mintime") pipeline::compute_raceline_and_save(base, center_for_opt, s0, L, closed_mode, inner, outer);
+    if (o.mode != "mintime") pipeline::compute_raceline_and_save(t.base, t.path, o.s0, *o.L, t.closed, t.inner, t.outer);
     const double t_mc = ms_since(t0);
     t0 = Clock::now();
-    if (mode != "mincurv") pipeline::compute_mintime_and_save(base, center_for_opt, s0, L, closed_mode, inner, outer);
+    if (o.mode != "mincurv") pipeline::compute_mintime_and_save(t.base, t.path, o.s0, *o.L, t.closed, t.inner, t.outer);
     std::cerr.setf(std::ios::fixed);
     std::cerr << "[TIME][SUMMARY] mincurv_race=" << t_mc << ", mintime_race=" << ms_since(t0) << "\n";
     return 0;
@@ -1875,13 +1875,14 @@ int main(int argc, char** argv) {
     std::ios::sync_with_stdio(false);
     auto& C = cfg::get();
     vector<string> pos;
-    double L = NAN, s0 = 0.0;
-    string mode = "both", stop_after;
-    int B = 0, repeat = 0, best = 0;
-    string score;
-    double traj_dt = 0.0, start_speed = NAN, stop_speed = NAN;
-    int traj_cap = 0, stop_sample = -1, stop_from = 0;
-    bool want_bounds = false;
+    string stop_after;
+    pipeline::BatchOpt o;
+    // (a NaN for --L, --start-speed or --stop-speed reads as the option left out)
+    auto number = [](const string& v) -> std::optional<double> {
+        const double d = std::stod(v);
+        if (std::isnan(d)) return std::nullopt;
+        return d;
+    };
     try {
         for (int i = 1; i < argc; ++i) {
             const string a = argv[i];
@@ -1890,50 +1891,41 @@ int main(int argc, char** argv) {
                 return argv[++i];
             };
             if (a.rfind("--", 0) != 0) pos.push_back(a);
-            else if (a == "--L") L = std::stod(next());
-            else if (a == "--s0") s0 = std::stod(next());
+            else if (a == "--L") o.L = number(next());
+            else if (a == "--s0") o.s0 = std::stod(next());
             else if (a == "--open") C.is_closed_track = false;
-            else if (a == "--mode") mode = next();
-            else if (a == "--seeds") B = std::stoi(next());
-            else if (a == "--repeat") repeat = std::stoi(next());
-            else if (a == "--best") best = std::stoi(next());
-            else if (a == "--score") score = next();
-            else if (a == "--trajectory-dt") traj_dt = std::stod(next());
-            else if (a == "--start-speed") start_speed = std::stod(next());
-            else if (a == "--trajectory-cap") traj_cap = std::stoi(next());
-            else if (a == "--stop-sample") {
-                stop_sample = std::stoi(next());
-                if (stop_sample == -1) stop_sample = -2;           // (-1 stands for "not given")
-            }
-            else if (a == "--stop-speed") stop_speed = std::stod(next());
-            else if (a == "--stop-from") {
-                stop_from = std::stoi(next());
-                if (stop_from == 0) stop_from = -1;                // (0 stands for "not given")
-            }
-            else if (a == "--retime-set") pipeline::g_retime.sets.push_back(next());
-            else if (a == "--retime-from") {
-                pipeline::g_retime.from = std::stoi(next());
-                if (pipeline::g_retime.from == -1) pipeline::g_retime.from = -2;   // (-1 stands for "not given")
-            }
+            else if (a == "--mode") o.mode = next();
+            else if (a == "--seeds") o.B = std::stoi(next());
+            else if (a == "--repeat") o.repeat = std::stoi(next());
+            else if (a == "--best") o.best = std::stoi(next());
+            else if (a == "--score") o.score = next();
+            else if (a == "--trajectory-dt") o.traj_dt = std::stod(next());
+            else if (a == "--start-speed") o.start_speed = number(next());
+            else if (a == "--trajectory-cap") o.traj_cap = std::stoi(next());
+            else if (a == "--stop-sample") o.stop.sample = std::stoi(next());
+            else if (a == "--stop-speed") o.stop.speed = number(next());
+            else if (a == "--stop-from") o.stop.from = std::stoi(next());
+            else if (a == "--retime-set") o.retime.sets.push_back(next());
+            else if (a == "--retime-from") o.retime.from = std::stoi(next());
             else if (a == "--recover-from" || a == "--recover-dir") {
                 const string xy = next();
                 const size_t comma = xy.find(',');
                 if (comma == string::npos) throw std::runtime_error(a + " needs two numbers X,Y");
                 const double u = std::stod(xy.substr(0, comma)), w = std::stod(xy.substr(comma + 1));
-                auto& g = pipeline::g_recover;
+                auto& g = o.recover;
                 if (a == "--recover-from") { g.given = true; g.x = u; g.y = w; }
                 else { g.has_dir = true; g.hx = u; g.hy = w; }
             }
-            else if (a == "--recover-len") pipeline::g_recover.len = std::stod(next());
+            else if (a == "--recover-len") o.recover.len = std::stod(next());
             else if (a == "--recover-fan") {                                        // (replaces --recover-len)
                 std::stringstream list(next());
                 string item;
-                pipeline::g_recover.fan.clear();
-                while (std::getline(list, item, ',')) pipeline::g_recover.fan.push_back(std::stod(item));
-                if (pipeline::g_recover.fan.empty()) throw std::runtime_error("--recover-fan needs lengths D1,D2,...");
+                o.recover.fan.clear();
+                while (std::getline(list, item, ',')) o.recover.fan.push_back(std::stod(item));
+                if (o.recover.fan.empty()) throw std::runtime_error("--recover-fan needs lengths D1,D2,...");
             }
-            else if (a == "--recover-speed") pipeline::g_recover.speed = std::stod(next());
-            else if (a == "--bounds") want_bounds = true;
+            else if (a == "--recover-speed") o.recover.speed = std::stod(next());
+            else if (a == "--bounds") o.bounds = true;
             else if (a == "--device") gpu::device = std::stoi(next());
             else if (a == "--devices") {
                 std::stringstream ss(next());
@@ -1963,11 +1955,11 @@ int main(int argc, char** argv) {
                       << "         [--bounds]   with --best K --trajectory-dt: the free track width along the winners\n";
             return 1;
         }
-        if (pos.size() == 3) return run_pipeline(pos[0], pos[1], pos[2], mode, stop_after == "centerline");
-        return run_from_centerline(pos[0], L, s0, mode, B, repeat, best, score, traj_dt, traj_cap, start_speed, stop_sample,
-                                   stop_speed, stop_from, want_bounds);
+        if (pos.size() == 3) return run_pipeline(pos[0], pos[1], pos[2], o.mode, stop_after == "centerline");
+        return run_from_centerline(pos[0], o);
     } catch (const std::exception& e) {
         std::cerr << "[ERR] " << e.what() << "\n";
         return 3;
     }
 }
+
