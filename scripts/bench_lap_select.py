@@ -21,55 +21,30 @@ GPU that has been idle.
 
   python scripts/bench_lap_select.py [--calls 20] [--out profiles/lap_select_c2.json]
 """
-import argparse
 import ctypes as C
 import json
-import os
-import statistics
-import sys
 import time
 
 import numpy as np
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [REPO, os.path.join(REPO, "tests")]
-
-import oracle_lib as O  # noqa: E402  (fixture loader only)
-from practice_path_planning_for_formula_student_driverless_amd import abi, raceline  # noqa: E402
+import stage_bench as sb
+from stage_bench import abi, last_call, raceline, stats
 
 
-def stats(v):
-    v = sorted(v)
-    return {"median": round(statistics.median(v), 4), "min": round(v[0], 4), "max": round(v[-1], 4), "n": len(v)}
-
-
-def last_call(lib):
-    k, c = C.c_float(), C.c_float()
-    assert lib.rl_last_call_ms(C.byref(k), C.byref(c)) == 0
-    return float(k.value), float(c.value)
+def variants(a):
+    return ["route", "lap", "default"]
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--calls", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--case", default="cmap1_n2000")
-    ap.add_argument("--batch", type=int, default=1024)
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "lap_select_c2.json"))
-    a = ap.parse_args()
-    if a.calls < 20:
-        ap.error("--calls: at least 20 per variant")
-    lib = abi.load_library()
-    if lib.rl_device_count() < 1:
-        raise SystemExit("bench_lap_select: no HIP device visible (nothing is measured without one)")
-    case = O.load_case(a.case)
-    prob, cfg = O.case_problem(case), O.case_cfg(case)
+    a = sb.parse(sb.parser("bench_lap_select"), variants)
+    lib = a.lib
+    prob, cfg = sb.problem(a.case)
     B, N = a.batch, prob.N
     seeds = np.arange(B, dtype=np.uint64)
     MC = abi.RL_MODE_MINCURV
     lib.rl_release_plan_cache()
     out = raceline.optimize_batch(prob, cfg, seeds=seeds, B=B, mincurv=True, mintime=False)
-    names = ("route", "lap", "default")
+    names = variants(a)
     t = {v: {"host_ms": [], "call_ms": [], "kernel_ms": []} for v in names}
     parts = {"optimize_batch_ms": [], "path_length_ms": [], "lap_eval_ms": [], "rank_scores_ms": []}
     res = {}
@@ -145,16 +120,15 @@ def main():
                                "upload": up_common + 2 * bn8 + B * 8 + C.sizeof(abi.RlCfg) + B * 8},
                      "lap": {"download": best_rows, "upload": up_common},
                      "default": {"download": default_rows, "upload": up_common}}}
-    for v in names:
-        rec[v] = {k: stats(x) for k, x in t[v].items()}
+    rec.update(sb.blocks(t))
     rec["route_parts_host_ms"] = {k: stats(v) for k, v in parts.items()}
-    rec["pair_only"] = {v: {k: stats(x) for k, x in t2[v].items()} for v in pair}
+    rec["pair_only"] = sb.blocks(t2)
     rec["pair_only"]["lap_minus_default_call_ms"] = round(rec["pair_only"]["lap"]["call_ms"]["median"]
                                                           - rec["pair_only"]["default"]["call_ms"]["median"], 4)
     rec["pair_only"]["lap_minus_default_kernel_ms"] = round(rec["pair_only"]["lap"]["kernel_ms"]["median"]
                                                             - rec["pair_only"]["default"]["kernel_ms"]["median"], 4)
     rec["plan"] = {k: stats(v) for k, v in st.items()}
-    med = lambda v, k: rec[v][k]["median"]          # noqa: E731
+    med = sb.medians(rec)
     rec["lap_minus_default_call_ms"] = round(med("lap", "call_ms") - med("default", "call_ms"), 4)
     rec["lap_minus_default_host_ms"] = round(med("lap", "host_ms") - med("default", "host_ms"), 4)
     rec["lap_over_route_host"] = round(med("lap", "host_ms") / med("route", "host_ms"), 6)
@@ -167,17 +141,11 @@ def main():
                                                       and np.array_equal(lap_sel.out.kappa[0], mc.kappa[b])),
                      "index_default_score": int(dflt.index[0, 0]),
                      "lap_of_default_winner_s": float(lap_sel.scores[int(dflt.index[0, 0])])}
-    doc = {"script": "scripts/bench_lap_select.py",
-           "method": "variants interleaved call by call in one process; host clock around each variant, "
-                     "rl_last_call_ms after the optimiser call for the in-call kernel (HIP events: the run, without "
-                     "the stages after it) and call time; rl_plan_kernel_ms(4, 5, 6, 3, 1) on a plan of the same shape "
-                     "for the lap stage, its two kernels, the selection and the optimiser; pair_only: lap and default "
-                     "interleaved without the route between them",
-           "records": [rec]}
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(doc, f, indent=1)
-        f.write("\n")
+    sb.write(a, "variants interleaved call by call in one process; host clock around each variant, "
+                "rl_last_call_ms after the optimiser call for the in-call kernel (HIP events: the run, without "
+                "the stages after it) and call time; rl_plan_kernel_ms(4, 5, 6, 3, 1) on a plan of the same shape "
+                "for the lap stage, its two kernels, the selection and the optimiser; pair_only: lap and default "
+                "interleaved without the route between them", [rec])
     print(json.dumps({k: rec[k] for k in ("lap_minus_default_call_ms", "lap_minus_default_host_ms", "lap_over_route_host",
                                           "stage_over_optimiser_kernel", "winner", "plan", "route_parts_host_ms", "pair_only")}
                      | {v + "_host_ms": rec[v]["host_ms"] for v in names}

@@ -5,9 +5,8 @@ Set-up: workload C2's plan (competition_map1, N=2000, B=1024 seeds, 14 outer ite
 once, the winner selected by lap, its trajectory stage (dt = 0.05 s, M_cap = 1024) and its bounds
 stage resident.  Then M_cap = 64 ticks, 0.05 s apart, every pose at the raceline's own speed, the
 plan's cfg, a merge length of 25 m and the car heading 10 degrees left of the raceline.  The
-variants are interleaved call by call, in an order that rotates from round to round so that none
-always follows the same one (>= 20 calls each after warm-up, the warm-up calls dropped), and
-reported as medians with min-max:
+variants are interleaved by stage_bench.interleave (>= 20 calls each after warm-up) and reported
+as medians with min-max:
 
   rcv_q1_k64, rcv_q1_k512         Plan.recover + fetch_recover of one pose over K_cap = 64 / 512 nodes
   rcv_q1024_k64, rcv_q1024_k512   1024 poses jittered around the raceline, the same K_cap
@@ -25,158 +24,67 @@ the medians and "rtm_spread_kernel_ms_*" the retime figure's max - min in this f
 
   python scripts/bench_recover.py [--calls 20] [--out profiles/recover_c2.json]
 """
-import argparse
-import json
-import os
-import statistics
-import sys
-import time
-
 import numpy as np
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [REPO, os.path.join(REPO, "tests")]
-
-import oracle_lib as O  # noqa: E402  (fixture loader only)
-from practice_path_planning_for_formula_student_driverless_amd import abi, raceline  # noqa: E402
+import stage_bench as sb
+from stage_bench import abi, raceline
 
 HEADING_TOL = 2.0 ** -49               # atan2_cr on the device, math.atan2 on the host (tests/recover_cases.py)
+K_CAP = abi.RL_RCV_MAX_NODES
+POSES = ("q1", "q1024")
+SHAPES = {f"{q}_k{k}": (q, k) for q in POSES for k in (64, K_CAP)}
 
 
-def stats(v):
-    v = sorted(v)
-    return {"median": round(statistics.median(v), 4), "min": round(v[0], 4), "max": round(v[-1], 4), "n": len(v)}
-
-
-def equal(got, want):
-    """Bit for bit in everything fetched but heading, which is within HEADING_TOL."""
-    ok = want.end_node >= 0
-    for f in abi.RCV_INTS:
-        if not np.array_equal(getattr(got, f)[ok], getattr(want, f)[ok]):
-            return False
-    for f in abi.HZN_LOC + abi.RCV_SCAL:
-        if not np.array_equal(getattr(got, f).view(np.uint64)[ok], getattr(want, f).view(np.uint64)[ok]):
-            return False
-    for q, m in enumerate(want.count):
-        for f in abi.TRAJ_COLS + abi.RCV_COLS:
-            g, w = getattr(got, f)[q, :m], getattr(want, f)[q, :m]
-            if f == "heading":
-                if not np.all((g.view(np.uint64) == w.view(np.uint64)) | (np.abs(g - w) <= HEADING_TOL)):
-                    return False
-            elif not np.array_equal(g.view(np.uint64), w.view(np.uint64)):
-                return False
-    return True
+def variants(a):
+    return [f"{kind}_{s}" for s in SHAPES for kind in ("rcv", "rtm")] + [f"host_{s}" for s in SHAPES]
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--calls", type=int, default=20)
+    ap = sb.parser("bench_recover", cap=64, queries=True)
     ap.add_argument("--host-calls", type=int, default=1)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--case", default="cmap1_n2000")
-    ap.add_argument("--batch", type=int, default=1024)
-    ap.add_argument("--dt", type=float, default=0.05)
-    ap.add_argument("--cap", type=int, default=64)
-    ap.add_argument("--queries", type=int, default=1024)
     ap.add_argument("--merge-len", type=float, default=25.0)
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "recover_c2.json"))
-    a = ap.parse_args()
-    if a.calls < 20:
-        ap.error("--calls: at least 20 per variant")
-    lib = abi.load_library()
-    if lib.rl_device_count() < 1:
-        raise SystemExit("bench_recover: no HIP device visible (nothing is measured without one)")
-    case = O.load_case(a.case)
-    prob, cfg = O.case_problem(case), O.case_cfg(case)
-    B, N = a.batch, prob.N
-    K_CAP = abi.RL_RCV_MAX_NODES
-    pl = raceline.Plan(prob, cfg, seeds=np.arange(B, dtype=np.uint64), B=B, modes=abi.RL_MODE_MINTIME)
-    pl.run()
-    pl.select("mintime", k=1, score="lap")
-    pl.trajectory("mintime", a.dt, 1024, rows="selected")
-    pl.bounds()
-    sel, traj, bnd = pl.fetch_selected(), pl.fetch_trajectory(), pl.fetch_bounds()
-    o = sel.out
-    rows, h = (o.x, o.y, o.heading, o.kappa, o.v, o.ax), prob.L / N
-    stamps = traj.stamps
-    rng = np.random.default_rng(1)
-    g = N // 3
-    at1 = np.array([g])
-    at = rng.integers(0, N - 1 - K_CAP if not prob.closed else N, size=a.queries)
+    a = sb.parse(ap, variants)
+    c2 = sb.c2_setup(a, "mintime", bounds=True)
+    pl, prob, cfg, rows, h, stamps, bnd = c2
+    poses, dirs = (dict(zip(POSES, x)) for x in sb.beside_poses(rows, bnd, prob, a.queries, K_CAP))
+    own = {q: sb.own_speed(c2, P, a.dt)[0] for q, P in poses.items()}
 
-    def beside(at, e):
-        return np.ascontiguousarray(np.stack([rows[0][0, at] + e * bnd.nx[0, at], rows[1][0, at] + e * bnd.ny[0, at]], axis=1))
+    def call(v):
+        kind, s = v.split("_", 1)
+        q, k = SHAPES[s]
+        if kind == "rcv":
+            pl.recover(poses[q], own[q], cfg, a.merge_len, dirs[q], dt=a.dt, m_cap=a.cap, k_cap=k)
+            return pl.fetch_recover(nodes=False)
+        if kind == "rtm":
+            pl.retime(poses[q], own[q], cfg, dt=a.dt, m_cap=a.cap, k_cap=k)
+            return pl.fetch_retime(nodes=False)
+        return raceline.recover_host(*rows, h, prob.closed, bnd.lo, bnd.hi, poses[q], own[q], cfg, a.merge_len, dirs[q],
+                                     nx=bnd.nx, ny=bnd.ny, dt=a.dt, m_cap=a.cap, k_cap=k, stamps=stamps)
 
-    def heading(at):
-        psi = rows[2][0, at] + np.pi / 18.0
-        return np.ascontiguousarray(np.stack([np.cos(psi), np.sin(psi)], axis=1))
-
-    poses = {"q1": beside(at1, 0.3), "q1024": beside(at, rng.uniform(-0.6, 0.6, size=a.queries))}
-    dirs = {"q1": heading(at1), "q1024": heading(at)}
-    own = {}
-    for q, P in poses.items():          # the raceline's own speed at the located points
-        hz = raceline.horizon_host(*rows, h, prob.closed, P, dt=a.dt, m_cap=1, stamps=stamps)
-        V = rows[4][0]
-        own[q] = V[hz.seg] + hz.u * (V[(hz.seg + 1) % N] - V[hz.seg])
-
-    shapes = {f"{q}_k{k}": (q, k) for q in poses for k in (64, K_CAP)}
-    names = [f"{kind}_{s}" for s in shapes for kind in ("rcv", "rtm")] + [f"host_{s}" for s in shapes]
-    t = {v: {"host_ms": []} for v in names}
-    for v in names:
-        if not v.startswith("host_"):
-            t[v]["kernel_ms"] = []
-    res = {}
-    for i in range(a.warmup + a.calls):
-        for v in names[i % len(names):] + names[:i % len(names)]:   # (what a variant follows changes from call to call)
-            slow = v.startswith("host_q1024")
-            if slow and (i < a.warmup or i - a.warmup >= a.host_calls):
-                continue
-            kind, s = v.split("_", 1)
-            q, k = shapes[s]
-            t0 = time.perf_counter()
-            if kind == "rcv":
-                pl.recover(poses[q], own[q], cfg, a.merge_len, dirs[q], dt=a.dt, m_cap=a.cap, k_cap=k)
-                res[v] = pl.fetch_recover(nodes=False)
-            elif kind == "rtm":
-                pl.retime(poses[q], own[q], cfg, dt=a.dt, m_cap=a.cap, k_cap=k)
-                res[v] = pl.fetch_retime(nodes=False)
-            else:
-                res[v] = raceline.recover_host(*rows, h, prob.closed, bnd.lo, bnd.hi, poses[q], own[q], cfg, a.merge_len, dirs[q],
-                                               nx=bnd.nx, ny=bnd.ny, dt=a.dt, m_cap=a.cap, k_cap=k, stamps=stamps)
-            ms = (time.perf_counter() - t0) * 1e3
-            if i >= a.warmup:
-                t[v]["host_ms"].append(ms)
-                if "kernel_ms" in t[v]:
-                    t[v]["kernel_ms"].append(pl.kernel_ms(14 if kind == "rcv" else 13))
+    t, res = sb.interleave(pl, variants(a), call, lambda v: {"rcv_": 14, "rtm_": 13}.get(v[:4]), a.calls, a.warmup,
+                           skip=sb.slow_host(a))
     pl.close()
-    rec = {"workload": "C2", "case": a.case, "N": N, "B": B, "mode": "mintime", "dt": a.dt, "M_cap": a.cap, "K_cap_max": K_CAP,
-           "Q_many": a.queries, "calls_per_variant": a.calls, "host_calls_q1024": a.host_calls, "warmup_calls": a.warmup,
-           "h_m": float(h), "merge_len_m": a.merge_len, "dir": "the raceline's heading + 10 degrees", "query_cfg": "the plan's"}
-    for v in names:
-        rec[v] = {k: stats(x) for k, x in t[v].items()}
-    for s in shapes:
+    rec = {**sb.header(a, prob.N, "mintime"), "K_cap_max": K_CAP, "Q_many": a.queries, "calls_per_variant": a.calls,
+           "host_calls_q1024": a.host_calls, "warmup_calls": a.warmup, "h_m": float(h), "merge_len_m": a.merge_len,
+           "dir": "the raceline's heading + 10 degrees", "query_cfg": "the plan's", **sb.blocks(t)}
+    for s in SHAPES:
         want, got = res[f"host_{s}"], res[f"rcv_{s}"]
         ke = want.end_node
         rec[f"end_node_{s}"] = {"min": int(ke.min()), "max": int(ke.max()), "feasible": int(want.feasible.sum()),
                                 "clamped": int(np.count_nonzero(want.clamped > 0)), "merged": int(np.count_nonzero(want.merge_node >= 0)),
                                 "offtrack": int(want.offtrack.sum()), "of": int(len(ke))}
-        rec[f"equal_{s}"] = bool(equal(got, want))
+        # bit for bit in everything fetched but heading, which is within HEADING_TOL
+        rec[f"equal_{s}"] = bool(sb.same_answer(got, want, mask="end_node", heading_tol=HEADING_TOL))
         rk, tk = rec[f"rcv_{s}"]["kernel_ms"], rec[f"rtm_{s}"]["kernel_ms"]
         rec[f"us_per_node_and_pass_{s}"] = round(rk["median"] * 1e3 / (2 * max(int(ke.max()), 1)), 4)
         rec[f"rcv_minus_rtm_kernel_ms_{s}"] = round(rk["median"] - tk["median"], 4)
         rec[f"rtm_spread_kernel_ms_{s}"] = round(tk["max"] - tk["min"], 4)
         rec[f"dev_over_host_{s}"] = round(rec[f"rcv_{s}"]["host_ms"]["median"] / rec[f"host_{s}"]["host_ms"]["median"], 6)
-    doc = {"script": "scripts/bench_recover.py",
-           "method": "variants interleaved call by call in one process in a rotating order, warm-up calls dropped; host clock around "
-                     "Plan.recover + fetch_recover / Plan.retime + fetch_retime (which synchronise) and around recover_host on rows, "
-                     "stamps and bounds already on the host (the 1024-pose host variants host_calls_q1024 times only); "
-                     "rl_plan_kernel_ms(14) / (13) of the same call",
-           "records": [rec]}
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(doc, f, indent=1)
-        f.write("\n")
-    print(json.dumps({k: v for k, v in rec.items() if k not in ("workload", "case")}))
+    sb.write(a, "variants interleaved call by call in one process in a rotating order, warm-up calls dropped; host clock around "
+                "Plan.recover + fetch_recover / Plan.retime + fetch_retime (which synchronise) and around recover_host on rows, "
+                "stamps and bounds already on the host (the 1024-pose host variants host_calls_q1024 times only); "
+                "rl_plan_kernel_ms(14) / (13) of the same call", [rec])
+    sb.summarise(rec)
 
 
 if __name__ == "__main__":

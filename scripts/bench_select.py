@@ -15,38 +15,25 @@ full-download call of this same process, never a number from another run.
 
   python scripts/bench_select.py [--calls 24] [--out profiles/select_c2.json]
 """
-import argparse
-import ctypes as C
 import json
-import os
 import statistics
-import sys
 import time
 
 import numpy as np
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [REPO, os.path.join(REPO, "tests")]
-
-import oracle_lib as O  # noqa: E402  (fixture loader only)
-from practice_path_planning_for_formula_student_driverless_amd import abi, raceline  # noqa: E402
+import stage_bench as sb
+from stage_bench import abi, last_call, raceline
 
 
 def stats(v):
+    """stage_bench.stats' with the 10th and the 90th percentile."""
     v = sorted(v)
     return {"median": round(statistics.median(v), 4), "min": round(v[0], 4), "max": round(v[-1], 4),
             "p10": round(v[len(v) // 10], 4), "p90": round(v[(9 * len(v)) // 10], 4), "n": len(v)}
 
 
-def last_call(lib):
-    k, c = C.c_float(), C.c_float()
-    assert lib.rl_last_call_ms(C.byref(k), C.byref(c)) == 0
-    return float(k.value), float(c.value)
-
-
 def workload(lib, label, case_name, B, mode, calls, warmup):
-    case = O.load_case(case_name)
-    prob, cfg = O.case_problem(case), O.case_cfg(case)
+    prob, cfg = sb.problem(case_name)
     seeds = np.arange(B, dtype=np.uint64)
     mt = mode == "mintime"
     bit = abi.RL_MODE_MINTIME if mt else abi.RL_MODE_MINCURV
@@ -104,25 +91,13 @@ def workload(lib, label, case_name, B, mode, calls, warmup):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--calls", type=int, default=24)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "select_c2.json"))
-    a = ap.parse_args()
-    if a.calls < 20:
-        ap.error("--calls: at least 20 per variant")
-    lib = abi.load_library()
-    if lib.rl_device_count() < 1:
-        raise SystemExit("bench_select: no HIP device visible (nothing is measured without one)")
+    a = sb.parse(sb.parser("bench_select", calls=24, case=False), lambda a: ("full", "best"))
+    lib = a.lib
     recs = [workload(lib, "C2", "cmap1_n2000", 1024, "mincurv", a.calls, a.warmup),
             workload(lib, "C3-shaped min-time", "cmap1_n2000_vp20", 512, "mintime", a.calls, a.warmup)]
-    doc = {"script": "scripts/bench_select.py", "method": "variants interleaved call by call in one process; host clock "
-           "around synchronous calls, rl_last_call_ms for the in-call kernel (HIP events) and call time, "
-           "rl_plan_kernel_ms(3) for the selection stage", "records": recs}
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(doc, f, indent=1)
-        f.write("\n")
+    sb.write(a, "variants interleaved call by call in one process; host clock "
+                "around synchronous calls, rl_last_call_ms for the in-call kernel (HIP events) and call time, "
+                "rl_plan_kernel_ms(3) for the selection stage", recs)
     for r in recs:
         print(json.dumps({k: r[k] for k in ("workload", "best_call_over_full_call", "best_call_minus_kernel_ms",
                                             "full_call_minus_kernel_ms", "selection_over_optimiser_kernel", "winner")}

@@ -1,5 +1,6 @@
 """CPU-side checks of scripts/: the A/B harness's tables name things that exist, and the
 ctypes declarations of abi.load_library are the recorded ones (no GPU, no compute calls)."""
+import copy
 import glob
 import json
 import os
@@ -8,13 +9,18 @@ import re
 import subprocess
 import sys
 
+import numpy as np
+import pytest
+
 import oracle_lib as O
-from practice_path_planning_for_formula_student_driverless_amd import abi, build
+from practice_path_planning_for_formula_student_driverless_amd import abi, build, raceline
+from query_cases import Q, ROW, synthetic_poses, synthetic_rows
 
 SCRIPTS = os.path.join(O.REPO, "scripts")
 if SCRIPTS not in sys.path:
     sys.path.insert(0, SCRIPTS)
 import ab  # noqa: E402
+import stage_bench as sb  # noqa: E402
 from build_variants import VARIANTS  # noqa: E402
 
 
@@ -96,3 +102,193 @@ def test_abi_table_declares_what_the_parent_declared():
         assert fn.restype is r, n
         if a is not None:
             assert list(fn.argtypes) == list(a), n
+
+
+# ------------------------------------------------------------------ scripts/stage_bench.py and the ten stage benchmarks
+STAGE_BENCHES = ("horizon", "rejoin", "stop", "retime", "recover", "recover_fan", "trajectory", "bounds", "select", "lap_select")
+
+
+def test_stage_bench_list_names_the_recorded_variants():
+    """`bench_*.py --list` in child processes whose RL_LIB names no file (loading librl.so would
+    raise): at default arguments the names are the record keys of the committed profile that hold
+    a host_ms block, no more and no fewer."""
+    env = dict(os.environ, RL_LIB=os.path.join(os.sep, "nonexistent", "librl.so"))
+    procs = {n: subprocess.Popen([sys.executable, os.path.join(SCRIPTS, f"bench_{n}.py"), "--list"], stdout=subprocess.PIPE,
+                                 stderr=subprocess.PIPE, text=True, env=env) for n in STAGE_BENCHES}
+    for n, p in procs.items():
+        out, err = p.communicate()
+        assert p.returncode == 0, (n, err)
+        names = out.split()
+        assert names and len(set(names)) == len(names), n
+        with open(os.path.join(O.REPO, "profiles", f"{n}_c2.json")) as f:
+            doc = json.load(f)
+        assert doc["script"] == f"scripts/bench_{n}.py"
+        for rec in doc["records"]:
+            assert names == [k for k, v in rec.items() if isinstance(v, dict) and "host_ms" in v], n
+
+
+def test_stage_bench_stats_shape_and_rounding():
+    assert sb.stats([3.00004, 1.23456789, 2.0, 10.0]) == {"median": 2.5, "min": 1.2346, "max": 10.0, "n": 4}
+    assert list(sb.stats([1.0])) == ["median", "min", "max", "n"]
+    assert sb.blocks({"v": {"host_ms": [2.0, 1.0, 4.0]}}) == {"v": {"host_ms": {"median": 2.0, "min": 1.0, "max": 4.0, "n": 3}}}
+
+
+def test_stage_bench_interleave_rotates_skips_and_drops_the_warm_up():
+    names, calls, warmup, log = ["a", "b", "c", "host_x"], 5, 2, []
+
+    class Pl:
+        def kernel_ms(self, idx):
+            return float(idx)
+
+    def call(v):
+        log.append(v)
+        return len(log)
+
+    t, res = sb.interleave(Pl(), names, call, lambda v: None if v.startswith("host_") else 7, calls, warmup)
+    n = len(names)
+    assert log == [v for i in range(warmup + calls) for v in names[i % n:] + names[:i % n]]
+    assert list(t) == names and res == {v: max(k + 1 for k, x in enumerate(log) if x == v) for v in names}
+    for v in names:
+        assert len(t[v]["host_ms"]) == calls and all(ms >= 0.0 for ms in t[v]["host_ms"])
+        assert t[v].get("kernel_ms") == (None if v == "host_x" else [7.0] * calls)
+    # skip(name, i): the variant is neither called nor timed in that round, the rotation of the others stays
+    log.clear()
+    skip = lambda v, i: v == "host_x" and (i < warmup or i - warmup >= 1)      # noqa: E731
+    t, res = sb.interleave(None, names, call, lambda v: None, calls, warmup, skip=skip)
+    assert log == [v for i in range(warmup + calls) for v in names[i % n:] + names[:i % n] if not skip(v, i)]
+    assert [len(t[v]["host_ms"]) for v in names] == [calls, calls, calls, 1]
+    # warm-up rounds only: every variant is called, none is timed
+    log.clear()
+    t, res = sb.interleave(Pl(), names, call, lambda v: 7, 0, warmup)
+    assert len(log) == warmup * n and all(d == {"host_ms": [], "kernel_ms": []} for d in t.values())
+
+
+def test_slow_host_is_the_host_calls_rule():
+    a = type("A", (), {"warmup": 3, "host_calls": 2})
+    skip = sb.slow_host(a)
+    assert [i for i in range(9) if not skip("host_q1024_k64", i)] == [3, 4]
+    assert not any(skip(v, i) for v in ("host_q1_k64", "rtm_q1024_k64") for i in range(9))
+
+
+# the verdicts of the stage benchmarks before stage_bench.same_answer replaced them, as they stood
+def _old_equal_horizon(got, want):
+    if not (np.array_equal(got.seg, want.seg) and np.array_equal(got.count, want.count)):
+        return False
+    for f in abi.HZN_LOC:
+        if not np.array_equal(getattr(got, f).view(np.uint64), getattr(want, f).view(np.uint64)):
+            return False
+    return all(np.array_equal(getattr(got, f)[q, :m].view(np.uint64), getattr(want, f)[q, :m].view(np.uint64))
+               for q, m in enumerate(want.count) for f in abi.TRAJ_COLS)
+
+
+def _old_equal_rejoin(got, want):
+    for f in abi.RJN_INTS:
+        if not np.array_equal(getattr(got, f), getattr(want, f)):
+            return False
+    for f in abi.HZN_LOC + abi.RJN_SCAL:
+        if not np.array_equal(getattr(got, f).view(np.uint64), getattr(want, f).view(np.uint64)):
+            return False
+    return all(np.array_equal(getattr(got, f)[q, :m].view(np.uint64), getattr(want, f)[q, :m].view(np.uint64))
+               for q, m in enumerate(want.count) for f in abi.TRAJ_COLS)
+
+
+def _old_equal_masked(ints, scal, mask):
+    def equal(got, want):
+        ok = getattr(want, mask) >= 0
+        for f in ints:
+            if not np.array_equal(getattr(got, f)[ok], getattr(want, f)[ok]):
+                return False
+        for f in abi.HZN_LOC + scal:
+            if not np.array_equal(getattr(got, f).view(np.uint64)[ok], getattr(want, f).view(np.uint64)[ok]):
+                return False
+        return all(np.array_equal(getattr(got, f)[q, :m].view(np.uint64), getattr(want, f)[q, :m].view(np.uint64))
+                   for q, m in enumerate(want.count) for f in abi.TRAJ_COLS)
+    return equal
+
+
+HEADING_TOL = 2.0 ** -49
+
+
+def _old_equal_recover(got, want):
+    ok = want.end_node >= 0
+    for f in abi.RCV_INTS:
+        if not np.array_equal(getattr(got, f)[ok], getattr(want, f)[ok]):
+            return False
+    for f in abi.HZN_LOC + abi.RCV_SCAL:
+        if not np.array_equal(getattr(got, f).view(np.uint64)[ok], getattr(want, f).view(np.uint64)[ok]):
+            return False
+    for q, m in enumerate(want.count):
+        for f in abi.TRAJ_COLS + abi.RCV_COLS:
+            g, w = getattr(got, f)[q, :m], getattr(want, f)[q, :m]
+            if f == "heading":
+                if not np.all((g.view(np.uint64) == w.view(np.uint64)) | (np.abs(g - w) <= HEADING_TOL)):
+                    return False
+            elif not np.array_equal(g.view(np.uint64), w.view(np.uint64)):
+                return False
+    return True
+
+
+M_CAP = 32
+
+
+@pytest.fixture(scope="module")
+def answers():
+    """stage -> (the host specification's answer on synthetic rows of N = 65 with Q = 7 poses, one
+    of them nowhere; the stage's verdict before the harness; same_answer's arguments for it)."""
+    N, closed = 65, False
+    rows, h = synthetic_rows(N, 7)
+    P, _ = synthetic_poses(rows, N, N - 1, np.random.default_rng(11))
+    P[3] = np.nan                                                  # (located nowhere: seg = -1, count = 0, no nodes)
+    cfg, v0 = abi.default_cfg(), np.full(Q, 5.0)
+    kw = dict(row=ROW, dt=0.01, m_cap=M_CAP)
+    hzn = raceline.horizon_host(*rows, h, closed, P, **kw)
+    i = np.maximum(hzn.seg, 0)
+    J = np.where(np.arange(Q) % 3 == 0, i, np.minimum(i + 5, N - 1)).astype(np.int32)     # (the segment's own start: stop_node = -1)
+    lo = np.full((3, N), -1.5)
+    return {
+        "horizon": (hzn, _old_equal_horizon, {}),
+        "rejoin": (raceline.rejoin_host(*rows, h, closed, P, v0, cfg, k_cap=7, **kw), _old_equal_rejoin, {}),
+        "stop": (raceline.stop_host(*rows, h, closed, P, v0, cfg, J, 0.0, k_cap=7, **kw),
+                 _old_equal_masked(abi.STP_INTS, abi.STP_SCAL, "stop_node"), {"mask": "stop_node"}),
+        "retime": (raceline.retime_host(*rows, h, closed, P, v0, sb.wet_cfg(cfg), k_cap=7, **kw),
+                   _old_equal_masked(abi.RTM_INTS, abi.RTM_SCAL, "end_node"), {"mask": "end_node"}),
+        "recover": (raceline.recover_host(*rows, h, closed, lo, -lo, P, v0, cfg, 5.0, k_cap=7, **{**kw, "dt": 0.3}),
+                    _old_equal_recover, {"mask": "end_node", "heading_tol": HEADING_TOL}),
+    }
+
+
+def _flipped(want, f, at, bit=1):
+    """A copy of want with one bit of field f flipped at index `at` (float64: of the mantissa)."""
+    got = copy.deepcopy(want)
+    a = getattr(got, f)
+    a.view(np.uint64 if a.dtype == np.float64 else np.uint32)[at] ^= bit
+    return got
+
+
+@pytest.mark.parametrize("stage", ["horizon", "rejoin", "stop", "retime", "recover"])
+def test_same_answer_is_the_verdict_each_stage_had(answers, stage):
+    want, old, kw = answers[stage]
+    cls, count = type(want), want.count
+    mask = getattr(want, kw["mask"]) if "mask" in kw else np.zeros(Q, dtype=np.int32)
+    assert (cls._COLS == abi.TRAJ_COLS + abi.RCV_COLS) == (stage == "recover")
+    assert np.any((count > 0) & (count < M_CAP)) and np.any(mask < 0) == ("mask" in kw) and np.any(mask >= 0)
+    assert sb.same_answer(want, want, **kw) and sb.same_answer(copy.deepcopy(want), want, **kw)
+    # one bit of one entry, every field, every query, around count[q]: the verdict is the old one
+    cases = [(f, (q, m)) for f in cls._COLS for q in range(Q) for m in {0, count[q] - 1, count[q], M_CAP - 1} if 0 <= m < M_CAP]
+    cases += [(f, q) for f in cls._PER + cls._INTS for q in range(Q)]
+    seen = set()
+    for f, at in cases:
+        for bit in (1, 1 << 30):
+            got = _flipped(want, f, at, bit)
+            new = sb.same_answer(got, want, **kw)
+            assert new == old(got, want), (f, at, bit)
+            if f in cls._COLS:
+                expect = at[1] >= count[at[0]] or (f == "heading" and bit == 1 and stage == "recover")
+            else:
+                expect = bool(mask[at] < 0)
+            assert new == expect, (f, at, bit)
+            seen.add((f in cls._COLS, new))
+    assert seen >= {(True, True), (True, False), (False, False)} and ((False, True) in seen) == ("mask" in kw)
+    # seg: unmasked where the stage's verdict had no mask; under a mask, that of a masked query does not count
+    for q in range(Q):
+        assert sb.same_answer(_flipped(want, "seg", q), want, **kw) == bool(mask[q] < 0)
