@@ -249,7 +249,8 @@ int rl_plan_bind_device_outputs(rl_plan* plan, int32_t which, const rl_out* dev_
  * last rl_plan_stop, 11 = the bounds stage of the last rl_plan_bounds, 12 = the bounds at the
  * horizon stage's ticks of the last rl_plan_horizon_bounds, 13 = the retime stage of the last
  * rl_plan_retime, 14 = the recover stage of the last rl_plan_recover, 15 = the fan stage of the
- * last rl_plan_recover_fan. */
+ * last rl_plan_recover_fan, 16 = the rollout stage of the last rl_plan_rollouts (its locate and
+ * rank kernels together). */
 int rl_plan_kernel_ms(rl_plan* plan, int32_t idx, float* ms);
 /* The batch size the plan's kernel shape is chosen for (rl_kernel_shape's B); 0 = the plan's
  * own B (the default).  Shapes differ in the tree order of the J / decrease / lap sums, so
@@ -972,6 +973,91 @@ int rl_recover_fan(const double* x, const double* y, const double* heading, cons
                    const double* nx, const double* ny, int32_t N, int32_t B, int32_t closed,
                    const rl_fan_query* query, int32_t device, rl_fan* out);
 
+/* ------------------------------------------------- rollout stage: sampled trajectories scored against the plan
+ * Every stage above is interpolated from the raceline and its speed profile; none can judge a
+ * trajectory the controller proposes itself.  A sampling controller (MPPI, a lattice planner, a
+ * learned policy's candidates) proposes a few thousand short rollouts at every step.  This stage
+ * locates each rollout's poses on a row of the last trajectory stage, pose t next to pose t-1, and
+ * returns per rollout how far along the line it gets, how far off it strays, whether it leaves the
+ * last bounds stage's free width, how its speed compares with the row's, one cost, and the best
+ * rollouts of every group.  In fp64 without contraction; smax, smin, the row, its S segments and
+ * its step h are the horizon stage's:
+ *   query   Q rollouts of T poses: xy [Q][T][2], optional speeds v [Q][T], row [Q] (NULL: 0),
+ *           seg_hint [Q] >= -1 for pose 0 (NULL: -1, every segment; a hint past the row is allowed).
+ *           1 <= Q <= RL_RLL_MAX_ROLLOUTS, 1 <= T <= RL_RLL_MAX_STEPS, Q*T <= RL_RLL_MAX_POSES.
+ *   chain   pose 0 is located exactly as the horizon stage locates a pose with hint seg_hint and
+ *           window window0; pose t >= 1 with hint seg_{t-1} and window `window`: the same candidates
+ *           (every segment of a closed row when 2W + 1 >= S; none for a hint past an open row), the
+ *           same distance D, the same least (isnan(D), D, i).  Per pose: seg, u, dist2 = D and e as
+ *           the horizon stage's location.  The chain ends at the first pose without a winner (a NaN
+ *           winner, or no candidate): count = t, the per-pose values from t on are NaN and seg -1,
+ *           valid = 0, progress = cost = NaN.  A row without a segment: count = 0.
+ *   progress   c_0 = 0; for t >= 1 on a closed row with d = seg_t - seg_{t-1}: c_t = c_{t-1} + 1 if
+ *           2d < -S, c_{t-1} - 1 if 2d > S, c_{t-1} otherwise; on an open row c_t = 0.
+ *           s_t = (((double)c_t*(double)S + (double)seg_t) + u_t)*h; progress = s_{T-1} - s_0.
+ *   room    i = seg_t, j = (i+1) mod N: lo_t = smax(lo_i, lo_j), hi_t = smin(hi_i, hi_j) of the bounds
+ *           rows (rl_hzn_bnd's pair); margin_t = smin(hi_t - e_t, e_t - lo_t).
+ *   speed   vref_t = v_i + u_t*(v_j - v_i) of the row.
+ *   per rollout   over the located poses t < count, in ascending t, every sum started from 0.0:
+ *           E = sum e_t*e_t, O = sum (margin_t < 0 ? margin_t*margin_t : 0.0),
+ *           V = sum (v_t - vref_t)*(v_t - vref_t) (0.0 when v is NULL); e_max = smax(e_max, |e_t|) from
+ *           0.0; margin_min = smin(margin_min, margin_t) from +inf; first_out = the first t with
+ *           margin_t < 0 (none: T).  valid = (count == T), and then
+ *           cost = ((w_e*E + w_out*O) + w_v*V) - w_prog*progress, replaced by +inf if hard_bounds is
+ *           set and first_out < T.
+ *   ranking   order [G][k], G = Q/group_size (group_size 0: Q), 1 <= k <= min(group_size,
+ *           RL_SELECT_MAX_K): the global indices of the k best rollouts of each group, ascending in
+ *           (isnan(cost), cost, index): rl_rank_scores' order on cost, by its kernel.
+ * raceline.rollouts_host states the same in NumPy; the kernel equals it bit for bit.  These are
+ * additions to ABI 6.1 that leave RL_ABI_MINOR as it is: RL_FEATURE_ROLLOUT announces them. */
+#define RL_RLL_MAX_ROLLOUTS 65536
+#define RL_RLL_MAX_STEPS 512
+#define RL_RLL_MAX_POSES (1 << 22)
+typedef struct rl_rll_query {
+    const double*  xy;           /* [Q][T][2] */
+    const double*  v;            /* [Q][T] the rollouts' speeds; NULL: no speed term */
+    const int32_t* row;          /* [Q] row of the trajectory stage; NULL: 0 */
+    const int32_t* seg_hint;     /* [Q] hint of pose 0, >= -1; NULL: -1 */
+    int32_t        Q, T;
+    int32_t        window0;      /* >= 0, used with seg_hint for pose 0 */
+    int32_t        window;       /* >= 0, used for poses t >= 1 */
+    double         w_e, w_out, w_v, w_prog;   /* each finite and >= 0 */
+    int32_t        hard_bounds;  /* 0 / 1 */
+    int32_t        group_size;   /* 0: Q; Q is a multiple of it */
+    int32_t        k;            /* 1..min(group_size, RL_SELECT_MAX_K) */
+    int32_t        _pad;
+} rl_rll_query;
+
+typedef struct rl_rll {          /* caller-allocated; NULL fields skipped */
+    int32_t *seg;                                   /* [Q][T] */
+    double *u, *e, *dist2, *s, *margin, *vref;      /* [Q][T]; downloaded only when asked for, as seg */
+    int32_t *count, *valid, *first_out;             /* [Q] */
+    double *progress, *e_max, *margin_min, *cost;   /* [Q] */
+    int32_t *order;                                 /* [G][k] */
+} rl_rll;
+
+/* Enqueue the stage after the plan's last trajectory and bounds stages: rl_plan_recover's stream,
+ * validity and invalidation rules (a later run, trajectory or bounds stage invalidates it).  It
+ * leaves the results and every other stage untouched; its buffers are plan-owned (they count toward
+ * the plan cache's budget) and grow with Q*T.  The query's arrays are read before the call returns.
+ * rl_plan_kernel_ms index 16 is the stage (locate and rank together).  RL_EINVAL before any device
+ * work for: a NULL plan, query or xy; no valid trajectory stage, or no valid bounds stage after it;
+ * Q, T or Q*T out of range; a negative window; a weight that is not finite or is < 0; a row outside
+ * the trajectory stage's [0, R); a seg_hint < -1; Q not a multiple of group_size; k out of range. */
+int rl_plan_rollouts(rl_plan* plan, const rl_rll_query* query, void* hip_stream);
+/* Download the last rollout stage (synchronises its stream) into the non-NULL fields of results:
+ * the per-rollout values and order always, the per-pose arrays only when results asks for one.
+ * RL_EINVAL before a stage, or after a run, a trajectory or a bounds stage that followed it. */
+int rl_plan_fetch_rollouts(rl_plan* plan, rl_rll* results);
+/* The same on B given rows [B][N] with steps h [B] and their bounds rows lo, hi [B][N] (host in,
+ * host out); `row` counts the given rows.  Of the rows the stage reads x, y and v; heading, kappa
+ * and ax are taken for the other one-shots' sake.  Errors as rl_plan_rollouts', and a NULL row, h,
+ * lo, hi or results, B < 1, N < 1; RL_ETOOBIG for N > 1048576. */
+int rl_rollouts(const double* x, const double* y, const double* heading, const double* kappa,
+                const double* v, const double* ax, const double* h, const double* lo, const double* hi,
+                int32_t N, int32_t B, int32_t closed, const rl_rll_query* query, int32_t device,
+                rl_rll* results);
+
 /* B lap evaluations of given paths: heading/curvature
  * (heading_curv_from_points_generic, ref:595-620) and velocity_profile_forward_backward
  * (ref:782-862) with h = L[b]/N on path b — the min-time driver's final step
@@ -1055,6 +1141,7 @@ int         rl_abi_minor(void);
 #define RL_FEATURE_RETIME 32      /* bit 5: the retime stage */
 #define RL_FEATURE_RECOVER 64     /* bit 6: the recover stage */
 #define RL_FEATURE_FAN 128        /* bit 7: the fan stage */
+#define RL_FEATURE_ROLLOUT 256    /* bit 8: the rollout stage */
 int         rl_abi_features(void);
 /* samples per lane of the THROUGHPUT shape for N (4: N <= 256, 5: N <= 320, 8: N <= 4096;
  * 1 = the streaming kernel), or RL_ETOOBIG.  Batches small enough for a latency shape launch fewer samples per lane:

@@ -292,6 +292,35 @@ class RlHznBnd(C.Structure):
     _fields_ = [(n, C.POINTER(C.c_double)) for n in HZN_BND]
 
 
+RL_FEATURE_ROLLOUT = 256   # rl_abi_features() bit 8: the rollout stage
+RL_RLL_MAX_ROLLOUTS = 65536
+RL_RLL_MAX_STEPS = 512
+RL_RLL_MAX_POSES = 1 << 22
+RLL_POSE = ("u", "e", "dist2", "s", "margin", "vref")
+RLL_INTS = ("count", "valid", "first_out")
+RLL_SCAL = ("progress", "e_max", "margin_min", "cost")
+
+
+class RlRllQuery(C.Structure):
+    """``rl_rll_query`` — Q rollouts of T poses: xy [Q][T][2], the optional speeds v [Q][T], row and
+    seg_hint [Q], the two windows, the four weights, hard_bounds, and group_size and k of the ranking."""
+
+    _fields_ = [("xy", C.POINTER(C.c_double)), ("v", C.POINTER(C.c_double)), ("row", C.POINTER(C.c_int32)),
+                ("seg_hint", C.POINTER(C.c_int32)), ("Q", C.c_int32), ("T", C.c_int32), ("window0", C.c_int32),
+                ("window", C.c_int32), ("w_e", C.c_double), ("w_out", C.c_double), ("w_v", C.c_double),
+                ("w_prog", C.c_double), ("hard_bounds", C.c_int32), ("group_size", C.c_int32), ("k", C.c_int32),
+                ("_pad", C.c_int32)]
+
+
+class RlRll(C.Structure):
+    """``rl_rll`` — caller-allocated seg and u, e, dist2, s, margin, vref [Q][T], count, valid,
+    first_out and progress, e_max, margin_min, cost [Q], order [G][k]; NULL fields are skipped."""
+
+    _fields_ = ([("seg", C.POINTER(C.c_int32))] + [(n, C.POINTER(C.c_double)) for n in RLL_POSE] +
+                [(n, C.POINTER(C.c_int32)) for n in RLL_INTS] + [(n, C.POINTER(C.c_double)) for n in RLL_SCAL] +
+                [("order", C.POINTER(C.c_int32))])
+
+
 OUT_F64 = ("x", "y", "heading", "kappa", "alpha_total", "alpha_last")
 OUT_F64_MT = OUT_F64 + ("v", "ax")
 
@@ -675,6 +704,15 @@ DECLS_BND = [
 ]
 
 
+# the rollout stage: bound only in a library whose rl_abi_features() has RL_FEATURE_ROLLOUT
+_RLL, _RLLQ = _P(RlRll), _P(RlRllQuery)
+DECLS_RLL = [
+    ("rl_plan_rollouts", C.c_int, [C.c_void_p, _RLLQ, C.c_void_p]),
+    ("rl_plan_fetch_rollouts", C.c_int, [C.c_void_p, _RLL]),
+    ("rl_rollouts", C.c_int, [_F64] * 9 + [C.c_int32, C.c_int32, C.c_int32, _RLLQ, C.c_int32, _RLL]),
+]
+
+
 def declare_optimize(fn) -> None:
     """rl_optimize's signature (the oracle's oracle_optimize shares it)."""
     fn.restype, fn.argtypes = DECLS[0][1], DECLS[0][2]
@@ -687,8 +725,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     """Load librl.so (the HIP path).  Raises if it is missing: there is no fallback; a library
     that lacks a function of DECLS or DECLS_EXT raises AttributeError naming it, and so does
     one that announces RL_FEATURE_HORIZON / RL_FEATURE_REJOIN / RL_FEATURE_STOP /
-    RL_FEATURE_BOUNDS / RL_FEATURE_RETIME / RL_FEATURE_RECOVER / RL_FEATURE_FAN and lacks a function
-    of DECLS_HZN / DECLS_RJN / DECLS_STP / DECLS_BND / DECLS_RTM / DECLS_RCV / DECLS_FAN."""
+    RL_FEATURE_BOUNDS / RL_FEATURE_RETIME / RL_FEATURE_RECOVER / RL_FEATURE_FAN / RL_FEATURE_ROLLOUT and
+    lacks a function of DECLS_HZN / DECLS_RJN / DECLS_STP / DECLS_BND / DECLS_RTM / DECLS_RCV / DECLS_FAN /
+    DECLS_RLL."""
     global _LIB
     if _LIB is not None and path == LIB_PATH:
         return _LIB
@@ -712,6 +751,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
             bind(_stage_decls(*st))
     if features & RL_FEATURE_BOUNDS:
         bind(DECLS_BND)
+    if features & RL_FEATURE_ROLLOUT:
+        bind(DECLS_RLL)
     if path == LIB_PATH:
         _LIB = lib
     return lib

@@ -97,7 +97,7 @@ int rl_abi_version(void) { return RL_ABI_VERSION; }
 int rl_abi_minor(void) { return RL_ABI_MINOR; }
 int rl_abi_features(void) {
     return RL_FEATURE_TRAJECTORY | RL_FEATURE_HORIZON | RL_FEATURE_REJOIN | RL_FEATURE_STOP | RL_FEATURE_BOUNDS |
-           RL_FEATURE_RETIME | RL_FEATURE_RECOVER | RL_FEATURE_FAN;
+           RL_FEATURE_RETIME | RL_FEATURE_RECOVER | RL_FEATURE_FAN | RL_FEATURE_ROLLOUT;
 }
 
 int rl_device_count(void) {
@@ -467,6 +467,50 @@ int rl_recover_fan(const double* x, const double* y, const double* heading, cons
                    const double* ax, const double* h, const double* lo, const double* hi, const double* nx, const double* ny,
                    int32_t N, int32_t B, int32_t closed, const rl_fan_query* query, int32_t device, rl_fan* out) {
     return one_shot<QueryKind::Fan>({x, y, heading, kappa, v, ax, h, lo, hi, nx, ny}, N, B, closed, query, device, out);
+}
+
+// the rollout stage's kernels (rl_rollout.hip, rl_select.hip's rank) on B host rows and their
+// bounds rows: of the rows only x, y, v and the steps go up, no stamps are needed
+int rl_rollouts(const double* x, const double* y, const double* heading, const double* kappa, const double* v,
+                const double* ax, const double* h, const double* lo, const double* hi, int32_t N, int32_t B,
+                int32_t closed, const rl_rll_query* query, int32_t device, rl_rll* out) {
+    if (!x || !y || !heading || !kappa || !v || !ax || !h || !lo || !hi || !query || !out)
+        return fail(RL_EINVAL, "rl_rollouts: an input row, h, a bounds row, the query or results is NULL");
+    if (B < 1 || N < 0) return fail(RL_EINVAL, "rl_rollouts: B < 1 or N < 0");
+    if (N > rl::RL_STREAM_MAX_N) return fail(RL_ETOOBIG, "rl_rollouts: N exceeds 1048576");
+    int gs = 0;
+    if (int rc = check_rollouts(*query, B, &gs)) return rc;
+    if (N < 1) return fail(RL_EINVAL, "rollouts: N == 0 (no row)");
+    if (int rc = select_device(device)) return rc;
+    const size_t BN = (size_t)B * (size_t)N;
+    const RllLayout L = rll_layout((size_t)query->Q, (size_t)query->T, (size_t)(query->Q / gs) * (size_t)query->k,
+                                   query->v != nullptr, query->row != nullptr, query->seg_hint != nullptr);
+    DevArena mem;
+    const double* const src[5] = {x, y, v, lo, hi};
+    double* d_row[5];
+    for (auto& d : d_row) d = mem.get<double>(BN);
+    double* d_h = mem.get<double>((size_t)B);
+    char* d_qry = mem.get<char>(L.in_bytes);
+    char* d_res = mem.get<char>(L.out_bytes);
+    if (!mem.ok()) return fail(RL_ENOMEM, "rl_rollouts: hipMalloc failed");
+    std::vector<char> block(std::max(L.in_bytes, L.out_bytes));
+    rll_pack(*query, L, block.data());
+    for (int c = 0; c < 5; ++c)
+        if (hipMemcpy(d_row[c], src[c], BN * 8, hipMemcpyHostToDevice) != hipSuccess) return fail(RL_EHIP, "rl_rollouts: upload");
+    if (hipMemcpy(d_h, h, (size_t)B * 8, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_qry, block.data(), L.in_bytes, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(RL_EHIP, "rl_rollouts: upload");
+    rl::TrajParams t{};
+    t.x = d_row[0]; t.y = d_row[1]; t.v = d_row[2];
+    t.h = d_h;
+    t.N = N; t.B = B; t.R = B; t.closed = closed ? 1 : 0;
+    if (rll_launch(L, *query, gs, t, d_row[3], d_row[4], d_qry, d_res, nullptr) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+        return fail(RL_EHIP, "rl_rollouts: kernel");
+    const bool poses = rll_wants_poses(out);
+    if (hipMemcpy(block.data(), d_res, poses ? L.out_bytes : L.head_bytes, hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(RL_EHIP, "rl_rollouts: download");
+    rll_unpack(block.data(), L, out, poses);
+    return RL_OK;
 }
 
 // rank host scores with rl_rank_kernel (rl_select.hip)

@@ -75,17 +75,16 @@ struct HznWin {
     uint64_t key;
     uint32_t idx;
 };
-__device__ __forceinline__ HznWin hzn_locate(const HznParams& p, int k, int tid, const double* x, const double* y,
-                                             double px, double py, uint64_t* s_key, uint32_t* s_idx) {
-    const TrajParams& q = p.src;
-    const int N = q.N;
-    const int S = q.closed ? N : N - 1;
-    // the candidates are lo + c, c in [0, C), taken mod S on a closed row (lo > -S, lo + C < 2S)
-    const int g = p.hint ? p.hint[k] : -1;
-    const int64_t W = p.window;
+// The candidates of a hint g (-1: every segment) and window W on a row of S segments: lo + c,
+// c in [0, C), taken mod S on a closed row (lo > -S, lo + C < 2S).  The rollout stage's chain
+// (rl_rollout.hip) takes its candidates from here too.
+struct HznRange {
+    int lo, C;
+};
+__device__ __forceinline__ HznRange hzn_range(int closed, int S, int g, int64_t W) {
     int lo = 0, C = S;
     if (g >= 0) {
-        if (q.closed) {
+        if (closed) {
             if (2 * W + 1 < (int64_t)S) {
                 lo = g % S - (int)W;
                 C = 2 * (int)W + 1;
@@ -96,6 +95,15 @@ __device__ __forceinline__ HznWin hzn_locate(const HznParams& p, int k, int tid,
             C = (int)(e > S - 1 ? S - 1 : e) - lo + 1;         // <= 0 for a hint past the row: no candidate
         }
     }
+    return {lo, C};
+}
+__device__ __forceinline__ HznWin hzn_locate(const HznParams& p, int k, int tid, const double* x, const double* y,
+                                             double px, double py, uint64_t* s_key, uint32_t* s_idx) {
+    const TrajParams& q = p.src;
+    const int N = q.N;
+    const int S = q.closed ? N : N - 1;
+    const HznRange rg = hzn_range(q.closed, S, p.hint ? p.hint[k] : -1, p.window);
+    const int lo = rg.lo, C = rg.C;
     uint64_t bk = HZN_KEY_NONE;
     uint32_t bi = HZN_IDX_NONE;
     for (int c = tid; c < C; c += HZN_THREADS) {

@@ -23,6 +23,7 @@
 #include "rl_rejoin.h"
 #include "rl_query.h"
 #include "rl_bounds.h"
+#include "rl_rollout.h"
 
 namespace rl {
 
@@ -549,17 +550,22 @@ struct rl_plan {
     size_t hb_cap_QM = 0, hb_cap_Q = 0;
     int hb_Q = 0, hb_M = 0;
     hipEvent_t ev_hb[2] = {nullptr, nullptr};
+    // rollout stage (rl_plan_rollouts, rl::RllParams): blocks and pinned staging of its own on the
+    // pose-query stages' pattern (rl::RllLayout has their layout); rll.Q = 0: no stage since the
+    // last run, trajectory or bounds stage.  rll.M is that stage's T, rll_R its G*k.
+    rl::QueryStage rll;
+    int rll_R = 0;
     // a run or a trajectory stage invalidates the pose-query stages that read the one before,
     // and the bounds of its rows
     void drop_queries() {
         for (auto& s : qs) s.Q = 0;
-        bnd_R = hb_Q = 0;
+        bnd_R = hb_Q = rll.Q = 0;
     }
     // a bounds stage invalidates what read the one before: the tick bounds and the stages whose kind reads_bounds
     void drop_bounds_readers() {
         for (int k = 0; k < rl::QUERY_KINDS; ++k)
             if (rl::kKinds[k].reads_bounds) qs[k].Q = 0;
-        bnd_R = hb_Q = 0;
+        bnd_R = hb_Q = rll.Q = 0;
     }
 
     template <class T>
@@ -572,7 +578,7 @@ struct rl_plan {
     size_t dev_bytes() const {
         size_t n = mem.bytes + sel_mem.bytes + lap_mem.bytes + traj_mem.bytes + bnd_mem.bytes + hb_mem.bytes;
         for (const auto& s : qs) n += s.dev_bytes();
-        return n;
+        return n + rll.dev_bytes();
     }
     // the stream of the last run or stage
     hipStream_t run_stream() const { return last_stream ? last_stream : own_stream; }
@@ -616,5 +622,26 @@ int check_query(QueryKind kind, const QueryView& q, int32_t R, int32_t N, int32_
 // the bounds rows lo, hi, nx, ny (device) of a kind that reads them; scratch: the fan stage's block
 hipError_t query_launch(const QueryLayout& L, const QueryView& q, const TrajParams& src, char* in, char* out,
                         const double* const (&bnd)[4], char* scratch, hipStream_t st);
+// The rollout stage's packed blocks.  in: xy [Q][T][2], v [Q][T] (if given), row, seg_hint [Q] (if
+// given).  out: the head (progress, e_max, margin_min, cost [Q] f64; count, valid, first_out [Q]
+// i32; order [R] i32, R = G*k), then the per-pose arrays (u, e, dist2, s, margin, vref [Q][T] f64;
+// seg [Q][T] i32).  Every f64 array starts on a multiple of 8 bytes.
+struct RllLayout {
+    size_t Q, T, R;
+    bool has_v, has_row, has_hint;
+    size_t in_bytes, head_bytes, out_bytes;
+};
+RllLayout rll_layout(size_t Q, size_t T, size_t R, bool has_v, bool has_row, bool has_hint);
+// argument checks of the rollout entry points (no device call): the query, NULL-checked by the
+// caller, against a trajectory stage of R rows; *gs = the group size
+int check_rollouts(const rl_rll_query& q, int32_t R, int* gs);
+void rll_pack(const rl_rll_query& q, const RllLayout& L, char* block);
+// the fields of o from the results' block; poses: the block holds the per-pose arrays as well
+void rll_unpack(const char* block, const RllLayout& L, const rl_rll* o, bool poses);
+bool rll_wants_poses(const rl_rll* o);
+// the rollout kernel on q, then the rank kernel on its costs: the blocks `in` and `out` (device)
+// laid out as L, reading the trajectory stage src and the bounds rows lo, hi (device)
+hipError_t rll_launch(const RllLayout& L, const rl_rll_query& q, int gs, const TrajParams& src, const double* lo,
+                      const double* hi, char* in, char* out, hipStream_t st);
 
 }  // namespace rl

@@ -194,6 +194,7 @@ int rl_plan_destroy(rl_plan* plan) {
     for (auto& e : plan->ev_traj)
         if (e) hipEventDestroy(e);
     for (auto& s : plan->qs) s.release();
+    plan->rll.release();
     plan->bnd_mem.release();
     plan->hb_mem.release();
     for (auto& e : plan->ev_bnd)
@@ -468,6 +469,11 @@ int rl_plan_kernel_ms(rl_plan* p, int32_t idx, float* ms) {
     else if (idx == 12 && p->hb_Q && p->traj_R) {       // 12: the bounds at the horizon stage's ticks
         a = p->ev_hb[0];
         b = p->ev_hb[1];
+        HIPCHK(hipEventSynchronize(b));
+    }
+    else if (idx == 16 && p->rll.Q && p->bnd_R && p->traj_R) {   // 16: the rollout stage (locate and rank)
+        a = p->rll.ev[0];
+        b = p->rll.ev[1];
         HIPCHK(hipEventSynchronize(b));
     }
     else if (idx == 1 && mc) { a = p->ev[1]; b = p->ev_end[0]; }

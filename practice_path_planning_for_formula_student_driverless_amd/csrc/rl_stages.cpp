@@ -13,7 +13,9 @@
 // they share one checked prologue, one enqueue (query_enqueue), one launch switch (query_launch) and
 // one fetch (query_fetch), and their entry points are one-line forwards that name the kind.
 // Bounds stage (rl_bounds.hip): the free track width about the trajectory stage's
-// rows, and at the horizon stage's ticks.
+// rows, and at the horizon stage's ticks.  Rollout stage (rl_rollout.hip): sampled
+// trajectories located pose by pose on those rows, scored and ranked; a stage of its own beside the
+// table, as the bounds stage is, because its arrays are [Q][T].
 #include "rl_host.h"
 
 using namespace rl;
@@ -176,6 +178,109 @@ hipError_t rl::query_launch(const QueryLayout& L, const QueryView& q, const Traj
     }
     }
     return hipErrorInvalidValue;
+}
+
+// ------------------------------------------------------------------ the rollout stage's blocks
+namespace {
+
+size_t up8(size_t n) { return (n + 7) & ~(size_t)7; }
+
+// the arrays of the results' block laid out as L, from its base: f64 [Q] x4, i32 [Q] x3, order
+// [R]; then f64 [Q][T] x6 and seg [Q][T]
+struct RllOut {
+    char *head[RLL_HEAD_F64], *ihead[RLL_HEAD_I32], *order, *pose[RLL_POSE_F64], *seg;
+};
+RllOut rll_out(const RllLayout& L, char* base) {
+    RllOut o;
+    char* c = base;
+    for (auto& a : o.head) { a = c; c += L.Q * 8; }
+    for (auto& a : o.ihead) { a = c; c += L.Q * 4; }
+    o.order = c;
+    c = base + L.head_bytes;
+    for (auto& a : o.pose) { a = c; c += L.Q * L.T * 8; }
+    o.seg = c;
+    return o;
+}
+
+}  // namespace
+
+RllLayout rl::rll_layout(size_t Q, size_t T, size_t R, bool has_v, bool has_row, bool has_hint) {
+    RllLayout L{Q, T, R, has_v, has_row, has_hint, 0, 0, 0};
+    L.in_bytes = up8(Q * T * 8 * (has_v ? 3 : 2) + Q * 4 * ((has_row ? 1 : 0) + (has_hint ? 1 : 0)));
+    L.head_bytes = up8(Q * 8 * RLL_HEAD_F64 + Q * 4 * RLL_HEAD_I32 + R * 4);
+    L.out_bytes = L.head_bytes + up8(Q * T * 8 * RLL_POSE_F64 + Q * T * 4);
+    return L;
+}
+
+int rl::check_rollouts(const rl_rll_query& q, int32_t R, int* gs) {
+    if (!q.xy) return fail(RL_EINVAL, "rollouts: the query or its xy is NULL");
+    if (q.Q < 1 || q.Q > RL_RLL_MAX_ROLLOUTS) return fail(RL_EINVAL, "rollouts: Q must be 1..65536");
+    if (q.T < 1 || q.T > RL_RLL_MAX_STEPS) return fail(RL_EINVAL, "rollouts: T must be 1..512");
+    if ((int64_t)q.Q * q.T > RL_RLL_MAX_POSES) return fail(RL_EINVAL, "rollouts: Q*T must be <= 4194304");
+    if (q.window0 < 0 || q.window < 0) return fail(RL_EINVAL, "rollouts: window0 or window < 0");
+    for (double w : {q.w_e, q.w_out, q.w_v, q.w_prog})
+        if (!std::isfinite(w) || w < 0.0) return fail(RL_EINVAL, "rollouts: a weight that is not finite or is < 0");
+    const int g = q.group_size == 0 ? q.Q : q.group_size;
+    if (g < 1 || g > q.Q || q.Q % g != 0) return fail(RL_EINVAL, "rollouts: Q must be a multiple of group_size");
+    if (q.k < 1 || q.k > g || q.k > RL_SELECT_MAX_K) return fail(RL_EINVAL, "rollouts: k must be 1..min(group_size, 64)");
+    for (int32_t k = 0; k < q.Q; ++k) {
+        if (q.row && (q.row[k] < 0 || q.row[k] >= R)) return fail(RL_EINVAL, "rollouts: a row outside the trajectory stage's [0, R)");
+        if (q.seg_hint && q.seg_hint[k] < -1) return fail(RL_EINVAL, "rollouts: a seg_hint < -1");
+    }
+    *gs = g;
+    return RL_OK;
+}
+
+void rl::rll_pack(const rl_rll_query& q, const RllLayout& L, char* block) {
+    const size_t QT = L.Q * L.T;
+    char* c = block;
+    std::memcpy(c, q.xy, QT * 16); c += QT * 16;
+    if (L.has_v) { std::memcpy(c, q.v, QT * 8); c += QT * 8; }
+    if (L.has_row) { std::memcpy(c, q.row, L.Q * 4); c += L.Q * 4; }
+    if (L.has_hint) std::memcpy(c, q.seg_hint, L.Q * 4);
+}
+
+bool rl::rll_wants_poses(const rl_rll* o) {
+    return o->seg || o->u || o->e || o->dist2 || o->s || o->margin || o->vref;
+}
+
+void rl::rll_unpack(const char* block, const RllLayout& L, const rl_rll* o, bool poses) {
+    const RllOut b = rll_out(L, const_cast<char*>(block));
+    auto take = [](void* dst, const char* src, size_t bytes) {
+        if (dst && bytes) std::memcpy(dst, src, bytes);
+    };
+    double* const head[RLL_HEAD_F64] = {o->progress, o->e_max, o->margin_min, o->cost};
+    int32_t* const ihead[RLL_HEAD_I32] = {o->count, o->valid, o->first_out};
+    for (int c = 0; c < RLL_HEAD_F64; ++c) take(head[c], b.head[c], L.Q * 8);
+    for (int c = 0; c < RLL_HEAD_I32; ++c) take(ihead[c], b.ihead[c], L.Q * 4);
+    take(o->order, b.order, L.R * 4);
+    if (!poses) return;
+    double* const pose[RLL_POSE_F64] = {o->u, o->e, o->dist2, o->s, o->margin, o->vref};
+    for (int c = 0; c < RLL_POSE_F64; ++c) take(pose[c], b.pose[c], L.Q * L.T * 8);
+    take(o->seg, b.seg, L.Q * L.T * 4);
+}
+
+hipError_t rl::rll_launch(const RllLayout& L, const rl_rll_query& q, int gs, const TrajParams& src, const double* lo,
+                          const double* hi, char* in, char* out, hipStream_t st) {
+    const size_t QT = L.Q * L.T;
+    const RllOut b = rll_out(L, out);
+    RllParams p{};
+    p.src = src;
+    p.lo = lo; p.hi = hi;
+    char* c = in;
+    p.xy = (const double*)c; c += QT * 16;
+    if (L.has_v) { p.v = (const double*)c; c += QT * 8; }
+    if (L.has_row) { p.row = (const int32_t*)c; c += L.Q * 4; }
+    if (L.has_hint) p.hint = (const int32_t*)c;
+    p.seg = (int32_t*)b.seg;
+    for (int a = 0; a < RLL_POSE_F64; ++a) p.pose[a] = (double*)b.pose[a];
+    for (int a = 0; a < RLL_HEAD_F64; ++a) p.head[a] = (double*)b.head[a];
+    for (int a = 0; a < RLL_HEAD_I32; ++a) p.ihead[a] = (int32_t*)b.ihead[a];
+    p.w_e = q.w_e; p.w_out = q.w_out; p.w_v = q.w_v; p.w_prog = q.w_prog;
+    p.Q = q.Q; p.T = q.T; p.window0 = q.window0; p.window = q.window; p.hard_bounds = q.hard_bounds ? 1 : 0;
+    const hipError_t e = rl::launch_rollouts(p, st);
+    if (e != hipSuccess) return e;
+    return rl::launch_rank(p.head[3], q.Q, gs, q.k, (int32_t*)b.order, nullptr, st);   // cost, rl_rank_scores' order
 }
 
 namespace {
@@ -642,6 +747,7 @@ int rl_plan_bounds(rl_plan* p, const rl_bnd_query* query, void* hip_stream) {
     HIPCHK(hipStreamWaitEvent(st, p->ev_traj[1], 0));
     for (int k = 0; k < QUERY_KINDS; ++k)              // (a recover or fan stage may still read the rows, on another stream)
         if (kKinds[k].reads_bounds && p->qs[k].ev[1]) HIPCHK(hipStreamWaitEvent(st, p->qs[k].ev[1], 0));
+    if (p->rll.ev[1]) HIPCHK(hipStreamWaitEvent(st, p->rll.ev[1], 0));   // (and so may a rollout stage)
     p->last_stream = st;
     HIPCHK(hipEventRecord(p->ev_bnd[0], st));
     const TrajParams& t = p->traj_q;
@@ -722,6 +828,63 @@ int rl_plan_fetch_horizon_bounds(rl_plan* p, rl_hzn_bnd* out) {
     for (int c = 0; c < 4; ++c) add_job(jobs, dst[c], p->hb[c], (c < 2 ? Q * M : Q) * 8);
     if (int rc = queue_downloads(jobs, st)) return rc;
     HIPCHK(hipStreamSynchronize(st));
+    return RL_OK;
+}
+
+// One launch of rl_rollout_kernel on the last trajectory stage's rows and the bounds stage's rows
+// of the same, then rl_rank_kernel on the costs.  The rollouts go up in one block, through the
+// stage's pinned block, ahead of the kernels on the same stream (query_enqueue's order).
+int rl_plan_rollouts(rl_plan* p, const rl_rll_query* query, void* hip_stream) {
+    if (!p) return fail(RL_EINVAL, "plan is NULL");
+    if (!query) return fail(RL_EINVAL, "rollouts: the query or its xy is NULL");
+    if (!p->traj_R) return fail(RL_EINVAL, "rl_plan_rollouts: no trajectory stage since the plan's last run");
+    int gs = 0;
+    if (int rc = check_rollouts(*query, p->traj_R, &gs)) return rc;
+    if (!p->bnd_R) return fail(RL_EINVAL, "rl_plan_rollouts: no bounds stage since the plan's last trajectory stage");
+    if (p->traj_q.index && p->traj_sel_epoch != p->sel_epoch)
+        return fail(RL_EINVAL, "rl_plan_rollouts: a selection has replaced the winners the trajectory stage read");
+    if (p->traj_mode == RL_MODE_MINCURV && p->traj_lap_epoch != p->lap_epoch)
+        return fail(RL_EINVAL, "rl_plan_rollouts: a lap stage has rewritten the rows the trajectory stage read");
+    HIPCHK(hipSetDevice(p->device));
+    hipStream_t run_st = p->run_stream();
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : run_st;
+    QueryStage& s = p->rll;
+    if (s.ev[0]) HIPCHK(hipEventSynchronize(s.ev[0]));   // an earlier upload may still read the pinned block
+    s.Q = 0;
+    const RllLayout L = rll_layout((size_t)query->Q, (size_t)query->T, (size_t)(query->Q / gs) * (size_t)query->k,
+                                   query->v != nullptr, query->row != nullptr, query->seg_hint != nullptr);
+    if (int rc = s.reserve(p->last_stream, L.in_bytes, L.out_bytes, "rollouts")) return rc;
+    for (auto& e : s.ev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    if (st != run_st) HIPCHK(hipStreamWaitEvent(st, p->ev_traj[1], 0));
+    HIPCHK(hipStreamWaitEvent(st, p->ev_bnd[1], 0));    // (the bounds stage may be on another stream)
+    p->last_stream = st;
+    rll_pack(*query, L, s.pin);
+    HIPCHK(hipMemcpyAsync(s.in, s.pin, L.in_bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(hipEventRecord(s.ev[0], st));
+    const hipError_t e = rll_launch(L, *query, gs, p->traj_q, p->bnd[0], p->bnd[1], s.in, s.out, st);
+    if (e != hipSuccess) return fail(RL_EHIP, std::string("rollouts launch: ") + hipGetErrorString(e));
+    HIPCHK(hipEventRecord(s.ev[1], st));
+    s.Q = query->Q;
+    s.M = query->T;
+    p->rll_R = (int)L.R;
+    return RL_OK;
+}
+
+int rl_plan_fetch_rollouts(rl_plan* p, rl_rll* out) {
+    if (!p) return fail(RL_EINVAL, "plan is NULL");
+    if (!out) return fail(RL_EINVAL, "rl_plan_fetch_rollouts: results is NULL");
+    if (!p->rll.Q || !p->traj_R || !p->bnd_R)
+        return fail(RL_EINVAL, "rl_plan_fetch_rollouts: no rollouts stage since the plan's last run, trajectory or bounds stage");
+    HIPCHK(hipSetDevice(p->device));
+    QueryStage& s = p->rll;
+    hipStream_t st = p->run_stream();
+    HIPCHK(hipStreamWaitEvent(st, s.ev[1], 0));         // (a later stage may have moved to another stream)
+    const RllLayout L = rll_layout((size_t)s.Q, (size_t)s.M, (size_t)p->rll_R, false, false, false);
+    const bool poses = rll_wants_poses(out);
+    HIPCHK(hipMemcpyAsync(s.pin, s.out, poses ? L.out_bytes : L.head_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    rll_unpack(s.pin, L, out, poses);
     return RL_OK;
 }
 

@@ -568,7 +568,8 @@ def _one_shot(symbol: str, rows, hs, N: int, B: int, closed: bool, qc, out, devi
 
 def _hzn_locate(X, Y, t, hb, px, py, g: int, W: int, closed: bool):
     """The horizon stage's candidates, distance, winner and location of one pose on one row:
-    (seg, u, dist2, e, t0, s0), or None for a NaN winner."""
+    (seg, u, dist2, e, t0, s0), or None for a NaN winner or no candidate at all (a hint past an
+    open row, which only the rollout stage's query admits)."""
     N = X.shape[0]
     S = N if closed else N - 1
     if g < 0 or (closed and 2 * W + 1 >= S):
@@ -577,6 +578,8 @@ def _hzn_locate(X, Y, t, hb, px, py, g: int, W: int, closed: bool):
         cand = (g + np.arange(-W, W + 1)) % S
     else:
         cand = np.arange(max(0, g - W), min(S - 1, g + W) + 1)
+    if cand.shape[0] == 0:
+        return None
     with np.errstate(all="ignore"):
         i = cand
         j = (i + 1) % N
@@ -1730,6 +1733,233 @@ def recover_fan(x, y, heading, kappa, v, ax, h, closed: bool, lo, hi, poses, v0,
     return out
 
 
+# ------------------------------------------------- rollouts: sampled trajectories scored against the plan
+@dataclass
+class Rollouts:
+    """The scores of Q rollouts of T poses (rl_rll).  Per pose [Q, T]: seg (-1 from the end of the
+    chain on), u, e, dist2 as the horizon stage's location, s (arc length, counted on across the
+    start line), margin (the room left to the nearer bound, negative outside) and vref (the row's
+    speed there); they are None when the fetch left them on the device.  Per rollout [Q]: count
+    (poses located before the chain ended), valid (count == T), first_out (the first pose with
+    margin < 0, T: none), progress, e_max, margin_min and cost.  order [G, k]: the k best rollouts
+    of each group, ascending in (isnan(cost), cost, index)."""
+
+    seg: Optional[np.ndarray]
+    u: Optional[np.ndarray]
+    e: Optional[np.ndarray]
+    dist2: Optional[np.ndarray]
+    s: Optional[np.ndarray]
+    margin: Optional[np.ndarray]
+    vref: Optional[np.ndarray]
+    count: np.ndarray
+    valid: np.ndarray
+    first_out: np.ndarray
+    progress: np.ndarray
+    e_max: np.ndarray
+    margin_min: np.ndarray
+    cost: np.ndarray
+    order: np.ndarray
+
+    @classmethod
+    def alloc(cls, Q: int, T: int, G: int, k: int, poses: bool = True) -> "Rollouts":
+        per = {n: np.zeros((Q, T)) if poses else None for n in abi.RLL_POSE}
+        return cls(seg=np.zeros((Q, T), dtype=np.int32) if poses else None, **per,
+                   **{n: np.zeros(Q, dtype=np.int32) for n in abi.RLL_INTS}, **{n: np.zeros(Q) for n in abi.RLL_SCAL},
+                   order=np.zeros((G, k), dtype=np.int32))
+
+    def as_c(self) -> abi.RlRll:
+        t = abi.RlRll()
+        for n in ("seg",) + abi.RLL_INTS + ("order",):
+            if getattr(self, n) is not None:
+                setattr(t, n, _ptr(getattr(self, n), np.int32, n))
+        for n in abi.RLL_POSE + abi.RLL_SCAL:
+            if getattr(self, n) is not None:
+                setattr(t, n, _ptr(getattr(self, n), np.float64, n))
+        return t
+
+
+ROLLOUT_WEIGHTS = (1.0, 1.0, 1.0, 1.0)      # w_e, w_out, w_v, w_prog
+
+
+def _rll_query(xy, v, row, seg_hint, window0, window, weights, hard_bounds, group_size, k) -> tuple:
+    """The query as arrays and numbers: xy [Q, T, 2] float64, v [Q, T] float64 or None, row and
+    seg_hint [Q] int32 or None, the windows, the four weights, hard_bounds, the group size and k."""
+    P = np.ascontiguousarray(xy, dtype=np.float64)
+    if P.ndim == 2 and P.shape[1] == 2:
+        P = P[None]
+    if P.ndim != 3 or P.shape[2] != 2 or not 1 <= P.shape[0] <= abi.RL_RLL_MAX_ROLLOUTS or \
+            not 1 <= P.shape[1] <= abi.RL_RLL_MAX_STEPS or P.shape[0] * P.shape[1] > abi.RL_RLL_MAX_POSES:
+        raise ValueError(f"rollouts: xy must be [Q, T, 2] with 1 <= Q <= {abi.RL_RLL_MAX_ROLLOUTS}, 1 <= T <= "
+                         f"{abi.RL_RLL_MAX_STEPS} and Q*T <= {abi.RL_RLL_MAX_POSES}, got shape {P.shape}")
+    Q, T = P.shape[:2]
+    V = None
+    if v is not None:
+        V = np.ascontiguousarray(v, dtype=np.float64)
+        if V.shape == (T,) and Q == 1:
+            V = V[None]
+        if V.shape != (Q, T):
+            raise ValueError(f"rollouts: v must be [Q={Q}, T={T}], got shape {V.shape}")
+
+    def ints(a, name):
+        if a is None:
+            return None
+        a = np.asarray(a)
+        if a.ndim == 0:
+            a = np.broadcast_to(a, (Q,))
+        if a.shape != (Q,) or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError(f"rollouts: {name} must be an integer or [Q={Q}] integers, got {a.dtype} {a.shape}")
+        return np.ascontiguousarray(a, dtype=np.int32)
+
+    for name, w in (("window0", window0), ("window", window)):
+        if int(w) != w or w < 0 or w >= 2 ** 31:
+            raise ValueError(f"rollouts: {name} must be an integer >= 0, got {w}")
+    wts = tuple(float(w) for w in weights)
+    if len(wts) != 4 or not all(np.isfinite(w) and w >= 0.0 for w in wts):
+        raise ValueError(f"rollouts: weights must be four finite numbers >= 0 (w_e, w_out, w_v, w_prog), got {weights}")
+    gs = Q if group_size in (None, 0) else int(group_size)
+    if gs < 1 or Q % gs != 0:
+        raise ValueError(f"rollouts: Q={Q} is not a multiple of group_size={group_size}")
+    if not 1 <= int(k) <= min(gs, abi.RL_SELECT_MAX_K):
+        raise ValueError(f"rollouts: need 1 <= k <= min(group_size={gs}, {abi.RL_SELECT_MAX_K}), got {k}")
+    hint = ints(seg_hint, "seg_hint")
+    if hint is not None and np.any(hint < -1):
+        raise ValueError("rollouts: seg_hint < -1")
+    return P, V, ints(row, "row"), hint, int(window0), int(window), wts, bool(hard_bounds), gs, int(k)
+
+
+def _rll_c(qy) -> abi.RlRllQuery:
+    P, V, rw, hint, W0, W, wts, hard, gs, k = qy
+    return abi.RlRllQuery(_ptr(P, np.float64, "xy"), None if V is None else _ptr(V, np.float64, "v"),
+                          None if rw is None else _ptr(rw, np.int32, "row"),
+                          None if hint is None else _ptr(hint, np.int32, "seg_hint"), P.shape[0], P.shape[1], W0, W,
+                          *wts, 1 if hard else 0, gs, k, 0)
+
+
+def _rll_bounds(rows, lo, hi) -> tuple:
+    lo = np.ascontiguousarray(lo, dtype=np.float64)
+    hi = np.ascontiguousarray(hi, dtype=np.float64)
+    if lo.ndim == 1:
+        lo, hi = lo[None], hi[None]
+    if lo.shape != rows[0].shape or hi.shape != rows[0].shape:
+        raise ValueError(f"rollouts: lo and hi must have the rows' shape {rows[0].shape}, got {lo.shape} and {hi.shape}")
+    return lo, hi
+
+
+def rank_order(cost, k: int, group_size: int) -> np.ndarray:
+    """index [G, k]: rank_scores' order in NumPy: the global indices of the k least of each group of
+    group_size, ascending in (isnan(cost), cost, index); -0.0 and 0.0 tie."""
+    cost = np.asarray(cost, dtype=np.float64).ravel()
+    G = cost.shape[0] // group_size
+    out = np.zeros((G, k), dtype=np.int32)
+    for g in range(G):
+        c = cost[g * group_size:(g + 1) * group_size]
+        nan = np.isnan(c)
+        out[g] = g * group_size + np.lexsort((np.arange(group_size), np.where(nan, 0.0, c), nan))[:k]
+    return out
+
+
+def rollouts_host(x, y, heading, kappa, v, ax, h, closed: bool, lo, hi, xy, speeds=None, row=None, seg_hint=None,
+                  window0: int = 0, window: int = 8, weights=ROLLOUT_WEIGHTS, hard_bounds: bool = False,
+                  group_size: Optional[int] = None, k: int = 1) -> Rollouts:
+    """The specification of the rollout stage (include/rl_abi.h) in NumPy; the kernel
+    equals it bit for bit.  Rows [B, N] (or one row [N]) with steps h as for trajectory_host, and
+    their bounds rows lo, hi [B, N] (the bounds stage's).  Rollout q, poses xy[q] [T, 2] with
+    optional speeds speeds[q] [T], lies on row[q] (None: row 0).  Pose 0 is located as the horizon
+    stage locates a pose with hint seg_hint[q] (None or -1: every segment; a hint past an open row
+    has no candidate) and window0; pose t >= 1 with the segment found for pose t - 1 as its hint and
+    `window`.  The first pose without a winner ends the chain: count = t, NaN and seg = -1 from
+    there on, valid = 0, progress and cost NaN.  c counts the crossings of the start line on a
+    closed row (a jump of more than half the row backward is a crossing forward, and the other way
+    round), s = ((c*S + seg) + u)*h, margin = smin(hi_t - e, e - lo_t) with horizon_bounds_host's
+    pair of the segment, vref the row's speed at the foot.  The sums E, O, V are added serially in
+    ascending t from 0.0; cost = ((w_e*E + w_out*O) + w_v*V) - w_prog*progress, +inf with
+    hard_bounds when a pose lies outside.  order is rank_order's."""
+    closed = bool(closed)
+    rows, hs, qy, B, N = _open_query("rollouts", (x, y, heading, kappa, v, ax, h),
+                                     lambda: _rll_query(xy, speeds, row, seg_hint, window0, window, weights, hard_bounds,
+                                                        group_size, k))
+    lo, hi = _rll_bounds(rows, lo, hi)
+    P, VQ, rw, hint, W0, W, (w_e, w_out, w_v, w_prog), hard, gs, k = qy
+    Q, T = P.shape[:2]
+    S = N if closed else N - 1
+    rw = np.zeros(Q, dtype=np.int32) if rw is None else rw
+    hint = np.full(Q, -1, dtype=np.int32) if hint is None else hint
+    if np.any(rw < 0) or np.any(rw >= B):
+        raise ValueError(f"rollouts: row outside [0, {B})")
+    out = Rollouts.alloc(Q, T, Q // gs, k)
+    out.seg[:] = -1
+    for n in abi.RLL_POSE:
+        getattr(out, n)[:] = np.nan
+    nostamps = np.zeros(N + 1)                                  # (the chain needs no time on the row)
+    f64 = np.float64
+    with np.errstate(all="ignore"):
+        for q in range(Q):
+            r = int(rw[q])
+            X, Y, Vr, hb = rows[0][r], rows[1][r], rows[4][r], hs[r]
+            g, c, cnt = int(hint[q]), 0, T
+            E = O = V = e_max = f64(0.0)
+            m_min, first_out = f64(np.inf), T
+            for t in range(T):
+                loc = _hzn_locate(X, Y, nostamps, hb, P[q, t, 0], P[q, t, 1], g, W0 if t == 0 else W, closed) if S >= 1 else None
+                if loc is None:
+                    cnt = t
+                    break
+                i, u, D, e = loc[:4]
+                if closed and t > 0:
+                    d = i - g
+                    c += 1 if 2 * d < -S else (-1 if 2 * d > S else 0)
+                g = i
+                j = (i + 1) % N
+                a, b, lo2, hi2 = lo[r, i], lo[r, j], hi[r, i], hi[r, j]
+                lo_t, hi_t = (b if a < b else a), (hi2 if hi2 < lo2 else lo2)       # smax(lo_i, lo_j), smin(hi_i, hi_j)
+                m1, m2 = hi_t - e, e - lo_t
+                m = m2 if m2 < m1 else m1                                             # smin(hi_t - e, e - lo_t)
+                vref = Vr[i] + u * (Vr[j] - Vr[i])
+                out.seg[q, t], out.u[q, t], out.e[q, t], out.dist2[q, t] = i, u, e, D
+                out.s[q, t] = ((f64(c) * f64(S) + f64(i)) + u) * hb
+                out.margin[q, t], out.vref[q, t] = m, vref
+                E = E + e * e
+                O = O + (m * m if m < 0.0 else f64(0.0))
+                if VQ is not None:
+                    dv = VQ[q, t] - vref
+                    V = V + dv * dv
+                ae = np.abs(e)
+                e_max = ae if e_max < ae else e_max
+                m_min = m if m < m_min else m_min
+                if m < 0.0 and first_out == T:
+                    first_out = t
+            out.count[q], out.valid[q], out.first_out[q] = cnt, 1 if cnt == T else 0, first_out
+            out.e_max[q], out.margin_min[q] = e_max, m_min
+            out.progress[q] = out.cost[q] = np.nan
+            if cnt == T:
+                prog = out.s[q, T - 1] - out.s[q, 0]
+                out.progress[q] = prog
+                out.cost[q] = ((w_e * E + w_out * O) + w_v * V) - w_prog * prog
+                if hard and first_out < T:
+                    out.cost[q] = np.inf
+    out.order[:] = rank_order(out.cost, k, gs)
+    return out
+
+
+def rollouts(x, y, heading, kappa, v, ax, h, closed: bool, lo, hi, xy, speeds=None, row=None, seg_hint=None,
+             window0: int = 0, window: int = 8, weights=ROLLOUT_WEIGHTS, hard_bounds: bool = False,
+             group_size: Optional[int] = None, k: int = 1, poses: bool = True, device: int = 0) -> Rollouts:
+    """rollouts_host on the GPU (rl_rollouts): the rollout kernel on the B given rows and their bounds
+    rows, then the rank kernel on the costs; row[q] counts the given rows.  poses=False leaves the
+    per-pose arrays on the device."""
+    rows, hs, qy, B, N = _open_query("rollouts", (x, y, heading, kappa, v, ax, h),
+                                     lambda: _rll_query(xy, speeds, row, seg_hint, window0, window, weights, hard_bounds,
+                                                        group_size, k))
+    lo, hi = _rll_bounds(rows, lo, hi)
+    Q, T = qy[0].shape[:2]
+    out = Rollouts.alloc(Q, T, Q // qy[8], qy[9], poses)
+    qc, oc = _rll_c(qy), out.as_c()
+    _check(_lib().rl_rollouts(*[_ptr(a, np.float64, "row") for a in rows], _ptr(hs, np.float64, "h"),
+                              _ptr(lo, np.float64, "lo"), _ptr(hi, np.float64, "hi"), N, B, 1 if closed else 0,
+                              C.byref(qc), int(device), C.byref(oc)))
+    return out
+
+
 def path_lengths(x, y, closed: bool, device: int = 0) -> np.ndarray:
     """L [B]: the debug dump's path_length (ref:1443-1448) of B paths given as rows x [B, N],
     y [B, N], summed on the GPU in the reference's order (rl_path_lengths): L[b] equals
@@ -2056,6 +2286,33 @@ class Plan:
         out = HorizonBounds.alloc(self._hbnd[0], self._hbnd[1])
         t = out.as_c()
         _check(_lib().rl_plan_fetch_horizon_bounds(self._h, C.byref(t)))
+        return out
+
+    def rollouts(self, xy, v=None, row=None, seg_hint=None, window0: int = 0, window: int = 8, weights=ROLLOUT_WEIGHTS,
+                 hard_bounds: bool = False, group_size: Optional[int] = None, k: int = 1, stream_ptr: int = 0) -> None:
+        """Enqueue the rollout stage after the last trajectory() and bounds() (rl_plan_rollouts): the
+        rollouts xy [Q, T, 2] (speeds v [Q, T], optional) are located pose by pose on rows of the
+        trajectory stage (row[q], None: row 0), pose 0 within window0 of seg_hint[q] (None or -1:
+        anywhere), every later pose within `window` of the segment found for the pose before it;
+        each rollout is scored with weights = (w_e, w_out, w_v, w_prog) and the k best of every
+        group of group_size (None: all Q) are ranked on the device.  As often as the caller likes
+        without another run(); every other stage stays as it is; a later bounds() invalidates it."""
+        qy = _rll_query(xy, v, row, seg_hint, window0, window, weights, hard_bounds, group_size, k)
+        self._rll = None
+        qc = _rll_c(qy)
+        _check(_lib().rl_plan_rollouts(self._h, C.byref(qc), C.c_void_p(stream_ptr) if stream_ptr else None))
+        self._rll = qy[0].shape[:2] + (qy[0].shape[0] // qy[8], qy[9])
+
+    def fetch_rollouts(self, poses: bool = False) -> Rollouts:
+        """Download the last rollouts() (rl_plan_fetch_rollouts): the per-rollout values and order;
+        poses=True brings the per-pose arrays down as well."""
+        if getattr(self, "_rll", None) is None:
+            t = abi.RlRll()                 # (the library's own answer: no stage on this plan)
+            _check(_lib().rl_plan_fetch_rollouts(self._h, C.byref(t)))
+            raise ValueError("fetch_rollouts: no rollouts() on this plan")
+        out = Rollouts.alloc(*self._rll, poses)
+        t = out.as_c()
+        _check(_lib().rl_plan_fetch_rollouts(self._h, C.byref(t)))
         return out
 
     def device_outputs(self, which: int) -> abi.RlOut:
