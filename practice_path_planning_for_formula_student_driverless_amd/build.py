@@ -19,7 +19,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
 KERNEL_SRCS = ["csrc/rl_kernels.hip", "csrc/rl_kernels_group.hip", "csrc/rl_kernels_lat.hip", "csrc/rl_kernels_mid.hip", "csrc/rl_stream.hip", "csrc/rl_geom.hip", "csrc/rl_format.hip", "csrc/rl_select.hip", "csrc/rl_lap_stage.hip", "csrc/rl_trajectory.hip", "csrc/rl_horizon.hip", "csrc/rl_rejoin.hip", "csrc/rl_stop.hip", "csrc/rl_retime.hip", "csrc/rl_recover.hip", "csrc/rl_recover_fan.hip", "csrc/rl_bounds.hip", "csrc/rl_rollout.hip", "csrc/rl_abi.cpp", "csrc/rl_plan.cpp", "csrc/rl_stages.cpp", "csrc/rl_cache.cpp"]
-KERNEL_DEPS = KERNEL_SRCS + ["csrc/rl_host.h", "csrc/rl_optimize_body.h", "csrc/rl_optimize_body.inc", "csrc/rl_kernels.h", "csrc/rl_device.h", "csrc/rl_math.h", "csrc/rl_corridor.h", "csrc/rl_select.h", "csrc/rl_lap_stage.h", "csrc/rl_trajectory.h", "csrc/rl_horizon.h", "csrc/rl_rejoin.h", "csrc/rl_stop.h", "csrc/rl_retime.h", "csrc/rl_recover.h", "csrc/rl_recover_fan.h", "csrc/rl_bounds.h", "csrc/rl_rollout.h", "csrc/rl_query.h"]
+KERNEL_DEPS = KERNEL_SRCS + ["csrc/rl_host.h", "csrc/rl_optimize_body.h", "csrc/rl_optimize_body.inc", "csrc/rl_kernels.h", "csrc/rl_device.h", "csrc/rl_math.h", "csrc/rl_corridor.h", "csrc/rl_select.h", "csrc/rl_lap_stage.h", "csrc/rl_trajectory.h", "csrc/rl_horizon.h", "csrc/rl_rejoin.h", "csrc/rl_stop.h", "csrc/rl_retime.h", "csrc/rl_recover.h", "csrc/rl_recover_fan.h", "csrc/rl_bounds.h", "csrc/rl_rollout.h", "csrc/rl_query.h", "csrc/rl_stage_graph.h"]
 # -ffp-contract=off: HIP defaults to fusing a*b+c into FMA, which would change
 # the reference's roundings.
 HIP_FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",

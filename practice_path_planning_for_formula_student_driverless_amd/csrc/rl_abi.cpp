@@ -39,7 +39,7 @@ int rows_on_device(DevArena& mem, const std::string& fn, const double* const (&i
 // downloaded), then the kind's kernel on them; `row` counts the B given rows
 int query_rows(const std::string& fn, const double* const (&in)[6], const double* h, int32_t N, int32_t B, int32_t closed,
                QueryKind kind, const QueryView& q, const void* out, const double* const (&bnd)[4]) {
-    const bool bounds = kind_info(kind).reads_bounds;
+    const bool bounds = reads_bounds(kind);
     DevArena mem;
     rl::TrajParams t;
     if (int rc = rows_on_device(mem, fn, in, h, N, B, closed, q.rj.dt, 1, &t)) return rc;
@@ -75,9 +75,9 @@ int one_shot(const double* const (&rows)[11], int32_t N, int32_t B, int32_t clos
     const KindInfo& k = kind_info(kind);
     const std::string fn = std::string("rl_") + k.name;
     bool null = !query || !out;
-    for (int c = 0; c < (k.reads_bounds ? 11 : 7); ++c) null = null || !rows[c];
+    for (int c = 0; c < (reads_bounds(kind) ? 11 : 7); ++c) null = null || !rows[c];
     if (null)
-        return fail(RL_EINVAL, fn + (k.reads_bounds ? ": an input row, h, a bounds row, the query or out is NULL"
+        return fail(RL_EINVAL, fn + (reads_bounds(kind) ? ": an input row, h, a bounds row, the query or out is NULL"
                                                     : ": an input row, h, the query or out is NULL"));
     if (B < 1 || N < 0) return fail(RL_EINVAL, fn + ": B < 1 or N < 0");
     if (N > rl::RL_STREAM_MAX_N) return fail(RL_ETOOBIG, fn + ": N exceeds 1048576");

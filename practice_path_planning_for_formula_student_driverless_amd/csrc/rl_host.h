@@ -381,11 +381,10 @@ inline int queue_downloads(const std::vector<CopyJob>& jobs, hipStream_t st) {
 // The plan's side of one pose-query stage; a plan has one per QueryKind (rl_query.h).  The queries
 // go up and the results come down as one packed block each (in, out; rl_query.h has their layout),
 // through one pinned host block (pin) of the larger capacity; all three grow with Q, M_cap and
-// K_cap.  ev[0] is recorded after the upload, which reads pin, ev[1] after the kernel.  Q = 0: no
-// stage since the last run or trajectory stage; M, K (0 for the horizon) and C (the candidates per
-// query of a fan stage, 0 for every other) are that stage's M_cap, K_cap and n_cand: with the
-// stage's kind they give its layout again.  The fan stage has a scratch block on the device as
-// well, which never comes down.
+// K_cap.  Q, M, K (0 for the horizon) and C (the candidates per query of a fan stage, 0 for every
+// other) are the last stage's Q, M_cap, K_cap and n_cand: with the stage's kind they give its
+// layout again.  The fan stage has a scratch block on the device as well, which never comes down.
+// Whether the stage holds results, and its events, are the plan's (rl_plan::valid, rl_plan::rec).
 struct QueryStage {
     char *in = nullptr, *out = nullptr, *pin = nullptr, *scratch = nullptr;
     size_t in_cap = 0, out_cap = 0, scratch_cap = 0;
@@ -393,7 +392,6 @@ struct QueryStage {
     DevArena scratch_mem;             // scratch: it counts as well
     int Q = 0, M = 0, K = 0, C = 0;
     double dt = 0;                    // that stage's tick step (the bounds stage's tick kernel reads it)
-    hipEvent_t ev[2] = {nullptr, nullptr};
 
     void release_blocks() {
         mem.release();
@@ -406,10 +404,6 @@ struct QueryStage {
         scratch_mem.release();
         scratch = nullptr;
         scratch_cap = 0;
-        for (auto& e : ev) {
-            if (e) hipEventDestroy(e);
-            e = nullptr;
-        }
     }
     // blocks of at least in_bytes and out_bytes; they only grow.  last_stream: the plan's, which
     // may still use the old ones.  `what` names the stage in the message.
@@ -453,6 +447,14 @@ struct QueryStage {
 }  // namespace rl
 
 // ------------------------------------------------------------------ the plan
+// What the plan keeps per rl::Stage (rl_stage_graph.h): the events around its last enqueue and the
+// stream it went to; created at the stage's first enqueue (stage_begin).  The run's events are
+// rl_plan::ev, so its record holds a stream only.
+struct StageRec {
+    hipEvent_t ev[2] = {nullptr, nullptr};   // start (of an uploading stage: after the upload, which reads pin), end
+    hipStream_t stream = nullptr;
+};
+
 struct rl_plan {
     int device = 0;
     int N = 0, B = 0, modes = 0, ncfg = 0, max_outer = 0, closed = 1, Ei = 0, Eo = 0;
@@ -469,7 +471,12 @@ struct rl_plan {
     hipStream_t aux_stream = nullptr;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // run start, mode starts, run end
     hipEvent_t ev_end[2] = {nullptr, nullptr};                 // mode ends
-    bool ran = false;
+    // The run and the twelve stages after it, by rl::Stage: which hold results (a stage's counts
+    // below, traj_R, bnd_R, hb_Q, qs[k].Q and the like, are sizes and say nothing about that), and
+    // each one's events and stream.  run_done, stage_begin and stage_end below keep them.
+    rl::StageSet valid;
+    StageRec rec[rl::N_STAGES];
+    hipEvent_t ev_lap_mid = nullptr;                           // between the lap stage's two kernels (kernel_ms 5, 6)
     double* d_center = nullptr;
     double* d_Ls = nullptr;           // per-instance L (lap evaluation) or nullptr
     int64_t center_stride = 0;        // doubles between instances' centres (0: shared)
@@ -491,7 +498,7 @@ struct rl_plan {
     rl::DevArena mem;                 // everything above
     // selection stage (rl_plan_select): the scores of the last select, its winners and their
     // rows in compact buffers sized for sel_cap rows; allocated at the first select and again
-    // when G*k outgrows sel_cap.  sel_mode = 0: nothing selected since the last run.
+    // when G*k outgrows sel_cap.
     double* d_score = nullptr;        // [B] min-curvature scores (min-time ranks mb[1].lap)
     int32_t* d_index = nullptr;       // [sel_cap]
     double* d_score_sel = nullptr;    // [sel_cap]
@@ -499,74 +506,53 @@ struct rl_plan {
     rl::DevArena sel_mem;
     int sel_cap = 0, sel_mode = 0, sel_G = 0, sel_k = 0;
     const double* sel_scores = nullptr;   // the [B] scores the last select ranked
-    hipEvent_t ev_sel[2] = {nullptr, nullptr};
     bool sel_lap = false;             // the last select ranked the lap stage's lap (RL_SCORE_LAP)
     // lap stage (rl_plan_lap): the min-curvature rows packed as per-instance centres, their
     // own lengths, the plan's cfgs with max_outer_iters = 0, and the result and scratch arrays
     // of the min-time kernel that evaluates them; allocated at the first rl_plan_lap.
-    // lap_valid: a stage has been queued since the last run.
     double* d_lap_center = nullptr;   // [B][N][2]
     double* d_Lmc = nullptr;          // [B]
     rl_cfg* d_cfg_lap = nullptr;      // [ncfg]
     rl::ModeBufs lapb;                // sweeps [B][1]; evals / accepts unused
     rl::DevArena lap_mem;
-    bool lap_valid = false;
-    hipStream_t lap_stream = nullptr;
-    hipEvent_t ev_lap[3] = {nullptr, nullptr, nullptr};   // start, after the preparation, end
     // trajectory stage (rl_plan_trajectory): the columns [traj_R][traj_M], the stamps
     // [traj_R][N + 1], T and count [traj_R] of the last stage, in buffers sized for traj_cap_R
     // rows of traj_cap_M ticks; allocated at the first stage and again when either grows.
-    // traj_R = 0: no stage since the last run.
     double* traj_col[rl::TRAJ_COLS] = {};
     double* traj_stamps = nullptr;
     double* traj_T = nullptr;
     int32_t* traj_count = nullptr;
     rl::DevArena traj_mem;
     int traj_cap_R = 0, traj_cap_M = 0, traj_R = 0, traj_M = 0;
-    hipEvent_t ev_traj[2] = {nullptr, nullptr};
     // pose-query stages (rl::QueryStage, one per rl::QueryKind): they read the last
     // trajectory stage through traj_q, that stage's launch parameters, which stay valid while
-    // traj_R != 0 and the rows they point at are those the stamps were made from:
+    // the stage is and the rows they point at are those the stamps were made from:
     // traj_sel_epoch / traj_lap_epoch are sel_epoch / lap_epoch (counted up by every selection /
     // lap stage) at that launch.  Each stage has blocks of its own, so the last horizon stage
     // stays fetchable after a rejoin, stop or retime stage and the other way round.
     rl::TrajParams traj_q{};
     int traj_mode = 0;
     uint32_t sel_epoch = 0, lap_epoch = 0, traj_sel_epoch = 0, traj_lap_epoch = 0;
-    rl::QueryStage qs[rl::QUERY_KINDS];            // by kind (some read the bounds stage as well: drop_bounds_readers)
+    rl::QueryStage qs[rl::QUERY_KINDS];            // by kind
     rl::QueryStage& stage(rl::QueryKind k) { return qs[(int)k]; }
     // bounds stage (rl_plan_bounds, rl::BndParams): lo, hi, nx, ny [bnd_R][N] of the last
-    // trajectory stage's rows, row for row, in buffers sized for bnd_cap_R rows; bnd_R = 0: no
-    // stage since the last run or trajectory stage.  Its tick kernel (rl_plan_horizon_bounds)
-    // reads them and the last horizon stage's results: lo, hi [hb_Q][hb_M] and lo0, hi0 [hb_Q] in
-    // buffers of hb_cap_QM and hb_cap_Q doubles; hb_Q = 0: none since the last horizon or bounds
-    // stage.
+    // trajectory stage's rows, row for row, in buffers sized for bnd_cap_R rows.  Its tick kernel
+    // (rl_plan_horizon_bounds) reads them and the last horizon stage's results: lo, hi
+    // [hb_Q][hb_M] and lo0, hi0 [hb_Q] in buffers of hb_cap_QM and hb_cap_Q doubles.
     double* bnd[4] = {};              // lo, hi, nx, ny (rl_bnd's order)
     rl::DevArena bnd_mem;
     int bnd_cap_R = 0, bnd_R = 0;
-    hipEvent_t ev_bnd[2] = {nullptr, nullptr};
     double* hb[4] = {};               // lo, hi, lo0, hi0 (rl_hzn_bnd's order)
     rl::DevArena hb_mem;
     size_t hb_cap_QM = 0, hb_cap_Q = 0;
     int hb_Q = 0, hb_M = 0;
-    hipEvent_t ev_hb[2] = {nullptr, nullptr};
     // rollout stage (rl_plan_rollouts, rl::RllParams): blocks and pinned staging of its own on the
-    // pose-query stages' pattern (rl::RllLayout has their layout); rll.Q = 0: no stage since the
-    // last run, trajectory or bounds stage.  rll.M is that stage's T, rll_R its G*k.
+    // pose-query stages' pattern (rl::RllLayout has their layout).  rll.M is the last stage's T,
+    // rll_R its G*k.
     rl::QueryStage rll;
     int rll_R = 0;
-    // a run or a trajectory stage invalidates the pose-query stages that read the one before,
-    // and the bounds of its rows
-    void drop_queries() {
-        for (auto& s : qs) s.Q = 0;
-        bnd_R = hb_Q = rll.Q = 0;
-    }
-    // a bounds stage invalidates what read the one before: the tick bounds and the stages whose kind reads_bounds
-    void drop_bounds_readers() {
-        for (int k = 0; k < rl::QUERY_KINDS; ++k)
-            if (rl::kKinds[k].reads_bounds) qs[k].Q = 0;
-        bnd_R = hb_Q = rll.Q = 0;
-    }
+    // the event that ends a stage's last enqueue (nullptr: never enqueued)
+    hipEvent_t end_event(rl::Stage s) const { return s == rl::Stage::Run ? ev[3] : rec[(int)s].ev[1]; }
 
     template <class T>
     int alloc(T** p, size_t n) {
@@ -587,6 +573,44 @@ struct rl_plan {
 };
 
 namespace rl {
+
+// ------------------------------------------------------------------ the plan's stages
+// Make `st` wait for the last enqueue of stage `of`, unless that went to st itself, where stream
+// order does the same; a stage never enqueued has nothing to wait for.
+inline int stage_wait(rl_plan* p, Stage of, hipStream_t st) {
+    const hipEvent_t e = p->end_event(of);
+    if (e && p->rec[(int)of].stream != st) HIPCHK(hipStreamWaitEvent(st, e, 0));
+    return RL_OK;
+}
+// Every stage's enqueue begins here, after its invalidate() and its allocations: the stage's events,
+// st behind every stage it reads (kStages) and every stage of the mask `also`, the plan's last
+// stream, and with `mark` the start event.  An uploading stage passes mark = false and records
+// rec.ev[0] itself, behind its upload.
+inline int stage_begin(rl_plan* p, Stage s, hipStream_t st, unsigned also = 0, bool mark = true) {
+    StageRec& r = p->rec[(int)s];
+    for (auto& e : r.ev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    const unsigned from = stage_info(s).reads | also;
+    for (int o = 0; o < N_STAGES; ++o)
+        if (from >> o & 1u)
+            if (int rc = stage_wait(p, (Stage)o, st)) return rc;
+    p->last_stream = st;
+    if (mark) HIPCHK(hipEventRecord(r.ev[0], st));
+    return RL_OK;
+}
+// and ends here, behind its last launch
+inline int stage_end(rl_plan* p, Stage s, hipStream_t st) {
+    HIPCHK(hipEventRecord(p->rec[(int)s].ev[1], st));
+    p->rec[(int)s].stream = st;
+    p->valid.set(s);
+    return RL_OK;
+}
+// the closing bookkeeping of a run on st, behind its end event: every stage is of an earlier run
+inline void run_done(rl_plan* p, hipStream_t st) {
+    p->valid.invalidate(Stage::Run);
+    p->valid.set(Stage::Run);
+    p->rec[(int)Stage::Run].stream = st;
+}
 
 // rl_plan.cpp
 // argument checks shared by every entry point that builds or reuses a plan (no device call)

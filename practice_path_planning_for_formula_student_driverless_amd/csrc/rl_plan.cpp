@@ -185,22 +185,16 @@ int rl_plan_destroy(rl_plan* plan) {
     if (plan->own_stream) hipStreamSynchronize(plan->own_stream);
     plan->mem.release();
     plan->sel_mem.release();
-    for (auto& e : plan->ev_sel)
-        if (e) hipEventDestroy(e);
     plan->lap_mem.release();
-    for (auto& e : plan->ev_lap)
-        if (e) hipEventDestroy(e);
     plan->traj_mem.release();
-    for (auto& e : plan->ev_traj)
-        if (e) hipEventDestroy(e);
     for (auto& s : plan->qs) s.release();
     plan->rll.release();
     plan->bnd_mem.release();
     plan->hb_mem.release();
-    for (auto& e : plan->ev_bnd)
-        if (e) hipEventDestroy(e);
-    for (auto& e : plan->ev_hb)
-        if (e) hipEventDestroy(e);
+    for (auto& r : plan->rec)
+        for (auto& e : r.ev)
+            if (e) hipEventDestroy(e);
+    if (plan->ev_lap_mid) hipEventDestroy(plan->ev_lap_mid);
     for (auto& e : plan->ev)
         if (e) hipEventDestroy(e);
     for (auto& e : plan->ev_end)
@@ -295,11 +289,7 @@ int rl_plan_run(rl_plan* p, void* hip_stream) {
     }
     if (both) HIPCHK(hipStreamWaitEvent(st, p->ev_end[1], 0));
     HIPCHK(hipEventRecord(p->ev[3], st));
-    p->ran = true;
-    p->sel_mode = 0;                                   // an earlier selection is of an earlier run
-    p->lap_valid = false;                              // and so is an earlier lap stage
-    p->traj_R = 0;                                     // and an earlier trajectory stage
-    p->drop_queries();                                 // and the pose-query stages that read it
+    run_done(p, st);
     return RL_OK;
 }
 
@@ -419,65 +409,29 @@ int rl_plan_run_group(rl_plan* const* plans, int32_t n, void* hip_stream) {
     for (hipEvent_t e : ends) HIPCHK(hipStreamWaitEvent(st, e, 0));
     for (int i = 0; i < n; ++i) {
         HIPCHK(hipEventRecord(plans[i]->ev[3], st));
-        plans[i]->ran = true;
-        plans[i]->sel_mode = 0;
-        plans[i]->lap_valid = false;
-        plans[i]->traj_R = 0;
-        plans[i]->drop_queries();
+        run_done(plans[i], st);
     }
     return RL_OK;
 }
 
+// idx 0: the whole run; 1, 2: its kernels; from 3 on: the stage kStages gives the index to
+// (include/rl_abi.h has the list), the lap stage with three of them
 int rl_plan_kernel_ms(rl_plan* p, int32_t idx, float* ms) {
-    if (!p || !ms || !p->ran) return fail(RL_EINVAL, "plan not run");
+    if (!p || !ms || !p->valid.has(Stage::Run)) return fail(RL_EINVAL, "plan not run");
     HIPCHK(hipSetDevice(p->device));
     HIPCHK(hipEventSynchronize(p->ev[3]));
-    // idx 0: whole run; 1: min-curv kernel; 2: min-time kernel; 3: the selection stage
     hipEvent_t a, b;
-    const bool mc = p->modes & RL_MODE_MINCURV, mt = p->modes & RL_MODE_MINTIME;
-    // 8..10, 13..15: the pose-query stages, by kKinds' ms_index (a bounds stage invalidates those that read it as well)
-    const rl::QueryStage* stage = nullptr;
-    for (int k = 0; k < rl::QUERY_KINDS; ++k)
-        if (rl::kKinds[k].ms_index == idx && (!rl::kKinds[k].reads_bounds || p->bnd_R)) stage = &p->qs[k];
+    const int s = stage_of_ms(idx);
     if (idx == 0) { a = p->ev[0]; b = p->ev[3]; }
-    else if (idx == 3 && p->sel_mode) {
-        a = p->ev_sel[0];
-        b = p->ev_sel[1];
-        HIPCHK(hipEventSynchronize(b));
+    else if (idx == 1 && (p->modes & RL_MODE_MINCURV)) { a = p->ev[1]; b = p->ev_end[0]; }
+    else if (idx == 2 && (p->modes & RL_MODE_MINTIME)) { a = p->ev[2]; b = p->ev_end[1]; }
+    else if (s > (int)Stage::Run && p->valid.has((Stage)s)) {
+        const StageRec& r = p->rec[s];
+        const int part = idx - kStages[s].ms_first;     // of the lap stage: 1 its preparation kernel, 2 its evaluation kernel
+        a = part == 2 ? p->ev_lap_mid : r.ev[0];
+        b = part == 1 ? p->ev_lap_mid : r.ev[1];
+        HIPCHK(hipEventSynchronize(r.ev[1]));
     }
-    else if (idx >= 4 && idx <= 6 && p->lap_valid) {
-        // 4: the lap stage; 5: its preparation kernel; 6: its evaluation kernel
-        a = p->ev_lap[idx == 6 ? 1 : 0];
-        b = p->ev_lap[idx == 5 ? 1 : 2];
-        HIPCHK(hipEventSynchronize(p->ev_lap[2]));
-    }
-    else if (idx == 7 && p->traj_R) {
-        a = p->ev_traj[0];
-        b = p->ev_traj[1];
-        HIPCHK(hipEventSynchronize(b));
-    }
-    else if (stage && stage->Q && p->traj_R) {
-        a = stage->ev[0];
-        b = stage->ev[1];
-        HIPCHK(hipEventSynchronize(b));
-    }
-    else if (idx == 11 && p->bnd_R && p->traj_R) {      // 11: the bounds stage
-        a = p->ev_bnd[0];
-        b = p->ev_bnd[1];
-        HIPCHK(hipEventSynchronize(b));
-    }
-    else if (idx == 12 && p->hb_Q && p->traj_R) {       // 12: the bounds at the horizon stage's ticks
-        a = p->ev_hb[0];
-        b = p->ev_hb[1];
-        HIPCHK(hipEventSynchronize(b));
-    }
-    else if (idx == 16 && p->rll.Q && p->bnd_R && p->traj_R) {   // 16: the rollout stage (locate and rank)
-        a = p->rll.ev[0];
-        b = p->rll.ev[1];
-        HIPCHK(hipEventSynchronize(b));
-    }
-    else if (idx == 1 && mc) { a = p->ev[1]; b = p->ev_end[0]; }
-    else if (idx == 2 && mt) { a = p->ev[2]; b = p->ev_end[1]; }
     else return fail(RL_EINVAL, "kernel index not in this plan");
     HIPCHK(hipEventElapsedTime(ms, a, b));
     return RL_OK;

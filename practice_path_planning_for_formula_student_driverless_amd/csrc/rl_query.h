@@ -3,16 +3,17 @@
 // kSlots names every array of the two packed blocks, in block order, with its element size, its
 // extent and the kinds that have it; query_layout_of walks it with one cursor, so a slot a kind has
 // not takes no room and moves nothing.  kKinds has, per kind, its name, the fields of its public
-// results struct as (slot, offsetof), its rl_plan_kernel_ms index, whether it reads the bounds
-// stage, and the messages that fit no pattern.  On these: one query form (QueryView), one
-// query_pack, the *_pointers that fill the kernels' parameter structs, one query_unpack and one
-// query_wants_nodes.  No HIP call: a host compiler builds it without a device
-// (tests/query_layout_check.cpp).  Not part of the public ABI.
+// results struct as (slot, offsetof) and the messages that fit no pattern; QueryKind itself, a
+// kind's rl_plan_kernel_ms index and whether it reads the bounds stage are rl_stage_graph.h's, under
+// stage_of(kind).  On these: one query form (QueryView), one query_pack, the *_pointers that fill
+// the kernels' parameter structs, one query_unpack and one query_wants_nodes.  No HIP call: a host
+// compiler builds it without a device (tests/query_layout_check.cpp).  Not part of the public ABI.
 #pragma once
 #include <cstddef>
 #include <cstring>
 
 #include "rl_abi.h"
+#include "rl_stage_graph.h"
 #include "rl_rejoin.h"
 #include "rl_stop.h"
 #include "rl_retime.h"
@@ -21,8 +22,6 @@
 
 namespace rl {
 
-enum class QueryKind { Horizon, Rejoin, Stop, Retime, Recover, Fan };
-constexpr int QUERY_KINDS = 6;
 constexpr unsigned kbit(QueryKind k) { return 1u << (int)k; }
 constexpr unsigned K_ALL = (1u << QUERY_KINDS) - 1;
 constexpr unsigned K_FAN = kbit(QueryKind::Fan);
@@ -159,35 +158,33 @@ static_assert(fields_cover(kHznFields, sizeof(rl_hzn), QueryKind::Horizon) && fi
                   fields_cover(kRcvFields, sizeof(rl_rcv), QueryKind::Recover) && fields_cover(kFanFields, sizeof(rl_fan), QueryKind::Fan),
               "each kind's table covers sizeof(struct) / sizeof(void*) fields");
 
-// A kind: its name in the entry points' names and messages, its results struct's fields, its
-// rl_plan_kernel_ms index, whether it reads the bounds stage (which then invalidates it), and the
+// A kind: its name in the entry points' names and messages, its results struct's fields, and the
 // messages for a NULL query and for a fetch without a stage.
 struct KindInfo {
     const char* name;
     const FieldAt* fields;
     int n_fields;
-    int ms_index;
-    bool reads_bounds;
     const char* null_query;
     const char* fetch_none;
 };
 #define RL_FIELDS(t) t, (int)(sizeof(t) / sizeof(t[0]))
 constexpr KindInfo kKinds[QUERY_KINDS] = {
-    {"horizon", RL_FIELDS(kHznFields), 8, false, "horizon: the query or its pose_xy is NULL",
+    {"horizon", RL_FIELDS(kHznFields), "horizon: the query or its pose_xy is NULL",
      "rl_plan_fetch_horizon: no horizon stage since the plan's last run or trajectory stage"},
-    {"rejoin", RL_FIELDS(kRjnFields), 9, false, "rejoin: the query is NULL",
+    {"rejoin", RL_FIELDS(kRjnFields), "rejoin: the query is NULL",
      "rl_plan_fetch_rejoin: no rejoin stage since the plan's last run or trajectory stage"},
-    {"stop", RL_FIELDS(kStpFields), 10, false, "stop: the query is NULL",
+    {"stop", RL_FIELDS(kStpFields), "stop: the query is NULL",
      "rl_plan_fetch_stop: no stop stage since the plan's last run or trajectory stage"},
-    {"retime", RL_FIELDS(kRtmFields), 13, false, "retime: the query is NULL",
+    {"retime", RL_FIELDS(kRtmFields), "retime: the query is NULL",
      "rl_plan_fetch_retime: no retime stage since the plan's last run or trajectory stage"},
-    {"recover", RL_FIELDS(kRcvFields), 14, true, "recover: the query is NULL",
+    {"recover", RL_FIELDS(kRcvFields), "recover: the query is NULL",
      "rl_plan_fetch_recover: no recover stage since the plan's last run, trajectory or bounds stage"},
-    {"recover_fan", RL_FIELDS(kFanFields), 15, true, "recover fan: the query is NULL",
+    {"recover_fan", RL_FIELDS(kFanFields), "recover fan: the query is NULL",
      "rl_plan_fetch_recover_fan: no fan stage since the plan's last run, trajectory or bounds stage"},
 };
 #undef RL_FIELDS
 inline const KindInfo& kind_info(QueryKind k) { return kKinds[(int)k]; }
+constexpr bool reads_bounds(QueryKind k) { return stage_reads(stage_of(k), Stage::Bounds); }
 
 // ---------------------------------------------------------------- the layout
 // Where every slot lies for a stage of Q queries, M ticks, K nodes (0 for the horizon) and C

@@ -16,6 +16,12 @@
 // rows, and at the horizon stage's ticks.  Rollout stage (rl_rollout.hip): sampled
 // trajectories located pose by pose on those rows, scored and ranked; a stage of its own beside the
 // table, as the bounds stage is, because its arrays are [Q][T].
+// Every stage is a rl::Stage of rl_stage_graph.h.  An enqueue is: the checks,
+// plan->valid.invalidate(stage), which also clears every stage that reads this one, the allocation,
+// stage_begin (events, the waits for the stages the table says it reads unless they ran on the same
+// stream, the start event), the launches, stage_end (end event, stream, valid).  The uploading stages
+// (the six kinds, the rollouts) share that as upload_launch; the fetches outside the query table
+// share stage_fetch; traj_current refuses new readers of rows a later selection or lap stage replaced.
 #include "rl_host.h"
 
 using namespace rl;
@@ -357,17 +363,11 @@ int select_impl(rl_plan* p, const rl_select* sel, int gs, bool by_lap, void* hip
     HIPCHK(hipSetDevice(p->device));
     const int m = sel->mode == RL_MODE_MINTIME ? 1 : 0;
     const int k = sel->k, G = p->B / gs, rows = G * k;
-    hipStream_t run_st = p->run_stream();
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : run_st;
-    p->sel_mode = 0;
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : p->run_stream();
+    p->valid.invalidate(Stage::Select);
     ++p->sel_epoch;                                    // d_index and the compact rows change
     if (int rc = select_alloc(p, rows)) return rc;
-    for (auto& e : p->ev_sel)
-        if (!e) HIPCHK(hipEventCreate(&e));
-    if (st != run_st) HIPCHK(hipStreamWaitEvent(st, p->ev[3], 0));
-    if (by_lap && st != p->lap_stream) HIPCHK(hipStreamWaitEvent(st, p->ev_lap[2], 0));
-    p->last_stream = st;
-    HIPCHK(hipEventRecord(p->ev_sel[0], st));
+    if (int rc = stage_begin(p, Stage::Select, st, by_lap ? sbit(Stage::Lap) : 0)) return rc;
     const ModeBufs& mb = p->mb[m];
     hipError_t e = hipSuccess;
     const double* scores = by_lap ? p->lapb.lap : mb.lap;   // min-time: the lap the optimiser wrote
@@ -407,50 +407,62 @@ int select_impl(rl_plan* p, const rl_select* sel, int gs, bool by_lap, void* hip
         e = rl::launch_gather(h, st);
         if (e != hipSuccess) return fail(RL_EHIP, std::string("gather launch: ") + hipGetErrorString(e));
     }
-    HIPCHK(hipEventRecord(p->ev_sel[1], st));
     p->sel_mode = sel->mode;
     p->sel_lap = by_lap;
     p->sel_G = G;
     p->sel_k = k;
     p->sel_scores = scores;
-    return RL_OK;
+    return stage_end(p, Stage::Select, st);
 }
 
-// every pose-query stage's rl_plan_<name> (arguments checked; a kind that reads the bounds stage
-// after a valid one): one launch of the kind's kernel on the last trajectory stage.  The queries go
-// up in one block, through the stage's pinned block, ahead of the kernel on the same stream.
-int query_enqueue(rl_plan* p, QueryKind kind, const QueryView& q, void* hip_stream) {
-    const KindInfo& k = kind_info(kind);
-    QueryStage& s = p->stage(kind);
-    const std::string fn = std::string("rl_plan_") + k.name;
+// Whether the rows the last trajectory stage read are still the ones its stamps were made from; a
+// later selection or lap stage leaves that stage and what was enqueued on it fetchable, and refuses
+// new readers of the rows, here.  fn: the entry point that asks.
+int traj_current(const rl_plan* p, const std::string& fn) {
     if (p->traj_q.index && p->traj_sel_epoch != p->sel_epoch)
         return fail(RL_EINVAL, fn + ": a selection has replaced the winners the trajectory stage read");
     if (p->traj_mode == RL_MODE_MINCURV && p->traj_lap_epoch != p->lap_epoch)
         return fail(RL_EINVAL, fn + ": a lap stage has rewritten the rows the trajectory stage read");
-    HIPCHK(hipSetDevice(p->device));
-    hipStream_t run_st = p->run_stream();
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : run_st;
+    return RL_OK;
+}
+
+// The enqueue of a stage whose queries go up in one block (the pose-query kinds, the rollouts): the
+// blocks of s for a layout L, pack(pin), the upload, then launch(), on st; s's sizes are the
+// caller's to set.  The start event is recorded behind the upload, which reads the pinned block.
+template <class Layout, class Pack, class Launch>
+int upload_launch(rl_plan* p, Stage stage, QueryStage& s, const Layout& L, size_t scratch_bytes, hipStream_t st, Pack pack,
+                  Launch launch) {
+    const char* name = stage_info(stage).name;
+    StageRec& r = p->rec[(int)stage];
     // An earlier upload may still read the pinned block, also one whose stage a run, a
     // trajectory stage or a failed launch has invalidated since (an event that was never
     // recorded is complete).
-    if (s.ev[0]) HIPCHK(hipEventSynchronize(s.ev[0]));
-    s.Q = 0;
-    if (kind == QueryKind::Horizon) p->hb_Q = 0;       // the tick bounds of the horizon stage before
-    const QueryLayout L = query_layout_of(kind, q);
-    if (int rc = s.reserve(p->last_stream, L.in_bytes, L.out_bytes, k.name)) return rc;
-    if (L.scratch_bytes)
-        if (int rc = s.reserve_scratch(p->last_stream, L.scratch_bytes, k.name)) return rc;
-    for (auto& e : s.ev)
-        if (!e) HIPCHK(hipEventCreate(&e));
-    if (st != run_st) HIPCHK(hipStreamWaitEvent(st, p->ev_traj[1], 0));
-    if (k.reads_bounds) HIPCHK(hipStreamWaitEvent(st, p->ev_bnd[1], 0));   // (the bounds stage may be on another stream)
-    p->last_stream = st;
-    query_pack(q, L, s.pin);
+    if (r.ev[0]) HIPCHK(hipEventSynchronize(r.ev[0]));
+    p->valid.invalidate(stage);
+    if (int rc = s.reserve(p->last_stream, L.in_bytes, L.out_bytes, name)) return rc;
+    if (scratch_bytes)
+        if (int rc = s.reserve_scratch(p->last_stream, scratch_bytes, name)) return rc;
+    if (int rc = stage_begin(p, stage, st, 0, false)) return rc;
+    pack(s.pin);
     HIPCHK(hipMemcpyAsync(s.in, s.pin, L.in_bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(hipEventRecord(s.ev[0], st));
-    const hipError_t e = query_launch(L, q, p->traj_q, s.in, s.out, {p->bnd[0], p->bnd[1], p->bnd[2], p->bnd[3]}, s.scratch, st);
-    if (e != hipSuccess) return fail(RL_EHIP, std::string(k.name) + " launch: " + hipGetErrorString(e));
-    HIPCHK(hipEventRecord(s.ev[1], st));
+    HIPCHK(hipEventRecord(r.ev[0], st));
+    const hipError_t e = launch();
+    if (e != hipSuccess) return fail(RL_EHIP, std::string(name) + " launch: " + hipGetErrorString(e));
+    return stage_end(p, stage, st);
+}
+
+// every pose-query stage's rl_plan_<name> (arguments checked; a kind that reads the bounds stage
+// after a valid one): one launch of the kind's kernel on the last trajectory stage
+int query_enqueue(rl_plan* p, QueryKind kind, const QueryView& q, void* hip_stream) {
+    QueryStage& s = p->stage(kind);
+    if (int rc = traj_current(p, std::string("rl_plan_") + kind_info(kind).name)) return rc;
+    HIPCHK(hipSetDevice(p->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : p->run_stream();
+    const QueryLayout L = query_layout_of(kind, q);
+    const int rc = upload_launch(
+        p, stage_of(kind), s, L, L.scratch_bytes, st, [&](char* pin) { query_pack(q, L, pin); },
+        [&] { return query_launch(L, q, p->traj_q, s.in, s.out, {p->bnd[0], p->bnd[1], p->bnd[2], p->bnd[3]}, s.scratch, st); });
+    if (rc) return rc;
     s.Q = q.rj.Q;
     s.M = q.rj.M_cap;
     s.K = q.rj.K_cap;
@@ -502,11 +514,22 @@ int query_fetch(rl_plan* p, QueryKind kind, const void* o) {
     QueryStage& s = p->stage(kind);
     HIPCHK(hipSetDevice(p->device));
     hipStream_t st = p->run_stream();
-    HIPCHK(hipStreamWaitEvent(st, s.ev[1], 0));         // (a later stage may have moved to another stream)
+    if (int rc = stage_wait(p, stage_of(kind), st)) return rc;   // (a later stage may have moved to another stream)
     const QueryLayout L = query_layout_of(kind, (size_t)s.Q, (size_t)s.M, (size_t)s.K, (size_t)s.C);
     HIPCHK(hipMemcpyAsync(s.pin, s.out, query_wants_nodes(kind, o) ? L.out_bytes : L.head_bytes, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     query_unpack(s.pin, L, o);
+    return RL_OK;
+}
+
+// the fetch of a stage outside the query table (a valid one): the jobs on the plan's stream, behind
+// the stage's end, and the wait for them
+int stage_fetch(rl_plan* p, Stage stage, const std::vector<CopyJob>& jobs) {
+    HIPCHK(hipSetDevice(p->device));
+    hipStream_t st = p->run_stream();
+    if (int rc = stage_wait(p, stage, st)) return rc;   // (a later stage may have moved to another stream)
+    if (int rc = queue_downloads(jobs, st)) return rc;
+    HIPCHK(hipStreamSynchronize(st));
     return RL_OK;
 }
 
@@ -518,10 +541,10 @@ int plan_stage(rl_plan* p, const Query* query, void* hip_stream) {
     if (!p) return fail(RL_EINVAL, "plan is NULL");
     if (!query) return fail(RL_EINVAL, k.null_query);
     const std::string fn = std::string("rl_plan_") + k.name;
-    if (!p->traj_R) return fail(RL_EINVAL, fn + ": no trajectory stage since the plan's last run");
+    if (!p->valid.has(Stage::Trajectory)) return fail(RL_EINVAL, fn + ": no trajectory stage since the plan's last run");
     const QueryView q = query_view(*query);
     if (int rc = check_query(kind, q, p->traj_R, p->N, p->closed)) return rc;
-    if (k.reads_bounds && !p->bnd_R) return fail(RL_EINVAL, fn + ": no bounds stage since the plan's last trajectory stage");
+    if (reads_bounds(kind) && !p->valid.has(Stage::Bounds)) return fail(RL_EINVAL, fn + ": no bounds stage since the plan's last trajectory stage");
     return query_enqueue(p, kind, q, hip_stream);
 }
 
@@ -532,7 +555,7 @@ int plan_fetch(rl_plan* p, const Out* out) {
     const KindInfo& k = kind_info(kind);
     if (!p) return fail(RL_EINVAL, "plan is NULL");
     if (!out) return fail(RL_EINVAL, std::string("rl_plan_fetch_") + k.name + ": out is NULL");
-    if (!p->stage(kind).Q || !p->traj_R || (k.reads_bounds && !p->bnd_R)) return fail(RL_EINVAL, k.fetch_none);
+    if (!p->valid.has(stage_of(kind))) return fail(RL_EINVAL, k.fetch_none);
     return query_fetch(p, kind, out);
 }
 
@@ -546,18 +569,14 @@ int rl_plan_lap(rl_plan* p, void* hip_stream) {
     if (!p) return fail(RL_EINVAL, "plan is NULL");
     if (!(p->modes & RL_MODE_MINCURV)) return fail(RL_EINVAL, "rl_plan_lap: the plan has no RL_MODE_MINCURV");
     if (p->N == 0) return fail(RL_EINVAL, "rl_plan_lap: N == 0 (no path)");
-    if (!p->ran) return fail(RL_EINVAL, "rl_plan_lap: the plan has not run");
+    if (!p->valid.has(Stage::Run)) return fail(RL_EINVAL, "rl_plan_lap: the plan has not run");
     HIPCHK(hipSetDevice(p->device));
-    hipStream_t run_st = p->run_stream();
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : run_st;
-    p->lap_valid = false;
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : p->run_stream();
+    p->valid.invalidate(Stage::Lap);
     ++p->lap_epoch;                                    // the stage's rows are written again
     if (int rc = lap_alloc(p)) return rc;
-    for (auto& e : p->ev_lap)
-        if (!e) HIPCHK(hipEventCreate(&e));
-    if (st != run_st) HIPCHK(hipStreamWaitEvent(st, p->ev[3], 0));
-    p->last_stream = st;
-    HIPCHK(hipEventRecord(p->ev_lap[0], st));
+    if (!p->ev_lap_mid) HIPCHK(hipEventCreate(&p->ev_lap_mid));
+    if (int rc = stage_begin(p, Stage::Lap, st)) return rc;
     rl::PrepParams q{};
     q.x = p->mb[0].x;
     q.y = p->mb[0].y;
@@ -568,7 +587,7 @@ int rl_plan_lap(rl_plan* p, void* hip_stream) {
     q.N = p->N; q.B = p->B; q.closed = p->closed; q.ncfg = p->ncfg;
     hipError_t e = rl::launch_path_prep(q, st);
     if (e != hipSuccess) return fail(RL_EHIP, std::string("path prep launch: ") + hipGetErrorString(e));
-    HIPCHK(hipEventRecord(p->ev_lap[1], st));
+    HIPCHK(hipEventRecord(p->ev_lap_mid, st));
     // rl_lap_eval's launch: per-instance centres and lengths, empty rings, no seeds, no
     // completion flags, no precomputed corridor
     const ModeBufs& lb = p->lapb;
@@ -586,31 +605,23 @@ int rl_plan_lap(rl_plan* p, void* hip_stream) {
     kp.L = p->L;
     e = p->stream ? rl::launch_stream(kp, lb.sb, true, st) : rl::launch_optimize(kp, true, st);
     if (e != hipSuccess) return fail(RL_EHIP, std::string("lap evaluation launch: ") + hipGetErrorString(e));
-    HIPCHK(hipEventRecord(p->ev_lap[2], st));
-    p->lap_valid = true;
-    p->lap_stream = st;
-    return RL_OK;
+    return stage_end(p, Stage::Lap, st);
 }
 
 int rl_plan_fetch_lap(rl_plan* p, rl_out* out, double* path_len) {
     if (!p) return fail(RL_EINVAL, "plan is NULL");
-    if (!p->lap_valid) return fail(RL_EINVAL, "rl_plan_fetch_lap: no lap stage since the plan's last run");
-    HIPCHK(hipSetDevice(p->device));
-    hipStream_t st = p->run_stream();
-    if (st != p->lap_stream) HIPCHK(hipStreamWaitEvent(st, p->ev_lap[2], 0));
+    if (!p->valid.has(Stage::Lap)) return fail(RL_EINVAL, "rl_plan_fetch_lap: no lap stage since the plan's last run");
     std::vector<CopyJob> jobs;
     field_jobs(out, p->lapb, {(size_t)p->B, (size_t)p->N, 0, 1}, true, true, jobs);
     add_job(jobs, path_len, p->d_Lmc, (size_t)p->B * 8);
-    if (int rc = queue_downloads(jobs, st)) return rc;
-    HIPCHK(hipStreamSynchronize(st));
-    return RL_OK;
+    return stage_fetch(p, Stage::Lap, jobs);
 }
 
 int rl_plan_select(rl_plan* p, const rl_select* sel, void* hip_stream) {
     if (!p) return fail(RL_EINVAL, "plan is NULL");
     int gs = 0;
     if (int rc = check_select(sel, p->B, p->N, p->modes, &gs)) return rc;
-    if (!p->ran) return fail(RL_EINVAL, "rl_plan_select: the plan has not run");
+    if (!p->valid.has(Stage::Run)) return fail(RL_EINVAL, "rl_plan_select: the plan has not run");
     return select_impl(p, sel, gs, false, hip_stream);
 }
 
@@ -619,9 +630,9 @@ int rl_plan_select_scored(rl_plan* p, const rl_select* sel, int32_t score, void*
     if (score != RL_SCORE_DEFAULT && score != RL_SCORE_LAP) return fail(RL_EINVAL, "select: unknown score");
     int gs = 0;
     if (int rc = check_select(sel, p->B, p->N, p->modes, &gs)) return rc;
-    if (!p->ran) return fail(RL_EINVAL, "rl_plan_select: the plan has not run");
+    if (!p->valid.has(Stage::Run)) return fail(RL_EINVAL, "rl_plan_select: the plan has not run");
     const bool by_lap = score == RL_SCORE_LAP && sel->mode == RL_MODE_MINCURV;
-    if (by_lap && !p->lap_valid)
+    if (by_lap && !p->valid.has(Stage::Lap))
         if (int rc = rl_plan_lap(p, hip_stream)) return rc;
     return select_impl(p, sel, gs, by_lap, hip_stream);
 }
@@ -629,14 +640,10 @@ int rl_plan_select_scored(rl_plan* p, const rl_select* sel, int32_t score, void*
 int rl_plan_fetch_selected(rl_plan* p, int32_t* index, double* score, double* all_scores, rl_out* out) {
     if (!p) return fail(RL_EINVAL, "plan is NULL");
     if (!index || !score) return fail(RL_EINVAL, "rl_plan_fetch_selected: index / score is NULL");
-    if (!p->sel_mode) return fail(RL_EINVAL, "rl_plan_fetch_selected: no selection since the plan's last run");
-    HIPCHK(hipSetDevice(p->device));
-    hipStream_t st = p->run_stream();
+    if (!p->valid.has(Stage::Select)) return fail(RL_EINVAL, "rl_plan_fetch_selected: no selection since the plan's last run");
     std::vector<CopyJob> jobs;
     sel_jobs(p, index, score, all_scores, out, jobs);
-    if (int rc = queue_downloads(jobs, st)) return rc;
-    HIPCHK(hipStreamSynchronize(st));
-    return RL_OK;
+    return stage_fetch(p, Stage::Select, jobs);
 }
 
 // One launch of rl_trajectory_kernel over the rows in force: the min-time optimiser's, or the
@@ -649,29 +656,19 @@ int rl_plan_trajectory(rl_plan* p, int32_t mode, int32_t rows, double dt, int32_
     if (int rc = check_traj(dt, M_cap)) return rc;
     if (p->N == 0) return fail(RL_EINVAL, "trajectory: N == 0 (no row)");
     if (rows != RL_TRAJ_ALL && rows != RL_TRAJ_SELECTED) return fail(RL_EINVAL, "trajectory: unknown rows");
-    if (!p->ran) return fail(RL_EINVAL, "rl_plan_trajectory: the plan has not run");
+    if (!p->valid.has(Stage::Run)) return fail(RL_EINVAL, "rl_plan_trajectory: the plan has not run");
     const bool selected = rows == RL_TRAJ_SELECTED;
-    if (selected && p->sel_mode != mode)
+    if (selected && (!p->valid.has(Stage::Select) || p->sel_mode != mode))
         return fail(RL_EINVAL, "rl_plan_trajectory: no selection of this mode since the plan's last run");
     const bool mc = mode == RL_MODE_MINCURV;
-    p->traj_R = 0;
-    p->drop_queries();                                 // they read the stage before this one
-    if (mc && !p->lap_valid)
+    p->valid.invalidate(Stage::Trajectory);            // and every stage that reads the one before this one
+    if (mc && !p->valid.has(Stage::Lap))
         if (int rc = rl_plan_lap(p, hip_stream)) return rc;
     HIPCHK(hipSetDevice(p->device));
     const int R = selected ? p->sel_G * p->sel_k : p->B;
-    hipStream_t run_st = p->run_stream();
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : run_st;
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : p->run_stream();
     if (int rc = traj_alloc(p, R, M_cap)) return rc;
-    for (auto& e : p->ev_traj)
-        if (!e) HIPCHK(hipEventCreate(&e));
-    if (st != run_st) {
-        HIPCHK(hipStreamWaitEvent(st, p->ev[3], 0));
-        if (selected) HIPCHK(hipStreamWaitEvent(st, p->ev_sel[1], 0));
-    }
-    if (mc && st != p->lap_stream) HIPCHK(hipStreamWaitEvent(st, p->ev_lap[2], 0));
-    p->last_stream = st;
-    HIPCHK(hipEventRecord(p->ev_traj[0], st));
+    if (int rc = stage_begin(p, Stage::Trajectory, st, (mc ? sbit(Stage::Lap) : 0) | (selected ? sbit(Stage::Select) : 0))) return rc;
     const ModeBufs& mb = p->mb[mc ? 0 : 1];
     const ModeBufs& src = mc ? p->lapb : mb;
     rl::TrajParams q{};
@@ -688,28 +685,22 @@ int rl_plan_trajectory(rl_plan* p, int32_t mode, int32_t rows, double dt, int32_
     q.N = p->N; q.B = p->B; q.R = R; q.closed = p->closed; q.M_cap = M_cap;
     const hipError_t e = rl::launch_trajectory(q, st);
     if (e != hipSuccess) return fail(RL_EHIP, std::string("trajectory launch: ") + hipGetErrorString(e));
-    HIPCHK(hipEventRecord(p->ev_traj[1], st));
     p->traj_R = R;
     p->traj_M = M_cap;
     p->traj_q = q;                                     // what the horizon stage reads
     p->traj_mode = mode;
     p->traj_sel_epoch = p->sel_epoch;
     p->traj_lap_epoch = p->lap_epoch;
-    return RL_OK;
+    return stage_end(p, Stage::Trajectory, st);
 }
 
 int rl_plan_fetch_trajectory(rl_plan* p, rl_traj* out) {
     if (!p) return fail(RL_EINVAL, "plan is NULL");
     if (!out) return fail(RL_EINVAL, "rl_plan_fetch_trajectory: out is NULL");
-    if (!p->traj_R) return fail(RL_EINVAL, "rl_plan_fetch_trajectory: no trajectory stage since the plan's last run");
-    HIPCHK(hipSetDevice(p->device));
-    hipStream_t st = p->run_stream();
-    HIPCHK(hipStreamWaitEvent(st, p->ev_traj[1], 0));   // (a later stage may have moved to another stream)
+    if (!p->valid.has(Stage::Trajectory)) return fail(RL_EINVAL, "rl_plan_fetch_trajectory: no trajectory stage since the plan's last run");
     std::vector<CopyJob> jobs;
     traj_jobs(p, out, jobs);
-    if (int rc = queue_downloads(jobs, st)) return rc;
-    HIPCHK(hipStreamSynchronize(st));
-    return RL_OK;
+    return stage_fetch(p, Stage::Trajectory, jobs);
 }
 
 // the pose-query stages: plan_stage and plan_fetch with the kind
@@ -733,23 +724,16 @@ int rl_plan_bounds(rl_plan* p, const rl_bnd_query* query, void* hip_stream) {
     if (!query) return fail(RL_EINVAL, "bounds: the query is NULL");
     if (!std::isfinite(query->veh_width) || !std::isfinite(query->margin))
         return fail(RL_EINVAL, "bounds: veh_width or margin is not finite");
-    if (!p->traj_R) return fail(RL_EINVAL, "rl_plan_bounds: no trajectory stage since the plan's last run");
-    if (p->traj_q.index && p->traj_sel_epoch != p->sel_epoch)
-        return fail(RL_EINVAL, "rl_plan_bounds: a selection has replaced the winners the trajectory stage read");
-    if (p->traj_mode == RL_MODE_MINCURV && p->traj_lap_epoch != p->lap_epoch)
-        return fail(RL_EINVAL, "rl_plan_bounds: a lap stage has rewritten the rows the trajectory stage read");
+    if (!p->valid.has(Stage::Trajectory)) return fail(RL_EINVAL, "rl_plan_bounds: no trajectory stage since the plan's last run");
+    if (int rc = traj_current(p, "rl_plan_bounds")) return rc;
     HIPCHK(hipSetDevice(p->device));
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : p->run_stream();
-    p->drop_bounds_readers();                          // (the tick bounds and the recover stage read the stage before this one)
+    p->valid.invalidate(Stage::Bounds);                // (and what read the stage before this one)
     if (int rc = bounds_alloc(p, p->traj_R)) return rc;
-    for (auto& e : p->ev_bnd)
-        if (!e) HIPCHK(hipEventCreate(&e));
-    HIPCHK(hipStreamWaitEvent(st, p->ev_traj[1], 0));
-    for (int k = 0; k < QUERY_KINDS; ++k)              // (a recover or fan stage may still read the rows, on another stream)
-        if (kKinds[k].reads_bounds && p->qs[k].ev[1]) HIPCHK(hipStreamWaitEvent(st, p->qs[k].ev[1], 0));
-    if (p->rll.ev[1]) HIPCHK(hipStreamWaitEvent(st, p->rll.ev[1], 0));   // (and so may a rollout stage)
-    p->last_stream = st;
-    HIPCHK(hipEventRecord(p->ev_bnd[0], st));
+    unsigned readers = 0;                              // (valid or not, they may still read the rows, on another stream)
+    for (int s = 0; s < N_STAGES; ++s)
+        if (stage_reads((Stage)s, Stage::Bounds)) readers |= 1u << s;
+    if (int rc = stage_begin(p, Stage::Bounds, st, readers)) return rc;
     const TrajParams& t = p->traj_q;
     rl::BndParams b{};
     b.x = t.x; b.y = t.y;
@@ -760,44 +744,33 @@ int rl_plan_bounds(rl_plan* p, const rl_bnd_query* query, void* hip_stream) {
     b.N = t.N; b.B = t.B; b.R = t.R; b.closed = t.closed;
     const hipError_t e = rl::launch_bounds(b, st);
     if (e != hipSuccess) return fail(RL_EHIP, std::string("bounds launch: ") + hipGetErrorString(e));
-    HIPCHK(hipEventRecord(p->ev_bnd[1], st));
     p->bnd_R = t.R;
-    return RL_OK;
+    return stage_end(p, Stage::Bounds, st);
 }
 
 int rl_plan_fetch_bounds(rl_plan* p, rl_bnd* out) {
     if (!p) return fail(RL_EINVAL, "plan is NULL");
     if (!out) return fail(RL_EINVAL, "rl_plan_fetch_bounds: out is NULL");
-    if (!p->bnd_R || !p->traj_R)
+    if (!p->valid.has(Stage::Bounds))
         return fail(RL_EINVAL, "rl_plan_fetch_bounds: no bounds stage since the plan's last run or trajectory stage");
-    HIPCHK(hipSetDevice(p->device));
-    hipStream_t st = p->run_stream();
-    HIPCHK(hipStreamWaitEvent(st, p->ev_bnd[1], 0));    // (a later stage may have moved to another stream)
     double* const dst[4] = {out->lo, out->hi, out->nx, out->ny};
     std::vector<CopyJob> jobs;
     for (int c = 0; c < 4; ++c) add_job(jobs, dst[c], p->bnd[c], (size_t)p->bnd_R * (size_t)p->N * 8);
-    if (int rc = queue_downloads(jobs, st)) return rc;
-    HIPCHK(hipStreamSynchronize(st));
-    return RL_OK;
+    return stage_fetch(p, Stage::Bounds, jobs);
 }
 
 // One launch of rl_horizon_bounds_kernel on what the last horizon stage left in its results'
 // block and the bounds stage's rows: no upload.
 int rl_plan_horizon_bounds(rl_plan* p, void* hip_stream) {
     if (!p) return fail(RL_EINVAL, "plan is NULL");
-    if (!p->traj_R || !p->stage(QueryKind::Horizon).Q || !p->bnd_R)
+    if (!p->valid.has(Stage::Horizon) || !p->valid.has(Stage::Bounds))
         return fail(RL_EINVAL, "rl_plan_horizon_bounds: no horizon stage and bounds stage since the plan's last trajectory stage");
     HIPCHK(hipSetDevice(p->device));
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : p->run_stream();
     const QueryStage& s = p->stage(QueryKind::Horizon);
-    p->hb_Q = 0;
+    p->valid.invalidate(Stage::HorizonBounds);
     if (int rc = horizon_bounds_alloc(p, (size_t)s.Q, (size_t)s.M)) return rc;
-    for (auto& e : p->ev_hb)
-        if (!e) HIPCHK(hipEventCreate(&e));
-    HIPCHK(hipStreamWaitEvent(st, s.ev[1], 0));
-    HIPCHK(hipStreamWaitEvent(st, p->ev_bnd[1], 0));
-    p->last_stream = st;
-    HIPCHK(hipEventRecord(p->ev_hb[0], st));
+    if (int rc = stage_begin(p, Stage::HorizonBounds, st)) return rc;
     // the horizon stage's launch again, as query_enqueue made it
     rl_rjn_query q{};
     q.Q = s.Q; q.M_cap = s.M; q.dt = s.dt;
@@ -808,63 +781,42 @@ int rl_plan_horizon_bounds(rl_plan* p, void* hip_stream) {
     h.tlo = p->hb[0]; h.thi = p->hb[1]; h.lo0 = p->hb[2]; h.hi0 = p->hb[3];
     const hipError_t e = rl::launch_horizon_bounds(h, st);
     if (e != hipSuccess) return fail(RL_EHIP, std::string("horizon bounds launch: ") + hipGetErrorString(e));
-    HIPCHK(hipEventRecord(p->ev_hb[1], st));
     p->hb_Q = s.Q;
     p->hb_M = s.M;
-    return RL_OK;
+    return stage_end(p, Stage::HorizonBounds, st);
 }
 
 int rl_plan_fetch_horizon_bounds(rl_plan* p, rl_hzn_bnd* out) {
     if (!p) return fail(RL_EINVAL, "plan is NULL");
     if (!out) return fail(RL_EINVAL, "rl_plan_fetch_horizon_bounds: out is NULL");
-    if (!p->hb_Q || !p->traj_R)
+    if (!p->valid.has(Stage::HorizonBounds))
         return fail(RL_EINVAL, "rl_plan_fetch_horizon_bounds: no rl_plan_horizon_bounds since the plan's last run or stage it reads");
-    HIPCHK(hipSetDevice(p->device));
-    hipStream_t st = p->run_stream();
-    HIPCHK(hipStreamWaitEvent(st, p->ev_hb[1], 0));
     const size_t Q = (size_t)p->hb_Q, M = (size_t)p->hb_M;
     double* const dst[4] = {out->lo, out->hi, out->lo0, out->hi0};
     std::vector<CopyJob> jobs;
     for (int c = 0; c < 4; ++c) add_job(jobs, dst[c], p->hb[c], (c < 2 ? Q * M : Q) * 8);
-    if (int rc = queue_downloads(jobs, st)) return rc;
-    HIPCHK(hipStreamSynchronize(st));
-    return RL_OK;
+    return stage_fetch(p, Stage::HorizonBounds, jobs);
 }
 
 // One launch of rl_rollout_kernel on the last trajectory stage's rows and the bounds stage's rows
-// of the same, then rl_rank_kernel on the costs.  The rollouts go up in one block, through the
-// stage's pinned block, ahead of the kernels on the same stream (query_enqueue's order).
+// of the same, then rl_rank_kernel on the costs (upload_launch, as the pose-query kinds).
 int rl_plan_rollouts(rl_plan* p, const rl_rll_query* query, void* hip_stream) {
     if (!p) return fail(RL_EINVAL, "plan is NULL");
     if (!query) return fail(RL_EINVAL, "rollouts: the query or its xy is NULL");
-    if (!p->traj_R) return fail(RL_EINVAL, "rl_plan_rollouts: no trajectory stage since the plan's last run");
+    if (!p->valid.has(Stage::Trajectory)) return fail(RL_EINVAL, "rl_plan_rollouts: no trajectory stage since the plan's last run");
     int gs = 0;
     if (int rc = check_rollouts(*query, p->traj_R, &gs)) return rc;
-    if (!p->bnd_R) return fail(RL_EINVAL, "rl_plan_rollouts: no bounds stage since the plan's last trajectory stage");
-    if (p->traj_q.index && p->traj_sel_epoch != p->sel_epoch)
-        return fail(RL_EINVAL, "rl_plan_rollouts: a selection has replaced the winners the trajectory stage read");
-    if (p->traj_mode == RL_MODE_MINCURV && p->traj_lap_epoch != p->lap_epoch)
-        return fail(RL_EINVAL, "rl_plan_rollouts: a lap stage has rewritten the rows the trajectory stage read");
+    if (!p->valid.has(Stage::Bounds)) return fail(RL_EINVAL, "rl_plan_rollouts: no bounds stage since the plan's last trajectory stage");
+    if (int rc = traj_current(p, "rl_plan_rollouts")) return rc;
     HIPCHK(hipSetDevice(p->device));
-    hipStream_t run_st = p->run_stream();
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : run_st;
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : p->run_stream();
     QueryStage& s = p->rll;
-    if (s.ev[0]) HIPCHK(hipEventSynchronize(s.ev[0]));   // an earlier upload may still read the pinned block
-    s.Q = 0;
     const RllLayout L = rll_layout((size_t)query->Q, (size_t)query->T, (size_t)(query->Q / gs) * (size_t)query->k,
                                    query->v != nullptr, query->row != nullptr, query->seg_hint != nullptr);
-    if (int rc = s.reserve(p->last_stream, L.in_bytes, L.out_bytes, "rollouts")) return rc;
-    for (auto& e : s.ev)
-        if (!e) HIPCHK(hipEventCreate(&e));
-    if (st != run_st) HIPCHK(hipStreamWaitEvent(st, p->ev_traj[1], 0));
-    HIPCHK(hipStreamWaitEvent(st, p->ev_bnd[1], 0));    // (the bounds stage may be on another stream)
-    p->last_stream = st;
-    rll_pack(*query, L, s.pin);
-    HIPCHK(hipMemcpyAsync(s.in, s.pin, L.in_bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(hipEventRecord(s.ev[0], st));
-    const hipError_t e = rll_launch(L, *query, gs, p->traj_q, p->bnd[0], p->bnd[1], s.in, s.out, st);
-    if (e != hipSuccess) return fail(RL_EHIP, std::string("rollouts launch: ") + hipGetErrorString(e));
-    HIPCHK(hipEventRecord(s.ev[1], st));
+    const int rc = upload_launch(
+        p, Stage::Rollouts, s, L, 0, st, [&](char* pin) { rll_pack(*query, L, pin); },
+        [&] { return rll_launch(L, *query, gs, p->traj_q, p->bnd[0], p->bnd[1], s.in, s.out, st); });
+    if (rc) return rc;
     s.Q = query->Q;
     s.M = query->T;
     p->rll_R = (int)L.R;
@@ -874,12 +826,12 @@ int rl_plan_rollouts(rl_plan* p, const rl_rll_query* query, void* hip_stream) {
 int rl_plan_fetch_rollouts(rl_plan* p, rl_rll* out) {
     if (!p) return fail(RL_EINVAL, "plan is NULL");
     if (!out) return fail(RL_EINVAL, "rl_plan_fetch_rollouts: results is NULL");
-    if (!p->rll.Q || !p->traj_R || !p->bnd_R)
+    if (!p->valid.has(Stage::Rollouts))
         return fail(RL_EINVAL, "rl_plan_fetch_rollouts: no rollouts stage since the plan's last run, trajectory or bounds stage");
     HIPCHK(hipSetDevice(p->device));
     QueryStage& s = p->rll;
     hipStream_t st = p->run_stream();
-    HIPCHK(hipStreamWaitEvent(st, s.ev[1], 0));         // (a later stage may have moved to another stream)
+    if (int rc = stage_wait(p, Stage::Rollouts, st)) return rc;   // (a later stage may have moved to another stream)
     const RllLayout L = rll_layout((size_t)s.Q, (size_t)s.M, (size_t)p->rll_R, false, false, false);
     const bool poses = rll_wants_poses(out);
     HIPCHK(hipMemcpyAsync(s.pin, s.out, poses ? L.out_bytes : L.head_bytes, hipMemcpyDeviceToHost, st));

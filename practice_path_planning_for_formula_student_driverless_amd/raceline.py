@@ -272,6 +272,8 @@ class Trajectory:
     count: np.ndarray
     dt: float
 
+    _C, _NODES = abi.RlTraj, ()          # (Plan._stage_fetch)
+
     @classmethod
     def alloc(cls, R: int, N: int, m_cap: int, dt: float) -> "Trajectory":
         cols = {n: np.zeros((R, m_cap)) for n in abi.TRAJ_COLS}
@@ -1262,6 +1264,8 @@ class Bounds:
     nx: np.ndarray
     ny: np.ndarray
 
+    _C, _NODES = abi.RlBnd, ()          # (Plan._stage_fetch)
+
     @classmethod
     def alloc(cls, R: int, N: int) -> "Bounds":
         return cls(*[np.zeros((R, N)) for _ in abi.BND_ROWS])
@@ -1281,6 +1285,8 @@ class HorizonBounds:
     hi: np.ndarray
     lo0: np.ndarray
     hi0: np.ndarray
+
+    _C, _NODES = abi.RlHznBnd, ()          # (Plan._stage_fetch)
 
     @classmethod
     def alloc(cls, Q: int, m_cap: int) -> "HorizonBounds":
@@ -1760,6 +1766,8 @@ class Rollouts:
     cost: np.ndarray
     order: np.ndarray
 
+    _C, _NODES = abi.RlRll, ()          # (Plan._stage_fetch)
+
     @classmethod
     def alloc(cls, Q: int, T: int, G: int, k: int, poses: bool = True) -> "Rollouts":
         per = {n: np.zeros((Q, T)) if poses else None for n in abi.RLL_POSE}
@@ -1995,7 +2003,8 @@ def rank_scores(scores, k: int, group_size: Optional[int] = None, device: int = 
 
 
 _STAGE_RESULTS = {"horizon": Horizon, "rejoin": Rejoin, "stop": Stop, "retime": Retime, "recover": Recover,
-                  "recover_fan": RecoverFan}
+                  "recover_fan": RecoverFan, "trajectory": Trajectory, "bounds": Bounds, "horizon_bounds": HorizonBounds,
+                  "rollouts": Rollouts}
 
 
 class Plan:
@@ -2080,18 +2089,18 @@ class Plan:
         by_lap = _check_score(score, m)
         s = abi.RlSelect(m, k, gs, 0)
         st = C.c_void_p(stream_ptr) if stream_ptr else None
-        self._sel = None
+        self._shapes["selected"] = None
         if _SCORES[score] == abi.RL_SCORE_DEFAULT:
             _check(_lib().rl_plan_select(self._h, C.byref(s), st))
         else:
             _check(_lib().rl_plan_select_scored(self._h, C.byref(s), _SCORES[score], st))
-        self._sel = (m, k, gs, by_lap)
+        self._shapes["selected"] = (m, k, gs, by_lap)
 
     def fetch_selected(self) -> Selected:
         """Download the last select(): indices, scores and the winners' rows (rl_plan_fetch_selected)."""
-        if getattr(self, "_sel", None) is None:
+        if self._shapes.get("selected") is None:
             raise ValueError("fetch_selected: no select() on this plan")
-        m, k, gs, by_lap = self._sel
+        m, k, gs, by_lap = self._shapes["selected"]
         sel = _selected_alloc(self.B, self.N, self.max_outer, m, k, gs, by_lap)
         o = sel.out.as_c()
         _check(_lib().rl_plan_fetch_selected(self._h, abi.iptr(sel.index), abi.dptr(sel.score),
@@ -2107,43 +2116,37 @@ class Plan:
             raise ValueError(f"mode must be 'mincurv' or 'mintime', got {mode!r}")
         if rows not in _TRAJ_ROWS:
             raise ValueError(f"rows must be 'all' or 'selected', got {rows!r}")
-        self._traj = None
-        _check(_lib().rl_plan_trajectory(self._h, _MODES[mode], _TRAJ_ROWS[rows], float(dt), int(m_cap),
-                                         C.c_void_p(stream_ptr) if stream_ptr else None))
-        sel = getattr(self, "_sel", None)
-        R = self.B if rows == "all" else (self.B // sel[2]) * sel[1]
-        self._traj = (R, int(m_cap), float(dt))
+        sel = self._shapes.get("selected")  # (rows="selected" without one: the library refuses the call)
+        R = self.B if rows == "all" or sel is None else (self.B // sel[2]) * sel[1]
+        self._stage_enqueue("trajectory", (R, self.N, int(m_cap), float(dt)), stream_ptr, _MODES[mode], _TRAJ_ROWS[rows],
+                            float(dt), int(m_cap))
 
     def fetch_trajectory(self) -> Trajectory:
         """Download the last trajectory() (rl_plan_fetch_trajectory)."""
-        if getattr(self, "_traj", None) is None:
-            t = abi.RlTraj()                # (the library's own answer: no stage on this plan)
-            _check(_lib().rl_plan_fetch_trajectory(self._h, C.byref(t)))
-            raise ValueError("fetch_trajectory: no trajectory() on this plan")
-        R, m_cap, dt = self._traj
-        out = Trajectory.alloc(R, self.N, m_cap, dt)
-        t = out.as_c()
-        _check(_lib().rl_plan_fetch_trajectory(self._h, C.byref(t)))
-        return out
+        return self._stage_fetch("trajectory")
 
-    # The pose-query stages (abi.QUERY_STAGES): `kind` names the C entry points rl_plan_<kind> and
-    # rl_plan_fetch_<kind>, the public methods <kind>() and fetch_<kind>() and, in _STAGE_RESULTS,
-    # the result class.  The shape of the last enqueued stage of each kind (the arguments of the
-    # class's alloc) is what its fetch allocates; None: no stage, or one that failed.
-    def _stage_enqueue(self, kind: str, qc, shape: tuple, stream_ptr: int = 0) -> None:
-        shapes = self.__dict__.setdefault("_stage_shapes", {})
-        shapes[kind] = None
-        _check(getattr(_lib(), "rl_plan_" + kind)(self._h, C.byref(qc), C.c_void_p(stream_ptr) if stream_ptr else None))
-        shapes[kind] = shape
+    # Every stage but the lap stage and the selection: `kind` names the C entry points
+    # rl_plan_<kind> and rl_plan_fetch_<kind>, the public methods <kind>() and fetch_<kind>() and, in
+    # _STAGE_RESULTS, the result class.  _shapes[kind], the shape of the last enqueued stage of the
+    # kind (the arguments of the class's alloc), is what its fetch allocates; None: no stage, or one
+    # that failed.  (_shapes["selected"] is the last select()'s mode, k, group size and score.)
+    @property
+    def _shapes(self) -> dict:
+        return self.__dict__.setdefault("_stage_shapes", {})
 
-    def _stage_fetch(self, kind: str, nodes: bool):
+    def _stage_enqueue(self, kind: str, shape: tuple, stream_ptr: int, *args) -> None:
+        self._shapes[kind] = None
+        _check(getattr(_lib(), "rl_plan_" + kind)(self._h, *args, C.c_void_p(stream_ptr) if stream_ptr else None))
+        self._shapes[kind] = shape
+
+    def _stage_fetch(self, kind: str, nodes: bool = True, *more):
         cls, fetch = _STAGE_RESULTS[kind], getattr(_lib(), "rl_plan_fetch_" + kind)
-        shape = self.__dict__.get("_stage_shapes", {}).get(kind)
+        shape = self._shapes.get(kind)
         if shape is None:
             t = cls._C()                    # (the library's own answer: no stage on this plan)
             _check(fetch(self._h, C.byref(t)))
             raise ValueError(f"fetch_{kind}: no {kind}() on this plan")
-        out = cls.alloc(*shape)
+        out = cls.alloc(*shape, *more)
         t = out.as_c()
         if not nodes:
             for n in cls._NODES:
@@ -2159,7 +2162,7 @@ class Plan:
         across the start line on a closed track.  As often as the caller likes without another
         run(); the trajectory stage stays as it is."""
         P, rw, hint = _hzn_query(poses, row, seg_hint, window, dt, m_cap)
-        self._stage_enqueue("horizon", _hzn_c(P, rw, hint, window, dt, m_cap), (P.shape[0], int(m_cap), float(dt)), stream_ptr)
+        self._stage_enqueue("horizon", (P.shape[0], int(m_cap), float(dt)), stream_ptr, C.byref(_hzn_c(P, rw, hint, window, dt, m_cap)))
 
     def fetch_horizon(self) -> Horizon:
         """Download the last horizon() (rl_plan_fetch_horizon)."""
@@ -2173,8 +2176,8 @@ class Plan:
         meets the row's own, at most k_cap samples ahead.  The trajectory stage and the last
         horizon() stay as they are."""
         P, rw, hint, V0 = _rjn_query(poses, v0, cfg, row, seg_hint, window, dt, m_cap, k_cap)
-        self._stage_enqueue("rejoin", _rjn_c(P, rw, hint, V0, cfg, window, dt, m_cap, k_cap),
-                            (P.shape[0], int(m_cap), float(dt), int(k_cap)), stream_ptr)
+        self._stage_enqueue("rejoin", (P.shape[0], int(m_cap), float(dt), int(k_cap)), stream_ptr,
+                            C.byref(_rjn_c(P, rw, hint, V0, cfg, window, dt, m_cap, k_cap)))
 
     def fetch_rejoin(self, nodes: bool = True) -> Rejoin:
         """Download the last rejoin() (rl_plan_fetch_rejoin); nodes=False leaves node_v, node_t on
@@ -2191,8 +2194,8 @@ class Plan:
         samples ahead.  The trajectory stage and the last horizon() and rejoin() stay as they
         are."""
         P, rw, hint, V0, J, VT = _stp_query(poses, v0, cfg, stop_sample, v_target, row, seg_hint, window, dt, m_cap, k_cap)
-        self._stage_enqueue("stop", _stp_c(P, rw, hint, V0, cfg, J, None if v_target is None else VT, window, dt, m_cap, k_cap),
-                            (P.shape[0], int(m_cap), float(dt), int(k_cap)), stream_ptr)
+        self._stage_enqueue("stop", (P.shape[0], int(m_cap), float(dt), int(k_cap)), stream_ptr,
+                            C.byref(_stp_c(P, rw, hint, V0, cfg, J, None if v_target is None else VT, window, dt, m_cap, k_cap)))
 
     def fetch_stop(self, nodes: bool = True) -> Stop:
         """Download the last stop() (rl_plan_fetch_stop); nodes=False leaves node_v, node_t, node_b
@@ -2207,8 +2210,8 @@ class Plan:
         row's.  The trajectory stage and the last horizon(), rejoin() and stop() stay as they
         are."""
         P, rw, hint, V0 = _rjn_query(poses, v0, cfg, row, seg_hint, window, dt, m_cap, k_cap)
-        self._stage_enqueue("retime", _rtm_c(P, rw, hint, V0, cfg, window, dt, m_cap, k_cap),
-                            (P.shape[0], int(m_cap), float(dt), int(k_cap)), stream_ptr)
+        self._stage_enqueue("retime", (P.shape[0], int(m_cap), float(dt), int(k_cap)), stream_ptr,
+                            C.byref(_rtm_c(P, rw, hint, V0, cfg, window, dt, m_cap, k_cap)))
 
     def fetch_retime(self, nodes: bool = True) -> Retime:
         """Download the last retime() (rl_plan_fetch_retime); nodes=False leaves node_v, node_t,
@@ -2223,8 +2226,8 @@ class Plan:
         offset back to the row inside the bounds stage's free width and cfg's speed profile on
         it.  Every other stage stays as it is; a later bounds() invalidates it."""
         P, rw, hint, V0, D, H = _rcv_query(poses, v0, cfg, merge_len, dir_xy, row, seg_hint, window, dt, m_cap, k_cap)
-        self._stage_enqueue("recover", _rcv_c(P, rw, hint, V0, D, H, cfg, window, dt, m_cap, k_cap),
-                            (P.shape[0], int(m_cap), float(dt), int(k_cap)), stream_ptr)
+        self._stage_enqueue("recover", (P.shape[0], int(m_cap), float(dt), int(k_cap)), stream_ptr,
+                            C.byref(_rcv_c(P, rw, hint, V0, D, H, cfg, window, dt, m_cap, k_cap)))
 
     def fetch_recover(self, nodes: bool = True) -> Recover:
         """Download the last recover() (rl_plan_fetch_recover); nodes=False leaves the node arrays
@@ -2239,8 +2242,8 @@ class Plan:
         fan_order's order and the winner is served.  Every other stage stays as it is; a later
         bounds() invalidates it."""
         P, rw, hint, V0, D, H = _fan_query(poses, v0, cfg, merge_lens, dir_xy, row, seg_hint, window, dt, m_cap, k_cap)
-        self._stage_enqueue("recover_fan", _fan_c(P, rw, hint, V0, D, H, cfg, window, dt, m_cap, k_cap),
-                            (P.shape[0], int(m_cap), float(dt), int(k_cap), D.shape[1]), stream_ptr)
+        self._stage_enqueue("recover_fan", (P.shape[0], int(m_cap), float(dt), int(k_cap), D.shape[1]), stream_ptr,
+                            C.byref(_fan_c(P, rw, hint, V0, D, H, cfg, window, dt, m_cap, k_cap)))
 
     def fetch_recover_fan(self, nodes: bool = True) -> RecoverFan:
         """Download the last recover_fan() (rl_plan_fetch_recover_fan): the winner's fields, best
@@ -2254,39 +2257,21 @@ class Plan:
         plan's first cfg).  Every other stage stays as it is."""
         w, m = _bnd_guard(self._keep[0].veh_width if veh_width is None else veh_width,
                           self._keep[1][0].safety_margin_m if margin is None else margin)
-        self._bnd = self._hbnd = None
-        q = abi.RlBndQuery(w, m)
-        _check(_lib().rl_plan_bounds(self._h, C.byref(q), C.c_void_p(stream_ptr) if stream_ptr else None))
-        self._bnd = getattr(self, "_traj", None)
+        self._shapes["horizon_bounds"] = None
+        self._stage_enqueue("bounds", (self._shapes.get("trajectory") or ())[:2], stream_ptr, C.byref(abi.RlBndQuery(w, m)))
 
     def fetch_bounds(self) -> Bounds:
         """Download the last bounds() (rl_plan_fetch_bounds): Bounds(lo, hi, nx, ny), [R, N] each."""
-        if getattr(self, "_bnd", None) is None:
-            t = abi.RlBnd()                 # (the library's own answer: no stage on this plan)
-            _check(_lib().rl_plan_fetch_bounds(self._h, C.byref(t)))
-            raise ValueError("fetch_bounds: no bounds() on this plan")
-        out = Bounds.alloc(self._bnd[0], self.N)
-        t = out.as_c()
-        _check(_lib().rl_plan_fetch_bounds(self._h, C.byref(t)))
-        return out
+        return self._stage_fetch("bounds")
 
     def horizon_bounds(self, stream_ptr: int = 0) -> None:
         """Enqueue the bounds at the ticks of the last horizon() (rl_plan_horizon_bounds), from
         the last bounds() of the same trajectory(); nothing is uploaded."""
-        self._hbnd = None
-        _check(_lib().rl_plan_horizon_bounds(self._h, C.c_void_p(stream_ptr) if stream_ptr else None))
-        self._hbnd = self.__dict__.get("_stage_shapes", {}).get("horizon")
+        self._stage_enqueue("horizon_bounds", (self._shapes.get("horizon") or ())[:2], stream_ptr)
 
     def fetch_horizon_bounds(self) -> HorizonBounds:
         """Download the last horizon_bounds() (rl_plan_fetch_horizon_bounds)."""
-        if getattr(self, "_hbnd", None) is None:
-            t = abi.RlHznBnd()              # (the library's own answer: no stage on this plan)
-            _check(_lib().rl_plan_fetch_horizon_bounds(self._h, C.byref(t)))
-            raise ValueError("fetch_horizon_bounds: no horizon_bounds() on this plan")
-        out = HorizonBounds.alloc(self._hbnd[0], self._hbnd[1])
-        t = out.as_c()
-        _check(_lib().rl_plan_fetch_horizon_bounds(self._h, C.byref(t)))
-        return out
+        return self._stage_fetch("horizon_bounds")
 
     def rollouts(self, xy, v=None, row=None, seg_hint=None, window0: int = 0, window: int = 8, weights=ROLLOUT_WEIGHTS,
                  hard_bounds: bool = False, group_size: Optional[int] = None, k: int = 1, stream_ptr: int = 0) -> None:
@@ -2298,22 +2283,12 @@ class Plan:
         group of group_size (None: all Q) are ranked on the device.  As often as the caller likes
         without another run(); every other stage stays as it is; a later bounds() invalidates it."""
         qy = _rll_query(xy, v, row, seg_hint, window0, window, weights, hard_bounds, group_size, k)
-        self._rll = None
-        qc = _rll_c(qy)
-        _check(_lib().rl_plan_rollouts(self._h, C.byref(qc), C.c_void_p(stream_ptr) if stream_ptr else None))
-        self._rll = qy[0].shape[:2] + (qy[0].shape[0] // qy[8], qy[9])
+        self._stage_enqueue("rollouts", qy[0].shape[:2] + (qy[0].shape[0] // qy[8], qy[9]), stream_ptr, C.byref(_rll_c(qy)))
 
     def fetch_rollouts(self, poses: bool = False) -> Rollouts:
         """Download the last rollouts() (rl_plan_fetch_rollouts): the per-rollout values and order;
         poses=True brings the per-pose arrays down as well."""
-        if getattr(self, "_rll", None) is None:
-            t = abi.RlRll()                 # (the library's own answer: no stage on this plan)
-            _check(_lib().rl_plan_fetch_rollouts(self._h, C.byref(t)))
-            raise ValueError("fetch_rollouts: no rollouts() on this plan")
-        out = Rollouts.alloc(*self._rll, poses)
-        t = out.as_c()
-        _check(_lib().rl_plan_fetch_rollouts(self._h, C.byref(t)))
-        return out
+        return self._stage_fetch("rollouts", True, poses)
 
     def device_outputs(self, which: int) -> abi.RlOut:
         d = abi.RlOut()

@@ -17,15 +17,16 @@ FLAGS = ["-O1", "-g", "-std=c++17", "--cuda-host-only", "-ffp-contract=off", "-f
 SANITIZE = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all"]
 
 
-def run_stage(tmp_path, stage: str) -> str:
-    """Build the program in tmp_path and run it on `stage`; its output, after asserting that it
-    ended well.  Prints whether the sanitizers were linked."""
-    exe = str(tmp_path / "query_layout_check")
-    r = subprocess.run([HIPCC, *FLAGS, *SANITIZE, SRC, "-o", exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+def run_stage(tmp_path, stage: str, src: str = SRC) -> str:
+    """Build the program (src: another stand-alone one of tests/, built the same way) in tmp_path and
+    run it on `stage`; its output, after asserting that it ended well.  Prints whether the sanitizers
+    were linked."""
+    exe = str(tmp_path / os.path.splitext(os.path.basename(src))[0])
+    r = subprocess.run([HIPCC, *FLAGS, *SANITIZE, src, "-o", exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     sanitized = r.returncode == 0
     if not sanitized:
         print("the sanitizer build failed, building without:\n" + r.stdout[-2000:])
-        subprocess.run([HIPCC, *FLAGS, SRC, "-o", exe], check=True)
+        subprocess.run([HIPCC, *FLAGS, src, "-o", exe], check=True)
     run = subprocess.run([exe, stage], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     print(("with" if sanitized else "WITHOUT") + " -fsanitize=address,undefined:\n" + run.stdout[:20000])
     assert run.returncode == 0, run.stdout[:20000]
